@@ -1,7 +1,7 @@
 """LTHM training-step benchmark (BASELINE.json metric: training samples/sec, LTHM
 fwd+bwd, plus embedding HBM GB/s).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c4x]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c4x] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,15 @@ One step = the reference's inner training step (accelerate_training_strategy.py:
 DP gradient exchange (N > 1) -> optimizer steps (fused AdamW on dense params,
 row-wise AdamW on the categorical KShift tables).  Inputs are synthetic batches
 of the C2 shape already resident in HBM.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+``--full`` adds everything else the line can carry, each at its own cost: the
+per-kernel breakdown and roofline figures (untimed profiling steps, the dominant
+kernel re-timed live), the embedding-gather HBM leg, the item-embedding generator
+step and the CPU baseline; the ``--no-*`` switches trim a ``--full`` run.
+``--dump-outputs DIR`` writes what the last timed step returned (loss, flags, the
+model's output tensors, the step's metrics) as DIR/<name>.npy for comparing two
+builds: the inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -372,6 +381,34 @@ def timed_median(step) -> float:
     return float(np.median(ts))
 
 
+DUMP_CAP = 2_000_000  # elements kept per dumped array (8 MB as float32): a seeded sample of larger ones
+
+
+def dump_outputs(path, named):
+    """Write every array of `named` ({name: tensor | mapping of floats | number}) as
+    path/<name>.npy, float32 (float64 for float64 / integer values).  An array of more
+    than DUMP_CAP elements is cut to a fixed, seeded sample of its flattened elements
+    (sorted indices, the same in every run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in named.items():
+        if isinstance(v, torch.Tensor):
+            t = v.detach().reshape(-1)
+            if t.numel() > DUMP_CAP:
+                g = torch.Generator().manual_seed(20240607)
+                idx = torch.randint(0, t.numel(), (DUMP_CAP,), generator=g).sort().values
+                t = t[idx.to(t.device)]
+                shape = (DUMP_CAP,)
+            else:
+                shape = tuple(v.shape)
+            wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+            a = t.to(torch.float64 if wide else torch.float32).cpu().numpy().reshape(shape)
+        elif hasattr(v, "keys"):
+            a = np.array([float(v[k]) for k in sorted(v.keys())], dtype=np.float64)
+        else:
+            a = np.array(float(v), dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -387,6 +424,13 @@ def main():
                     help="recompute block activations in the backward (the reference yaml's "
                          "enable_gradient_checkpointing, a memory knob; off by default: the "
                          "activations fit in 288 GB of HBM)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel timing and the "
+                         "roofline figures, the embedding-gather HBM leg, the item-embedding generator step "
+                         "and the CPU baseline (each can be switched off again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (loss, flags, the "
+                         "model's outputs, the step's metrics) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=0,
                     help="CPU-baseline sample (sequences); default per BASELINE.md: C2 256, C5 16, C1 the batch")
@@ -397,6 +441,10 @@ def main():
     ap.add_argument("--check-launch", action="store_true",
                     help="form the process group, print the world size it reports and exit (launcher test)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the timed steps and the headline line only
+        args.no_kernel_timing = args.no_hbm_gather = args.no_generator = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: this parent never touches the GPU; it starts one rank
@@ -451,6 +499,7 @@ def main():
         pool = [synthetic_lthm_batch(B, cfgd["T"], n_cat=cfgd["n_cat"], seed=1234 + 7919 * i, rank=rank, device=dev)
                 for i in range(nb)]
     cursor = [0]
+    last = {} if args.dump_outputs else None  # the last step's model output and metrics, for --dump-outputs
 
     # C3 on N > 1 GPUs: the row-sharded item table's lookup of the next step (routing, the
     # count exchange the host reads, two all_to_alls on a communicator of their own) runs on
@@ -470,7 +519,9 @@ def main():
         batch = pool[cursor[0] % nb]
         cursor[0] += 1
         out = model(batch)
-        loss, _ = model.train_step(batch, out)
+        loss, metrics = model.train_step(batch, out)
+        if last is not None:
+            last["out"], last["metrics"] = out, metrics
         loss.backward()
         if pipelined:  # after the backward is enqueued: the count read overlaps it
             model.prefetch(pool[cursor[0] % nb], batch_ready)
@@ -696,6 +747,15 @@ def main():
         res["kernels_source"] = (f"{PROF_STEPS} untimed profiling steps after warm-up (HIP events around every "
                                  f"entry point; share = fraction of the summed kernel time); the roofline kernel "
                                  f"is re-timed live inside the timed region")
+    if args.dump_outputs and rank == 0:
+        named = {"loss": loss, "flags": flags}
+        out = last["out"]
+        for k, v in (out.items() if hasattr(out, "items") else enumerate(out if isinstance(out, (tuple, list)) else [out])):
+            if isinstance(v, torch.Tensor):
+                named[f"out_{k}"] = v
+        if last["metrics"] is not None and hasattr(last["metrics"], "keys"):
+            named["metrics"] = last["metrics"]
+        dump_outputs(args.dump_outputs, named)
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not cfgd.get("item_table_sharded"):
         cpu_b = args.cpu_batch or {"c2": 256, "c5": 16}.get(args.config, min(B, 256))
         res["cpu_baseline"] = (cpu_baseline_ranker(cfg, model, cfgd, 32768) if ranker else

@@ -87,6 +87,25 @@ def test_bench_launches_n_ranks_by_itself():
     assert out["world"] == 2 and out["sum"] == 2.0
 
 
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.dump_outputs: one <name>.npy per entry, float32 (float64 for integer / float64
+    values and metric mappings), a larger array cut to the same seeded sample in every call."""
+    import bench
+    g =torch.Generator().manual_seed(3)
+    big = torch.randn(bench.DUMP_CAP // 2 + 1, 2, generator=g).to(torch.bfloat16)
+    named = {"loss": torch.tensor(1.5), "ids": torch.tensor([[2 ** 40, -7]]), "big": big,
+             "metrics": {"b": 2.0, "a": 1.0}}
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), named)
+    x = {n: np.load(str(tmp_path / "x" / (n + ".npy"))) for n in named}
+    assert x["loss"].dtype == np.float32 and x["loss"].shape == () and x["loss"] == 1.5
+    assert x["ids"].dtype == np.float64 and x["ids"].tolist() == [[2.0 ** 40, -7.0]]
+    assert x["metrics"].dtype == np.float64 and x["metrics"].tolist() == [1.0, 2.0]
+    assert x["big"].dtype == np.float32 and x["big"].shape == (bench.DUMP_CAP,)
+    assert np.isin(x["big"], big.float().numpy()).all()
+    assert np.array_equal(x["big"], np.load(str(tmp_path / "y" / "big.npy")))
+
+
 def test_loss_log_batches_host_syncs():
     """embedding_module_gen._LossLog: per-batch device losses reach the logger in order,
     in groups of log_every (0 = at flush / epoch end)."""
