@@ -126,10 +126,6 @@ __global__ __launch_bounds__(KS_BLOCK) void kshift_fwd_k(
 // wave iterations of 64 / LPR items); the next iteration's id load is issued before this
 // iteration's row loads retire.  Same arithmetic as kshift_fwd_k: f32 sum in the order
 // c = 0 .. K - 1, then / sqrt(K) or / max(|v|, 1e-12).
-// LTHM_KS_NT=1 (A/B build): the row loads non-temporal (read-once rows of a table far past the caches)
-#ifndef LTHM_KS_NT
-#define LTHM_KS_NT 0
-#endif
 template <typename TW, typename TO, int KT, int LPR>
 __global__ __launch_bounds__(KS_BLOCK) void kshift_fwd_reg_k(const int64_t* __restrict__ ids, int64_t n_items, int F,
                                                            const TW* __restrict__ W, int64_t P, int D, int mode,
@@ -164,11 +160,7 @@ __global__ __launch_bounds__(KS_BLOCK) void kshift_fwd_reg_k(const int64_t* __re
       const int src = gb + (c % LPR);
       const uint64_t r = ((uint64_t)(uint32_t)__shfl((int)rhi[c / LPR], src, 64) << 32) |
                          (uint32_t)__shfl((int)rlo[c / LPR], src, 64);
-#if LTHM_KS_NT
-      raw[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(colp + (int64_t)r * D));
-#else
       raw[c] = *reinterpret_cast<const u32x4*>(colp + (int64_t)r * D);
-#endif
     }
     float acc[NE];
 #pragma unroll
@@ -212,9 +204,6 @@ __global__ __launch_bounds__(KS_BLOCK) void kshift_fwd_reg_k(const int64_t* __re
 // Backward: LDS-staged dedup + wave-segmented reduction + one f32 add per
 // unique row per workgroup.
 // ---------------------------------------------------------------------------
-#ifndef LTHM_KSB_X
-#define LTHM_KSB_X 0  // cost-ladder builds of kshift_bwd_dense_k (tools/build_variant.sh; wrong results)
-#endif
 constexpr int KB_NP = 2048;            // max (row, item) pairs per workgroup
 constexpr int KB_G_FLOATS = 16384;     // LDS budget for per-item gradients (64 KiB)
 
@@ -277,8 +266,8 @@ __global__ __launch_bounds__(256) void kshift_bwd_dense_k(
       keys[p] = key;
     }
     __syncthreads();
-    // 3) bitonic sort of NP2 keys in LDS (LTHM_KSB_X=1 cost-ladder build: skipped, timing only)
-    for (int k = 2; k <= (LTHM_KSB_X == 1 ? 1 : NP2); k <<= 1) {
+    // 3) bitonic sort of NP2 keys in LDS
+    for (int k = 2; k <= NP2; k <<= 1) {
       for (int j = k >> 1; j > 0; j >>= 1) {
         for (int t = tid; t < NP2 / 2; t += 256) {
           const int i0 = 2 * t - (t & (j - 1));
@@ -339,7 +328,7 @@ __global__ __launch_bounds__(256) void kshift_bwd_dense_k(
           const int it = (int)(keys[p] & 0xfff) / K;
           acc += g[it * D + d];
         }
-        if (LTHM_KSB_X != 2) atomicAdd(dW + row * D + d, acc);  // LTHM_KSB_X=2: no row adds (timing only)
+        atomicAdd(dW + row * D + d, acc);
       }
     }
     // touched-row flags: every segment's first-touch test with its returning atomic issued side

@@ -1272,7 +1272,6 @@ __device__ __forceinline__ void cl_bwd32_head(ClTile32<NW>& sh, f32x16 (&dacc)[4
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
           const int yl = 32 * ib + 8 * (v >> 2) + 4 * hh + (v & 3), y = ys0 + yl;
-#if defined(CL_SP2)
           // branch-free: the register row's own sequence is [xlo, xlo + L); beyond-n image rows
           // are zero (ROWS) or carry weight 0 (COLS)
           const bool same = (unsigned)(y - xlo) < (unsigned)g.L;
@@ -1292,25 +1291,6 @@ __device__ __forceinline__ void cl_bwd32_head(ClTile32<NW>& sh, f32x16 (&dacc)[4
             ds = (keep && yw != 0.f) ? e : 0.f;
           }
           acc[ib][v] = ds;
-#else
-          const int ysq = y < g.n ? seq_of(g, y) : -1;
-          const bool keep = xr.live && (ysq != xr.sq || xr.x == y);
-          float ds = 0.f;
-          if (ROWS) {
-            const float yq = FIXED ? 0.f : sh.r.m0[cb][w][yl] * LOG2E;
-            if (keep && xr.w != 0.f) {
-              float t = __builtin_fmaf(acc[ib][v], c1, xr.sh + (xr.x == y ? 0.f : yq));
-              if (!FIXED) t = fminf(t, xr.cap);
-              ds = __builtin_amdgcn_exp2f(t) - (xr.x == y ? xr.w : 0.f);
-            }
-          } else {
-            const float ysh = sh.r.m0[cb][w][yl], yw = sh.r.m1[cb][w][yl];
-            if (keep && yw != 0.f)
-              ds = __builtin_amdgcn_exp2f(__builtin_fmaf(acc[ib][v], c1, ysh + (xr.x == y ? 0.f : xr.q))) -
-                   (xr.x == y ? yw : 0.f);
-          }
-          acc[ib][v] = ds;
-#endif
         }
       }
       // dacc[32 x 128] += dS[32 x 32] . img[32 x 128] of this image block: k-step ks = 2 ib + hf
@@ -1602,26 +1582,16 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
   stage(0);
   if (ntile > 1) stage(1);
   if (ntile > 2) stage(2);
-#if defined(CL_EXP) && CL_EXP >= 6
-  wait_vm<0>();
-  __builtin_amdgcn_s_barrier();
-#endif
   for (int tI = 0; tI < ntile; ++tI) {
-#if defined(CL_EXP) && CL_EXP >= 6
-    // skeleton experiment: no staging / waits / barriers (the first tiles are reused)
-    const int cb = tI % 3, y0 = tI * 64;
-#else
     const int cb = tI % CL_NB32, y0 = tI * 64;
     if (tI + 2 < ntile) wait_vm<2 * PT>();
     else if (tI + 1 < ntile) wait_vm<PT>();
     else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     if (tI + 3 < ntile) stage(tI + 3);
-#endif
     const unsigned char* img = sh.r.img[cb];
     const float* colb = sh.r.m0[cb][w];
     f32x16 acc[2];
-#if defined(CL_PF)
     // the two image blocks' S chains interleaved (no back-to-back dependent MFMA), each
     // k-step's A fragments read one step ahead behind a compiler fence
     {
@@ -1642,23 +1612,7 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
         asm volatile("" ::: "memory");
       }
     }
-#else
-#pragma unroll
-    for (int ib = 0; ib < 2; ++ib) {
-#pragma unroll
-      for (int v = 0; v < 16; ++v) acc[ib][v] = 0.f;
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const bf16x8v af = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + ib * 8192 + roff[s]));
-        acc[ib] = mfma32(af, qf[s], acc[ib]);
-      }
-    }
-#endif
-#if defined(CL_EXP) && CL_EXP >= 2
-    const bool special = false;
-#else
     const bool special = y0 < spec_hi && y0 + 64 > spec_lo;
-#endif
     if (!special) {
       // every valid column is kept; pad / beyond-n columns are zero image rows (S = 0) with a
       // -inf bias: counted out of cn, and out of the rank when 0 > thr
@@ -1677,19 +1631,9 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
           for (int j = 0; j < 4; ++j) {
             const int v = 4 * qd + j;
             const float sv = acc[ib][v];
-#if defined(CL_EXP) && CL_EXP >= 5
-            const float p = sv;
-#elif defined(CL_EXP) && CL_EXP >= 4
-            const float p = __builtin_fmaf(sv, c1, cv[j]);
-#else
             const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sv, c1, cv[j]));
-#endif
-#if !defined(CL_EXP) || CL_EXP < 5
             Z += p;
-#endif
-#if !defined(CL_EXP) || CL_EXP < 3
             rk += sv > thr ? 1 : 0;
-#endif
             acc[ib][v] = p;
           }
         } else {
@@ -1699,7 +1643,6 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
           for (int j = 0; j < 4; ++j) {
             const int v = 4 * qd + j, yl = 32 * ib + 8 * qd + 4 * hh + j, y = ys0 + yl;
             const float sv = acc[ib][v];
-#if defined(CL_SP2)
             // branch-free: x's own sequence is [xlo, xlo + L); pads / beyond-n carry cv = -inf
             if (y == x) pv = sv * it;
             const bool same = (unsigned)(y - xlo) < (unsigned)g.L;
@@ -1709,24 +1652,11 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
             Z += p;
             cn += keep ? 1 : 0;
             rk += (keep && y != x && sv > thr) ? 1 : 0;
-#else
-            if (y == x) pv = sv * it;
-            const int ysq = y < g.n ? seq_of(g, y) : -1;
-            const bool keep = live && cv[j] != -INFINITY && (ysq != xsq || y == x);
-            float p = 0.f;
-            if (keep) {
-              p = __builtin_amdgcn_exp2f(__builtin_fmaf(sv, c1, cv[j]));
-              Z += p;
-              cn += 1;
-              rk += (y != x && sv > thr) ? 1 : 0;
-            }
-#endif
             acc[ib][v] = p;
           }
         }
       }
       // dacc[32 x 128] += p[32 x 32] . img[32 x 128] (as cl_bwd32_head)
-#if defined(CL_PF)
       {
         const f32x16& pvv = acc[ib];
         const bf16x8v af0 = __builtin_bit_cast(bf16x8v, u32x4{pk_bf16(pvv[0], pvv[1]), pk_bf16(pvv[2], pvv[3]),
@@ -1747,21 +1677,6 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
           asm volatile("" ::: "memory");
         }
       }
-#else
-#pragma unroll
-      for (int hf = 0; hf < 2; ++hf) {
-        const int ks = 2 * ib + hf, o = 8 * hf;
-        const f32x16& pvv = acc[ib];
-        const u32x4 hpk = {pk_bf16(pvv[o], pvv[o + 1]), pk_bf16(pvv[o + 2], pvv[o + 3]), pk_bf16(pvv[o + 4], pvv[o + 5]),
-                           pk_bf16(pvv[o + 6], pvv[o + 7])};
-        const bf16x8v af = __builtin_bit_cast(bf16x8v, hpk);
-#pragma unroll
-        for (int nd = 0; nd < 4; ++nd) {
-          const bf16x8v bfr = tr_frag32(img, toff[nd][0] + ks * 4096, toff[nd][1] + ks * 4096);
-          dacc[nd] = mfma32(af, bfr, dacc[nd]);
-        }
-      }
-#endif
     }
   }
 }
@@ -2290,30 +2205,20 @@ __global__ __launch_bounds__(256, 2) void cl_fr32v_k(ClArgs a0) {
     __builtin_amdgcn_s_barrier();
     if (i + 3 < ntile) cur.stage(sh.img[(i + 3) % CL_NB32], ord.at(i + 3), w, lane);
   };
-#if defined(CL_VX) && (CL_VX & 1)
-  wait_vm<0>();  // experiment: the clean loop re-reads the staged slots (no staging / waits / barriers)
-  __builtin_amdgcn_s_barrier();
-#endif
   // clean tiles: no exclusion, no pad, every element kept
   for (int i = 0; i < ord.nclean; ++i) {
-#if !defined(CL_VX) || !(CL_VX & 1)
     open_step(i);
-#endif
     const unsigned char* img = sh.img[i % CL_NB32];
     const unsigned char* imgn = sh.img[(i + 1) % CL_NB32];
 #pragma unroll
     for (int ib = 0; ib < 2; ++ib) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
-#if defined(CL_VX) && (CL_VX & 2)
-        (void)thr;  // experiment: no element work (P = S)
-#else
         const float sv = sacc[ib][v];
         const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sv, c1, csh));
         Z += p;
         rk += sv > thr ? 1 : 0;
         sacc[ib][v] = p;
-#endif
       }
     }
     cn += 32;
@@ -2330,11 +2235,7 @@ __global__ __launch_bounds__(256, 2) void cl_fr32v_k(ClArgs a0) {
   // the clean body's operations give p = 0 and no rank.  The diagonal (always kept) enters in
   // the epilogue, from the positive logit dg.
   auto below = [](int k) { return k >= 64 ? ~0ull : (1ull << k) - 1ull; };
-#if defined(CL_VX) && (CL_VX & 1)
-  for (int i = ntile; i < ntile; ++i) {  // experiment: special tiles skipped
-#else
   for (int i = ord.nclean; i < ntile; ++i) {
-#endif
     open_step(i);
     const unsigned char* img = sh.img[i % CL_NB32];
     const unsigned char* imgn = sh.img[(i + 1) % CL_NB32];

@@ -307,39 +307,10 @@ __device__ __forceinline__ void mlp_load_ln(const MlpArgs& a, const float* lw, c
   }
 }
 
-// Weight chunks ride a 3-slot LDS-DMA ring.  STAG (two waves per SIMD): waves NW/2 .. NW - 1
-// share their SIMDs with waves 0 .. NW/2 - 1 and would run in lockstep with them (one barrier per
-// chunk), so both would issue the S chain, then both the GELU, then both the output products.
-// The upper half instead lags half a chunk: at step j it finishes chunk j - 1 (GELU, then
-// Y += H W2T_{j-1}) and then forms S of chunk j, carried across the barrier; its VALU runs
-// beside the partner's S MFMAs and its output MFMAs beside the partner's GELU
-// (MI355X_MICROARCH.md, two waves per SIMD, item 9).  The ring then prefetches one chunk ahead
-// (chunk j - 1 stays readable during step j); without STAG it prefetches two.
-// cost-ladder builds of mlp_fwd_k (tools/build_variant.sh ... -DLTHM_MLPF_X=n; timing only, wrong
-// results): 1 no DMA waits, 2 no GELU (the bias add only), 3 no per-chunk barrier, 4 no S MFMAs
-#ifndef LTHM_MLPF_X
-#define LTHM_MLPF_X 0
-#endif
-// LTHM_MLPF_STAMP=1 (diagnostic build, tools/build_variant.sh): mlp_fwd_k sums per wave the
-// s_memtime cycles of each phase of the chunk loop (wait + barrier, DMA issue + S issue, S
-// completion, GELU + Y issue) and of the tile epilogues into g_mlpf_stamps, read back with
-// lthm_debug_mlpf_stamps.  Timing only (the stamps' lgkmcnt waits perturb the LDS prefetch).
-#ifndef LTHM_MLPF_STAMP
-#define LTHM_MLPF_STAMP 0
-#endif
-// LTHM_MLPF_TRPF=2: W2T fragments read before the GELU and two output tiles ahead (A/B build)
-#ifndef LTHM_MLPF_TRPF
-#define LTHM_MLPF_TRPF 0
-#endif
-#if LTHM_MLPF_STAMP
-__device__ unsigned long long g_mlpf_stamps[2048 * 8 * 8];
-#define MLPF_T(v) const uint64_t v = __builtin_amdgcn_s_memtime()
-#else
-#define MLPF_T(v)
-#endif
-template <int D, int NW, bool STAG>
+// Weight chunks ride a 3-slot LDS-DMA ring that prefetches two chunks ahead.
+template <int D, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
-  constexpr int NS = 3, DIST = STAG ? 1 : 2;
+  constexpr int NS = 3, DIST = 2;
   constexpr int NTH = 64 * NW, IMG = 32 * D * 2, KS = D / 16, NT = D / 32, TR = 32 * NW;
   constexpr int DPC = 2 * (32 * D / 8) / NTH;  // DMAs per thread and chunk (both images)
   __shared__ __attribute__((aligned(16))) unsigned char img[NS][2][IMG];  // [slot][W1_j, W2T_j]
@@ -349,7 +320,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
   float* lws = b2s + D;
   float* lbs = lws + D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r32 = lane & 31, h = lane >> 5;
-  const bool lag = STAG && wave >= NW / 2;  // wave-uniform
   const int NC = a.HID / 32;
   const int64_t rs = a.M * blockIdx.x / gridDim.x, re = a.M * (blockIdx.x + 1) / gridDim.x;
   if (rs >= re) return;  // uniform
@@ -362,10 +332,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
     }
   float* stg = stg_all[wave];
   retire_loads();
-#if LTHM_MLPF_STAMP
-  MLPF_T(tk0);
-  uint64_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
   const int64_t ntile_wg = (re - rs + TR - 1) / TR;
   // chunks 0 .. DIST - 1 of the stream (chunk c: index c % NC of tile c / NC)
 #pragma unroll
@@ -380,10 +346,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
     // LDS reads one step ahead of their MFMA; the compiler fences keep the unrolled loops
     // from hoisting every read (register pressure: 2 waves per SIMD)
     f32x16 S = f32x16{};
-    if (LTHM_MLPF_X == 4) {
-      S[0] = (float)mlp_row_frag<D>(w1, lane, 0)[0];
-      return S;
-    }
     bf16x8m fa = mlp_row_frag<D>(w1, lane, 0);
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
@@ -396,44 +358,12 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
   };
   // H = bf16(GELU(S + b1_j)), Y += H . W2T_j
   auto gelu_out = [&](const f32x16& S, int j, const unsigned char* w2, f32x16(&acc)[NT]) {
-    if (LTHM_MLPF_TRPF >= 2) {
-      // the first two output tiles' W2T fragments are read BEFORE the GELU (they land while its
-      // VALU runs), then two tiles ahead of their MFMAs: the phase-stamp build measured the
-      // GELU + Y block at 53 % of a chunk step with the reads one tile ahead (tools/mlp_stamp.py)
-      bf16x8m b0 = mlp_tr_frag<D>(w2, lane, 0, 0), b1 = mlp_tr_frag<D>(w2, lane, 1, 0);
-      bf16x8m c0 = mlp_tr_frag<D>(w2, lane, 0, 1), c1 = mlp_tr_frag<D>(w2, lane, 1, 1);
-      u32x4 hw0, hw1;  // H packed as it is formed (no 16-float staging)
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 8 * m + 4 * h);
-        float hv4[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv4[e] = LTHM_MLPF_X == 2 ? S[4 * m + e] + bb[e] : gelu_tanh(S[4 * m + e] + bb[e]);
-        const uint32_t p0 = pack_bf16x2(hv4[0], hv4[1]), p1 = pack_bf16x2(hv4[2], hv4[3]);
-        if (m < 2) { hw0[2 * m] = p0; hw0[2 * m + 1] = p1; }
-        else { hw1[2 * (m - 2)] = p0; hw1[2 * (m - 2) + 1] = p1; }
-      }
-      const bf16x8m hf0 = __builtin_bit_cast(bf16x8m, hw0), hf1 = __builtin_bit_cast(bf16x8m, hw1);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int tn = t + 2 < NT ? t + 2 : NT - 1;
-        const bf16x8m n0 = mlp_tr_frag<D>(w2, lane, 0, tn), n1 = mlp_tr_frag<D>(w2, lane, 1, tn);
-        acc[t] = mfma32(hf0, b0, acc[t]);
-        acc[t] = mfma32(hf1, b1, acc[t]);
-        b0 = c0;
-        b1 = c1;
-        c0 = n0;
-        c1 = n1;
-        asm volatile("" ::: "memory");
-      }
-      return;
-    }
     float hv[16];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 8 * m + 4 * h);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) hv[4 * m + e] = LTHM_MLPF_X == 2 ? S[4 * m + e] + bb[e] : gelu_tanh(S[4 * m + e] + bb[e]);
+      for (int e = 0; e < 4; ++e) hv[4 * m + e] = gelu_tanh(S[4 * m + e] + bb[e]);
     }
     const bf16x8m hf0 = mlp_pack(hv), hf1 = mlp_pack(hv + 8);
     bf16x8m b0 = mlp_tr_frag<D>(w2, lane, 0, 0), b1 = mlp_tr_frag<D>(w2, lane, 1, 0);
@@ -459,16 +389,12 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
     f32x16 acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = f32x16{};
-    f32x16 S = f32x16{};  // lagging waves: chunk j - 1's S across the barrier
     for (int j = 0; j < NC; ++j, ++g) {
-      MLPF_T(ts0);
       // retire chunk g; at prefetch distance 2 chunk g + 1 stays in flight (a tile's first step
       // drains: the x / residual / output accesses were issued behind the DMAs)
-      if (LTHM_MLPF_X != 1) {
-        if (DIST == 1 || j == 0) wait_vm<0>();
-        else wait_vm<DPC>();
-      }
-      if (LTHM_MLPF_X != 3) __syncthreads();  // chunk g landed everywhere; every wave is done with chunk g + DIST - NS
+      if (j == 0) wait_vm<0>();
+      else wait_vm<DPC>();
+      __syncthreads();  // chunk g landed everywhere; every wave is done with chunk g + DIST - NS
       asm volatile("" ::: "memory");
       {
         // chunk g + DIST: of this tile, or the next tile's (same weights, chunk index wraps)
@@ -481,356 +407,13 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
         }
       }
       if (!active) continue;
-      if (lag) {
-        if (j > 0) gelu_out(S, j - 1, img[(g + NS - 1) % NS][1], acc);
-        S = s_phase(img[g % NS][0], xf);
-      } else {
-#if LTHM_MLPF_STAMP
-        MLPF_T(ts1);
-        const f32x16 Sj = s_phase(img[g % NS][0], xf);
-        MLPF_T(ts2);
-        {
-          float dep = Sj[15] + Sj[0];  // in-order issue: the stamp below waits for the S chain
-          asm volatile("" : "+v"(dep));
-          asm volatile("" ::"v"(dep));
-        }
-        MLPF_T(ts3);
-        gelu_out(Sj, j, img[g % NS][1], acc);
-        MLPF_T(ts4);
-        if (tix > 0) {
-          st_acc[0] += ts1 - ts0;  // wait + barrier + DMA issue
-          st_acc[1] += ts2 - ts1;  // S issue (LDS row reads)
-          st_acc[2] += ts3 - ts2;  // S completion
-          st_acc[3] += ts4 - ts3;  // GELU + Y issue
-          st_acc[4] += 1;
-        }
-#else
-        const f32x16 Sj = s_phase(img[g % NS][0], xf);
-        gelu_out(Sj, j, img[g % NS][1], acc);
-#endif
-        S = f32x16{};  // nothing carried: keeps the loop-carried S out of this path's live range
-      }
+      const f32x16 Sj = s_phase(img[g % NS][0], xf);
+      gelu_out(Sj, j, img[g % NS][1], acc);
     }
-#if LTHM_MLPF_STAMP
-    MLPF_T(te0);
-#endif
     if (active) {
-      if (lag) gelu_out(S, NC - 1, img[(g + NS - 1) % NS][1], acc);  // chunk g - 1: slot kept until step g + 1
       if (a.res1 && a.res2) mlp_fwd_epi<D, NT, 2>(a, acc, b2s, stg, rb, lim, lane);
       else if (a.res1) mlp_fwd_epi<D, NT, 1>(a, acc, b2s, stg, rb, lim, lane);
       else mlp_fwd_epi<D, NT, 0>(a, acc, b2s, stg, rb, lim, lane);
-    }
-#if LTHM_MLPF_STAMP
-    MLPF_T(te1);
-    if (tix > 0) {
-      st_acc[5] += te1 - te0;  // tile epilogue issue
-      st_acc[6] += 1;
-    }
-#endif
-  }
-#if LTHM_MLPF_STAMP
-  MLPF_T(tk);
-  st_acc[7] = tk - tk0;
-  if (lane == 0 && blockIdx.x < 2048)
-    for (int k = 0; k < 8; ++k) g_mlpf_stamps[(blockIdx.x * 8 + wave) * 8 + k] = st_acc[k];
-#endif
-}
-
-// ---------------------------------------------------------------- forward, two workgroups per CU
-// mlp_fwd_k's chunk loop at 4 waves (128-row tiles) with everything that kept a second workgroup
-// off the CU removed, so that two independent workgroups share each CU and one's tile edges (the
-// x / residual loads, the output stores, the first chunk's drain) run beside the other's MFMAs:
-//  * the accumulator starts as b2 + res1 (+ res2), loaded straight into the C layout when the tile
-//    starts (register i of tile t: row 4 h + (i & 3) + 8 (i >> 2), column 32 t + r32; each
-//    half-wave reads one 128-B row piece), and leaves from the C layout the same way, so the tile
-//    end is stores only, no LDS strip and no load after a store;
-//  * W1 / W2T chunks on a 2-slot ring (prefetch distance 1): 64 KiB of images + 5 KiB of biases.
-// Two workgroups of 4 waves are 2 waves per SIMD (256 registers each, as the 8-wave form).
-#ifndef LTHM_MLPF2_PF
-#define LTHM_MLPF2_PF 1
-#endif
-template <int D, int NRES>
-__global__ __launch_bounds__(256, 2) void mlp_fwd2_k(MlpArgs a) {
-  constexpr int NW = 4, NTH = 64 * NW, IMG = 32 * D * 2, KS = D / 16, NT = D / 32, TR = 32 * NW;
-  __shared__ __attribute__((aligned(16))) unsigned char img[2][2][IMG];  // [slot][W1_j, W2T_j]
-  extern __shared__ float b1s[];                                         // [HID] b1, [D] b2
-  float* b2s = b1s + a.HID;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r32 = lane & 31, h = lane >> 5;
-  const int NC = a.HID / 32;
-  const int64_t rs = a.M * blockIdx.x / gridDim.x, re = a.M * (blockIdx.x + 1) / gridDim.x;
-  if (rs >= re) return;  // uniform
-  for (int i = tid; i < a.HID; i += NTH) b1s[i] = a.b1 ? a.b1[i] : 0.f;
-  for (int i = tid; i < D; i += NTH) b2s[i] = a.b2 ? a.b2[i] : 0.f;
-  retire_loads();
-  const int64_t ntile_wg = (re - rs + TR - 1) / TR;
-  mlp_dma32<D, NTH>(img[0][0], a.W1, tid);
-  mlp_dma32<D, NTH>(img[0][1], a.W2T, tid);
-  __syncthreads();  // b1s / b2s
-  int g = 0;
-  int64_t tix = 0;
-  for (int64_t t0 = rs; t0 < re; t0 += TR, ++tix) {
-    const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
-    const bool active = rb < lim;  // wave-uniform: a wave past the tile's rows only streams weights
-    bf16x8m xf[KS];
-    mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
-    f32x16 acc[NT];
-    // register i of tile t holds wave row (i & 3) + 8 (i >> 2) + 4 h; rows past `last` (the wave's
-    // last row in range) read row `last` and are never stored
-    const int last = active ? (int)min((int64_t)32, lim - rb) - 1 : 0;
-    if (active) {  // acc = b2 + res1 (res2 joins in the epilogue, where the registers are free)
-      const float* r1 = a.res1 + rb * D;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const float bb = b2s[32 * t + r32];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int o = min((i & 3) + 8 * (i >> 2) + 4 * h, last) * D + 32 * t + r32;
-          float v = bb;
-          if constexpr (NRES >= 1) v += r1[o];
-          acc[t][i] = v;
-        }
-      }
-    }
-    for (int j = 0; j < NC; ++j, ++g) {
-      wait_vm<0>();     // chunk g landed (a tile's first step also drains its x / residual loads)
-      __syncthreads();  // ... everywhere; every wave is done with chunk g - 1's slot
-      asm volatile("" ::: "memory");
-      if (j + 1 < NC || tix + 1 < ntile_wg) {
-        const int jn = j + 1 < NC ? j + 1 : 0;
-        mlp_dma32<D, NTH>(img[(g + 1) & 1][0], a.W1 + (int64_t)jn * 32 * D, tid);
-        mlp_dma32<D, NTH>(img[(g + 1) & 1][1], a.W2T + (int64_t)jn * 32 * D, tid);
-      }
-      if (!active) continue;
-      const unsigned char* w1 = img[g & 1][0];
-      const unsigned char* w2 = img[g & 1][1];
-      // S^T = W1_j . x^T (LDS row reads LTHM_MLPF2_PF steps ahead of their MFMA)
-      f32x16 S = f32x16{};
-      if (LTHM_MLPF2_PF >= 2) {
-        bf16x8m fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w1, lane, 1);
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-          const bf16x8m fn = mlp_row_frag<D>(w1, lane, k + 2 < KS ? k + 2 : KS - 1);
-          S = mfma32(fa, xf[k], S);
-          fa = fb;
-          fb = fn;
-          asm volatile("" ::: "memory");
-        }
-      } else {
-        bf16x8m fa = mlp_row_frag<D>(w1, lane, 0);
-#pragma unroll
-        for (int k = 0; k < KS; ++k) {
-          const bf16x8m fn = mlp_row_frag<D>(w1, lane, k + 1 < KS ? k + 1 : k);
-          S = mfma32(fa, xf[k], S);
-          fa = fn;
-          asm volatile("" ::: "memory");
-        }
-      }
-      // H = bf16(GELU(S + b1_j)), Y += H . W2T_j
-      float hv[16];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 8 * m + 4 * h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[4 * m + e] = gelu_tanh(S[4 * m + e] + bb[e]);
-      }
-      const bf16x8m hf0 = mlp_pack(hv), hf1 = mlp_pack(hv + 8);
-      bf16x8m b0 = mlp_tr_frag<D>(w2, lane, 0, 0), b1 = mlp_tr_frag<D>(w2, lane, 1, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int tn = t + 1 < NT ? t + 1 : t;
-        const bf16x8m n0 = mlp_tr_frag<D>(w2, lane, 0, tn), n1 = mlp_tr_frag<D>(w2, lane, 1, tn);
-        acc[t] = mfma32(hf0, b0, acc[t]);
-        acc[t] = mfma32(hf1, b1, acc[t]);
-        b0 = n0;
-        b1 = n1;
-        asm volatile("" ::: "memory");
-      }
-    }
-    if (active) {
-      float* o = a.out + rb * D;
-      if constexpr (NRES >= 2) {  // + res2, two column tiles' loads in flight at a time
-        const float* r2 = a.res2 + rb * D;
-#pragma unroll
-        for (int t = 0; t < NT; t += 2) {
-          float rv[2][16];
-#pragma unroll
-          for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              rv[u][i] = r2[min((i & 3) + 8 * (i >> 2) + 4 * h, last) * D + 32 * (t + u) + r32];
-#pragma unroll
-          for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[t + u][i] += rv[u][i];
-          asm volatile("" ::: "memory");
-        }
-      }
-      if (last == 31) {  // wave-uniform: a full 32-row wave tile
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) o[((i & 3) + 8 * (i >> 2) + 4 * h) * D + 32 * t + r32] = acc[t][i];
-      } else {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int rr = (i & 3) + 8 * (i >> 2) + 4 * h;
-            if (rr <= last) o[rr * D + 32 * t + r32] = acc[t][i];
-          }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------- forward, software-pipelined
-// One wave per SIMD (4 waves, 512 registers each), the chunk stream software-pipelined inside
-// the wave so that the MFMAs and the GELU VALU of different chunks issue side by side: phase k
-// of a tile runs
-//   S_k   = W1_k . x^T                        (16 MFMAs, one accumulation chain)
-//   H_k-1 = bf16(GELU(S_k-1 + b1))            (VALU, between those MFMAs)
-//   Y    += H_k-2 . W2T_k-2                   (16 MFMAs on the 8 output tiles)
-// for k = 0 .. NC + 1 (the terms whose chunk exists).  Per steady phase 32 MFMAs (1,024 cycles
-// of the matrix pipe) carry ~620 cycles of GELU in their issue gaps.  W1 and W2T chunks ride
-// separate 2-slot LDS-DMA rings, one barrier per phase.  The accumulator starts as the residual
-// (+ b2), loaded straight into the C layout (each half-wave reads a 128-B row piece), and is
-// stored from the C layout the same way: no LDS restaging.
-// one phase of mlp_fwd_pipe_k: DS: S_k = W1_k . x^T into Sp (after its GELU is taken); DG: H =
-// GELU(Sp + b1) into ho (after its products are issued); DO: Y += ho . W2T.  Step i pairs S
-// MFMA i with output MFMA i (tile i / 2, k-step i % 2) and GELU element i; the LDS fragments
-// are read one step ahead (compiler fences keep the unrolled steps from hoisting every read).
-// LTHM_MLPP_PF: LDS fragment reads this many steps ahead of their MFMA (1 or 2; one wave per
-// SIMD, so an LDS read the MFMA waits on idles the matrix pipe)
-#ifndef LTHM_MLPP_PF
-#define LTHM_MLPP_PF 2
-#endif
-template <int D, bool DS, bool DG, bool DO>
-__device__ __forceinline__ void mlp_pipe_phase(const unsigned char* w1, const unsigned char* w2, const float* bj,
-                                               const bf16x8m (&xf)[D / 16], f32x16 (&acc)[D / 32], f32x16& Sp,
-                                               bf16x8m& ho0, bf16x8m& ho1, int lane) {
-  constexpr int KS = D / 16;
-  static_assert(16 % KS == 0, "GELU elements per step");
-  f32x16 Sn = f32x16{};
-  float hv[16];
-  bf16x8m fa[LTHM_MLPP_PF], fb[LTHM_MLPP_PF];
-#pragma unroll
-  for (int q = 0; q < LTHM_MLPP_PF; ++q) {
-    fa[q] = fb[q] = bf16x8m{};
-    if (DS) fa[q] = mlp_row_frag<D>(w1, lane, q < KS ? q : KS - 1);
-    if (DO) fb[q] = mlp_tr_frag<D>(w2, lane, (q < KS ? q : KS - 1) & 1, (q < KS ? q : KS - 1) >> 1);
-  }
-#pragma unroll
-  for (int i = 0; i < KS; ++i) {
-    const int in = i + LTHM_MLPP_PF < KS ? i + LTHM_MLPP_PF : KS - 1;
-    bf16x8m na = fa[0], nb = fb[0];
-    if (DS) na = mlp_row_frag<D>(w1, lane, in);
-    if (DO) nb = mlp_tr_frag<D>(w2, lane, in & 1, in >> 1);
-    if (DS) Sn = mfma32(fa[0], xf[i], Sn);
-    if (DO) acc[i >> 1] = mfma32((i & 1) ? ho1 : ho0, fb[0], acc[i >> 1]);
-    // 16 / KS GELU elements per step (element e: unit 8 (e >> 2) + 4 h + (e & 3) of the chunk)
-    if (DG) {
-#pragma unroll
-      for (int ee = 0; ee < 16 / KS; ++ee) {
-        const int e = i * (16 / KS) + ee;
-        hv[e] = gelu_tanh(Sp[e] + bj[8 * (e >> 2) + (e & 3)]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q + 1 < LTHM_MLPP_PF; ++q) {
-      fa[q] = fa[q + 1];
-      fb[q] = fb[q + 1];
-    }
-    fa[LTHM_MLPP_PF - 1] = na;
-    fb[LTHM_MLPP_PF - 1] = nb;
-    asm volatile("" ::: "memory");
-  }
-  if (DG) {
-    ho0 = mlp_pack(hv);
-    ho1 = mlp_pack(hv + 8);
-  }
-  if (DS) Sp = Sn;
-}
-
-template <int D, int NRES>
-__global__ __launch_bounds__(256, 1) void mlp_fwd_pipe_k(MlpArgs a) {
-  constexpr int NW = 4, NTH = 64 * NW, IMG = 32 * D * 2, KS = D / 16, NT = D / 32, TR = 32 * NW;
-  static_assert(KS == 2 * NT, "one S MFMA and one output MFMA per step");
-  __shared__ __attribute__((aligned(16))) unsigned char im1[2][IMG];  // W1 chunk ring
-  __shared__ __attribute__((aligned(16))) unsigned char im2[2][IMG];  // W2T chunk ring
-  extern __shared__ float b1s[];                                      // [HID] b1, [D] b2
-  float* b2s = b1s + a.HID;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r32 = lane & 31, h = lane >> 5;
-  const int NC = a.HID / 32;
-  const int64_t rs = a.M * blockIdx.x / gridDim.x, re = a.M * (blockIdx.x + 1) / gridDim.x;
-  if (rs >= re) return;  // uniform
-  for (int i = tid; i < a.HID; i += NTH) b1s[i] = a.b1 ? a.b1[i] : 0.f;
-  for (int i = tid; i < D; i += NTH) b2s[i] = a.b2 ? a.b2[i] : 0.f;
-  retire_loads();
-  const int64_t ntile_wg = (re - rs + TR - 1) / TR;
-  mlp_dma32<D, NTH>(im1[0], a.W1, tid);
-  mlp_dma32<D, NTH>(im2[0], a.W2T, tid);
-  __syncthreads();  // b1s / b2s
-  // W1 / W2T chunk reads so far (ring slot: count & 1), and the chunk / tile of the next read
-  int w1c = 0, w2c = 0, n1c = NC > 1 ? 1 : 0, n1t = NC > 1 ? 0 : 1, n2c = n1c, n2t = n1t;
-  for (int64_t t0 = rs; t0 < re; t0 += TR) {
-    const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
-    const bool active = rb < lim;  // wave-uniform
-    bf16x8m xf[KS];
-    mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
-    f32x16 acc[NT];
-    // acc = b2 + res1 (+ res2) in the C layout: register i of tile t is row rb + 4 h + (i & 3) +
-    // 8 (i >> 2), column 32 t + r32.  One 32-bit offset per register row (rows past the range
-    // clamped to its last row: their values are never stored), the tile in the immediate.
-    const int nrow = (int)min((int64_t)32, lim - rb) - 4 * h;  // live register rows: (i & 3) + 8 (i >> 2) < nrow
-    uint32_t ro[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) ro[i] = (uint32_t)(min(rb + 4 * h + (i & 3) + 8 * (i >> 2), lim - 1) * D + r32);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const float bb = b2s[32 * t + r32];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float v = bb;
-        if constexpr (NRES >= 1) v += a.res1[ro[i] + 32 * t];
-        if constexpr (NRES >= 2) v += a.res2[ro[i] + 32 * t];
-        acc[t][i] = v;
-      }
-    }
-    f32x16 Sp = f32x16{};       // S of the previous phase's chunk
-    bf16x8m ho0 = {}, ho1 = {};  // H of the chunk two phases back
-    for (int k = 0; k < NC + 2; ++k) {
-      const bool rd1 = k < NC, rd2 = k >= 2;
-      wait_vm<0>();
-      __syncthreads();  // this phase's chunks landed; the slots the DMAs below refill are free
-      asm volatile("" ::: "memory");
-      if (rd1 && n1t < ntile_wg) mlp_dma32<D, NTH>(im1[(w1c + 1) & 1], a.W1 + n1c * 32 * D, tid);
-      if (rd2 && n2t < ntile_wg) mlp_dma32<D, NTH>(im2[(w2c + 1) & 1], a.W2T + n2c * 32 * D, tid);
-      if (active) {
-        // every phase runs all three streams (one code path keeps the register allocation within
-        // the 512 of one wave per SIMD); the edge phases' extra terms are inert: H starts as zero
-        // (the products of phases 0 and 1 add exact zeros, their W2T slot holds finite weights),
-        // the S chains of phases NC and NC + 1 read finite stale or next-tile W1 data and feed
-        // only a GELU whose H is discarded when the tile ends
-        const int jg = min(max(k - 1, 0), NC - 1);  // chunk of the GELU
-        mlp_pipe_phase<D, true, true, true>(im1[w1c & 1], im2[w2c & 1], b1s + 32 * jg + 4 * h, xf, acc, Sp, ho0, ho1,
-                                            lane);
-        if (k == 0) ho0 = ho1 = bf16x8m{};
-      }
-      if (rd1) {
-        ++w1c;
-        if (++n1c == NC) n1c = 0, ++n1t;
-      }
-      if (rd2) {
-        ++w2c;
-        if (++n2c == NC) n2c = 0, ++n2t;
-      }
-    }
-    if (active) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-          if ((i & 3) + 8 * (i >> 2) < nrow) a.out[ro[i] + 32 * t] = acc[t][i];
     }
   }
 }
@@ -1161,11 +744,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
   // the previous step issued its 4 G / dP stores AFTER the DMA of this step's chunk: a full-tile
   // wave retires the DMA with vmcnt 4, leaving its stores in flight (vmcnt retires in order)
   bool st4 = false;
-#if LTHM_MLPF_STAMP
-  MLPF_T(tk0);
-  uint64_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int64_t tix = 0;
-#endif
   for (int64_t t0 = rs; t0 < re; t0 += TR) {
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform
@@ -1175,7 +753,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
     mlp_load_x<D, KS>(a.dY, rb + r32, rb + r32 < lim, h, df);
     const bool more_tiles = t0 + TR < re;
     for (int j = 0; j < NC; ++j, ++g) {
-      MLPF_T(ts0);
       if (st4) wait_vm<4>();
       else wait_vm<0>();
       st4 = false;
@@ -1187,7 +764,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
         mlp_dma32<D, NTH>(img[(g + 1) & 1][1], a.W2T + (int64_t)jn * 32 * D, tid);
       }
       if (!active) continue;
-      MLPF_T(ts1);
       const unsigned char* w1 = img[g & 1][0];
       const unsigned char* w2 = img[g & 1][1];
       f32x16 S = f32x16{}, dH = f32x16{};
@@ -1202,15 +778,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
         fb = nb;
         asm volatile("" ::: "memory");
       }
-#if LTHM_MLPF_STAMP
-      MLPF_T(ts2);
-      {
-        float dep = S[15] + dH[15];  // in-order issue: the stamp below waits for both chains
-        asm volatile("" : "+v"(dep));
-        asm volatile("" ::"v"(dep));
-      }
-      MLPF_T(ts3);
-#endif
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 8 * m + 4 * h);
@@ -1227,9 +794,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
       }
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
-#if LTHM_MLPF_STAMP
-      MLPF_T(ts4);
-#endif
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int rl = (lane >> 2) + 16 * q, pc = 8 * (lane & 3);
@@ -1242,123 +806,6 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
         }
       }
       st4 = full;  // every lane stored: exactly 4 store instructions issued
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("" ::: "memory");
-#if LTHM_MLPF_STAMP
-      MLPF_T(ts5);
-      if (tix > 0) {
-        st_acc[0] += ts1 - ts0;  // wait + barrier + DMA issue
-        st_acc[1] += ts2 - ts1;  // S / dH issue
-        st_acc[2] += ts3 - ts2;  // S / dH completion
-        st_acc[3] += ts4 - ts3;  // GELU' + strip writes
-        st_acc[4] += 1;
-        st_acc[5] += ts5 - ts4;  // strip reads + G / dP store issue
-      }
-#endif
-    }
-#if LTHM_MLPF_STAMP
-    ++tix;
-#endif
-  }
-#if LTHM_MLPF_STAMP
-  MLPF_T(tk);
-  st_acc[7] = tk - tk0;
-  if (lane == 0 && blockIdx.x < 2048)
-    for (int k = 0; k < 8; ++k) g_mlpf_stamps[(blockIdx.x * 8 + wave) * 8 + k] = st_acc[k];
-#endif
-}
-
-// mlp_bwdp_k at 4 waves with two workgroups per CU (round 6, as mlp_fwd2_k): 2-slot W1 / W2T ring
-// (64 KiB), one 2-KiB strip per wave that g and then dp pass through, b1 in dynamic LDS: 76 KiB
-// per workgroup, so a second workgroup's chunk loop runs beside one's tile edges and store bursts.
-template <int D>
-__global__ __launch_bounds__(256, 2) void mlp_bwdp2_k(MlpBwdArgs a) {
-  constexpr int NW = 4, NTH = 64 * NW, IMG = 32 * D * 2, KS = D / 16, TR = 32 * NW;
-  __shared__ __attribute__((aligned(16))) unsigned char img[2][2][IMG];  // [stage][W1_j, W2T_j]
-  __shared__ __attribute__((aligned(16))) bf16_t stb_all[NW][32 * 32];   // g, then dp, of the chunk
-  extern __shared__ float b1s[];                                          // [HID]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r32 = lane & 31, h = lane >> 5;
-  const int NC = a.HID / 32;
-  const int64_t rs = a.M * blockIdx.x / gridDim.x, re = a.M * (blockIdx.x + 1) / gridDim.x;
-  if (rs >= re) return;  // uniform
-  for (int i = tid; i < a.HID; i += NTH) b1s[i] = a.b1 ? a.b1[i] : 0.f;
-  bf16_t* stb = stb_all[wave];
-  retire_loads();
-  mlp_dma32<D, NTH>(img[0][0], a.W1, tid);
-  mlp_dma32<D, NTH>(img[0][1], a.W2T, tid);
-  __syncthreads();  // b1s
-  int g = 0;
-  for (int64_t t0 = rs; t0 < re; t0 += TR) {
-    const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
-    const bool active = rb < lim;  // wave-uniform
-    bf16x8m xf[KS], df[KS];
-    mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
-    mlp_load_x<D, KS>(a.dY, rb + r32, rb + r32 < lim, h, df);
-    const bool more_tiles = t0 + TR < re;
-    for (int j = 0; j < NC; ++j, ++g) {
-      wait_vm<0>();
-      __syncthreads();  // chunk j landed everywhere; every wave is done with chunk j - 1's stage
-      asm volatile("" ::: "memory");
-      if (j + 1 < NC || more_tiles) {
-        const int jn = j + 1 < NC ? j + 1 : 0;
-        mlp_dma32<D, NTH>(img[(g + 1) & 1][0], a.W1 + (int64_t)jn * 32 * D, tid);
-        mlp_dma32<D, NTH>(img[(g + 1) & 1][1], a.W2T + (int64_t)jn * 32 * D, tid);
-      }
-      if (!active) continue;
-      const unsigned char* w1 = img[g & 1][0];
-      const unsigned char* w2 = img[g & 1][1];
-      f32x16 S = f32x16{}, dH = f32x16{};
-      bf16x8m fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w2, lane, 0);
-#pragma unroll
-      for (int k = 0; k < KS; ++k) {
-        const int kn = k + 1 < KS ? k + 1 : k;
-        const bf16x8m na = mlp_row_frag<D>(w1, lane, kn), nb = mlp_row_frag<D>(w2, lane, kn);
-        S = mfma32(fa, xf[k], S);
-        dH = mfma32(fb, df[k], dH);
-        fa = na;
-        fb = nb;
-        asm volatile("" ::: "memory");
-      }
-      uint2 dpk[4];  // dp of the chunk, packed, until g has left the strip
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 8 * m + 4 * h);
-        float gv[4], dv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float gd;
-          gv[e] = gelu_tanh_and_grad(S[4 * m + e] + bb[e], gd);
-          dv[e] = dH[4 * m + e] * gd;
-        }
-        *reinterpret_cast<uint2*>(stb + r32 * 32 + 8 * (m ^ ((r32 >> 2) & 3)) + 4 * h) =
-            uint2{pack_bf16x2(gv[0], gv[1]), pack_bf16x2(gv[2], gv[3])};
-        dpk[m] = uint2{pack_bf16x2(dv[0], dv[1]), pack_bf16x2(dv[2], dv[3])};
-      }
-      // [32 tokens][32 units] bf16 out of the strip as 16-B row pieces: lane -> row l / 4 (+ 16), piece l % 4
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        bf16_t* dst = pass == 0 ? a.G : a.dP;
-        u32x4 v[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int rl = (lane >> 2) + 16 * q, pc = 8 * (lane & 3);
-          v[q] = *reinterpret_cast<const u32x4*>(stb + rl * 32 + (pc ^ (8 * ((rl >> 2) & 3))));
-        }
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("" ::: "memory");
-        if (pass == 0) {
-#pragma unroll
-          for (int m = 0; m < 4; ++m) *reinterpret_cast<uint2*>(stb + r32 * 32 + 8 * (m ^ ((r32 >> 2) & 3)) + 4 * h) = dpk[m];
-        }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int rl = (lane >> 2) + 16 * q, pc = 8 * (lane & 3);
-          const int64_t row = rb + rl;
-          if (row < lim) *reinterpret_cast<u32x4*>(dst + row * a.HID + 32 * j + pc) = v[q];
-        }
-      }
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
     }
@@ -1609,23 +1056,6 @@ static int mlp_cu_count() {
   return cus;
 }
 
-// waves per forward workgroup: 8 (one workgroup per CU, 256-row tiles) or 4 (two per CU);
-// LTHM_MLP_NW overrides (measurement)
-static int mlp_fwd_waves() {
-  static int nw = 0;
-  if (nw == 0) {
-    const char* e = getenv("LTHM_MLP_NW");
-    nw = (e && e[0] == '4') ? 4 : 8;
-  }
-  return nw;
-}
-
-#if LTHM_MLPF_STAMP
-extern "C" int lthm_debug_mlpf_stamps(unsigned long long* host, int64_t n) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mlpf_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
-
 extern "C" int lthm_mlp_supported(int32_t D, int32_t HID) {
   return (D == 128 || D == 256) && HID >= 32 && HID % 32 == 0 && HID <= 8192;
 }
@@ -1669,54 +1099,12 @@ static int mlp_fwd_launch(MlpArgs a, int D, void* stream) {
   const int HID = a.HID;
   hipStream_t s = (hipStream_t)stream;
   const size_t dyn = (size_t)(HID + 3 * D) * 4;
-  const int nw = mlp_fwd_waves();
-  a.ntiles = (int)((M + 32 * nw - 1) / (32 * nw));
-  const int per_cu = 1;
-  int grid = std::min<int64_t>(a.ntiles, (int64_t)mlp_cu_count() * per_cu);
-  // LTHM_MLP_PIPE=1: the software-pipelined one-wave-per-SIMD form (no ln_2 prologue)
-  static const bool pipe = getenv("LTHM_MLP_PIPE") && getenv("LTHM_MLP_PIPE")[0] == '1';
-  if (pipe && !a.ln_w && M * D < ((int64_t)1 << 29)) {
-    a.ntiles = (int)((M + 127) / 128);
-    const int gp = std::min<int64_t>(a.ntiles, (int64_t)mlp_cu_count());
-    const size_t dynp = (size_t)(HID + D) * 4;
-    if (!a.res1 && a.res2) std::swap(a.res1, a.res2);
-    const int nres = a.res2 ? 2 : a.res1 ? 1 : 0;
-#define LTHM_MLPP(D_)                                                                                      \
-    if (nres == 2) hipLaunchKernelGGL((mlp_fwd_pipe_k<D_, 2>), dim3(gp), dim3(256), dynp, s, a);           \
-    else if (nres == 1) hipLaunchKernelGGL((mlp_fwd_pipe_k<D_, 1>), dim3(gp), dim3(256), dynp, s, a);      \
-    else hipLaunchKernelGGL((mlp_fwd_pipe_k<D_, 0>), dim3(gp), dim3(256), dynp, s, a);
-    if (D == 256) { LTHM_MLPP(256) } else { LTHM_MLPP(128) }
-#undef LTHM_MLPP
-    LTHM_CHECK_LAUNCH();
-    return 0;
-  }
-  // two 4-wave workgroups per CU (mlp_fwd2_k; LTHM_MLP_FWD2=1: on), no ln_2 prologue
-  static const bool fwd2 = getenv("LTHM_MLP_FWD2") && getenv("LTHM_MLP_FWD2")[0] == '1';
-  if (fwd2 && !a.ln_w) {
-    a.ntiles = (int)((M + 127) / 128);
-    const int g2 = std::min<int64_t>(a.ntiles, (int64_t)mlp_cu_count() * 2);
-    const size_t dyn2 = (size_t)(HID + D) * 4;
-    if (!a.res1 && a.res2) std::swap(a.res1, a.res2);
-    const int nres = a.res2 ? 2 : a.res1 ? 1 : 0;
-#define LTHM_MLPF2(D_)                                                                                     \
-    if (nres == 2) hipLaunchKernelGGL((mlp_fwd2_k<D_, 2>), dim3(g2), dim3(256), dyn2, s, a);               \
-    else if (nres == 1) hipLaunchKernelGGL((mlp_fwd2_k<D_, 1>), dim3(g2), dim3(256), dyn2, s, a);          \
-    else hipLaunchKernelGGL((mlp_fwd2_k<D_, 0>), dim3(g2), dim3(256), dyn2, s, a);
-    if (D == 256) { LTHM_MLPF2(256) } else { LTHM_MLPF2(128) }
-#undef LTHM_MLPF2
-    LTHM_CHECK_LAUNCH();
-    return 0;
-  }
-  // LTHM_MLP_STAG=1: the 8-wave form with the half-chunk lag of waves 4-7 (A/B)
-  static const bool stag = getenv("LTHM_MLP_STAG") && getenv("LTHM_MLP_STAG")[0] == '1';
-#define LTHM_MLPF(D_, NW_)                                                                                 \
-  do {                                                                                                     \
-    if (stag && NW_ == 8) hipLaunchKernelGGL((mlp_fwd_k<D_, NW_, true>), dim3(grid), dim3(64 * NW_), dyn, s, a); \
-    else hipLaunchKernelGGL((mlp_fwd_k<D_, NW_, false>), dim3(grid), dim3(64 * NW_), dyn, s, a);          \
-  } while (0)
-  if (D == 256) { if (nw == 8) LTHM_MLPF(256, 8); else LTHM_MLPF(256, 4); }
-  else { if (nw == 8) LTHM_MLPF(128, 8); else LTHM_MLPF(128, 4); }
-#undef LTHM_MLPF
+  // 8 waves: one workgroup per CU, 256-row tiles
+  constexpr int NW = 8;
+  a.ntiles = (int)((M + 32 * NW - 1) / (32 * NW));
+  const int grid = (int)std::min<int64_t>(a.ntiles, (int64_t)mlp_cu_count());
+  if (D == 256) hipLaunchKernelGGL((mlp_fwd_k<256, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
+  else hipLaunchKernelGGL((mlp_fwd_k<128, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
   LTHM_CHECK_LAUNCH();
   return 0;
 }
@@ -1840,16 +1228,6 @@ extern "C" int lthm_mlp_bwd_hidden(const void* X, const void* dY, int64_t M, int
   a.b1 = b1; a.G = (bf16_t*)G; a.dP = (bf16_t*)dP;
   a.M = M; a.HID = HID;
   hipStream_t s = (hipStream_t)stream;
-  // two 4-wave workgroups per CU (mlp_bwdp2_k; LTHM_MLP_BWDP2=1: on)
-  static const bool p2 = getenv("LTHM_MLP_BWDP2") && getenv("LTHM_MLP_BWDP2")[0] == '1';
-  if (p2) {
-    const int64_t nt2 = (M + 127) / 128;
-    const int g2 = (int)std::min<int64_t>(nt2, (int64_t)mlp_cu_count() * 2);
-    if (D == 256) hipLaunchKernelGGL((mlp_bwdp2_k<256>), dim3(g2), dim3(256), (size_t)HID * 4, s, a);
-    else hipLaunchKernelGGL((mlp_bwdp2_k<128>), dim3(g2), dim3(256), (size_t)HID * 4, s, a);
-    LTHM_CHECK_LAUNCH();
-    return 0;
-  }
   constexpr int NW = 8;
   const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
   const int grid = (int)std::min<int64_t>(ntiles, (int64_t)mlp_cu_count());

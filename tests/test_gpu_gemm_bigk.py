@@ -1,5 +1,5 @@
-"""GPU parity of the 256 x 256 big-K GEMM (csrc/gemm.hip gemm_bt_k: both operands K-contiguous,
-K > 256, M >= 4096, N >= 512 -- the ranker MLPs and the C5 encoder forms) against the fp32
+"""GPU parity of the big-K GEMM forms (csrc/gemm.hip gemm_pp_k and the kernels it falls back to: both
+operands K-contiguous, K > 256, M >= 4096, N >= 512 -- the ranker MLPs and the C5 encoder forms) against the fp32
 oracle on the SAME bf16 operands: every epilogue form the layer code uses (bias + QuickGELU /
 GELU with the pre-activation store, the activation-gradient multiply, the residual add) and
 ragged M / N / K edges.  Bound: 1e-5 relative Frobenius for f32 outputs (fp32 accumulation in

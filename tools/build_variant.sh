@@ -8,7 +8,6 @@ cd "$(dirname "$0")/.."
 NAME=$1; SRC=$2; EXTRA=$3
 C=recommendations_amd/csrc
 base=$(basename "$SRC" .hip)
-base=${base%%_*}   # loss_3loop.hip replaces loss.o
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Werror=shadow -Wno-unused-function -Wno-unused-variable -Wno-unused-result -munsafe-fp-atomics -I$C"
 [ "$base" = loss ] && FLAGS="$FLAGS -fno-slp-vectorize"
 mkdir -p $C/build/var

@@ -47,7 +47,7 @@ def main():
     res = torch.randn(M, D, device=dev, generator=g)
     fl = 4.0 * M * D * HID
     pre = torch.empty(M, HID, dtype=bf, device=dev)
-    out = {"M": M, "D": D, "HID": HID, "nw": os.environ.get("LTHM_MLP_NW", "8")}
+    out = {"M": M, "D": D, "HID": HID}
 
     def unfused():
         h = K.linear_fwd(x, w1, b1, act=K.ACT_GELU_D, aux_out=pre)
