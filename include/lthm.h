@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define LTHM_ABI_VERSION 43 /* bumped on any signature / struct layout change */
+#define LTHM_ABI_VERSION 44 /* bumped on any signature / struct layout change */
 
 #define LTHM_F32 0
 #define LTHM_BF16 1
@@ -807,6 +807,47 @@ int lthm_logq_stream(const int64_t* ids, int64_t ids_stride, const uint8_t* mask
 int lthm_trim_stats(const uint8_t* mask, int64_t B, int32_t T, int32_t* work, void* stream);
 /* y = act(x) (dy == NULL) or y = dy * act'(x); act = LTHM_ACT_GELU / LTHM_ACT_QGELU */
 int lthm_activation(const void* x, const void* dy, void* y, int32_t dtype, int64_t n, int32_t act, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Full-catalogue top-K retrieval (csrc/retrieve.hip)                        */
+/* ------------------------------------------------------------------------- */
+/* The two-tower model's use: next_token_emb[:, t, head] is a query, the product tower's
+ * prod_emb a candidate (wrapper.py:114-119 normalises both for the loss).  For every query
+ * the k catalogue rows with the largest dot product, sorted by (score descending, row
+ * ascending), without a [Q, N] score buffer.
+ *   items         bf16 [N, 128], row-major, already normalised; 1 <= N < 2^31
+ *   q             f32 / bf16 [Q, 128]; with normalize_q each row goes through F.normalize
+ *                 (eps 1e-12) first and is rounded to bf16 as lthm_rownorm does
+ *   target_row    int32 [Q] or NULL: a catalogue row per query, or -1 (rows outside [0, N)
+ *                 count as -1)
+ *   scores, rows  f32 / int32 [Q, k], k in 1..128; where N < k the tail is -inf / -1
+ *   rank          int32 [Q] (with target_row): #{j != target : s[q, j] > s[q, target]}, the
+ *                 strict-greater count of the in-batch hit position; -1 without a target
+ *   target_score  f32 [Q] (with target_row): the f32 dot of the two bf16 rows (-inf without)
+ *   slab_rows     catalogue rows per block of the scoring kernel: a multiple of 64, or 0 for
+ *                 the size the call derives from Q and N
+ *   workspace     lthm_retrieve_ws_bytes(Q, N, k, slab_rows) bytes, 16-byte aligned
+ * items and q must be 16-byte aligned.  The outputs are a pure function of the inputs. */
+typedef struct lthm_retrieve_desc {
+  const void* items;
+  const void* q;
+  const int32_t* target_row;
+  float* scores;
+  int32_t* rows;
+  int32_t* rank;
+  float* target_score;
+  void* workspace;
+  int64_t ws_bytes;
+  int64_t Q;
+  int64_t N;
+  int32_t k;
+  int32_t q_dtype;
+  int32_t normalize_q;
+  int32_t slab_rows;
+} lthm_retrieve_desc;
+/* workspace bytes of lthm_retrieve_topk, or -1 for sizes it refuses */
+int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows);
+int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -1,0 +1,399 @@
+// Full-catalogue top-K retrieval for the LTHM towers, for gfx950.
+//
+//   scores[q, :k], rows[q, :k] = the k best items of  s[q, j] = qn[q] . items[j]
+// under the total order (score descending, row ascending), with no [Q, N] buffer:
+//   retr_prep_k   queries -> bf16 (optionally through F.normalize, as rownorm_v8_k does for the
+//                 loss), and target_score[q] = qn[q] . items[target_row[q]] as a plain f32 dot;
+//   retr_topk_k   grid (query tiles of 64) x (catalogue slabs): the block keeps its queries as
+//                 MFMA B fragments, streams the slab's item rows through two LDS images and
+//                 keeps, per query, the candidates that pass a threshold filter (below);
+//   retr_merge_k  one wave per query merges the slabs' sorted k-lists and sums their counts.
+// A candidate travels as one 64-bit key: the score's order-preserving integer image in the
+// high word, ~row in the low word, so that "a precedes b" in the total order is key_a > key_b
+// and the key 0 is free to mean "empty".  Selection never depends on the order in which the
+// LDS atomics hand out slots (a prune writes each key at its rank), so the result is a pure
+// function of the inputs.  No global atomics anywhere.
+#include "common.hpp"
+
+#include <cmath>
+
+namespace lthm {
+namespace {
+
+typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
+typedef unsigned long long u64;
+
+constexpr int RT_D = 128;     // LOSS_DE: the one embedding width
+constexpr int RT_QT = 64;     // queries per block (two waves of 32 MFMA columns)
+constexpr int RT_IT = 64;     // item rows per LDS image (two waves of 32 MFMA rows)
+constexpr int RT_KMAX = 128;  // largest k
+constexpr int RT_CAP = 192;   // candidate slots per query
+constexpr int RT_LIM = RT_CAP - RT_IT;  // a query's count at the start of every tile is <= RT_LIM
+// The selection invariant: a prune leaves at most k <= RT_KMAX candidates, a tile appends at
+// most RT_IT per query (one per item row), and a query is pruned before the next tile
+// whenever its count is above RT_LIM.  So no append can run past the buffer.
+static_assert(RT_KMAX <= RT_LIM, "a pruned buffer must have a whole item tile of free slots");
+static_assert(RT_LIM + RT_IT <= RT_CAP, "a tile's appends must fit behind the limit");
+
+struct RetrShared {
+  unsigned char img[2][RT_IT * 256];
+  u64 cand[RT_QT][RT_CAP];
+  float tau[RT_QT];  // current k-th best score of the query (-inf until k candidates are held)
+  int cnt[RT_QT];    // candidates held
+  int pc[RT_QT];     // #{rows of the slab scoring above the target}
+  int flag[3];       // flag[i % 3]: tile i pushed some query past RT_LIM
+};
+static_assert(sizeof(RetrShared) <= 160 * 1024, "LDS budget");
+
+__device__ __attribute__((aligned(16))) unsigned char retr_zero_row[256];
+
+// the 32x32x16 tile engine's image (as loss.hip): chunk ch of row r at slot ch ^ swz32(r)
+__device__ __forceinline__ int swz32(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
+__device__ __forceinline__ int ko32(int row, int ch) { return row * 256 + ((ch ^ swz32(row)) << 4); }
+
+__device__ __forceinline__ u64 retr_key(float s, int row) {
+  uint32_t u = __float_as_uint(s + 0.f);  // -0 -> +0: equal scores get equal images
+  u ^= (uint32_t)((int32_t)u >> 31) | 0x80000000u;
+  return ((u64)u << 32) | (uint32_t)~row;
+}
+__device__ __forceinline__ float retr_key_score(u64 key) {
+  const uint32_t o = (uint32_t)(key >> 32);
+  return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu));
+}
+__device__ __forceinline__ int retr_key_row(u64 key) { return (int)~(uint32_t)key; }
+
+// One wave sorts buf[0, n) (distinct keys, n <= 64 PL) descending and keeps the first k:
+// every key is written at its rank, the number of keys above it.  Returns min(n, k).
+template <int PL>
+__device__ __forceinline__ int retr_prune(u64* buf, int n, int k, int lane) {
+  u64 key[PL];
+  int rk[PL];
+#pragma unroll
+  for (int j = 0; j < PL; ++j) {
+    const int idx = lane + 64 * j;
+    key[j] = idx < n ? buf[idx] : 0ull;
+    rk[j] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    const u64 kk = buf[i];
+#pragma unroll
+    for (int j = 0; j < PL; ++j) rk[j] += kk > key[j] ? 1 : 0;
+  }
+  // a wave's LDS accesses complete in order: every read above precedes these writes
+#pragma unroll
+  for (int j = 0; j < PL; ++j)
+    if (lane + 64 * j < n && rk[j] < k) buf[rk[j]] = key[j];
+  return n < k ? n : k;
+}
+
+struct RetrArgs {
+  const bf16_t* items;  // [N, 128]
+  const bf16_t* qn;     // [Q, 128] queries as the MFMA reads them
+  const int* trow;      // [Q] or null
+  const float* tscore;  // [Q] (with trow)
+  u64* keys;            // [nslab, Q, k]
+  int* pcnt;            // [nslab, Q]
+  int64_t Q, N, slab_rows;
+  int k;
+};
+
+// ---------------------------------------------------------------- queries -> bf16, target score
+// 16 lanes per query, 8 contiguous elements per lane (rownorm_v8_k's arithmetic for D = 128)
+template <typename TQ>
+__global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int64_t Q, int normalize,
+                                                   bf16_t* __restrict__ qn, const bf16_t* __restrict__ items,
+                                                   int64_t N, const int* __restrict__ trow,
+                                                   float* __restrict__ tscore) {
+  const int sub = threadIdx.x & 15;
+  const int64_t r0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+  const bool in = r0 < Q;
+  const int64_t r = in ? r0 : Q - 1;  // every lane takes part in the group sums
+  float v[8];
+  if constexpr (sizeof(TQ) == 2) {
+    load_vec<TQ, 16>(q + r * RT_D + 8 * sub, v);
+  } else {
+    load_vec<TQ, 16>(q + r * RT_D + 8 * sub, v);
+    load_vec<TQ, 16>(q + r * RT_D + 8 * sub + 4, v + 4);
+  }
+  if (normalize) {
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ss += v[i] * v[i];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+    const float den = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = v[i] / den;
+  }
+  u32x4 w;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
+  if (in) *reinterpret_cast<u32x4*>(qn + r * RT_D + 8 * sub) = w;
+  if (trow) {
+    const int tr = trow[r];
+    const bool ok = tr >= 0 && tr < N;
+    float it[8];
+    load_vec<bf16_t, 16>(items + (int64_t)(ok ? tr : 0) * RT_D + 8 * sub, it);
+    float dot = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dot = __builtin_fmaf(__uint_as_float(w[i] << 16), it[2 * i], dot);
+      dot = __builtin_fmaf(__uint_as_float(w[i] & 0xffff0000u), it[2 * i + 1], dot);
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+    if (in && sub == 0) tscore[r] = ok ? dot : -INFINITY;
+  }
+}
+
+// ---------------------------------------------------------------- scores + threshold selection
+// Wave w: queries 32 (w & 1) + (lane & 31) of the tile (MFMA columns, so every per-query value
+// is a per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3).
+__global__ __launch_bounds__(256) void retr_topk_k(RetrArgs a) {
+  __shared__ __attribute__((aligned(16))) RetrShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
+  const int slab = blockIdx.y;
+  const int64_t row_lo = (int64_t)slab * a.slab_rows;
+  const int64_t row_hi = row_lo + a.slab_rows < a.N ? row_lo + a.slab_rows : a.N;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const int64_t q = q0 + ql;
+  const bool live = q < a.Q;
+
+  if (tid < RT_QT) {
+    sh.tau[tid] = q0 + tid < a.Q ? -INFINITY : INFINITY;  // a query past Q never passes the filter
+    sh.cnt[tid] = 0;
+    sh.pc[tid] = 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  {
+    const bf16_t* rp = a.qn + (live ? q : 0) * RT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live) v = *reinterpret_cast<const u32x4*>(rp + 16 * s + 8 * hh);
+      qf[s] = __builtin_bit_cast(bf16x8v, v);
+    }
+  }
+  int tr = -1;
+  float ts = INFINITY;  // no target: nothing counts
+  if (live && a.trow) {
+    tr = a.trow[q];
+    if (tr >= 0 && tr < a.N) ts = a.tscore[q];
+    else tr = -1;
+  }
+  int roff[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
+
+  // wave w stages rows 16 w .. 16 w + 15 of an image with four DMAs of 4 rows x 256 B (lane l:
+  // row 16 w + 4 j + l / 16, slot l % 16, source chunk slot ^ swz32(row)); rows at or past
+  // row_hi come from the zero row
+  const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 4 * j;
+      const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 15));
+      glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+  };
+  retire_loads();
+  stage(0);
+  int above = 0;
+  for (int i = 0; i < ntile; ++i) {
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;  // last read in tile i - 1, next set in tile i + 1
+    if (sh.flag[(i + 2) % 3]) {              // tile i - 1 pushed a query past the limit
+      for (int pq = w; pq < RT_QT; pq += 4) {
+        const int n = sh.cnt[pq];
+        if (n > RT_LIM) {
+          const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], n, a.k, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.cand[pq][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const bf16x8v af = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + roff[s]));
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[s], acc, 0, 0, 0);
+    }
+    // first catalogue row of this lane's elements: element v is row rb + 8 (v >> 2) + (v & 3)
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {  // partial tile: the rows past the slab never count or pass
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      above += acc[v] > ts ? 1 : 0;
+      mx = fmaxf(mx, acc[v]);
+    }
+    const int64_t rel = (int64_t)tr - rb;
+    if (tr >= 0 && rel >= 0 && rel < 32 && !(rel & 4)) {  // the target's own row is not counted
+      const int vt = (int)(((rel >> 3) << 2) | (rel & 3));
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (v == vt && acc[v] > ts) --above;
+    }
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (slot < RT_CAP) sh.cand[ql][slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RT_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  above += __shfl_xor(above, 32, 64);
+  if (hh == 0 && live && above) atomicAdd(&sh.pc[ql], above);
+  __syncthreads();
+  // the slab's k best of every query, sorted; empty slots are key 0
+  for (int pq = w; pq < RT_QT; pq += 4) {
+    if (q0 + pq >= a.Q) break;
+    const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], sh.cnt[pq], a.k, lane);
+    u64* out = a.keys + ((int64_t)slab * a.Q + q0 + pq) * a.k;
+    for (int idx = lane; idx < a.k; idx += 64) out[idx] = idx < m ? sh.cand[pq][idx] : 0ull;
+  }
+  if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+}
+
+// ---------------------------------------------------------------- merge of the slabs' k-lists
+// One wave per query; the lists are sorted and hold their empty slots (key 0) at the end.
+__global__ __launch_bounds__(256) void retr_merge_k(const u64* __restrict__ keys, const int* __restrict__ pcnt,
+                                                    const int* __restrict__ trow, int64_t Q, int64_t N, int nslab,
+                                                    int k, float* __restrict__ scores, int* __restrict__ rows,
+                                                    int* __restrict__ rank) {
+  __shared__ u64 sbuf[4][2 * RT_KMAX];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t q = (int64_t)blockIdx.x * 4 + w;
+  if (q >= Q) return;  // whole waves; no block barrier below
+  u64* buf = sbuf[w];
+  int n = 0;
+  for (int s = 0; s < nslab; ++s) {
+    const u64* src = keys + ((int64_t)s * Q + q) * k;
+    if (n == k && src[0] < buf[k - 1]) continue;  // nothing in this list reaches the k best
+    int v = 0;
+    for (int idx = lane; idx < 64 * ((k + 63) / 64); idx += 64) {
+      const u64 key = idx < k ? src[idx] : 0ull;
+      if (key) buf[n + idx] = key;
+      v += __popcll(__ballot(key != 0ull));
+    }
+    n = retr_prune<2 * RT_KMAX / 64>(buf, n + v, k, lane);
+  }
+  for (int idx = lane; idx < k; idx += 64) {
+    const bool has = idx < n;
+    const u64 key = has ? buf[idx] : 0ull;
+    scores[q * k + idx] = has ? retr_key_score(key) : -INFINITY;
+    rows[q * k + idx] = has ? retr_key_row(key) : -1;
+  }
+  if (rank) {
+    const int tr = trow[q];
+    int c = 0;
+    for (int s = lane; s < nslab; s += 64) c += pcnt[(int64_t)s * Q + q];  // integers: any order, one sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) rank[q] = (tr >= 0 && tr < N) ? c : -1;
+  }
+}
+
+constexpr int64_t RETR_MAX_SLABS = 65535;  // grid.y
+
+// rows per slab (a multiple of the item tile), or -1 for sizes the kernels do not take
+int64_t retr_slab_rows(int64_t Q, int64_t N, int k, int64_t slab_rows) {
+  if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || k < 1 || k > RT_KMAX) return -1;
+  int64_t sr = slab_rows;
+  if (sr == 0) {
+    // one block per CU: with few query tiles (serving) the catalogue is cut into enough slabs
+    // to fill 256 CUs; with many (evaluation) into few long ones, which prune and merge less
+    const int64_t nqt = (Q + RT_QT - 1) / RT_QT;
+    const int64_t want = nqt >= 256 ? 1 : (256 + nqt - 1) / nqt;
+    sr = (N + want - 1) / want;
+    if (sr < 1024) sr = 1024;
+    sr = (sr + RT_IT - 1) / RT_IT * RT_IT;
+  }
+  if (sr < RT_IT || sr % RT_IT != 0) return -1;
+  if ((N + sr - 1) / sr > RETR_MAX_SLABS) return -1;
+  return sr;
+}
+
+inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
+
+}  // namespace
+}  // namespace lthm
+
+using namespace lthm;
+
+extern "C" int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows) {
+  if (slab_rows < 0) return -1;
+  const int64_t sr = retr_slab_rows(Q, N, k, slab_rows);
+  if (sr < 0) return -1;
+  const int64_t nslab = (N + sr - 1) / sr;
+  return up256(Q * RT_D * 2) + up256(nslab * Q * k * 8) + up256(nslab * Q * 4);
+}
+
+extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
+  LTHM_REQUIRE(d != nullptr);
+  LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
+  LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
+  LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
+  const int64_t need = lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
+  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
+  const int64_t Q = d->Q, N = d->N;
+  const int64_t sr = retr_slab_rows(Q, N, d->k, d->slab_rows);
+  const int64_t nslab = (N + sr - 1) / sr;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)d->workspace;
+  bf16_t* qn = (bf16_t*)ws;
+  u64* keys = (u64*)(ws + up256(Q * RT_D * 2));
+  int* pcnt = (int*)(ws + up256(Q * RT_D * 2) + up256(nslab * Q * d->k * 8));
+  const bf16_t* items = (const bf16_t*)d->items;
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  if (d->q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, Q, d->normalize_q, qn,
+                       items, N, d->target_row, d->target_score);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, Q, d->normalize_q, qn,
+                       items, N, d->target_row, d->target_score);
+  LTHM_CHECK_LAUNCH();
+  RetrArgs a;
+  a.items = items;
+  a.qn = qn;
+  a.trow = d->target_row;
+  a.tscore = d->target_score;
+  a.keys = keys;
+  a.pcnt = pcnt;
+  a.Q = Q;
+  a.N = N;
+  a.slab_rows = sr;
+  a.k = d->k;
+  hipLaunchKernelGGL(retr_topk_k, dim3((unsigned)((Q + RT_QT - 1) / RT_QT), (unsigned)nslab), dim3(256), 0, s, a);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, Q, N,
+                     (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}

@@ -16,10 +16,12 @@
 //   lthm::mlp_chain     MLP + QuickGELU             commons/layers.py:65-81 (+ backward)
 //   lthm::activation    QuickGELU / GELU(tanh)      commons/layers.py:9-11 (+ backward)
 //   lthm::item_artifact ModelWrapper.forward        embedding_module_gen.py:32-41 (fused)
+//   lthm::retrieve_topk full-catalogue top-K        (build-defined, csrc/retrieve.hip; forward only)
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
 
+#include <tuple>
 #include <vector>
 
 #include "../../../include/lthm.h"
@@ -407,6 +409,38 @@ Tensor item_artifact_cuda(const Tensor& ids_, const Tensor& W, int64_t K, int64_
   return out;
 }
 
+// ---------------------------------------------------------------- full-catalogue top-K (forward only)
+std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q) {
+  on_gpu(q_, "q");
+  on_gpu(items_, "items");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
+              "items must be a bf16 [N, 128] catalogue");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128, "q must be [Q, 128]");
+  TORCH_CHECK(k >= 1 && k <= 128, "k must be in 1..128, got ", k);
+  TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk takes a non-empty catalogue and query set");
+  auto q = q_.contiguous(), items = items_.contiguous();
+  const int64_t Q = q.size(0), N = items.size(0);
+  const int64_t need = lthm_retrieve_ws_bytes(Q, N, (int32_t)k, 0);
+  TORCH_CHECK(need >= 0, "retrieve_topk: unsupported sizes Q=", Q, " N=", N);
+  auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
+  auto rows = at::empty({Q, k}, q.options().dtype(at::kInt));
+  auto ws = at::empty({need}, q.options().dtype(at::kByte));
+  lthm_retrieve_desc d = {};
+  d.items = items.data_ptr();
+  d.q = q.data_ptr();
+  d.scores = scores.data_ptr<float>();
+  d.rows = rows.data_ptr<int32_t>();
+  d.workspace = ws.data_ptr();
+  d.ws_bytes = need;
+  d.Q = Q;
+  d.N = N;
+  d.k = (int32_t)k;
+  d.q_dtype = dcode(q);
+  d.normalize_q = normalize_q ? 1 : 0;
+  hip_ok(lthm_retrieve_topk(&d, cur_stream()), "lthm_retrieve_topk");
+  return std::make_tuple(scores, rows);
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -424,6 +458,7 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "item_artifact(Tensor ids, Tensor weight, int K, int mode, Tensor mask_weight, int mask_K, Tensor w1, "
       "Tensor b1, Tensor w2, Tensor b2, ScalarType out_dtype=float) -> Tensor");
+  m.def("retrieve_topk(Tensor q, Tensor items, int k, bool normalize_q) -> (Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -433,6 +468,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("mlp_chain", &mlp_chain_cuda);
   m.impl("activation", &activation_cuda);
   m.impl("item_artifact", &item_artifact_cuda);
+  m.impl("retrieve_topk", &retrieve_topk_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

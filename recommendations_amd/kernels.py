@@ -1644,3 +1644,47 @@ class MSELossFn(torch.autograd.Function):
 
 def mse_loss(y, x):
     return MSELossFn.apply(y, x)
+
+
+# ----------------------------------------------------------------- full-catalogue retrieval
+RETRIEVE_WIDTH = 128          # csrc/retrieve.hip RT_D (= the loss kernels' LOSS_DE)
+RETRIEVE_MAX_K = 128          # RT_KMAX
+RETRIEVE_MIN_SLAB_ROWS = 64   # RT_IT: the smallest (and the granularity of) slab_rows
+
+
+def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0):
+    """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
+
+    q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
+    Returns (scores f32 [Q, k], rows int32 [Q, k], rank int32 [Q] | None, target_score f32 [Q] |
+    None), each query's entries sorted by (score descending, row ascending) and padded with
+    -inf / -1 where N < k.  Forward only; no [Q, N] buffer is formed."""
+    import ctypes
+    from ._lib import STRUCTS
+    require_gpu(q, items, target_rows)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"retrieve_topk takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"retrieve_topk takes [Q, {RETRIEVE_WIDTH}] queries")
+    Q, N, k = q.shape[0], items.shape[0], int(k)
+    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    _check(N >= 1 and Q >= 1, f"retrieve_topk takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    need = load().lthm_retrieve_ws_bytes(Q, N, k, int(slab_rows))
+    _check(need >= 0, f"retrieve_topk: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
+                      f"that cuts N={N} into at most 65535 slabs")
+    dev = q.device
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    rank = tscore = None
+    if target_rows is not None:
+        _check(target_rows.dtype == torch.int32 and target_rows.shape == (Q,), "target_rows must be int32 [Q]")
+        rank = torch.empty(Q, dtype=torch.int32, device=dev)
+        tscore = torch.empty(Q, dtype=torch.float32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    d = STRUCTS["lthm_retrieve_desc"]()
+    d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
+    d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
+    d.workspace, d.ws_bytes = ptr(ws), need
+    d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = Q, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
+    call("lthm_retrieve_topk", ctypes.addressof(d), stream(), _key="retr_topk_k", _work=2.0 * Q * N * RETRIEVE_WIDTH,
+         _unit="flop", _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8))
+    return scores, rows, rank, tscore

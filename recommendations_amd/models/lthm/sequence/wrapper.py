@@ -344,6 +344,50 @@ class LTHMModelWrapper(BaseModelWrapper):
         stats, offs, step_type, B, T, mbs, whole = self.last_stats
         return lthm_metrics(stats.cpu().numpy(), offs, step_type, self._metrics_k_all, B, T, mbs, whole)
 
+    @torch.no_grad()
+    def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0) -> Dict[str, torch.Tensor]:
+        """The k best catalogue items for each sequence's next event (build-defined; see
+        retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
+        most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
+        f32 [B, k], sorted by (score descending, catalogue row ascending)."""
+        y = self.forward(batch)["next_token_emb"]
+        q = y[:, -1, head].contiguous()
+        if q.dtype not in (torch.float32, torch.bfloat16):
+            q = q.float()
+        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True)
+        return {"item_ids": item_ids, "scores": scores}
+
+    @torch.no_grad()
+    def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0) -> Dict[str, float]:
+        """Hit rate and hit position of one forward against the whole catalogue: the in-batch
+        metrics of wrapper.py:228-238 with every catalogue item as a negative.  Queries are the
+        positions t whose target ``current_token_ids[:, t + lookahead[head]]`` is a non-pad
+        token (wrapper.py:155-163) the catalogue holds; the hit position is the number of items
+        scoring strictly above the target."""
+        ks = list(self._metrics_k_all if ks is None else ks)
+        y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
+        off = int(self._lookahead[head])
+        L = ids.shape[1] - off
+        res: Dict[str, float] = {"catalogue_queries": 0}
+        if L <= 0:
+            return res
+        rows = catalogue.rows_of(ids[:, off:])
+        keep = (mask[:, off:] == 0) & (rows >= 0)
+        n = int(keep.sum())
+        if n == 0:
+            return res
+        q = y[:, :L, head][keep].contiguous()
+        if q.dtype not in (torch.float32, torch.bfloat16):
+            q = q.float()
+        _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=rows[keep].contiguous())
+        pos = rank.float()
+        res["catalogue_queries"] = n
+        for k in ks:
+            res[f"hit_rate_at_{k}_catalogue"] = float((rank < k).float().mean())
+        res["average_hit_position_catalogue"] = float(pos.mean())
+        res["median_hit_position_catalogue"] = float(pos.quantile(q=0.5))
+        return res
+
     def is_sparse(self, param_name: str):
         return super().is_sparse(param_name) or "user_context.tables" in param_name
 

@@ -1,0 +1,124 @@
+"""Full-catalogue retrieval benchmark: K.retrieve_topk against the torch baseline
+``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
+
+    python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000]
+
+Each shape runs in a child process of its own (checked exit status, time limit); a failed
+shape stops the run.  One JSON line per shape:
+  fused_ms / base_ms      median device time of one call (HIP events; the fused call is its
+                          three launches: prep, scores + selection, merge), with min / max
+  *_floor_frac            the least time the hardware could take over the measured time, the
+                          floor being max(catalogue + query + output bytes / 8.0 TB/s,
+                          2 Q N 128 flop / 2.5 Pflop/s); ``bound`` names the larger term
+  speedup, speedup_lo     base / fused on the medians, and on the worst pairing (base min /
+                          fused max): faster only if speedup_lo > 1
+  check_rows_equal        the fused rows of the first queries equal an f32 torch top-k's
+The two paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
+(baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
+"""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+HBM_PEAK = 8.0e12     # B/s, spec
+MFMA_PEAK = 2.5e15    # bf16 flop/s, dense, spec
+SHAPES = {"serving": 256, "evaluation": 4096}
+BASE_CHUNK = 256      # baseline queries per matmul: a [256, N] f32 score matrix is 2 GB at N = 2M
+
+
+def child(name: str, N: int, k: int, reps: int) -> None:
+    import torch
+    from recommendations_amd import kernels as K
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):  # normalised random rows, built in pieces
+        x = torch.randn((min(1 << 18, N - lo), 128), generator=g, device=dev)
+        items[lo:lo + x.shape[0]] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    q = torch.nn.functional.normalize(torch.randn((Q, 128), generator=g, device=dev), dim=-1)
+    q_bf = q.to(torch.bfloat16)
+
+    def fused():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False)
+
+    def base():
+        out = []
+        for lo in range(0, Q, BASE_CHUNK):
+            out.append((q_bf[lo:lo + BASE_CHUNK] @ items.T).float().topk(k))
+        return out
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    nb = max(3, reps // 4) if name == "evaluation" else reps  # the chunked baseline is long
+    for _ in range(2):
+        fused()
+        base()
+    torch.cuda.synchronize()
+    tf, tb = [], []
+    for i in range(reps):
+        tf.append(timed(fused))
+        if i < nb:
+            tb.append(timed(base))
+    scores, rows, _, _ = fused()
+    nq = min(Q, 8)
+    ref = (q_bf[:nq].float() @ items.float().T).topk(k)
+    same = float((rows[:nq].long() == ref.indices).float().mean())
+    flop = 2.0 * Q * N * 128
+    nbytes = N * 256 + Q * 256 + Q * k * 8
+    t_mem, t_mm = nbytes / HBM_PEAK, flop / MFMA_PEAK
+    floor_ms = max(t_mem, t_mm) * 1e3
+    fm, bm = statistics.median(tf), statistics.median(tb)
+    print(json.dumps({
+        "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
+        "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
+        "fused_floor_frac": round(floor_ms / fm, 4), "fused_tflops": round(flop / fm / 1e9, 1),
+        "fused_catalogue_tbps": round(N * 256 / fm / 1e9, 3),
+        "base_ms": round(bm, 4), "base_min_ms": round(min(tb), 4), "base_max_ms": round(max(tb), 4), "base_reps": len(tb),
+        "base_floor_frac": round(floor_ms / bm, 4), "base_tflops": round(flop / bm / 1e9, 1),
+        "speedup": round(bm / fm, 3), "speedup_lo": round(min(tb) / max(tf), 3), "check_rows_equal": round(same, 4),
+    }), flush=True)
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="serving,evaluation")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--n-items", type=int, default=2_000_000)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--step-timeout", type=int, default=240)
+    ap.add_argument("--child", default=None)
+    a = ap.parse_args()
+    if a.child:
+        child(a.child, a.n_items, a.k, a.reps)
+        return 0
+    for name in a.shapes.split(","):
+        if name not in SHAPES:
+            raise SystemExit(f"unknown shape {name}")
+        try:
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
+                                 "--n-items", str(a.n_items), "--k", str(a.k)], timeout=a.step_timeout).returncode
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
+            return 1
+        if rc != 0:  # a failed GPU step ends the run: nothing more is started on the device
+            print(json.dumps({"shape": name, "error": f"exit status {rc}"}), flush=True)
+            return 1
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
