@@ -11,7 +11,7 @@
 // [T, T] score matrix never touches HBM.  The backward recomputes P from the
 // saved LSE in two passes (rows: dQ and the bias gradient; columns: dK, dV), so
 // no T x T buffer is needed at all.
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <cstdlib>
 
@@ -287,10 +287,6 @@ __global__ __launch_bounds__(256) void attn_bwd_k(AttnArgs a) {
 // scratch and enter the next MFMA as bf16 hi + lo halves, so the second
 // product (P.V, dS.K, P^T.dO, dS^T.Q) carries ~16 mantissa bits of P / dS.
 // ===========================================================================
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int SCR_LD = 36;  // scratch row stride (floats): conflict-free C-layout writes, 16 B aligned reads
 
 template <int E>
@@ -337,7 +333,7 @@ __device__ __forceinline__ void stage_img_dma(unsigned char* img, const bf16_t* 
 // row fragment: B[k = 32s + 8(l>>4) + i][n = row0 + (l&15)] = img[row0 + (l&15)][32s + ...]
 template <int E>
 __device__ __forceinline__ bf16x8v img_row_frag(const unsigned char* img, int row0, int s, int lane) {
-  return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + img_off<E>(row0 + (lane & 15), s * 4 + (lane >> 4))));
+  return frag_at(img + img_off<E>(row0 + (lane & 15), s * 4 + (lane >> 4)));
 }
 
 // transposed fragment: B[k = kb + 8(l>>4) + i][n = nb + (l&15)] = img[kb + ...][nb + (l&15)]
@@ -348,10 +344,7 @@ __device__ __forceinline__ bf16x8v img_tr_frag(const unsigned char* img, int kb,
   const int ch = (nb >> 3) + (p >> 1);
   const unsigned char* a0 = img + img_off<E>(kr, ch) + 8 * (p & 1);
   const unsigned char* a1 = img + img_off<E>(kr + 4, ch) + 8 * (p & 1);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8v, v);
+  return tr_frag(a0, a1);
 }
 
 // A fragments of 16 global rows r0 + (l&15) (zero for rows >= T)
@@ -452,8 +445,6 @@ __device__ __forceinline__ uint32_t lpt_tiles(int ntiles, int Tk, bool causal, b
   return mine;
 }
 
-#define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-
 template <int E>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_k(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -497,8 +488,8 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_k(AttnArgs a) {
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        s0 = MFMA(qf[s], img_row_frag<E>(Ki, k0, s, lane), s0);
-        s1 = MFMA(qf[s], img_row_frag<E>(Ki, k0 + 16, s, lane), s1);
+        s0 = mfma16(qf[s], img_row_frag<E>(Ki, k0, s, lane), s0);
+        s1 = mfma16(qf[s], img_row_frag<E>(Ki, k0 + 16, s, lane), s1);
       }
       float bm[4];
 #pragma unroll
@@ -529,8 +520,8 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_k(AttnArgs a) {
 #pragma unroll
       for (int e = 0; e < NE; ++e) {
         const bf16x8v vf = img_tr_frag<E>(Vi, k0, e * 16, lane);
-        o[e] = MFMA(ph, vf, o[e]);
-        o[e] = MFMA(pl, vf, o[e]);
+        o[e] = mfma16(ph, vf, o[e]);
+        o[e] = mfma16(pl, vf, o[e]);
       }
     }
     bf16_t* og = a.o + b * a.o_bs + h * a.o_hs;
@@ -641,10 +632,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_mfma_k(AttnArgs a) {
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          s0 = MFMA(qf[s], img_row_frag<E>(I0, k0, s, lane), s0);
-          s1 = MFMA(qf[s], img_row_frag<E>(I0, k0 + 16, s, lane), s1);
-          p0 = MFMA(df[s], img_row_frag<E>(I1, k0, s, lane), p0);
-          p1 = MFMA(df[s], img_row_frag<E>(I1, k0 + 16, s, lane), p1);
+          s0 = mfma16(qf[s], img_row_frag<E>(I0, k0, s, lane), s0);
+          s1 = mfma16(qf[s], img_row_frag<E>(I0, k0 + 16, s, lane), s1);
+          p0 = mfma16(df[s], img_row_frag<E>(I1, k0, s, lane), p0);
+          p1 = mfma16(df[s], img_row_frag<E>(I1, k0 + 16, s, lane), p1);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -681,8 +672,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_mfma_k(AttnArgs a) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
           const bf16x8v kf = img_tr_frag<E>(I0, k0, e * 16, lane);
-          dq[e] = MFMA(gh, kf, dq[e]);
-          dq[e] = MFMA(gl, kf, dq[e]);
+          dq[e] = mfma16(gh, kf, dq[e]);
+          dq[e] = mfma16(gl, kf, dq[e]);
         }
       }
       bf16_t* dqg = a.dq + b * a.q_bs + h * a.q_hs;
@@ -716,10 +707,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_mfma_k(AttnArgs a) {
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          s0 = MFMA(kf[s], img_row_frag<E>(I0, q0, s, lane), s0);
-          s1 = MFMA(kf[s], img_row_frag<E>(I0, q0 + 16, s, lane), s1);
-          p0 = MFMA(vf[s], img_row_frag<E>(I1, q0, s, lane), p0);
-          p1 = MFMA(vf[s], img_row_frag<E>(I1, q0 + 16, s, lane), p1);
+          s0 = mfma16(kf[s], img_row_frag<E>(I0, q0, s, lane), s0);
+          s1 = mfma16(kf[s], img_row_frag<E>(I0, q0 + 16, s, lane), s1);
+          p0 = mfma16(vf[s], img_row_frag<E>(I1, q0, s, lane), p0);
+          p1 = mfma16(vf[s], img_row_frag<E>(I1, q0 + 16, s, lane), p1);
         }
         const int qa = q0 + col, qb = q0 + 16 + col;
         const float la = lse[qa], lb = lse[qb], da_ = delta[qa], db_ = delta[qb];
@@ -742,11 +733,11 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_mfma_k(AttnArgs a) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
           const bf16x8v dof = img_tr_frag<E>(I1, q0, e * 16, lane);
-          dv[e] = MFMA(ph, dof, dv[e]);
-          dv[e] = MFMA(pl, dof, dv[e]);
+          dv[e] = mfma16(ph, dof, dv[e]);
+          dv[e] = mfma16(pl, dof, dv[e]);
           const bf16x8v qf = img_tr_frag<E>(I0, q0, e * 16, lane);
-          dk[e] = MFMA(gh, qf, dk[e]);
-          dk[e] = MFMA(gl, qf, dk[e]);
+          dk[e] = mfma16(gh, qf, dk[e]);
+          dk[e] = mfma16(gl, qf, dk[e]);
         }
       }
       bf16_t* dkg = a.dk + b * a.k_bs + h * a.k_hs;
@@ -777,8 +768,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_mfma_k(AttnArgs a) {
 // ((u >> 1) & 3): the row-fragment reads (16 lanes, 16 rows, one chunk) and the
 // transposed reads (4 rows x 4 chunks per 32 lanes) are both conflict-free.
 constexpr int E_BWD32 = 64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 
 // image of rows [0, Tk) (row r at src + r * ts; rows >= T zero) by LDS-DMA: 1-KiB pieces of
 // 8 rows, the lane loading the chunk that the swizzle puts in its lane-linear slot
@@ -793,20 +782,6 @@ __device__ __forceinline__ void stage_img32(unsigned char* img, const bf16_t* __
     const void* p = rr >= 0 ? (const void*)(src + rr * ts + ch * 8) : (const void*)attn_zero16;
     glds16(p, img + d * 1024);
   }
-}
-
-__device__ __forceinline__ uint32_t pk_bf16_rne(float lo, float hi) {
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){lo, hi}, bf16x2_t));
-}
-
-// registers 8 s .. 8 s + 7 of a 32 x 32 accumulator as the bf16 A operand of k-step s
-__device__ __forceinline__ bf16x8v acc_frag32(const f32x16& x, int s) {
-  const int o = 8 * s;
-  const u32x4 h = {pk_bf16_rne(x[o], x[o + 1]), pk_bf16_rne(x[o + 2], x[o + 3]), pk_bf16_rne(x[o + 4], x[o + 5]),
-                   pk_bf16_rne(x[o + 6], x[o + 7])};
-  return __builtin_bit_cast(bf16x8v, h);
 }
 
 // dot of two bf16x8 fragments in fp32
@@ -855,17 +830,6 @@ __device__ __forceinline__ Frag32Off frag32_off(int lane) {
     }
   return o;
 }
-__device__ __forceinline__ bf16x8v frag_at(const unsigned char* p) {
-  return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(p));
-}
-__device__ __forceinline__ bf16x8v tr_at(const unsigned char* lo, const unsigned char* hi) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((address_space(3))) unsigned char lds_u8_t;
-  const s16x4 l = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds_u8_t*)lo);
-  const s16x4 h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds_u8_t*)hi);
-  const s16x8 v = {l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]};
-  return __builtin_bit_cast(bf16x8v, v);
-}
 
 // 32 x 32 transposed-gradient accumulator (row e = 32 nd + 8 g + 4 hh + j in the registers,
 // column = the token r0 + (lane & 31)) stored as 8-byte runs of the token's row
@@ -882,8 +846,8 @@ __device__ __forceinline__ void store_accT32(const f32x16& x, float scale, bf16_
   uint32_t w[4][2];
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
-    w[g][0] = pk_bf16_rne(x[4 * g] * scale, x[4 * g + 1] * scale);
-    w[g][1] = pk_bf16_rne(x[4 * g + 2] * scale, x[4 * g + 3] * scale);
+    w[g][0] = pack_bf16x2(x[4 * g] * scale, x[4 * g + 1] * scale);
+    w[g][1] = pack_bf16x2(x[4 * g + 2] * scale, x[4 * g + 3] * scale);
   }
 #pragma unroll
   for (int g = 0; g < 2; ++g)
@@ -1024,8 +988,8 @@ __device__ __forceinline__ void bwd32_rows(const AttnArgs& a, const Bwd32Smem& m
     asm volatile("" : "+v"(qo));
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      st = MFMA32(frag_at(m.IK + k0 * 128 + fo.row[s]), G ? gq[s] : frag_at(m.IQ + qo + fo.row[s]), st);
-      pt = MFMA32(frag_at(m.IV + k0 * 128 + fo.row[s]), G ? gd[s] : frag_at(m.IO + qo + fo.row[s]), pt);
+      st = mfma32(frag_at(m.IK + k0 * 128 + fo.row[s]), G ? gq[s] : frag_at(m.IQ + qo + fo.row[s]), st);
+      pt = mfma32(frag_at(m.IV + k0 * 128 + fo.row[s]), G ? gd[s] : frag_at(m.IO + qo + fo.row[s]), pt);
     }
     // S^T[k][q]: the key k = k0 + 8 g + 4 hh + jj in register 4 g + jj, the query q in the lane
     if ((a.causal && j == i) || (ragged && (i == nt - 1 || j == nt - 1)))
@@ -1057,10 +1021,10 @@ __device__ __forceinline__ void bwd32_rows(const AttnArgs& a, const Bwd32Smem& m
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const bf16x8v gf = acc_frag32(st, s);
+      const bf16x8v gf = pack_frag(st, 8 * s);
       const unsigned char* kt = m.IK + (k0 + 16 * s) * 128;
 #pragma unroll
-      for (int nd = 0; nd < 2; ++nd) dq[nd] = MFMA32(tr_at(kt + fo.tr[nd][0], kt + fo.tr[nd][1]), gf, dq[nd]);
+      for (int nd = 0; nd < 2; ++nd) dq[nd] = mfma32(tr_frag(kt + fo.tr[nd][0], kt + fo.tr[nd][1]), gf, dq[nd]);
     }
   }
   if (has_tab) {
@@ -1151,8 +1115,8 @@ __device__ __forceinline__ void bwd32_cols(const AttnArgs& a, const Bwd32Smem& m
     asm volatile("" : "+v"(ko));
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-      sx = MFMA32(frag_at(m.IQ + q0 * 128 + fo.row[s]), G ? gk[s] : frag_at(m.IK + ko + fo.row[s]), sx);
-      px = MFMA32(frag_at(m.IO + q0 * 128 + fo.row[s]), G ? gv[s] : frag_at(m.IV + ko + fo.row[s]), px);
+      sx = mfma32(frag_at(m.IQ + q0 * 128 + fo.row[s]), G ? gk[s] : frag_at(m.IK + ko + fo.row[s]), sx);
+      px = mfma32(frag_at(m.IO + q0 * 128 + fo.row[s]), G ? gv[s] : frag_at(m.IV + ko + fo.row[s]), px);
     }
     // S[q][k]: the query q = q0 + 8 g + 4 hh + jj in register 4 g + jj, the key k in the lane
     const int qb0 = q0 + 4 * hh;
@@ -1162,13 +1126,13 @@ __device__ __forceinline__ void bwd32_cols(const AttnArgs& a, const Bwd32Smem& m
       cols_math<false>(sx, px, bp, m.lse + qb0, m.dlt + qb0, c2, qb0, qlo, span);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      const bf16x8v pf = acc_frag32(sx, s), gf = acc_frag32(px, s);
+      const bf16x8v pf = pack_frag(sx, 8 * s), gf = pack_frag(px, 8 * s);
       const unsigned char* ot = m.IO + (q0 + 16 * s) * 128;
       const unsigned char* qt = m.IQ + (q0 + 16 * s) * 128;
 #pragma unroll
       for (int nd = 0; nd < 2; ++nd) {
-        dv[nd] = MFMA32(tr_at(ot + fo.tr[nd][0], ot + fo.tr[nd][1]), pf, dv[nd]);
-        dk[nd] = MFMA32(tr_at(qt + fo.tr[nd][0], qt + fo.tr[nd][1]), gf, dk[nd]);
+        dv[nd] = mfma32(tr_frag(ot + fo.tr[nd][0], ot + fo.tr[nd][1]), pf, dv[nd]);
+        dk[nd] = mfma32(tr_frag(qt + fo.tr[nd][0], qt + fo.tr[nd][1]), gf, dk[nd]);
       }
     }
   }
@@ -1259,16 +1223,16 @@ __device__ __forceinline__ void bwd32_tail_unit(const AttnArgs& a, const Bwd32Sm
   a1 += __shfl_xor(a1, 32, 64);
   const int off = qs * 128 + (((c >> 3) ^ a32_swz(qs)) << 4) + 2 * (c & 7);
   if (hh == 0) {
-    *reinterpret_cast<uint32_t*>(a.dq + b * a.q_bs + h * a.q_hs + (int64_t)qs * a.q_ts + c) = pk_bf16_rne(rs * a0, rs * a1);
+    *reinterpret_cast<uint32_t*>(a.dq + b * a.q_bs + h * a.q_hs + (int64_t)qs * a.q_ts + c) = pack_bf16x2(rs * a0, rs * a1);
     const uint32_t qv = *reinterpret_cast<const uint32_t*>(m.IQ + off);
     const float f = rs * m.tds[qs];
     *reinterpret_cast<uint32_t*>(a.dk + b * a.k_bs + h * a.k_hs + (int64_t)qs * a.k_ts + c) =
-        pk_bf16_rne(f * __uint_as_float(qv << 16), f * __uint_as_float(qv & 0xffff0000u));
+        pack_bf16x2(f * __uint_as_float(qv << 16), f * __uint_as_float(qv & 0xffff0000u));
   } else {
     const uint32_t ov = *reinterpret_cast<const uint32_t*>(m.IO + off);
     const float f = m.tp[qs];
     *reinterpret_cast<uint32_t*>(a.dv + b * a.v_bs + h * a.v_hs + (int64_t)qs * a.v_ts + c) =
-        pk_bf16_rne(f * __uint_as_float(ov << 16), f * __uint_as_float(ov & 0xffff0000u));
+        pack_bf16x2(f * __uint_as_float(ov << 16), f * __uint_as_float(ov & 0xffff0000u));
   }
 }
 
@@ -1517,8 +1481,8 @@ __device__ __forceinline__ void fwd_kblock(const unsigned char* Ki, const unsign
   f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    s0 = MFMA(qf[s], img_row_frag<E>(Ki, kimg, s, lane), s0);
-    s1 = MFMA(qf[s], img_row_frag<E>(Ki, kimg + 16, s, lane), s1);
+    s0 = mfma16(qf[s], img_row_frag<E>(Ki, kimg, s, lane), s0);
+    s1 = mfma16(qf[s], img_row_frag<E>(Ki, kimg + 16, s, lane), s1);
   }
   float bm[4];
 #pragma unroll
@@ -1549,8 +1513,8 @@ __device__ __forceinline__ void fwd_kblock(const unsigned char* Ki, const unsign
 #pragma unroll
   for (int e = 0; e < NE; ++e) {
     const bf16x8v vf = img_tr_frag<E>(Vi, kimg, e * 16, lane);
-    o[e] = MFMA(ph, vf, o[e]);
-    o[e] = MFMA(pl, vf, o[e]);
+    o[e] = mfma16(ph, vf, o[e]);
+    o[e] = mfma16(pl, vf, o[e]);
   }
 }
 
@@ -1700,10 +1664,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_rows_win_k(AttnArgs a) {
         f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-          s0 = MFMA(qf[s], img_row_frag<E>(I0, ki, s, lane), s0);
-          s1 = MFMA(qf[s], img_row_frag<E>(I0, ki + 16, s, lane), s1);
-          p0 = MFMA(df[s], img_row_frag<E>(I1, ki, s, lane), p0);
-          p1 = MFMA(df[s], img_row_frag<E>(I1, ki + 16, s, lane), p1);
+          s0 = mfma16(qf[s], img_row_frag<E>(I0, ki, s, lane), s0);
+          s1 = mfma16(qf[s], img_row_frag<E>(I0, ki + 16, s, lane), s1);
+          p0 = mfma16(df[s], img_row_frag<E>(I1, ki, s, lane), p0);
+          p1 = mfma16(df[s], img_row_frag<E>(I1, ki + 16, s, lane), p1);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1734,8 +1698,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_rows_win_k(AttnArgs a) {
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
           const bf16x8v kf = img_tr_frag<E>(I0, ki, e * 16, lane);
-          dq[e] = MFMA(gh, kf, dq[e]);
-          dq[e] = MFMA(gl, kf, dq[e]);
+          dq[e] = mfma16(gh, kf, dq[e]);
+          dq[e] = mfma16(gl, kf, dq[e]);
         }
       }
     }
@@ -1800,10 +1764,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_cols_win_k(AttnArgs a) {
       f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, p0 = s0, p1 = s0;
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        s0 = MFMA(kf[s], img_row_frag<E>(I0, qi, s, lane), s0);
-        s1 = MFMA(kf[s], img_row_frag<E>(I0, qi + 16, s, lane), s1);
-        p0 = MFMA(vf[s], img_row_frag<E>(I1, qi, s, lane), p0);
-        p1 = MFMA(vf[s], img_row_frag<E>(I1, qi + 16, s, lane), p1);
+        s0 = mfma16(kf[s], img_row_frag<E>(I0, qi, s, lane), s0);
+        s1 = mfma16(kf[s], img_row_frag<E>(I0, qi + 16, s, lane), s1);
+        p0 = mfma16(vf[s], img_row_frag<E>(I1, qi, s, lane), p0);
+        p1 = mfma16(vf[s], img_row_frag<E>(I1, qi + 16, s, lane), p1);
       }
       const int qa = q0 + col, qb = q0 + 16 + col;
       const float la = wl[qi + col], lb = wl[qi + 16 + col], da_ = wd[qi + col], db_ = wd[qi + 16 + col];
@@ -1826,11 +1790,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_cols_win_k(AttnArgs a) {
 #pragma unroll
       for (int e = 0; e < NE; ++e) {
         const bf16x8v dof = img_tr_frag<E>(I1, qi, e * 16, lane);
-        dv[e] = MFMA(ph, dof, dv[e]);
-        dv[e] = MFMA(pl, dof, dv[e]);
+        dv[e] = mfma16(ph, dof, dv[e]);
+        dv[e] = mfma16(pl, dof, dv[e]);
         const bf16x8v qf = img_tr_frag<E>(I0, qi, e * 16, lane);
-        dk[e] = MFMA(gh, qf, dk[e]);
-        dk[e] = MFMA(gl, qf, dk[e]);
+        dk[e] = mfma16(gh, qf, dk[e]);
+        dk[e] = mfma16(gl, qf, dk[e]);
       }
     }
   }
@@ -1843,7 +1807,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_cols_win_k(AttnArgs a) {
     c_store_rows(scr, dv[e], dv[e + 1], 1.f, lane, dvg + e * 16, a.v_ts, k0, T);
   }
 }
-#undef MFMA
 
 static size_t fwd_win_lds(int T, int E) {
   return (size_t)2 * AW_W * E * 2 + (size_t)((2 * T + 4) & ~3) * 4 + (size_t)4 * 16 * SCR_LD * 4;
@@ -1902,17 +1865,6 @@ static size_t bwd_mfma_lds(int T, int E) {
   return (size_t)2 * Tk * E * 2 + (size_t)(2 * T + 2) * 8 + (size_t)2 * Tk * 4 + (size_t)4 * 16 * SCR_LD * 4;
 }
 
-static int attn_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 template <int E>
 static int attn_launch_mfma(const AttnArgs& a, int B, bool bwd, hipStream_t s) {
   static const bool old_bwd = getenv("LTHM_ATTN_BWD_OLD") && atoi(getenv("LTHM_ATTN_BWD_OLD"));  // A/B switch
@@ -1926,7 +1878,7 @@ static int attn_launch_mfma(const AttnArgs& a, int B, bool bwd, hipStream_t s) {
   if (E == 64 && bwd && !old_bwd) {
     AttnArgs t = a;
     t.tail = !no_tail && bwd32_tail_mode(a.T, a.causal);
-    const int cus = attn_cu_count();
+    const int cus = cu_count();
     int S = std::min(B, std::max(1, cus / a.H));  // workgroups per head
     if (!no_pers && bwd32p_lds(a.T, t.tail) <= 160 * 1024 && B >= 2 * S && S >= 1) {
       hipLaunchKernelGGL(attn_bwd32p_k<4>, dim3(S * a.H), dim3(256), bwd32p_lds(a.T, t.tail), s, t, B, S);
@@ -2153,7 +2105,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd32_k(AttnArgs a) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) st[v] = 0.f;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) st = MFMA32(frag_at(IK + k0 * 128 + fo.row[s]), qf[s], st);
+      for (int s = 0; s < 4; ++s) st = mfma32(frag_at(IK + k0 * 128 + fo.row[s]), qf[s], st);
       // S^T[k][q] -> log2-scaled logits; the key k = k0 + 8 g + 4 hh + jj in register 4 g + jj
       const bool edge = (a.causal && j == i) || (ragged && (i == nt - 1 || j == nt - 1));
       float mt = -INFINITY;
@@ -2190,20 +2142,20 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd32_k(AttnArgs a) {
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8v hf = acc_frag32(st, s2);
+        const bf16x8v hf = pack_frag(st, 8 * s2);
         const u32x4 hb = __builtin_bit_cast(u32x4, hf);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {  // the remainder p - bf16(p), exact in f32
           lo[8 * s2 + 2 * e] = st[8 * s2 + 2 * e] - __uint_as_float(hb[e] << 16);
           lo[8 * s2 + 2 * e + 1] = st[8 * s2 + 2 * e + 1] - __uint_as_float(hb[e] & 0xffff0000u);
         }
-        const bf16x8v lf = acc_frag32(lo, s2);
+        const bf16x8v lf = pack_frag(lo, 8 * s2);
         const unsigned char* vt = IV + (k0 + 16 * s2) * 128;
 #pragma unroll
         for (int nd = 0; nd < 2; ++nd) {
-          const bf16x8v vf = tr_at(vt + fo.tr[nd][0], vt + fo.tr[nd][1]);
-          o[nd] = MFMA32(vf, hf, o[nd]);
-          o[nd] = MFMA32(vf, lf, o[nd]);
+          const bf16x8v vf = tr_frag(vt + fo.tr[nd][0], vt + fo.tr[nd][1]);
+          o[nd] = mfma32(vf, hf, o[nd]);
+          o[nd] = mfma32(vf, lf, o[nd]);
         }
       }
     }

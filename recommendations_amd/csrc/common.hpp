@@ -54,9 +54,6 @@ template <> struct Elem<bf16_t> {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Load VB bytes (4/8/16) starting at p as f32 values into out[0..VB/sizeof(T))
 template <typename T, int VB>
@@ -247,6 +244,18 @@ __host__ __forceinline__ int grid_for(int64_t work, int per_block, int cap = 256
   if (g < 1) g = 1;
   if (g > cap) g = cap;
   return (int)g;
+}
+
+// compute units of the current device, queried once for the whole library (256 if the query fails)
+inline int cu_count() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+  }
+  return cus;
 }
 
 }  // namespace lthm

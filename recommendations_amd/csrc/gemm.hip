@@ -18,7 +18,7 @@
 // commons/layers.py:65-81 (MLP + QuickGELU), models/lthm/sequence/*.py Linears.
 #include <algorithm>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace lthm {
 
@@ -244,27 +244,19 @@ __device__ __forceinline__ void store_tile(unsigned char* lds, int tid, const u3
   }
 }
 
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 template <bool KCONTIG>
 __device__ __forceinline__ bf16x8v read_frag(const unsigned char* lds, int rbase, int s, int lane) {
   if constexpr (KCONTIG) {
     const int r = rbase + (lane & 15);
     const int chunk = s * 4 + (lane >> 4);
-    u32x4 v = *reinterpret_cast<const u32x4*>(lds + kc_off(r, chunk));
-    return __builtin_bit_cast(bf16x8v, v);
+    return frag_at(lds + kc_off(r, chunk));
   } else {
     const int gq = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
     const int kr = s * 32 + 8 * gq + q;
     const int ch = (rbase >> 3) + (p >> 1);
     const unsigned char* a0 = lds + ks_off(kr, ch) + 8 * (p & 1);
     const unsigned char* a1 = lds + ks_off(kr + 4, ch) + 8 * (p & 1);
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8v, v);
+    return tr_frag(a0, a1);
   }
 }
 
@@ -340,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void gemm_k(GemmArgs g, int tiles_n) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
     }
     if (has_next) {
       unsigned char* nxt = smem + (cur ^ 1) * 2 * TILE_BYTES;
@@ -746,7 +738,7 @@ __global__ __launch_bounds__(PS_THREADS, 1) void gemm_ps_k(GemmArgs g, int tiles
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
       }
     }
   };
@@ -809,7 +801,7 @@ __global__ __launch_bounds__(PS_THREADS, 1) void gemm_ps_k(GemmArgs g, int tiles
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
       }
     }
     if (++kk < NK) continue;
@@ -979,7 +971,7 @@ __global__ __launch_bounds__(512, 1) void gemm_wg_k(GemmArgs g, int tiles_m, int
     for (int j = 0; j < 8; ++j) {
       const bf16x8v bfr = read_frag<false>(sb, j * 16, 0, lane);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr, acc[i][j], 0, 0, 0);
+      for (int i = 0; i < 4; ++i) acc[i][j] = mfma16(af[i], bfr, acc[i][j]);
     }
   }
   // raw alpha * partial tile -> split-K slab [split][M][N] (16 lanes = 64 contiguous bytes)
@@ -1150,15 +1142,13 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_k(GemmArgs g, int tiles_m, int
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
-          af[i][s2] = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(
-                                                      Ah + (64 * mi + 16 * i) * 128 + fa + (((4 * s2 + c4) ^ sw) << 4)));
+          af[i][s2] = frag_at(Ah + (64 * mi + 16 * i) * 128 + fa + (((4 * s2 + c4) ^ sw) << 4));
       if (ph == 0 || ph == 1) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int s2 = 0; s2 < 2; ++s2) {
-            const bf16x8v v = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(
-                                                    Bh + (32 * nj + 16 * j) * 128 + fa + (((4 * s2 + c4) ^ sw) << 4)));
+            const bf16x8v v = frag_at(Bh + (32 * nj + 16 * j) * 128 + fa + (((4 * s2 + c4) ^ sw) << 4));
             if (ph == 0) b0[j][s2] = v;
             else b1[j][s2] = v;
           }
@@ -1169,8 +1159,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_k(GemmArgs g, int tiles_m, int
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            acc[4 * mi + i][2 * nj + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                af[i][s2], nj ? b1[j][s2] : b0[j][s2], acc[4 * mi + i][2 * nj + j], 0, 0, 0);
+            acc[4 * mi + i][2 * nj + j] = mfma16(af[i][s2], nj ? b1[j][s2] : b0[j][s2], acc[4 * mi + i][2 * nj + j]);
     }
   }
   // epilogue: the buffers are free once every wave's last fragment reads are done
@@ -1368,17 +1357,6 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_k(GemmArgs g, int tiles_m, int
 
 using namespace lthm;
 
-static int lthm_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // 0: never, 1: when eligible (default), set by LTHM_GEMM_PS
 static int lthm_gemm_ps_mode() {
   static int mode = -1;
@@ -1514,9 +1492,9 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
       d->N % 8 == 0 && d->act == LTHM_ACT_NONE && !d->bias && d->M * d->N > 0 && (wg_ragged || d->K % WG_BK == 0)) {
     const int tm = (int)((d->M + 255) / 256), tn = (int)((d->N + 255) / 256);
     const int64_t cap = (int64_t)(d->workspace_bytes / ((size_t)d->M * d->N * 4));
-    int64_t sp = std::min<int64_t>(std::max(1, lthm_cu_count() / (tm * tn)), cap);
+    int64_t sp = std::min<int64_t>(std::max(1, cu_count() / (tm * tn)), cap);
     sp = std::min<int64_t>(sp, d->K / (WG_BK * 8));  // >= 8 stages per split
-    if (sp >= 2 && tm * tn <= lthm_cu_count()) {
+    if (sp >= 2 && tm * tn <= cu_count()) {
       int64_t kpw = (d->K + sp - 1) / sp;
       kpw = (kpw + WG_BK - 1) / WG_BK * WG_BK;
       const int spl = (int)((d->K + kpw - 1) / kpw);
@@ -1537,7 +1515,7 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
       return amax_after();
     }
   }
-  const int per_xcd = lthm_cu_count() / 8;
+  const int per_xcd = cu_count() / 8;
   int epi = -1;
   {
     const bool a16 = ((uintptr_t)d->C % 16) == 0 && d->ldc % 8 == 0 && ((uintptr_t)d->bias % 16) == 0;

@@ -390,17 +390,6 @@ static int kag_layout(int64_t n_items, int K, int D, int end_bit, KagLayout* L) 
   return 0;
 }
 
-static int kag_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 template <int LG, int NQ, int CW>
 static int kag_launch_groups(const KagLayout& L, unsigned char* w, int64_t N, int D, float* W, float* S, float clr,
                              float eps, hipStream_t s) {
@@ -416,7 +405,7 @@ static int kag_launch_groups(const KagLayout& L, unsigned char* w, int64_t N, in
   // LTHM_KAG_BPC overrides (A/B, profiles/r06p/: 8 / 16 / 32 per CU -> 0.658 / 0.602 / 0.592 ms per
   // generator step)
   static const int bpc = getenv("LTHM_KAG_BPC") ? atoi(getenv("LTHM_KAG_BPC")) : 32;
-  const int cap = kag_cu_count() * (bpc > 0 ? bpc : 32);
+  const int cap = cu_count() * (bpc > 0 ? bpc : 32);
   const int gpb = 256 / LG;
   hipLaunchKernelGGL((kag_apply_k<LG, NQ, CW>), dim3(grid_for(N, gpb, cap)), dim3(256), 0, s, skeys, svals, starts, cnt, N,
                      g, D, W, S, clr, eps, longlist, (int*)(cnt + 1));
@@ -427,7 +416,7 @@ static int kag_launch_groups(const KagLayout& L, unsigned char* w, int64_t N, in
   hipLaunchKernelGGL((kag_chunk_k<LG, NQ, CW>), dim3(grid_for(2 * (N / KAG_CH) + 2, gpb, cap)), dim3(256), 0, s, svals,
                      starts, cnt, N, (const uint32_t*)longlist, cnt + 1, (const uint32_t*)lpref, g, D, part);
   LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(kag_long_apply_k, dim3(grid_for(N / (KAG_CH + 1) + 1, 1, kag_cu_count() * 2)),
+  hipLaunchKernelGGL(kag_long_apply_k, dim3(grid_for(N / (KAG_CH + 1) + 1, 1, cu_count() * 2)),
                      dim3(64 * KAG_LW), 0, s, skeys, starts, (const uint32_t*)longlist, cnt + 1,
                      (const uint32_t*)lpref, (const float*)part, D, W, S, clr, eps);
   LTHM_CHECK_LAUNCH();
@@ -478,7 +467,7 @@ extern "C" int lthm_kshift_adagrad_fused(const int64_t* ids, int64_t n, int32_t 
   // lanes per item: >= K and >= D / 4, a power of two in [16, 64]
   const int need = K > (D + 3) / 4 ? K : (D + 3) / 4;
   const int lpi = need <= 16 ? 16 : need <= 32 ? 32 : 64;
-  const int pg = grid_for(items, 4 * (64 / lpi), kag_cu_count() * 16);
+  const int pg = grid_for(items, 4 * (64 / lpi), cu_count() * 16);
 #define KAG_PREP_L(TY, TO, LPI)                                                                                   \
   hipLaunchKernelGGL((kag_prep_k<TY, TO, LPI>), dim3(pg), dim3(256), 0, s, ids, items, F, (const TY*)dY,           \
                      (const TO*)out, norms, P, D, K, mode, scale, g, keys, vals)
@@ -504,7 +493,7 @@ extern "C" int lthm_kshift_adagrad_fused(const int64_t* ids, int64_t n, int32_t 
                                          (int)N, 0, end_bit, s) != hipSuccess)
     return (int)hipErrorLaunchFailure;
   uint8_t* heads = (uint8_t*)(w + L.heads);
-  hipLaunchKernelGGL(kag_heads_k, dim3(grid_for(N, 256, kag_cu_count() * 8)), dim3(256), 0, s, (const uint32_t*)skeys, N,
+  hipLaunchKernelGGL(kag_heads_k, dim3(grid_for(N, 256, cu_count() * 8)), dim3(256), 0, s, (const uint32_t*)skeys, N,
                      heads);
   LTHM_CHECK_LAUNCH();
   size_t selb = L.sel_bytes;

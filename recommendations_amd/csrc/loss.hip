@@ -16,23 +16,12 @@
 // no atomics, no LDS round trip, no T^2 buffer.
 // The argsort / topk metrics (wrapper.py:228-238) become the in-kernel rank
 // count #{c != r : logit[r, c] > logit[r, r]}.
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace lthm {
-
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-
-// two f32 -> packed bf16 pair, round-to-nearest-even (one v_cvt_pk_bf16_f32)
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){lo, hi}, bf16x2v));
-}
 
 constexpr int DE = 128;  // product_emb_dim (model/lthm.yaml:22)
 
@@ -50,12 +39,6 @@ __device__ __forceinline__ int swz(int row) {
   return ((((row & 7) << 1) + (h << 3)) & 15) | h;
 }
 __device__ __forceinline__ int ks_off256(int row, int ch) { return row * 256 + ((ch ^ swz(row)) << 4); }
-// The 32x32x16 tile engine's image (cdna_hip_programming.md T10, image (b)): chunk ch of
-// row r at slot ch ^ swz32(r), conflict-free for the ds_read_b128 row fragments of the
-// 32x32x16 A operand and for the ds_read_b64_tr_b16 transposed B fragments (each aligned
-// quad of rows takes four distinct aligned blocks of four slots).
-__device__ __forceinline__ int swz32(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int ko32(int row, int ch) { return row * 256 + ((ch ^ swz32(row)) << 4); }
 
 // ---------------------------------------------------------------- row normalisation
 // out[r] = bf16(x[r] / max(|x[r]|, 1e-12)), norms[r] = |x[r]|   (F.normalize, wrapper.py:118-119)
@@ -325,7 +308,7 @@ __device__ __forceinline__ bool pad_of(const ClArgs& a, const Geo& g, int c) {
 }
 
 __device__ __forceinline__ bf16x8v row_frag(const unsigned char* img, int row, int chunk) {
-  return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + ks_off256(row, chunk)));
+  return frag_at(img + ks_off256(row, chunk));
 }
 
 // load this wave's 16 register rows as 4 k32 A fragments
@@ -683,7 +666,6 @@ __device__ __forceinline__ void trp_offsets(int (&off)[8], int lane) {
 #pragma unroll
   for (int nd = 0; nd < 8; ++nd) off[nd] = row * 256 + (((2 * nd + (p >> 1)) ^ swz(row)) << 4) + 8 * (p & 1);
 }
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
 // per-tile base of column block nd, laundered through an empty asm so the compiler
 // cannot re-associate it with the kb / k offsets (which then fold into ds_read
 // immediates instead of costing two VALU adds per read)
@@ -694,10 +676,7 @@ __device__ __forceinline__ lds_u8* trp_base(const unsigned char* img, int off) {
 }
 __device__ __forceinline__ bf16x8v trp_frag(lds_u8* base, int kb) {
   lds_u8* a0 = base + kb * 256;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 16 * 256));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8v, v);
+  return tr_frag(tr_half(a0), tr_half(a0 + 16 * 256));
 }
 
 // S^T tile: acc[mi][yb][j] = img[yb*16 + 4(lane>>4) + j] . X[xbase + 16 mi + (lane&15)]
@@ -715,7 +694,7 @@ __device__ __forceinline__ void st_tile(f32x4 (&acc)[2][4], const bf16x8v (&qf)[
       const bf16x8v af = row_frag(img, yb * 16 + (lane & 15), s * 4 + (lane >> 4));
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
-        acc[mi][yb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, qf[mi][s], acc[mi][yb], 0, 0, 0);
+        acc[mi][yb] = mfma16(af, qf[mi][s], acc[mi][yb]);
     }
 }
 
@@ -1061,7 +1040,7 @@ __global__ __launch_bounds__(256, 2) void cl_bwd_k(ClArgs a) {
       for (int mi = 0; mi < 2; ++mi) {
         const f32x4& p = acc[mi][2 * ks];
         const f32x4& q = acc[mi][2 * ks + 1];
-        const u32x4 h = {pk_bf16(p[0], p[1]), pk_bf16(p[2], p[3]), pk_bf16(q[0], q[1]), pk_bf16(q[2], q[3])};
+        const u32x4 h = {pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(q[0], q[1]), pack_bf16x2(q[2], q[3])};
         af[mi] = __builtin_bit_cast(bf16x8v, h);
       }
 #pragma unroll
@@ -1069,7 +1048,7 @@ __global__ __launch_bounds__(256, 2) void cl_bwd_k(ClArgs a) {
         const bf16x8v bfr = trp_frag(tb[nd], ks * 32);
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
-          dacc[mi][nd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mi], bfr, dacc[mi][nd], 0, 0, 0);
+          dacc[mi][nd] = mfma16(af[mi], bfr, dacc[mi][nd]);
       }
     }
   }
@@ -1142,12 +1121,6 @@ __global__ __launch_bounds__(256, 2) void cl_bwd_k(ClArgs a) {
 // COLS: grid (physical-row blocks, n_mb): register rows = physical `in` rows (b, t) (the same
 //   operand for every head); the image walks the out rows of every head in turn, so dIn is
 //   summed over the heads in registers (no f32 d_in read-modify-write per head).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ f32x16 mfma32(bf16x8v a, bf16x8v b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 constexpr int CL_EPS = 132;  // epilogue restage row stride (floats): conflict-free b32 writes / b128 reads
 
 constexpr int CL_NB32 = 4;  // image ring depth of the 32x32x16 backward: three tiles of DMA in flight
@@ -1180,11 +1153,7 @@ __device__ __forceinline__ void frag32_offsets(int (&roff)[8], int (&toff)[4][2]
 }
 
 __device__ __forceinline__ bf16x8v tr_frag32(const unsigned char* img, int off_lo, int off_hi) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)((lds_u8*)img + off_lo));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)((lds_u8*)img + off_hi));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8v, v);
+  return tr_frag(tr_half((const lds_u8*)img + off_lo), tr_half((const lds_u8*)img + off_hi));
 }
 
 // the register row's per-lane state for one head
@@ -1243,7 +1212,7 @@ __device__ __forceinline__ void cl_bwd32_head(ClTile32<NW>& sh, f32x16 (&dacc)[4
       for (int v = 0; v < 16; ++v) acc[ib][v] = 0.f;
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        const bf16x8v af = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + ib * 8192 + roff[s]));
+        const bf16x8v af = frag_at(img + ib * 8192 + roff[s]);
         acc[ib] = mfma32(af, qf[s], acc[ib]);
       }
     }
@@ -1299,8 +1268,8 @@ __device__ __forceinline__ void cl_bwd32_head(ClTile32<NW>& sh, f32x16 (&dacc)[4
       for (int hf = 0; hf < 2; ++hf) {
         const int ks = 2 * ib + hf, o = 8 * hf;
         const f32x16& pv = acc[ib];
-        u32x4 hpk = {pk_bf16(pv[o], pv[o + 1]), pk_bf16(pv[o + 2], pv[o + 3]), pk_bf16(pv[o + 4], pv[o + 5]),
-                     pk_bf16(pv[o + 6], pv[o + 7])};
+        u32x4 hpk = {pack_bf16x2(pv[o], pv[o + 1]), pack_bf16x2(pv[o + 2], pv[o + 3]), pack_bf16x2(pv[o + 4], pv[o + 5]),
+                     pack_bf16x2(pv[o + 6], pv[o + 7])};
         if (wmask && !xr.live) hpk = u32x4{0u, 0u, 0u, 0u};  // COLS: a column this head does not have
         const bf16x8v af = __builtin_bit_cast(bf16x8v, hpk);
 #pragma unroll
@@ -1598,7 +1567,7 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
       acc[0] = f32x16{};
       acc[1] = f32x16{};
       auto rd = [&](int ib, int s2) {
-        return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + ib * 8192 + roff[s2]));
+        return frag_at(img + ib * 8192 + roff[s2]);
       };
       bf16x8v a0 = rd(0, 0), a1 = rd(1, 0);
 #pragma unroll
@@ -1658,11 +1627,7 @@ __device__ __forceinline__ void cl_fr32_head(ClTile32<4>& sh, f32x16 (&dacc)[4],
       }
       // dacc[32 x 128] += p[32 x 32] . img[32 x 128] (as cl_bwd32_head)
       {
-        const f32x16& pvv = acc[ib];
-        const bf16x8v af0 = __builtin_bit_cast(bf16x8v, u32x4{pk_bf16(pvv[0], pvv[1]), pk_bf16(pvv[2], pvv[3]),
-                                                              pk_bf16(pvv[4], pvv[5]), pk_bf16(pvv[6], pvv[7])});
-        const bf16x8v af1 = __builtin_bit_cast(bf16x8v, u32x4{pk_bf16(pvv[8], pvv[9]), pk_bf16(pvv[10], pvv[11]),
-                                                              pk_bf16(pvv[12], pvv[13]), pk_bf16(pvv[14], pvv[15])});
+        const bf16x8v af0 = pack_frag(acc[ib], 0), af1 = pack_frag(acc[ib], 8);
         const int k0 = 2 * ib * 4096, k1 = (2 * ib + 1) * 4096;
         bf16x8v b0 = tr_frag32(img, toff[0][0] + k0, toff[0][1] + k0), b1 = tr_frag32(img, toff[0][0] + k1, toff[0][1] + k1);
 #pragma unroll
@@ -1974,7 +1939,7 @@ __global__ __launch_bounds__(256) void cl_vgather_k(ClArgs a0) {
         float o[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = yv[u][k] / den;
-        ov[u] = u32x4{pk_bf16(o[0], o[1]), pk_bf16(o[2], o[3]), pk_bf16(o[4], o[5]), pk_bf16(o[6], o[7])};
+        ov[u] = u32x4{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
         if (i < m && sub == 0) {
           const int b = rr[u] / g.L, t = rr[u] - b * g.L;
           a.vnorm_out[((g.b0 + b) * (a.T + 1) + t) * a.NH + a.head] = nrm;
@@ -2093,7 +2058,7 @@ __device__ __forceinline__ void s_tile32(f32x16 (&acc)[2], const unsigned char* 
   acc[0] = f32x16{};
   acc[1] = f32x16{};
   auto rd = [&](int ib, int s) {
-    return __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + ib * 8192 + roff[s]));
+    return frag_at(img + ib * 8192 + roff[s]);
   };
   bf16x8v f0 = rd(0, 0), f1 = rd(1, 0);
 #pragma unroll
@@ -2110,10 +2075,7 @@ __device__ __forceinline__ void s_tile32(f32x16 (&acc)[2], const unsigned char* 
 // dacc[32 x 128] += P[32 x 32] . img[32 x 128] for image block ib (k-steps 2 ib, 2 ib + 1)
 __device__ __forceinline__ void pv_tile32(f32x16 (&dacc)[4], const f32x16& p, int ib, const unsigned char* img,
                                           const int (&toff)[4][2]) {
-  const bf16x8v af0 = __builtin_bit_cast(bf16x8v, u32x4{pk_bf16(p[0], p[1]), pk_bf16(p[2], p[3]),
-                                                        pk_bf16(p[4], p[5]), pk_bf16(p[6], p[7])});
-  const bf16x8v af1 = __builtin_bit_cast(bf16x8v, u32x4{pk_bf16(p[8], p[9]), pk_bf16(p[10], p[11]),
-                                                        pk_bf16(p[12], p[13]), pk_bf16(p[14], p[15])});
+  const bf16x8v af0 = pack_frag(p, 0), af1 = pack_frag(p, 8);
   const int k0 = 2 * ib * 4096, k1 = (2 * ib + 1) * 4096;
 #pragma unroll
   for (int nd = 0; nd < 4; ++nd) {

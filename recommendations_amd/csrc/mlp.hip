@@ -27,7 +27,7 @@
 // re-reads (2 x 2 x 4d B written, read twice more in the backward).
 #include <algorithm>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace lthm {
 
@@ -82,10 +82,6 @@ struct MlpWgArgs {
   int nslice;         // token slices
   int ngroup;         // hidden groups (HID / (32 NW))
 };
-
-typedef __bf16 bf16x8m __attribute__((ext_vector_type(8)));
-typedef short s16x4m __attribute__((ext_vector_type(4)));
-typedef short s16x8m __attribute__((ext_vector_type(8)));
 
 // [rows][D] bf16 images as 8-row x 32-column subtiles of 512 B (cdna_hip_programming.md T10,
 // layout (a)): byte offset of 16-B chunk c (8 columns) of row r.  Every offset is a per-lane
@@ -158,35 +154,19 @@ struct MlpDmaPlan {
 
 // A operand of 32x32x16 from a [32][D] image: lane (r = l & 31, h = l >> 5) row r, k 16 ks + 8 h ..
 template <int D>
-__device__ __forceinline__ bf16x8m mlp_row_frag(const unsigned char* img, int lane, int ks) {
-  return *reinterpret_cast<const bf16x8m*>(img + mlp_off<D>(lane & 31, 2 * ks + (lane >> 5)));
+__device__ __forceinline__ bf16x8v mlp_row_frag(const unsigned char* img, int lane, int ks) {
+  return frag_at(img + mlp_off<D>(lane & 31, 2 * ks + (lane >> 5)));
 }
 
 // B operand of 32x32x16 over the PERMUTED k order of a packed accumulator (k-step s2 of a
 // 32-row block of the image, output columns 32 t ..): element e of lane half h is image row
 // 16 s2 + 8 (e >> 2) + 4 h + (e & 3), column 32 t + (lane & 31) -- two transposed reads.
 template <int D>
-__device__ __forceinline__ bf16x8m mlp_tr_frag(const unsigned char* img, int lane, int s2, int t) {
+__device__ __forceinline__ bf16x8v mlp_tr_frag(const unsigned char* img, int lane, int s2, int t) {
   const int h = lane >> 5, q = (lane >> 2) & 3, p = lane & 3, g1 = (lane >> 4) & 1;
   const int c = 4 * t + 2 * g1 + (p >> 1);
   const int r0 = 16 * s2 + 4 * h + q;
-  typedef __attribute__((address_space(3))) s16x4m lds_s16x4;
-  const s16x4m lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + mlp_off<D>(r0, c) + 8 * (p & 1)));
-  const s16x4m hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + mlp_off<D>(r0 + 8, c) + 8 * (p & 1)));
-  const s16x8m v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8m, v);
-}
-
-// registers 8 s .. 8 s + 7 of a 32x32 accumulator, packed to bf16: the k-step s fragment
-__device__ __forceinline__ bf16x8m mlp_pack(const float* v) {
-  u32x4 w;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-  return __builtin_bit_cast(bf16x8m, w);
-}
-
-__device__ __forceinline__ f32x16 mfma32(bf16x8m a, bf16x8m b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+  return tr_frag(tr_half(img + mlp_off<D>(r0, c) + 8 * (p & 1)), tr_half(img + mlp_off<D>(r0 + 8, c) + 8 * (p & 1)));
 }
 
 // ---------------------------------------------------------------- forward
@@ -238,11 +218,11 @@ __device__ __forceinline__ void mlp_fwd_epi(const MlpArgs& a, const f32x16 (&acc
 }
 
 template <int D, int KS>
-__device__ __forceinline__ void mlp_load_x(const bf16_t* X, int64_t row, bool ok, int h, bf16x8m (&xf)[KS]) {
+__device__ __forceinline__ void mlp_load_x(const bf16_t* X, int64_t row, bool ok, int h, bf16x8v (&xf)[KS]) {
   const bf16_t* p = X + (ok ? row : 0) * D + 8 * h;
 #pragma unroll
   for (int s = 0; s < KS; ++s)
-    xf[s] = __builtin_bit_cast(bf16x8m, ok ? *reinterpret_cast<const u32x4*>(p + 16 * s) : u32x4{0u, 0u, 0u, 0u});
+    xf[s] = __builtin_bit_cast(bf16x8v, ok ? *reinterpret_cast<const u32x4*>(p + 16 * s) : u32x4{0u, 0u, 0u, 0u});
 }
 
 // ln_2 in the prologue: lane (row r, half h) holds columns 16 s + 8 h .. + 7 of its row (the B
@@ -261,7 +241,7 @@ __device__ __forceinline__ void mlp_ld8f(const float* p, bool ok, float (&v)[8])
 // the first) instead of held in 128 registers.
 template <int D, int KS>
 __device__ __forceinline__ void mlp_load_ln(const MlpArgs& a, const float* lw, const float* lb, int64_t row, bool ok,
-                                            int h, bf16x8m (&xf)[KS]) {
+                                            int h, bf16x8v (&xf)[KS]) {
   const float* p = a.x32 + (ok ? row : 0) * D + 8 * h;
   float s = 0.f;
 #pragma unroll 4
@@ -298,7 +278,7 @@ __device__ __forceinline__ void mlp_load_ln(const MlpArgs& a, const float* lw, c
     u32x4 w4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) w4[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
-    xf[k] = __builtin_bit_cast(bf16x8m, w4);
+    xf[k] = __builtin_bit_cast(bf16x8v, w4);
     if (ok && a.h_out) *reinterpret_cast<u32x4*>(a.h_out + row * D + 16 * k + 8 * h) = w4;
   }
   if (ok && h == 0) {
@@ -342,14 +322,14 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
     }
   __syncthreads();  // b1s / b2s / ln
   // S^T = W1_j . x^T (hidden units of chunk j on the registers, the token on the lane)
-  auto s_phase = [&](const unsigned char* w1, const bf16x8m(&xf)[KS]) {
+  auto s_phase = [&](const unsigned char* w1, const bf16x8v(&xf)[KS]) {
     // LDS reads one step ahead of their MFMA; the compiler fences keep the unrolled loops
     // from hoisting every read (register pressure: 2 waves per SIMD)
     f32x16 S = f32x16{};
-    bf16x8m fa = mlp_row_frag<D>(w1, lane, 0);
+    bf16x8v fa = mlp_row_frag<D>(w1, lane, 0);
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
-      const bf16x8m fn = mlp_row_frag<D>(w1, lane, k + 1 < KS ? k + 1 : k);
+      const bf16x8v fn = mlp_row_frag<D>(w1, lane, k + 1 < KS ? k + 1 : k);
       S = mfma32(fa, xf[k], S);
       fa = fn;
       asm volatile("" ::: "memory");
@@ -365,12 +345,12 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) hv[4 * m + e] = gelu_tanh(S[4 * m + e] + bb[e]);
     }
-    const bf16x8m hf0 = mlp_pack(hv), hf1 = mlp_pack(hv + 8);
-    bf16x8m b0 = mlp_tr_frag<D>(w2, lane, 0, 0), b1 = mlp_tr_frag<D>(w2, lane, 1, 0);
+    const bf16x8v hf0 = pack_frag(hv, 0), hf1 = pack_frag(hv, 8);
+    bf16x8v b0 = mlp_tr_frag<D>(w2, lane, 0, 0), b1 = mlp_tr_frag<D>(w2, lane, 1, 0);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int tn = t + 1 < NT ? t + 1 : t;
-      const bf16x8m n0 = mlp_tr_frag<D>(w2, lane, 0, tn), n1 = mlp_tr_frag<D>(w2, lane, 1, tn);
+      const bf16x8v n0 = mlp_tr_frag<D>(w2, lane, 0, tn), n1 = mlp_tr_frag<D>(w2, lane, 1, tn);
       acc[t] = mfma32(hf0, b0, acc[t]);
       acc[t] = mfma32(hf1, b1, acc[t]);
       b0 = n0;
@@ -383,7 +363,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
   for (int64_t t0 = rs; t0 < re; t0 += TR, ++tix) {
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform: a wave past the tile's rows only streams weights
-    bf16x8m xf[KS];
+    bf16x8v xf[KS];
     if (a.ln_w) mlp_load_ln<D, KS>(a, lws, a.ln_b ? lbs : nullptr, rb + r32, rb + r32 < lim, h, xf);
     else mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
     f32x16 acc[NT];
@@ -456,7 +436,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwd_k(MlpBwdArgs a) {
   for (int64_t t0 = rs; t0 < re; t0 += TR) {
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform
-    bf16x8m xf[KS], df[KS];
+    bf16x8v xf[KS], df[KS];
     mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
     mlp_load_x<D, KS>(a.dY, rb + r32, rb + r32 < lim, h, df);
     f32x16 acc[NT];
@@ -498,7 +478,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwd_k(MlpBwdArgs a) {
           *reinterpret_cast<uint2*>(stb + r32 * 32 + 8 * (m ^ ((r32 >> 2) & 3)) + 4 * h) =
               uint2{pack_bf16x2(gv[0], gv[1]), pack_bf16x2(gv[2], gv[3])};
       }
-      const bf16x8m d0 = mlp_pack(dp), d1 = mlp_pack(dp + 8);
+      const bf16x8v d0 = pack_frag(dp, 0), d1 = pack_frag(dp, 8);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         acc[t] = mfma32(d0, mlp_tr_frag<D>(w1, lane, 0, t), acc[t]);
@@ -602,7 +582,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdx_k(MlpBwdArgs a) {
     // nothing): no wave-dependent branch around the accumulator updates
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform
-    bf16x8m xf[KS], df[KS];
+    bf16x8v xf[KS], df[KS];
     mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
     mlp_load_x<D, KS>(a.dY, rb + r32, rb + r32 < lim, h, df);
     f32x16 acc[NT];
@@ -615,11 +595,11 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdx_k(MlpBwdArgs a) {
     {
       const unsigned char* w1 = img[g & (NS - 1)][0];
       const unsigned char* w2 = img[g & (NS - 1)][1];
-      bf16x8m fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w2, lane, 0);
+      bf16x8v fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w2, lane, 0);
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
         const int kn = k + 1 < KS ? k + 1 : k;
-        const bf16x8m na = mlp_row_frag<D>(w1, lane, kn), nb = mlp_row_frag<D>(w2, lane, kn);
+        const bf16x8v na = mlp_row_frag<D>(w1, lane, kn), nb = mlp_row_frag<D>(w2, lane, kn);
         S = mfma32(fa, xf[k], S);
         H = mfma32(fb, df[k], H);
         fa = na;
@@ -641,21 +621,21 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdx_k(MlpBwdArgs a) {
       const unsigned char* w1p = img[(j > 0 ? g - 1 : g) & (NS - 1)][0];  // dX: chunk g - 1's W1 (or dp = 0)
       const unsigned char* w1n = img[(g + 1) & (NS - 1)][0];              // S' / dH' of chunk g + 1
       const unsigned char* w2n = img[(g + 1) & (NS - 1)][1];
-      const bf16x8m d0 = __builtin_bit_cast(bf16x8m, dp0), d1 = __builtin_bit_cast(bf16x8m, dp1);
+      const bf16x8v d0 = __builtin_bit_cast(bf16x8v, dp0), d1 = __builtin_bit_cast(bf16x8v, dp1);
       f32x16 Sn = f32x16{}, Hn = f32x16{};
       float dl = 0.f;
       f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + 32 * j + 4 * h);
       // LDS fragments two iterations ahead (one iteration is 3 MFMAs, ~100 cycles: less than an LDS
       // read's latency under load)
-      bf16x8m fa = mlp_row_frag<D>(w1n, lane, 0), fb = mlp_row_frag<D>(w2n, lane, 0);
-      bf16x8m bt = mlp_tr_frag<D>(w1p, lane, 0, 0);
-      bf16x8m fa1 = mlp_row_frag<D>(w1n, lane, 1), fb1 = mlp_row_frag<D>(w2n, lane, 1);
-      bf16x8m bt1 = mlp_tr_frag<D>(w1p, lane, 1, 0);
+      bf16x8v fa = mlp_row_frag<D>(w1n, lane, 0), fb = mlp_row_frag<D>(w2n, lane, 0);
+      bf16x8v bt = mlp_tr_frag<D>(w1p, lane, 0, 0);
+      bf16x8v fa1 = mlp_row_frag<D>(w1n, lane, 1), fb1 = mlp_row_frag<D>(w2n, lane, 1);
+      bf16x8v bt1 = mlp_tr_frag<D>(w1p, lane, 1, 0);
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
         const int kn = k + 2 < KS ? k + 2 : KS - 1;
-        const bf16x8m na = mlp_row_frag<D>(w1n, lane, kn), nb = mlp_row_frag<D>(w2n, lane, kn);
-        const bf16x8m nt_ = mlp_tr_frag<D>(w1p, lane, kn & 1, kn >> 1);
+        const bf16x8v na = mlp_row_frag<D>(w1n, lane, kn), nb = mlp_row_frag<D>(w2n, lane, kn);
+        const bf16x8v nt_ = mlp_tr_frag<D>(w1p, lane, kn & 1, kn >> 1);
         Sn = mfma32(fa, xf[k], Sn);
         acc[k >> 1] = mfma32((k & 1) ? d1 : d0, bt, acc[k >> 1]);
         Hn = mfma32(fb, df[k], Hn);
@@ -686,7 +666,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdx_k(MlpBwdArgs a) {
     }
     {  // dX of the tile's last chunk (g - 1)
       const unsigned char* w1p = img[(g - 1) & (NS - 1)][0];
-      const bf16x8m d0 = __builtin_bit_cast(bf16x8m, dp0), d1 = __builtin_bit_cast(bf16x8m, dp1);
+      const bf16x8v d0 = __builtin_bit_cast(bf16x8v, dp0), d1 = __builtin_bit_cast(bf16x8v, dp1);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         acc[t] = mfma32(d0, mlp_tr_frag<D>(w1p, lane, 0, t), acc[t]);
@@ -748,7 +728,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform
     const bool full = rb + 32 <= lim;
-    bf16x8m xf[KS], df[KS];
+    bf16x8v xf[KS], df[KS];
     mlp_load_x<D, KS>(a.X, rb + r32, rb + r32 < lim, h, xf);
     mlp_load_x<D, KS>(a.dY, rb + r32, rb + r32 < lim, h, df);
     const bool more_tiles = t0 + TR < re;
@@ -767,11 +747,11 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_bwdp_k(MlpBwdArgs a) {
       const unsigned char* w1 = img[g & 1][0];
       const unsigned char* w2 = img[g & 1][1];
       f32x16 S = f32x16{}, dH = f32x16{};
-      bf16x8m fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w2, lane, 0);
+      bf16x8v fa = mlp_row_frag<D>(w1, lane, 0), fb = mlp_row_frag<D>(w2, lane, 0);
 #pragma unroll
       for (int k = 0; k < KS; ++k) {
         const int kn = k + 1 < KS ? k + 1 : k;
-        const bf16x8m na = mlp_row_frag<D>(w1, lane, kn), nb = mlp_row_frag<D>(w2, lane, kn);
+        const bf16x8v na = mlp_row_frag<D>(w1, lane, kn), nb = mlp_row_frag<D>(w2, lane, kn);
         S = mfma32(fa, xf[k], S);
         dH = mfma32(fb, df[k], dH);
         fa = na;
@@ -845,11 +825,11 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_wgrad_k(MlpWgArgs a) {
   const int64_t t_lo = ntile_all * slice / a.nslice, t_hi = ntile_all * (slice + 1) / a.nslice;
   const int j0 = (grp * NW + wave) * 32;  // this wave's hidden units j0 .. j0 + 31
   // B operands over d of the wave's W1 rows: lane -> unit j0 + r32, k 16 k + 8 h ..
-  bf16x8m w1f[KS];
+  bf16x8v w1f[KS];
   {
     const bf16_t* p1 = a.W1 + (int64_t)(j0 + r32) * D + 8 * h;
 #pragma unroll
-    for (int k = 0; k < KS; ++k) w1f[k] = __builtin_bit_cast(bf16x8m, *reinterpret_cast<const u32x4*>(p1 + 16 * k));
+    for (int k = 0; k < KS; ++k) w1f[k] = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(p1 + 16 * k));
   }
   unsigned char* w2i = wimg[wave];
   const float bj = a.b1 ? a.b1[j0 + r32] : 0.f;
@@ -887,14 +867,14 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_wgrad_k(MlpWgArgs a) {
   if (nt > 1) stage(t_lo + 1, 1);
   f32x16 S = f32x16{}, H = f32x16{};
   auto phase_a = [&](const unsigned char* xn, const unsigned char* yn) {
-    bf16x8m fa = mlp_row_frag<D>(xn, lane, 0), fb = mlp_row_frag<D>(yn, lane, 0), fw = mlp_row_frag<D>(w2i, lane, 0);
+    bf16x8v fa = mlp_row_frag<D>(xn, lane, 0), fb = mlp_row_frag<D>(yn, lane, 0), fw = mlp_row_frag<D>(w2i, lane, 0);
     S = f32x16{};
     H = f32x16{};
 #pragma unroll
     for (int k = 0; k < KS; ++k) {
       const int kn = k + 1 < KS ? k + 1 : k;
-      const bf16x8m na = mlp_row_frag<D>(xn, lane, kn), nb = mlp_row_frag<D>(yn, lane, kn);
-      const bf16x8m nw = mlp_row_frag<D>(w2i, lane, kn);
+      const bf16x8v na = mlp_row_frag<D>(xn, lane, kn), nb = mlp_row_frag<D>(yn, lane, kn);
+      const bf16x8v nw = mlp_row_frag<D>(w2i, lane, kn);
       S = mfma32(fa, w1f[k], S);
       H = mfma32(fb, fw, H);
       fa = na;
@@ -919,16 +899,16 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_wgrad_k(MlpWgArgs a) {
       const unsigned char* xi = img[ip % NS][0];
       const unsigned char* yi = img[ip % NS][1];
       const int nv = (int)min((int64_t)32, a.M - (t_lo + i) * 32);  // valid token rows of tile i
-      const bf16x8m d0 = __builtin_bit_cast(bf16x8m, dp0), d1 = __builtin_bit_cast(bf16x8m, dp1);
-      const bf16x8m g0 = __builtin_bit_cast(bf16x8m, gp0), g1 = __builtin_bit_cast(bf16x8m, gp1);
+      const bf16x8v d0 = __builtin_bit_cast(bf16x8v, dp0), d1 = __builtin_bit_cast(bf16x8v, dp1);
+      const bf16x8v g0 = __builtin_bit_cast(bf16x8v, gp0), g1 = __builtin_bit_cast(bf16x8v, gp1);
       float gl = 0.f, dl = 0.f;
-      bf16x8m b0 = mlp_tr_frag<D>(xi, lane, 0, 0), b1 = mlp_tr_frag<D>(xi, lane, 1, 0);
+      bf16x8v b0 = mlp_tr_frag<D>(xi, lane, 0, 0), b1 = mlp_tr_frag<D>(xi, lane, 1, 0);
 #pragma unroll
       for (int k = 0; k < 2 * NT; ++k) {  // step k: output tile t = k / 2, half u = k % 2 (dW1, dW2^T)
         const int t = k >> 1, u = k & 1, tn = t + 1 < NT ? t + 1 : t;
         const unsigned char* nimg = u == 0 ? yi : xi;
         const int nt_ = u == 0 ? t : tn;
-        const bf16x8m n0 = mlp_tr_frag<D>(nimg, lane, 0, nt_), n1 = mlp_tr_frag<D>(nimg, lane, 1, nt_);
+        const bf16x8v n0 = mlp_tr_frag<D>(nimg, lane, 0, nt_), n1 = mlp_tr_frag<D>(nimg, lane, 1, nt_);
         if (u == 0) {
           acc1[t] = mfma32(d0, b0, acc1[t]);
           acc1[t] = mfma32(d1, b1, acc1[t]);
@@ -980,8 +960,8 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_wgrad_k(MlpWgArgs a) {
   if (nt > 0) {  // phase B of the last tile
     const unsigned char* xi = img[(nt - 1) % NS][0];
     const unsigned char* yi = img[(nt - 1) % NS][1];
-    const bf16x8m d0 = __builtin_bit_cast(bf16x8m, dp0), d1 = __builtin_bit_cast(bf16x8m, dp1);
-    const bf16x8m g0 = __builtin_bit_cast(bf16x8m, gp0), g1 = __builtin_bit_cast(bf16x8m, gp1);
+    const bf16x8v d0 = __builtin_bit_cast(bf16x8v, dp0), d1 = __builtin_bit_cast(bf16x8v, dp1);
+    const bf16x8v g0 = __builtin_bit_cast(bf16x8v, gp0), g1 = __builtin_bit_cast(bf16x8v, gp1);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       acc1[t] = mfma32(d0, mlp_tr_frag<D>(xi, lane, 0, t), acc1[t]);
@@ -1045,17 +1025,6 @@ __global__ __launch_bounds__(256) void mlp_wgrad_fold_k(const float* __restrict_
 
 using namespace lthm;
 
-static int mlp_cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 extern "C" int lthm_mlp_supported(int32_t D, int32_t HID) {
   return (D == 128 || D == 256) && HID >= 32 && HID % 32 == 0 && HID <= 8192;
 }
@@ -1102,7 +1071,7 @@ static int mlp_fwd_launch(MlpArgs a, int D, void* stream) {
   // 8 waves: one workgroup per CU, 256-row tiles
   constexpr int NW = 8;
   a.ntiles = (int)((M + 32 * NW - 1) / (32 * NW));
-  const int grid = (int)std::min<int64_t>(a.ntiles, (int64_t)mlp_cu_count());
+  const int grid = (int)std::min<int64_t>(a.ntiles, (int64_t)cu_count());
   if (D == 256) hipLaunchKernelGGL((mlp_fwd_k<256, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
   else hipLaunchKernelGGL((mlp_fwd_k<128, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
   LTHM_CHECK_LAUNCH();
@@ -1127,7 +1096,7 @@ extern "C" int lthm_mlp_bwd(const void* X, const void* dY, int64_t M, int32_t D,
   hipStream_t s = (hipStream_t)stream;
   constexpr int NW = 4;
   const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)mlp_cu_count());
+  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
   if (D == 256) hipLaunchKernelGGL((mlp_bwd_k<256, NW, true>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwd_k<128, NW, true>), dim3(grid), dim3(64 * NW), 0, s, a);
   LTHM_CHECK_LAUNCH();
@@ -1141,7 +1110,7 @@ static void mlp_wgrad_geometry(int64_t M, int D, int HID, int* nslice, int* ngro
   *ngroup = HID / (32 * MLP_WG_NW);
   const int64_t ntile = (M + 31) / 32;
   // one workgroup per CU: slices x groups ~ the CU count, at least one token tile per slice
-  int ns = std::max(1, mlp_cu_count() / std::max(1, *ngroup));
+  int ns = std::max(1, cu_count() / std::max(1, *ngroup));
   *nslice = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ntile));
   (void)D;
 }
@@ -1207,7 +1176,7 @@ extern "C" int lthm_mlp_bwd_dx(const void* X, const void* dY, int64_t M, int32_t
   hipStream_t s = (hipStream_t)stream;
   constexpr int NW = 4;
   const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)mlp_cu_count());
+  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
   LTHM_REQUIRE(HID <= 4096);
   if (D == 256) hipLaunchKernelGGL((mlp_bwdx_k<256, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwdx_k<128, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
@@ -1230,7 +1199,7 @@ extern "C" int lthm_mlp_bwd_hidden(const void* X, const void* dY, int64_t M, int
   hipStream_t s = (hipStream_t)stream;
   constexpr int NW = 8;
   const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)mlp_cu_count());
+  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
   if (D == 256) hipLaunchKernelGGL((mlp_bwdp_k<256, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwdp_k<128, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   LTHM_CHECK_LAUNCH();

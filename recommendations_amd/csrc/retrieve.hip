@@ -13,14 +13,13 @@
 // and the key 0 is free to mean "empty".  Selection never depends on the order in which the
 // LDS atomics hand out slots (a prune writes each key at its rank), so the result is a pure
 // function of the inputs.  No global atomics anywhere.
-#include "common.hpp"
+#include "mfma.hpp"
 
 #include <cmath>
 
 namespace lthm {
 namespace {
 
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
 typedef unsigned long long u64;
 
 constexpr int RT_D = 128;     // LOSS_DE: the one embedding width
@@ -46,10 +45,6 @@ struct RetrShared {
 static_assert(sizeof(RetrShared) <= 160 * 1024, "LDS budget");
 
 __device__ __attribute__((aligned(16))) unsigned char retr_zero_row[256];
-
-// the 32x32x16 tile engine's image (as loss.hip): chunk ch of row r at slot ch ^ swz32(r)
-__device__ __forceinline__ int swz32(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ int ko32(int row, int ch) { return row * 256 + ((ch ^ swz32(row)) << 4); }
 
 __device__ __forceinline__ u64 retr_key(float s, int row) {
   uint32_t u = __float_as_uint(s + 0.f);  // -0 -> +0: equal scores get equal images
@@ -230,8 +225,8 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrArgs a) {
     f32x16 acc = {};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      const bf16x8v af = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(img + roff[s]));
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, qf[s], acc, 0, 0, 0);
+      const bf16x8v af = frag_at(img + roff[s]);
+      acc = mfma32(af, qf[s], acc);
     }
     // first catalogue row of this lane's elements: element v is row rb + 8 (v >> 2) + (v & 3)
     const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;

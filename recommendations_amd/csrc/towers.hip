@@ -12,7 +12,7 @@
 //   * history flip (models/lthm/sequence/encoder.py:52-54, 60-61).
 #include <algorithm>
 
-#include "common.hpp"
+#include "mfma.hpp"
 
 namespace lthm {
 
@@ -164,10 +164,6 @@ __global__ __launch_bounds__(256) void ptower_fwd_k(lthm_ptower_desc d, int tota
   }
 }
 
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
 // swizzled row-major [rows, D] bf16 LDS image (16-byte chunks XOR row group) and
 // its ds_read_tr16_b64 fragment B[k = 8(lane>>4) + i][n = nb + (lane&15)]
 template <int D>
@@ -195,10 +191,7 @@ __device__ __forceinline__ bf16x8v ct_tr_frag(const unsigned char* img, int nb, 
   const int ch = (nb >> 3) + (p >> 1);
   const unsigned char* a0 = img + ct_off<D>(kr, ch) + 8 * (p & 1);
   const unsigned char* a1 = img + ct_off<D>(kr + 4, ch) + 8 * (p & 1);
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a1));
-  s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8v, v);
+  return tr_frag(a0, a1);
 }
 
 // ------------------------------------------------------------------ product-tower bucket rows
@@ -545,9 +538,9 @@ __global__ __launch_bounds__(512) void ptower_emb_mfma_k(lthm_ptower_desc d, int
       split8(wN + (nb0 + f * 16 + (lane & 15)) * DinP + kb, valid, wh, wl);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
-        acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[mt], wh, acc[mt][f], 0, 0, 0);
-        acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh[mt], wl, acc[mt][f], 0, 0, 0);
-        acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl[mt], wh, acc[mt][f], 0, 0, 0);
+        acc[mt][f] = mfma16(xh[mt], wh, acc[mt][f]);
+        acc[mt][f] = mfma16(xh[mt], wl, acc[mt][f]);
+        acc[mt][f] = mfma16(xl[mt], wh, acc[mt][f]);
       }
     }
   }
@@ -591,7 +584,7 @@ __global__ __launch_bounds__(512) void ptower_emb_mfma_k(lthm_ptower_desc d, int
       const bf16x8v bf = ct_tr_frag<D>(img, nb0 + f * 16, lane);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
-        acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], bf, acc[mt][f], 0, 0, 0);
+        acc[mt][f] = mfma16(af[mt], bf, acc[mt][f]);
     }
     if constexpr (!DMA) {
       if (more) store(cur ^ 1);
@@ -869,12 +862,12 @@ __global__ __launch_bounds__(512) void cve_tab_bwd_k(const uint16_t* __restrict_
     for (int f = 0; f < NFW; ++f) {
       const bf16x8v bh = ct_tr_frag<D>(img, nb0 + f * 16, lane);
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], bh, acc[mt][f], 0, 0, 0);
+      for (int mt = 0; mt < MT; ++mt) acc[mt][f] = mfma16(af[mt], bh, acc[mt][f]);
       if constexpr (F32) {
         const bf16x8v bl = ct_tr_frag<D>(img + IMG, nb0 + f * 16, lane);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-          acc[mt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[mt], bl, acc[mt][f], 0, 0, 0);
+          acc[mt][f] = mfma16(af[mt], bl, acc[mt][f]);
       }
     }
     if (st + 1 < nsteps) store(cur ^ 1);
@@ -1203,17 +1196,6 @@ extern "C" int lthm_segmented_table_bwd(const uint16_t* rows, int32_t nidx, int3
   return 0;
 }
 
-static int lthm_tower_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  return cus;
-}
-
 // resident 512-thread blocks per CU of one cve_tab_bwd_k form (registers and LDS), cached
 template <int DD>
 static int cve_tab_bpc_d(bool f32, bool gen, size_t sh) {
@@ -1251,7 +1233,7 @@ static int launch_table_mfma(const uint16_t* rows, int32_t nidx, CveTiles& ct, S
   // ~200 VGPRs, i.e. one 512-thread block per CU).  522 blocks for 256 slots ran three
   // rounds, the last with ten blocks.
   const int bpc = cve_tab_blocks_per_cu(D, f32, gen, sh);
-  int64_t gz = std::max<int64_t>(1, (int64_t)lthm_tower_cus() * bpc / nt);
+  int64_t gz = std::max<int64_t>(1, (int64_t)cu_count() * bpc / nt);
   gz = std::min<int64_t>(gz, (n + 1023) / 1024);
   gz = std::min<int64_t>(gz, workspace ? workspace_bytes / zbytes : (int64_t)1);
   if (gz < 2) gz = 1;
