@@ -208,6 +208,11 @@ def test_layernorm_golden(dev):
                                             # windowed long-sequence path (T' > 256; C5 has T' = 513)
                                             (2, 513, 2, 64, True), (3, 300, 1, 64, False), (17, 257, 1, 32, True),
                                             (1, 400, 2, 128, True), (20, 520, 1, 64, True),
+                                            # E = 64 past the resident-image kernels (see
+                                            # test_attention_e64_resident_limits): T' = 553 the fwd32
+                                            # forward with the windowed backward, 585 and 641 both windowed
+                                            (2, 553, 1, 64, True), (2, 585, 1, 64, True), (2, 641, 1, 64, True),
+                                            (2, 641, 1, 64, False),
                                             # the persistent double-buffered E = 64 backward (B >= 2 x the
                                             # workgroups per head): tail mode, uneven entries per slot
                                             (300, 129, 4, 64, True), (520, 65, 1, 64, False), (600, 100, 2, 64, True)])
@@ -238,6 +243,20 @@ def test_attention_vs_oracle(dev, B, T, H, E, causal):
             assert float(got.abs().max()) < 1e-4
         else:
             check('got, want', relerr(got, want), 1e-2)
+
+
+def test_attention_e64_resident_limits(dev):
+    """Which E = 64 kernels the T' = 553 / 585 / 641 cases of test_attention_vs_oracle run.
+    lthm_attn_packed_ok is the dispatcher's own fwd32_ok && bwd32l_ok: it holds up to T' = 552,
+    where the backward's two images and float region (bwd32l_lds) last fit in 160 KiB of LDS,
+    so 553 takes attn_delta_k / attn_bwd_rows_win_k / attn_bwd_cols_win_k.  The forward's K and V
+    images alone are 2 T' x 128 B, more than 160 KiB from T' = 641 on whatever the bias copies
+    take, so 641 takes attn_fwd_win_k as well (with the copies, fwd32_lds, from T' = 585)."""
+    from recommendations_amd._lib import load
+    lib = load()
+    assert lib.lthm_attn_packed_ok(552, 64) == 1 and lib.lthm_attn_packed_ok(553, 64) == 0
+    assert all(lib.lthm_attn_packed_ok(t, 64) == 0 for t in (585, 641))
+    assert 2 * 641 * 128 > 160 * 1024
 
 
 def test_attention_persistent_bwd_matches_default(dev, tmp_path):
