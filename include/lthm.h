@@ -848,6 +848,24 @@ typedef struct lthm_retrieve_desc {
 /* workspace bytes of lthm_retrieve_topk, or -1 for sizes it refuses */
 int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows);
 int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream);
+/* The same with per-query exclusion: the k best rows a query has not named.
+ *   rows   int32 [Q, X], contiguous, 1 <= X <= 1024, each query's entries in any order;
+ *          entries < 0 or >= N are ignored (-1 pads a short list), duplicates are allowed
+ * An excluded row is scored as -inf: it never appears in scores / rows (where fewer than k rows
+ * remain the tail is -inf / -1) and never counts in rank.  Order and tie rule are unchanged, and
+ * the outputs do not depend on the order of a list.  The target is never excluded as a target:
+ * target_score is the plain f32 dot and rank = #{j != target, j not excluded : s[q, j] >
+ * s[q, target]}, also where a query lists its own target.  A query with no valid entry gets
+ * exactly what lthm_retrieve_topk returns. */
+typedef struct lthm_retrieve_excl {
+  const int32_t* rows;
+  int64_t X;
+} lthm_retrieve_excl;
+/* workspace bytes of lthm_retrieve_topk_excl (the plain call's plus the sorted lists), or -1
+ * for what lthm_retrieve_ws_bytes refuses and for X outside 1..1024 */
+int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows, int64_t X);
+/* x == NULL is lthm_retrieve_topk; otherwise d->ws_bytes must cover lthm_retrieve_excl_ws_bytes */
+int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -13,9 +13,20 @@
 // and the key 0 is free to mean "empty".  Selection never depends on the order in which the
 // LDS atomics hand out slots (a prune writes each key at its rank), so the result is a pure
 // function of the inputs.  No global atomics anywhere.
+//
+// Exclusion (lthm_retrieve_topk_excl): every query may name up to RT_XMAX catalogue rows that
+// are scored as -inf, so that they take none of the k slots and never count in the rank.
+//   retr_excl_prep_k  sorts each query's list ascending into the workspace ([Q, X + 1] with
+//                     ignored entries and the sentinel at index X set to INT_MAX);
+//   retr_topk_k<true> a lane owns one query and a tile covers 64 consecutive rows, so the lane
+//                     walks its sorted list with one cursor and sets the accumulator elements
+//                     of excluded rows to -inf before the count and the filter see them.
+// The plain call runs retr_topk_k<false>, which holds none of this.
 #include "mfma.hpp"
 
+#include <climits>
 #include <cmath>
+#include <type_traits>
 
 namespace lthm {
 namespace {
@@ -92,6 +103,50 @@ struct RetrArgs {
   int k;
 };
 
+constexpr int RT_XMAX = 1024;  // longest exclusion list of a query
+// retr_topk_k<true> takes the plain arguments and the sorted lists behind them, so that the
+// plain instantiation's argument block is the one it always had
+struct RetrExclArgs : RetrArgs {
+  const int* xs;  // [Q, xstride] ascending; ignored entries and the last one are INT_MAX
+  int xstride;    // X + 1
+};
+
+// ---------------------------------------------------------------- exclusion lists, sorted
+// One block per query: a bitonic sort of the list, padded to a power of two with INT_MAX, in
+// LDS.  Entries outside [0, N) become INT_MAX (no catalogue row: N < 2^31), so they sort behind
+// every row and the first X sorted values hold every valid entry.
+__global__ __launch_bounds__(256) void retr_excl_prep_k(const int* __restrict__ rows, int X, int P, int64_t N,
+                                                        int* __restrict__ xs) {
+  __shared__ int buf[RT_XMAX];
+  const int tid = threadIdx.x;
+  const int* src = rows + (int64_t)blockIdx.x * X;
+  for (int i = tid; i < P; i += 256) {
+    int r = INT_MAX;
+    if (i < X) {
+      r = src[i];
+      if (r < 0 || r >= N) r = INT_MAX;
+    }
+    buf[i] = r;
+  }
+  __syncthreads();
+  for (int len = 2; len <= P; len <<= 1) {
+    for (int j = len >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P >> 1); t += 256) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const int x = buf[lo], y = buf[hi];
+        if ((x > y) == ((lo & len) == 0)) {
+          buf[lo] = y;
+          buf[hi] = x;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  int* dst = xs + (int64_t)blockIdx.x * (X + 1);
+  for (int i = tid; i < X; i += 256) dst[i] = buf[i];
+  if (tid == 0) dst[X] = INT_MAX;  // the sentinel: a cursor never reads past it
+}
+
 // ---------------------------------------------------------------- queries -> bf16, target score
 // 16 lanes per query, 8 contiguous elements per lane (rownorm_v8_k's arithmetic for D = 128)
 template <typename TQ>
@@ -144,7 +199,14 @@ __global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int
 // ---------------------------------------------------------------- scores + threshold selection
 // Wave w: queries 32 (w & 1) + (lane & 31) of the tile (MFMA columns, so every per-query value
 // is a per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3).
-__global__ __launch_bounds__(256) void retr_topk_k(RetrArgs a) {
+//
+// EXCL: the lane keeps a cursor into its query's sorted exclusion list (xp, with the entry it
+// points at in nx).  The cursor starts at the first entry >= row_lo; every tile consumes the
+// entries below its end, so at a tile's start nx is at or past the tile's first row and a
+// tile without excluded rows costs one compare.  INT_MAX ends every list and is never below a
+// tile's end (<= N < 2^31), so the cursor stops on it.
+template <bool EXCL>
+__global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, RetrExclArgs, RetrArgs> a) {
   __shared__ __attribute__((aligned(16))) RetrShared sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
@@ -180,6 +242,21 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrArgs a) {
     tr = a.trow[q];
     if (tr >= 0 && tr < a.N) ts = a.tscore[q];
     else tr = -1;
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // a query past Q excludes nothing and reads nothing
+  if constexpr (EXCL) {
+    if (live) {
+      const int* xl = a.xs + q * a.xstride;
+      int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (xl[mid] < row_lo) lo = mid + 1;
+        else hi = mid;
+      }
+      xp = xl + lo;
+      nx = *xp;
+    }
   }
   int roff[8];
 #pragma unroll
@@ -234,6 +311,23 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrArgs a) {
 #pragma unroll
       for (int v = 0; v < 16; ++v)
         if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if constexpr (EXCL) {
+      // the tile's excluded rows, folded into a mask of this lane's own elements (the target's
+      // mapping below: 0 <= rel < 32 and !(rel & 4) are this lane's rows), then applied with
+      // static indices: an excluded row scores -inf for the count and the filter alike
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
     }
     float mx = acc[0];
 #pragma unroll
@@ -348,14 +442,25 @@ extern "C" int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32
   return up256(Q * RT_D * 2) + up256(nslab * Q * k * 8) + up256(nslab * Q * 4);
 }
 
-extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
+extern "C" int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows, int64_t X) {
+  const int64_t base = lthm_retrieve_ws_bytes(Q, N, k, slab_rows);
+  if (base < 0 || X < 1 || X > RT_XMAX) return -1;
+  return base + up256(Q * (X + 1) * 4);
+}
+
+namespace {
+
+// both entry points: x == nullptr is the plain call
+int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
   LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
   LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
-  const int64_t need = lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  const int64_t need = x ? lthm_retrieve_excl_ws_bytes(d->Q, d->N, d->k, d->slab_rows, x->X)
+                         : lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
   const int64_t Q = d->Q, N = d->N;
   const int64_t sr = retr_slab_rows(Q, N, d->k, d->slab_rows);
@@ -374,7 +479,7 @@ extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
     hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, Q, d->normalize_q, qn,
                        items, N, d->target_row, d->target_score);
   LTHM_CHECK_LAUNCH();
-  RetrArgs a;
+  RetrExclArgs a;
   a.items = items;
   a.qn = qn;
   a.trow = d->target_row;
@@ -385,10 +490,34 @@ extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
   a.N = N;
   a.slab_rows = sr;
   a.k = d->k;
-  hipLaunchKernelGGL(retr_topk_k, dim3((unsigned)((Q + RT_QT - 1) / RT_QT), (unsigned)nslab), dim3(256), 0, s, a);
+  a.xs = nullptr;
+  a.xstride = 0;
+  const dim3 tgrid((unsigned)((Q + RT_QT - 1) / RT_QT), (unsigned)nslab);
+  if (x) {
+    // the sorted lists live behind the plain call's workspace
+    int* xs = (int*)(ws + lthm_retrieve_ws_bytes(Q, N, d->k, d->slab_rows));
+    const int X = (int)x->X;
+    int P = 1;
+    while (P < X) P <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)Q), dim3(256), 0, s, x->rows, X, P, N, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+    hipLaunchKernelGGL(retr_topk_k<true>, tgrid, dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(retr_topk_k<false>, tgrid, dim3(256), 0, s, static_cast<const RetrArgs&>(a));
+  }
   LTHM_CHECK_LAUNCH();
   hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, Q, N,
                      (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
   LTHM_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) { return retr_launch(d, nullptr, stream); }
+
+extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
+  return retr_launch(d, x, stream);
 }

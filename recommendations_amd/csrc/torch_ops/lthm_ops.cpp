@@ -17,6 +17,7 @@
 //   lthm::activation    QuickGELU / GELU(tanh)      commons/layers.py:9-11 (+ backward)
 //   lthm::item_artifact ModelWrapper.forward        embedding_module_gen.py:32-41 (fused)
 //   lthm::retrieve_topk full-catalogue top-K        (build-defined, csrc/retrieve.hip; forward only)
+//   lthm::retrieve_topk_excl  the same without each query's listed rows
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -410,7 +411,9 @@ Tensor item_artifact_cuda(const Tensor& ids_, const Tensor& W, int64_t K, int64_
 }
 
 // ---------------------------------------------------------------- full-catalogue top-K (forward only)
-std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q) {
+// excl: the exclusion lists (int32 [Q, X]) of retrieve_topk_excl, or null for the plain op
+std::tuple<Tensor, Tensor> retrieve_topk_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
+                                              const Tensor* excl) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
@@ -420,7 +423,18 @@ std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q_, const Tensor& it
   TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk takes a non-empty catalogue and query set");
   auto q = q_.contiguous(), items = items_.contiguous();
   const int64_t Q = q.size(0), N = items.size(0);
-  const int64_t need = lthm_retrieve_ws_bytes(Q, N, (int32_t)k, 0);
+  Tensor xr;
+  if (excl) {
+    on_gpu(*excl, "exclude_rows");
+    TORCH_CHECK(excl->scalar_type() == at::kInt && excl->dim() == 2 && excl->size(0) == Q,
+                "exclude_rows must be int32 [Q, X]");
+    TORCH_CHECK(excl->size(1) >= 1 && excl->size(1) <= 1024, "exclude_rows takes 1..1024 rows per query, got ",
+                excl->size(1));
+    TORCH_CHECK(excl->device() == q.device(), "exclude_rows must be on the queries' device");
+    xr = excl->contiguous();
+  }
+  const int64_t need = excl ? lthm_retrieve_excl_ws_bytes(Q, N, (int32_t)k, 0, xr.size(1))
+                            : lthm_retrieve_ws_bytes(Q, N, (int32_t)k, 0);
   TORCH_CHECK(need >= 0, "retrieve_topk: unsupported sizes Q=", Q, " N=", N);
   auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
   auto rows = at::empty({Q, k}, q.options().dtype(at::kInt));
@@ -437,8 +451,24 @@ std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q_, const Tensor& it
   d.k = (int32_t)k;
   d.q_dtype = dcode(q);
   d.normalize_q = normalize_q ? 1 : 0;
-  hip_ok(lthm_retrieve_topk(&d, cur_stream()), "lthm_retrieve_topk");
+  if (excl) {
+    lthm_retrieve_excl x = {};
+    x.rows = xr.data_ptr<int32_t>();
+    x.X = xr.size(1);
+    hip_ok(lthm_retrieve_topk_excl(&d, &x, cur_stream()), "lthm_retrieve_topk_excl");
+  } else {
+    hip_ok(lthm_retrieve_topk(&d, cur_stream()), "lthm_retrieve_topk");
+  }
   return std::make_tuple(scores, rows);
+}
+
+std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q) {
+  return retrieve_topk_impl(q, items, k, normalize_q, nullptr);
+}
+
+std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                   const Tensor& exclude_rows) {
+  return retrieve_topk_impl(q, items, k, normalize_q, &exclude_rows);
 }
 
 int64_t abi_version() { return lthm_abi_version(); }
@@ -459,6 +489,9 @@ TORCH_LIBRARY(lthm, m) {
       "item_artifact(Tensor ids, Tensor weight, int K, int mode, Tensor mask_weight, int mask_K, Tensor w1, "
       "Tensor b1, Tensor w2, Tensor b2, ScalarType out_dtype=float) -> Tensor");
   m.def("retrieve_topk(Tensor q, Tensor items, int k, bool normalize_q) -> (Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_excl(Tensor q, Tensor items, int k, bool normalize_q, Tensor exclude_rows) -> "
+      "(Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -469,6 +502,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("activation", &activation_cuda);
   m.impl("item_artifact", &item_artifact_cuda);
   m.impl("retrieve_topk", &retrieve_topk_cuda);
+  m.impl("retrieve_topk_excl", &retrieve_topk_excl_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -1650,18 +1650,27 @@ def mse_loss(y, x):
 RETRIEVE_WIDTH = 128          # csrc/retrieve.hip RT_D (= the loss kernels' LOSS_DE)
 RETRIEVE_MAX_K = 128          # RT_KMAX
 RETRIEVE_MIN_SLAB_ROWS = 64   # RT_IT: the smallest (and the granularity of) slab_rows
+RETRIEVE_MAX_EXCLUDE = 1024   # RT_XMAX: the longest exclusion list of a query
 
 
-def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0):
+def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
+                  exclude_rows=None):
     """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
 
     q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
     Returns (scores f32 [Q, k], rows int32 [Q, k], rank int32 [Q] | None, target_score f32 [Q] |
     None), each query's entries sorted by (score descending, row ascending) and padded with
-    -inf / -1 where N < k.  Forward only; no [Q, N] buffer is formed."""
+    -inf / -1 where N < k.  Forward only; no [Q, N] buffer is formed.
+
+    exclude_rows int32 [Q, X] (contiguous, 1 <= X <= 1024) or None: rows query q must not
+    return, in any order; entries outside [0, N) are ignored (-1 pads).  An excluded row is
+    scored as -inf: it takes none of the k slots (the tail is -inf / -1 where fewer than k rows
+    remain) and does not count in rank.  The target is never excluded as a target: target_score
+    stays the plain dot, and rank counts the non-excluded rows other than the target scoring
+    above it, also for a target inside its own list."""
     import ctypes
     from ._lib import STRUCTS
-    require_gpu(q, items, target_rows)
+    require_gpu(q, items, target_rows, exclude_rows)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"retrieve_topk takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
     _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"retrieve_topk takes [Q, {RETRIEVE_WIDTH}] queries")
@@ -1671,6 +1680,16 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     need = load().lthm_retrieve_ws_bytes(Q, N, k, int(slab_rows))
     _check(need >= 0, f"retrieve_topk: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
                       f"that cuts N={N} into at most 65535 slabs")
+    X = 0
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == Q,
+               f"exclude_rows must be int32 [Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, Q={Q})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
+        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
+        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
+        need = load().lthm_retrieve_excl_ws_bytes(Q, N, k, int(slab_rows), X)
+        _check(need >= 0, f"retrieve_topk: no workspace size for Q={Q} N={N} k={k} X={X}")
     dev = q.device
     scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
     rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
@@ -1685,6 +1704,13 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
     d.workspace, d.ws_bytes = ptr(ws), need
     d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = Q, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
-    call("lthm_retrieve_topk", ctypes.addressof(d), stream(), _key="retr_topk_k", _work=2.0 * Q * N * RETRIEVE_WIDTH,
-         _unit="flop", _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8))
+    nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8)
+    if exclude_rows is None:
+        call("lthm_retrieve_topk", ctypes.addressof(d), stream(), _key="retr_topk_k",
+             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
+    else:
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
+        call("lthm_retrieve_topk_excl", ctypes.addressof(d), ctypes.addressof(x), stream(), _key="retr_topk_excl_k",
+             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * Q * X)
     return scores, rows, rank, tscore

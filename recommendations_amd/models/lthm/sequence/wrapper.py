@@ -345,30 +345,46 @@ class LTHMModelWrapper(BaseModelWrapper):
         return lthm_metrics(stats.cpu().numpy(), offs, step_type, self._metrics_k_all, B, T, mbs, whole)
 
     @torch.no_grad()
-    def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0) -> Dict[str, torch.Tensor]:
+    def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
+                 exclude_history: bool = False) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
-        f32 [B, k], sorted by (score descending, catalogue row ascending)."""
-        y = self.forward(batch)["next_token_emb"]
-        q = y[:, -1, head].contiguous()
+        f32 [B, k], sorted by (score descending, catalogue row ascending).  With
+        ``exclude_history`` sequence b never gets an item of its own ``current_token_ids[b, :]``
+        back (T <= 1024): the k best items it has not interacted with."""
+        out = self.forward(batch)
+        q = out["next_token_emb"][:, -1, head].contiguous()
         if q.dtype not in (torch.float32, torch.bfloat16):
             q = q.float()
-        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True)
+        seen = None
+        if exclude_history:
+            seen = out["current_token_ids"]
+            if seen.shape[1] > K.RETRIEVE_MAX_EXCLUDE:
+                raise ValueError(f"exclude_history takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens "
+                                 f"(T = {seen.shape[1]})")
+        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen)
         return {"item_ids": item_ids, "scores": scores}
 
     @torch.no_grad()
-    def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0) -> Dict[str, float]:
+    def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0,
+                          exclude_seen: bool = False) -> Dict[str, float]:
         """Hit rate and hit position of one forward against the whole catalogue: the in-batch
         metrics of wrapper.py:228-238 with every catalogue item as a negative.  Queries are the
         positions t whose target ``current_token_ids[:, t + lookahead[head]]`` is a non-pad
         token (wrapper.py:155-163) the catalogue holds; the hit position is the number of items
-        scoring strictly above the target."""
+        scoring strictly above the target.
+
+        With ``exclude_seen`` the query at (b, t) ranks its target among the items sequence b has
+        not seen up to t: the rows of ``current_token_ids[b, :t + 1]`` do not count (a target
+        that is itself among them is still ranked, over the remaining rows).  The keys then end
+        in ``_unseen``.  T <= 1024; the lists are built for at most 16,384 queries at a time."""
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])
         L = ids.shape[1] - off
-        res: Dict[str, float] = {"catalogue_queries": 0}
+        sfx = "_unseen" if exclude_seen else ""
+        res: Dict[str, float] = {"catalogue_queries" + sfx: 0}
         if L <= 0:
             return res
         rows = catalogue.rows_of(ids[:, off:])
@@ -379,13 +395,29 @@ class LTHMModelWrapper(BaseModelWrapper):
         q = y[:, :L, head][keep].contiguous()
         if q.dtype not in (torch.float32, torch.bfloat16):
             q = q.float()
-        _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=rows[keep].contiguous())
+        trow = rows[keep].contiguous()
+        if not exclude_seen:
+            _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=trow)
+        else:
+            T = ids.shape[1]
+            if T > K.RETRIEVE_MAX_EXCLUDE:
+                raise ValueError(f"exclude_seen takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens (T = {T})")
+            seen = catalogue.rows_of(ids)  # [B, T]; the pad id and unknown ids are -1
+            bi, ti = keep.nonzero(as_tuple=True)  # the order of q's rows
+            col = torch.arange(T, device=seen.device)
+            ranks = []
+            for lo in range(0, n, 16384):  # an [n, T] int32 list matrix, at most 32 MB at a time at T = 512
+                b, t = bi[lo:lo + 16384], ti[lo:lo + 16384]
+                xr = torch.where(col[None, :] <= t[:, None], seen[b], torch.full_like(seen[b], -1)).contiguous()
+                ranks.append(K.retrieve_topk(q[lo:lo + 16384], catalogue.emb, 1, normalize_q=True,
+                                             target_rows=trow[lo:lo + 16384], exclude_rows=xr)[2])
+            rank = torch.cat(ranks)
         pos = rank.float()
-        res["catalogue_queries"] = n
+        res["catalogue_queries" + sfx] = n
         for k in ks:
-            res[f"hit_rate_at_{k}_catalogue"] = float((rank < k).float().mean())
-        res["average_hit_position_catalogue"] = float(pos.mean())
-        res["median_hit_position_catalogue"] = float(pos.quantile(q=0.5))
+            res[f"hit_rate_at_{k}_catalogue{sfx}"] = float((rank < k).float().mean())
+        res["average_hit_position_catalogue" + sfx] = float(pos.mean())
+        res["median_hit_position_catalogue" + sfx] = float(pos.quantile(q=0.5))
         return res
 
     def is_sparse(self, param_name: str):

@@ -1,7 +1,7 @@
 """Full-catalogue retrieval benchmark: K.retrieve_topk against the torch baseline
 ``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
 
-    python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000]
+    python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -13,7 +13,11 @@ shape stops the run.  One JSON line per shape:
   speedup, speedup_lo     base / fused on the medians, and on the worst pairing (base min /
                           fused max): faster only if speedup_lo > 1
   check_rows_equal        the fused rows of the first queries equal an f32 torch top-k's
-The two paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
+  excl_* (--exclude X)    the fused call with X random valid rows excluded per query
+                          (exclude_rows), timed next to the plain one: median / min / max,
+                          excl_over_fused = excl / fused on the medians (_hi: excl max / fused
+                          min), and its rows against a torch top-k with those rows at -inf
+The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
 import argparse
@@ -33,7 +37,7 @@ SHAPES = {"serving": 256, "evaluation": 4096}
 BASE_CHUNK = 256      # baseline queries per matmul: a [256, N] f32 score matrix is 2 GB at N = 2M
 
 
-def child(name: str, N: int, k: int, reps: int) -> None:
+def child(name: str, N: int, k: int, reps: int, exclude: int = 0) -> None:
     import torch
     from recommendations_amd import kernels as K
     Q = SHAPES[name]
@@ -48,6 +52,13 @@ def child(name: str, N: int, k: int, reps: int) -> None:
 
     def fused():
         return K.retrieve_topk(q_bf, items, k, normalize_q=False)
+
+    xr = None
+    if exclude:  # X random valid rows per query
+        xr = torch.randint(0, N, (Q, exclude), generator=g, device=dev, dtype=torch.int32)
+
+    def fused_excl():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False, exclude_rows=xr)
 
     def base():
         out = []
@@ -66,11 +77,15 @@ def child(name: str, N: int, k: int, reps: int) -> None:
     nb = max(3, reps // 4) if name == "evaluation" else reps  # the chunked baseline is long
     for _ in range(2):
         fused()
+        if exclude:
+            fused_excl()
         base()
     torch.cuda.synchronize()
-    tf, tb = [], []
+    tf, tx, tb = [], [], []
     for i in range(reps):
         tf.append(timed(fused))
+        if exclude:
+            tx.append(timed(fused_excl))
         if i < nb:
             tb.append(timed(base))
     scores, rows, _, _ = fused()
@@ -82,6 +97,17 @@ def child(name: str, N: int, k: int, reps: int) -> None:
     t_mem, t_mm = nbytes / HBM_PEAK, flop / MFMA_PEAK
     floor_ms = max(t_mem, t_mm) * 1e3
     fm, bm = statistics.median(tf), statistics.median(tb)
+    extra = {}
+    if exclude:
+        # the excluding call's rows against an f32 torch top-k with the lists' rows at -inf
+        x_rows = fused_excl()[1]
+        sref = q_bf[:nq].float() @ items.float().T
+        sref.scatter_(1, xr[:nq].long(), float("-inf"))
+        x_same = float((x_rows[:nq].long() == sref.topk(k).indices).float().mean())
+        xm = statistics.median(tx)
+        extra = {"exclude": exclude, "excl_ms": round(xm, 4), "excl_min_ms": round(min(tx), 4),
+                 "excl_max_ms": round(max(tx), 4), "excl_reps": len(tx), "excl_over_fused": round(xm / fm, 4),
+                 "excl_over_fused_hi": round(max(tx) / min(tf), 4), "excl_check_rows_equal": round(x_same, 4)}
     print(json.dumps({
         "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
         "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
@@ -90,6 +116,7 @@ def child(name: str, N: int, k: int, reps: int) -> None:
         "base_ms": round(bm, 4), "base_min_ms": round(min(tb), 4), "base_max_ms": round(max(tb), 4), "base_reps": len(tb),
         "base_floor_frac": round(floor_ms / bm, 4), "base_tflops": round(flop / bm / 1e9, 1),
         "speedup": round(bm / fm, 3), "speedup_lo": round(min(tb) / max(tf), 3), "check_rows_equal": round(same, 4),
+        **extra,
     }), flush=True)
 
 
@@ -99,18 +126,23 @@ def main() -> int:
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--n-items", type=int, default=2_000_000)
     ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--exclude", type=int, default=0,
+                    help="also time the call with X random excluded rows per query (1..1024), in the same loop")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
+    if not 0 <= a.exclude <= 1024:
+        raise SystemExit("--exclude takes 0 (off) or 1..1024 rows per query")
     if a.child:
-        child(a.child, a.n_items, a.k, a.reps)
+        child(a.child, a.n_items, a.k, a.reps, a.exclude)
         return 0
     for name in a.shapes.split(","):
         if name not in SHAPES:
             raise SystemExit(f"unknown shape {name}")
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
-                                 "--n-items", str(a.n_items), "--k", str(a.k)], timeout=a.step_timeout).returncode
+                                 "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude)],
+                                timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
             return 1
