@@ -866,6 +866,32 @@ typedef struct lthm_retrieve_excl {
 int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows, int64_t X);
 /* x == NULL is lthm_retrieve_topk; otherwise d->ws_bytes must cover lthm_retrieve_excl_ws_bytes */
 int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream);
+/* Groups: every user has G queries (1 <= G <= 8, say one per lookahead head) and an item is
+ * scored by its best match over them.  In the desc d->q is [U, G, 128] (contiguous) and d->Q = U;
+ * scores / rows [U, k], target_row / rank / target_score [U] and x->rows [U, X] are per user.
+ *   s_g[u, j]        the f32 score lthm_retrieve_topk gives query (u, g) against row j (the same
+ *                    preparation, normalisation and accumulation)
+ *   s[u, j]          max_g s_g[u, j], and -inf for a row user u excludes (one list per user, the
+ *                    entries under the rules of lthm_retrieve_excl)
+ *   scores, rows     the k <= 128 best rows of s[u, :] by (score descending, row ascending), the
+ *                    tail -inf / -1 where fewer than k rows remain
+ *   target_score[u]  max_g of the plain per-query target dots (-inf where target_row[u] is no
+ *                    catalogue row)
+ *   rank[u]          #{j != target, j not excluded : s[u, j] > target_score[u]}, or -1 where
+ *                    the target is no catalogue row
+ * The outputs are a pure function of the inputs and do not depend on the order of a user's
+ * queries.  Which query attained a maximum is not reported.  Inputs are finite. */
+typedef struct lthm_retrieve_group {
+  int32_t G;
+} lthm_retrieve_group;
+/* workspace bytes of lthm_retrieve_topk_group; X = 0: no exclusion.  At G = 1 the value of
+ * lthm_retrieve_ws_bytes (X = 0) or lthm_retrieve_excl_ws_bytes; -1 for what those refuse and
+ * for G outside 1..8 */
+int64_t lthm_retrieve_group_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows, int64_t X);
+/* x == NULL: no exclusion.  g == NULL or g->G == 1 is lthm_retrieve_topk_excl(d, x, stream);
+ * otherwise d->ws_bytes must cover lthm_retrieve_group_ws_bytes */
+int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                             void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

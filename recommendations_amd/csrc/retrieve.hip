@@ -22,6 +22,15 @@
 //                     walks its sorted list with one cursor and sets the accumulator elements
 //                     of excluded rows to -inf before the count and the filter see them.
 // The plain call runs retr_topk_k<false>, which holds none of this.
+//
+// Groups (lthm_retrieve_topk_group): user u has G <= 8 queries and an item's score is its best
+// over them, s[u, j] = max_g s_g[u, j].  The queries are laid out in slots, GP = next power of
+// two of G per user (retr_prep_group_k; a pad slot repeats the user's first query, since a zero
+// vector would score 0 and beat every negative score), so a user's slots are GP adjacent MFMA
+// columns: GP adjacent lanes of one wave half.  retr_topk_k<EXCL, GP> takes the maximum of every
+// accumulator element over those lanes, and the group's first lane (the leader) alone counts,
+// masks, filters and appends, for the user: lists, targets, keys and counts are per user.  The
+// other lanes of a group are inert the way the queries past Q are.
 #include "mfma.hpp"
 
 #include <climits>
@@ -104,12 +113,35 @@ struct RetrArgs {
 };
 
 constexpr int RT_XMAX = 1024;  // longest exclusion list of a query
+constexpr int RT_GMAX = 8;     // most queries of a group
 // retr_topk_k<true> takes the plain arguments and the sorted lists behind them, so that the
 // plain instantiation's argument block is the one it always had
 struct RetrExclArgs : RetrArgs {
   const int* xs;  // [Q, xstride] ascending; ignored entries and the last one are INT_MAX
   int xstride;    // X + 1
 };
+// retr_topk_k<EXCL, GP > 1>: Q counts the slots (U GP), trow / tscore / keys / pcnt / xs are
+// per user
+struct RetrGroupArgs : RetrExclArgs {
+  int64_t U;
+};
+template <bool EXCL, int GP>
+using RetrTopkArgs = std::conditional_t<(GP > 1), RetrGroupArgs, std::conditional_t<EXCL, RetrExclArgs, RetrArgs>>;
+
+// The maximum of x over the GP adjacent lanes of a group, in every lane of it: xor distances 1
+// and 2 as DPP quad permutes ([1,0,3,2], [2,3,0,1]); then all four lanes of a quad hold the
+// quad's maximum and the half-row mirror (lane i of 8 reads lane 7 - i) brings the other quad's.
+// All 64 lanes are active where this runs.
+template <int GP>
+__device__ __forceinline__ float retr_group_max(float x) {
+  if constexpr (GP >= 2)
+    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false)));
+  if constexpr (GP >= 4)
+    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, false)));
+  if constexpr (GP >= 8)
+    x = fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xF, 0xF, false)));
+  return x;
+}
 
 // ---------------------------------------------------------------- exclusion lists, sorted
 // One block per query: a bitonic sort of the list, padded to a power of two with INT_MAX, in
@@ -196,6 +228,65 @@ __global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int
   }
 }
 
+// The grouped layout: 16 lanes per user walk the user's GP slots; slot g holds query g of
+// q [U, G, 128], a slot at or past G the user's query 0.  Every slot goes through retr_prep_k's
+// arithmetic, and tscore[u] is the maximum of the slots' target dots.
+template <typename TQ>
+__global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ q, int64_t U, int G, int GP,
+                                                         int normalize, bf16_t* __restrict__ qn,
+                                                         const bf16_t* __restrict__ items, int64_t N,
+                                                         const int* __restrict__ trow, float* __restrict__ tscore) {
+  const int sub = threadIdx.x & 15;
+  const int64_t u0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+  const bool in = u0 < U;
+  const int64_t u = in ? u0 : U - 1;  // every lane takes part in the group sums
+  int tr = -1;
+  bool ok = false;
+  float it[8];
+  if (trow) {
+    tr = trow[u];
+    ok = tr >= 0 && tr < N;
+    load_vec<bf16_t, 16>(items + (int64_t)(ok ? tr : 0) * RT_D + 8 * sub, it);
+  }
+  float best = -INFINITY;
+  for (int g = 0; g < GP; ++g) {
+    const int64_t r = u * G + (g < G ? g : 0);
+    float v[8];
+    if constexpr (sizeof(TQ) == 2) {
+      load_vec<TQ, 16>(q + r * RT_D + 8 * sub, v);
+    } else {
+      load_vec<TQ, 16>(q + r * RT_D + 8 * sub, v);
+      load_vec<TQ, 16>(q + r * RT_D + 8 * sub + 4, v + 4);
+    }
+    if (normalize) {
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) ss += v[i] * v[i];
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+      const float den = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) v[i] = v[i] / den;
+    }
+    u32x4 w;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
+    if (in) *reinterpret_cast<u32x4*>(qn + (u * GP + g) * RT_D + 8 * sub) = w;
+    if (trow) {
+      float dot = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        dot = __builtin_fmaf(__uint_as_float(w[i] << 16), it[2 * i], dot);
+        dot = __builtin_fmaf(__uint_as_float(w[i] & 0xffff0000u), it[2 * i + 1], dot);
+      }
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+      best = fmaxf(best, dot);
+    }
+  }
+  if (trow && in && sub == 0) tscore[u] = ok ? best : -INFINITY;
+}
+
 // ---------------------------------------------------------------- scores + threshold selection
 // Wave w: queries 32 (w & 1) + (lane & 31) of the tile (MFMA columns, so every per-query value
 // is a per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3).
@@ -205,8 +296,13 @@ __global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int
 // entries below its end, so at a tile's start nx is at or past the tile's first row and a
 // tile without excluded rows costs one compare.  INT_MAX ends every list and is never below a
 // tile's end (<= N < 2^31), so the cursor stops on it.
-template <bool EXCL>
-__global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, RetrExclArgs, RetrArgs> a) {
+//
+// GP > 1: queries are slots, GP per user and never across a wave half.  A group's first lane
+// (lead) owns user uq = q / GP: it alone has a threshold, a target, a list cursor and a
+// candidate buffer (those of its own slot ql), after every lane of the group took the group's
+// maximum of its accumulator.
+template <bool EXCL, int GP = 1>
+__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
   __shared__ __attribute__((aligned(16))) RetrShared sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
@@ -218,9 +314,20 @@ __global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, Retr
   const int ql = 32 * (w & 1) + r32;
   const int64_t q = q0 + ql;
   const bool live = q < a.Q;
+  bool lead = live;
+  int64_t uq = q;
+  if constexpr (GP > 1) {
+    lead = live && (r32 & (GP - 1)) == 0;
+    uq = q / GP;
+  }
+  int64_t nout = a.Q;  // rows of keys and pcnt per slab
+  if constexpr (GP > 1) nout = a.U;
 
   if (tid < RT_QT) {
-    sh.tau[tid] = q0 + tid < a.Q ? -INFINITY : INFINITY;  // a query past Q never passes the filter
+    // a query past Q never passes the filter, nor does a slot that is not its group's first
+    bool first = q0 + tid < a.Q;
+    if constexpr (GP > 1) first = first && (tid & (GP - 1)) == 0;
+    sh.tau[tid] = first ? -INFINITY : INFINITY;
     sh.cnt[tid] = 0;
     sh.pc[tid] = 0;
   }
@@ -238,16 +345,16 @@ __global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, Retr
   }
   int tr = -1;
   float ts = INFINITY;  // no target: nothing counts
-  if (live && a.trow) {
-    tr = a.trow[q];
-    if (tr >= 0 && tr < a.N) ts = a.tscore[q];
+  if (lead && a.trow) {
+    tr = a.trow[uq];
+    if (tr >= 0 && tr < a.N) ts = a.tscore[uq];
     else tr = -1;
   }
   const int* xp = nullptr;
   int nx = INT_MAX;  // a query past Q excludes nothing and reads nothing
   if constexpr (EXCL) {
-    if (live) {
-      const int* xl = a.xs + q * a.xstride;
+    if (lead) {
+      const int* xl = a.xs + uq * a.xstride;
       int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -286,7 +393,7 @@ __global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, Retr
     if (i + 1 < ntile) stage(i + 1);
     if (tid == 0) sh.flag[(i + 1) % 3] = 0;  // last read in tile i - 1, next set in tile i + 1
     if (sh.flag[(i + 2) % 3]) {              // tile i - 1 pushed a query past the limit
-      for (int pq = w; pq < RT_QT; pq += 4) {
+      for (int pq = w * GP; pq < RT_QT; pq += 4 * GP) {  // the groups' first slots
         const int n = sh.cnt[pq];
         if (n > RT_LIM) {
           const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], n, a.k, lane);
@@ -311,6 +418,10 @@ __global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, Retr
 #pragma unroll
       for (int v = 0; v < 16; ++v)
         if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if constexpr (GP > 1) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[v] = retr_group_max<GP>(acc[v]);
     }
     if constexpr (EXCL) {
       // the tile's excluded rows, folded into a mask of this lane's own elements (the target's
@@ -359,13 +470,18 @@ __global__ __launch_bounds__(256) void retr_topk_k(std::conditional_t<EXCL, Retr
   if (hh == 0 && live && above) atomicAdd(&sh.pc[ql], above);
   __syncthreads();
   // the slab's k best of every query, sorted; empty slots are key 0
-  for (int pq = w; pq < RT_QT; pq += 4) {
+  for (int pq = w * GP; pq < RT_QT; pq += 4 * GP) {
     if (q0 + pq >= a.Q) break;
     const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], sh.cnt[pq], a.k, lane);
-    u64* out = a.keys + ((int64_t)slab * a.Q + q0 + pq) * a.k;
+    u64* out = a.keys + ((int64_t)slab * nout + (q0 + pq) / GP) * a.k;
     for (int idx = lane; idx < a.k; idx += 64) out[idx] = idx < m ? sh.cand[pq][idx] : 0ull;
   }
-  if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+  if constexpr (GP == 1) {
+    if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+  } else {
+    if (a.trow && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
+      a.pcnt[(int64_t)slab * nout + (q0 + tid) / GP] = sh.pc[tid];
+  }
 }
 
 // ---------------------------------------------------------------- merge of the slabs' k-lists
@@ -450,7 +566,103 @@ extern "C" int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, 
 
 namespace {
 
-// both entry points: x == nullptr is the plain call
+// slots per user: the next power of two of G
+inline int retr_gp(int G) {
+  int gp = 1;
+  while (gp < G) gp <<= 1;
+  return gp;
+}
+
+}  // namespace
+
+extern "C" int64_t lthm_retrieve_group_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
+                                                int64_t X) {
+  if (G < 1 || G > RT_GMAX || X < 0 || X > RT_XMAX || slab_rows < 0) return -1;
+  if (G == 1) return X ? lthm_retrieve_excl_ws_bytes(U, N, k, slab_rows, X) : lthm_retrieve_ws_bytes(U, N, k, slab_rows);
+  if (U < 1 || U >= (1ll << 31)) return -1;
+  const int64_t S = U * retr_gp(G);  // the slab rule sees the query tiles of the padded slots
+  const int64_t sr = retr_slab_rows(S, N, k, slab_rows);
+  if (sr < 0) return -1;
+  const int64_t nslab = (N + sr - 1) / sr;
+  return up256(S * RT_D * 2) + up256(nslab * U * k * 8) + up256(nslab * U * 4) + (X ? up256(U * (X + 1) * 4) : 0);
+}
+
+namespace {
+
+template <bool EXCL>
+void retr_launch_group(int gp, dim3 grid, hipStream_t s, const RetrGroupArgs& a) {
+  if (gp == 2) hipLaunchKernelGGL((retr_topk_k<EXCL, 2>), grid, dim3(256), 0, s, a);
+  else if (gp == 4) hipLaunchKernelGGL((retr_topk_k<EXCL, 4>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((retr_topk_k<EXCL, 8>), grid, dim3(256), 0, s, a);
+}
+
+// lthm_retrieve_topk_group with G >= 2: d->Q users of G queries each
+int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G, void* stream) {
+  LTHM_REQUIRE(d != nullptr);
+  LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
+  LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
+  LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
+  LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  const int64_t need = lthm_retrieve_group_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
+  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
+  const int64_t U = d->Q, N = d->N;
+  const int gp = retr_gp(G);
+  const int64_t S = U * gp;
+  const int64_t sr = retr_slab_rows(S, N, d->k, d->slab_rows);
+  const int64_t nslab = (N + sr - 1) / sr;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)d->workspace;
+  bf16_t* qn = (bf16_t*)ws;
+  u64* keys = (u64*)(ws + up256(S * RT_D * 2));
+  int* pcnt = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * d->k * 8));
+  int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * d->k * 8) + up256(nslab * U * 4));
+  const bf16_t* items = (const bf16_t*)d->items;
+  const unsigned pgrid = (unsigned)((U + 15) / 16);
+  if (d->q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
+                       d->normalize_q, qn, items, N, d->target_row, d->target_score);
+  else
+    hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
+                       d->normalize_q, qn, items, N, d->target_row, d->target_score);
+  LTHM_CHECK_LAUNCH();
+  RetrGroupArgs a;
+  a.items = items;
+  a.qn = qn;
+  a.trow = d->target_row;
+  a.tscore = d->target_score;
+  a.keys = keys;
+  a.pcnt = pcnt;
+  a.Q = S;
+  a.N = N;
+  a.slab_rows = sr;
+  a.k = d->k;
+  a.xs = nullptr;
+  a.xstride = 0;
+  a.U = U;
+  const dim3 tgrid((unsigned)((S + RT_QT - 1) / RT_QT), (unsigned)nslab);
+  if (x) {
+    const int X = (int)x->X;
+    int P = 1;
+    while (P < X) P <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)U), dim3(256), 0, s, x->rows, X, P, N, xs);  // one list per user
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+    retr_launch_group<true>(gp, tgrid, s, a);
+  } else {
+    retr_launch_group<false>(gp, tgrid, s, a);
+  }
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, U, N,
+                     (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}
+
+// the plain and the excluding entry points: x == nullptr is the plain call
 int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
@@ -520,4 +732,10 @@ extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) { r
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
   return retr_launch(d, x, stream);
+}
+
+extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                        const lthm_retrieve_group* g, void* stream) {
+  if (!g || g->G == 1) return retr_launch(d, x, stream);
+  return retr_launch_group_call(d, x, g->G, stream);
 }

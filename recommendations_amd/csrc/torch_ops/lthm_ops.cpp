@@ -18,6 +18,7 @@
 //   lthm::item_artifact ModelWrapper.forward        embedding_module_gen.py:32-41 (fused)
 //   lthm::retrieve_topk full-catalogue top-K        (build-defined, csrc/retrieve.hip; forward only)
 //   lthm::retrieve_topk_excl  the same without each query's listed rows
+//   lthm::retrieve_topk_group the same for users of several queries, by the best score over them
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -471,6 +472,59 @@ std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor
   return retrieve_topk_impl(q, items, k, normalize_q, &exclude_rows);
 }
 
+// q [U, G, 128]: an item's score is its best over the user's G <= 8 queries; exclude_rows is one
+// list per user (int32 [U, X]) or None
+std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
+                                                    const c10::optional<Tensor>& exclude_rows) {
+  on_gpu(q_, "q");
+  on_gpu(items_, "items");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
+              "items must be a bf16 [N, 128] catalogue");
+  TORCH_CHECK(q_.dim() == 3 && q_.size(2) == 128, "q must be [U, G, 128]");
+  TORCH_CHECK(q_.size(1) >= 1 && q_.size(1) <= 8, "retrieve_topk_group takes 1..8 queries per user, got ", q_.size(1));
+  TORCH_CHECK(k >= 1 && k <= 128, "k must be in 1..128, got ", k);
+  TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk_group takes a non-empty catalogue and user set");
+  auto q = q_.contiguous(), items = items_.contiguous();
+  const int64_t U = q.size(0), G = q.size(1), N = items.size(0);
+  Tensor xr;
+  const bool excl = exclude_rows.has_value() && exclude_rows->defined();
+  if (excl) {
+    on_gpu(*exclude_rows, "exclude_rows");
+    TORCH_CHECK(exclude_rows->scalar_type() == at::kInt && exclude_rows->dim() == 2 && exclude_rows->size(0) == U,
+                "exclude_rows must be int32 [U, X], one list per user");
+    TORCH_CHECK(exclude_rows->size(1) >= 1 && exclude_rows->size(1) <= 1024,
+                "exclude_rows takes 1..1024 rows per user, got ", exclude_rows->size(1));
+    TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
+    xr = exclude_rows->contiguous();
+  }
+  const int64_t need = lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
+  TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
+  auto scores = at::empty({U, k}, q.options().dtype(at::kFloat));
+  auto rows = at::empty({U, k}, q.options().dtype(at::kInt));
+  auto ws = at::empty({need}, q.options().dtype(at::kByte));
+  lthm_retrieve_desc d = {};
+  d.items = items.data_ptr();
+  d.q = q.data_ptr();
+  d.scores = scores.data_ptr<float>();
+  d.rows = rows.data_ptr<int32_t>();
+  d.workspace = ws.data_ptr();
+  d.ws_bytes = need;
+  d.Q = U;
+  d.N = N;
+  d.k = (int32_t)k;
+  d.q_dtype = dcode(q);
+  d.normalize_q = normalize_q ? 1 : 0;
+  lthm_retrieve_excl x = {};
+  if (excl) {
+    x.rows = xr.data_ptr<int32_t>();
+    x.X = xr.size(1);
+  }
+  lthm_retrieve_group g = {};
+  g.G = (int32_t)G;
+  hip_ok(lthm_retrieve_topk_group(&d, excl ? &x : nullptr, &g, cur_stream()), "lthm_retrieve_topk_group");
+  return std::make_tuple(scores, rows);
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -492,6 +546,9 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_topk_excl(Tensor q, Tensor items, int k, bool normalize_q, Tensor exclude_rows) -> "
       "(Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_group(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows=None) -> "
+      "(Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -503,6 +560,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("item_artifact", &item_artifact_cuda);
   m.impl("retrieve_topk", &retrieve_topk_cuda);
   m.impl("retrieve_topk_excl", &retrieve_topk_excl_cuda);
+  m.impl("retrieve_topk_group", &retrieve_topk_group_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

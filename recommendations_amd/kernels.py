@@ -1714,3 +1714,69 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
         call("lthm_retrieve_topk_excl", ctypes.addressof(d), ctypes.addressof(x), stream(), _key="retr_topk_excl_k",
              _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * Q * X)
     return scores, rows, rank, tscore
+
+
+RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
+
+
+def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
+                        exclude_rows=None):
+    """retrieve_topk for users with several queries each: an item's score is its best over the
+    user's queries, s[u, j] = max_g s_g[u, j], with s_g the score retrieve_topk gives query
+    (u, g) (csrc/retrieve.hip, retr_topk_k<EXCL, GP>).
+
+    q f32 / bf16 [U, G, 128], 1 <= G <= 8; items bf16 [N, 128]; target_rows int32 [U] or None;
+    exclude_rows int32 [U, X] or None, one list per user under retrieve_topk's rules.  Returns
+    (scores f32 [U, k], rows int32 [U, k], rank int32 [U] | None, target_score f32 [U] | None) by
+    (score descending, row ascending), -inf / -1 where fewer than k rows remain.  target_score
+    is the best of the user's plain target dots and rank = #{j != target, j not excluded :
+    s[u, j] > target_score[u]} (-1 where the target is no catalogue row).  The outputs do not
+    depend on the order of a user's queries; G = 1 is retrieve_topk on q[:, 0].  Which query
+    attained a score is not reported."""
+    import ctypes
+    from ._lib import STRUCTS
+    require_gpu(q, items, target_rows, exclude_rows)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"retrieve_topk_group takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() == 3 and q.shape[2] == RETRIEVE_WIDTH,
+           f"retrieve_topk_group takes [U, G, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    U, G, N, k = q.shape[0], q.shape[1], items.shape[0], int(k)
+    _check(1 <= G <= RETRIEVE_MAX_GROUP, f"retrieve_topk_group takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
+    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk_group takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    _check(N >= 1 and U >= 1, f"retrieve_topk_group takes a non-empty catalogue and at least one user (N={N}, U={U})")
+    X = 0
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == U,
+               f"exclude_rows must be int32 [U, X], one list per user (got {exclude_rows.dtype} "
+               f"{tuple(exclude_rows.shape)}, U={U})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per user (got {X})")
+        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
+    if target_rows is not None:
+        _check(target_rows.dtype == torch.int32 and target_rows.shape == (U,), "target_rows must be int32 [U]")
+    need = load().lthm_retrieve_group_ws_bytes(U, G, N, k, int(slab_rows), X)
+    _check(need >= 0, f"retrieve_topk_group: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
+                      f"that cuts N={N} into at most 65535 slabs (U={U} G={G} k={k} X={X})")
+    dev = q.device
+    scores = torch.empty((U, k), dtype=torch.float32, device=dev)
+    rows = torch.empty((U, k), dtype=torch.int32, device=dev)
+    rank = tscore = None
+    if target_rows is not None:
+        rank = torch.empty(U, dtype=torch.int32, device=dev)
+        tscore = torch.empty(U, dtype=torch.float32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    d = STRUCTS["lthm_retrieve_desc"]()
+    d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
+    d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
+    d.workspace, d.ws_bytes = ptr(ws), need
+    d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = U, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
+    x = None
+    if exclude_rows is not None:
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
+    g = STRUCTS["lthm_retrieve_group"]()
+    g.G = G
+    call("lthm_retrieve_topk_group", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
+         ctypes.addressof(g), stream(), _key="retr_topk_group_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
+         _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X))
+    return scores, rows, rank, tscore

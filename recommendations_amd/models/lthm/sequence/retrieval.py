@@ -76,15 +76,19 @@ class ItemCatalogue:
         not hold the target) and ``target_score`` the target's score; else both are None.
         ``exclude_ids`` int64 [Q, X] (X <= 1024) names items query q must not return, in any
         order: they take no slot and do not count in ``rank`` (``K.retrieve_topk``'s
-        ``exclude_rows``).  Ids the catalogue does not hold, and the pad id 0, exclude nothing."""
+        ``exclude_rows``).  Ids the catalogue does not hold, and the pad id 0, exclude nothing.
+        A 3-D ``q`` [U, G, 128] (G <= 8) holds G queries per user: an item's score is its best
+        over them (``K.retrieve_topk_group``), and the outputs, ``target_ids`` [U] and
+        ``exclude_ids`` [U, X] are per user."""
         tr = self.rows_of(target_ids).contiguous() if target_ids is not None else None
         xr = None
         if exclude_ids is not None:
             if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
                 raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
             xr = self.rows_of(exclude_ids).contiguous()  # -1 for unknown ids and for 0, which no catalogue holds
-        scores, rows, rank, tscore = K.retrieve_topk(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
-                                                     slab_rows=slab_rows, exclude_rows=xr)
+        call = K.retrieve_topk_group if q.dim() == 3 else K.retrieve_topk
+        scores, rows, rank, tscore = call(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
+                                          slab_rows=slab_rows, exclude_rows=xr)
         item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
         return item_ids, scores, rank, tscore
 

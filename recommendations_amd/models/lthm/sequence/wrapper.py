@@ -23,7 +23,7 @@ import ctypes
 import os
 import random
 from collections.abc import MutableMapping
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -346,15 +346,28 @@ class LTHMModelWrapper(BaseModelWrapper):
 
     @torch.no_grad()
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
-                 exclude_history: bool = False) -> Dict[str, torch.Tensor]:
+                 exclude_history: bool = False, heads: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
         f32 [B, k], sorted by (score descending, catalogue row ascending).  With
         ``exclude_history`` sequence b never gets an item of its own ``current_token_ids[b, :]``
-        back (T <= 1024): the k best items it has not interacted with."""
+        back (T <= 1024): the k best items it has not interacted with.  With ``heads`` (1 to 8
+        distinct head indices; ``head`` is then ignored) the queries are
+        ``next_token_emb[:, -1, heads]`` and an item is scored by its best match over them: the k
+        items the sequence is most likely to touch at any of those lookahead offsets."""
+        if heads is not None:
+            heads = [int(h) for h in heads]
+            n_heads = len(self._lookahead)
+            if not 1 <= len(heads) <= K.RETRIEVE_MAX_GROUP or len(set(heads)) != len(heads) \
+                    or any(h < 0 or h >= n_heads for h in heads):
+                raise ValueError(f"heads takes 1..{K.RETRIEVE_MAX_GROUP} distinct indices in 0..{n_heads - 1} "
+                                 f"(got {heads})")
         out = self.forward(batch)
-        q = out["next_token_emb"][:, -1, head].contiguous()
+        if heads is None:
+            q = out["next_token_emb"][:, -1, head].contiguous()
+        else:
+            q = out["next_token_emb"][:, -1, heads].contiguous()  # [B, G, 128]
         if q.dtype not in (torch.float32, torch.bfloat16):
             q = q.float()
         seen = None

@@ -2,6 +2,7 @@
 ``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
 
     python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
+                                    [--group G]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -17,6 +18,12 @@ shape stops the run.  One JSON line per shape:
                           (exclude_rows), timed next to the plain one: median / min / max,
                           excl_over_fused = excl / fused on the medians (_hi: excl max / fused
                           min), and its rows against a torch top-k with those rows at -inf
+  group_* (--group G)     U = Q // G users of G queries each (Q becomes U G): the grouped call
+                          (K.retrieve_topk_group) timed next to the plain call on the same U G
+                          queries (fused_*) and next to what a caller without it does, G plain calls
+                          of U queries and a merge of the G lists with torch sorts on the device
+                          (heads_*): group_over_fused and group_over_heads on the medians (_hi /
+                          _lo: the worst pairing), group_check_rows_equal against that merge
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -37,10 +44,27 @@ SHAPES = {"serving": 256, "evaluation": 4096}
 BASE_CHUNK = 256      # baseline queries per matmul: a [256, N] f32 score matrix is 2 GB at N = 2M
 
 
-def child(name: str, N: int, k: int, reps: int, exclude: int = 0) -> None:
+def merge_heads(lists, k):
+    """G per-head (scores [U, k], rows [U, k]) -> the k best distinct rows per user by (best score
+    descending, row ascending), with stable sorts: by score, by row, the duplicates out, by score."""
+    import torch
+    sc = torch.cat([x[0] for x in lists], dim=1)
+    rw = torch.cat([x[1] for x in lists], dim=1)
+    o = sc.argsort(dim=1, descending=True, stable=True)
+    sc, rw = sc.gather(1, o), rw.gather(1, o)
+    o = rw.argsort(dim=1, stable=True)
+    sc, rw = sc.gather(1, o), rw.gather(1, o)  # equal rows adjacent, the best score first
+    sc[:, 1:] = torch.where(rw[:, 1:] == rw[:, :-1], torch.full_like(sc[:, 1:], float("-inf")), sc[:, 1:])
+    o = sc.argsort(dim=1, descending=True, stable=True)[:, :k]
+    return sc.gather(1, o), rw.gather(1, o)
+
+
+def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0) -> None:
     import torch
     from recommendations_amd import kernels as K
     Q = SHAPES[name]
+    if group:
+        Q = Q // group * group
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(1)
     items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
@@ -59,6 +83,17 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0) -> None:
 
     def fused_excl():
         return K.retrieve_topk(q_bf, items, k, normalize_q=False, exclude_rows=xr)
+
+    q_grp, q_heads = None, []
+    if group:
+        q_grp = q_bf.view(Q // group, group, 128)
+        q_heads = [q_grp[:, h].contiguous() for h in range(group)]
+
+    def fused_group():
+        return K.retrieve_topk_group(q_grp, items, k, normalize_q=False)
+
+    def heads_merge():
+        return merge_heads([K.retrieve_topk(qh, items, k, normalize_q=False)[:2] for qh in q_heads], k)
 
     def base():
         out = []
@@ -79,13 +114,19 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0) -> None:
         fused()
         if exclude:
             fused_excl()
+        if group:
+            fused_group()
+            heads_merge()
         base()
     torch.cuda.synchronize()
-    tf, tx, tb = [], [], []
+    tf, tx, tb, tg, th = [], [], [], [], []
     for i in range(reps):
         tf.append(timed(fused))
         if exclude:
             tx.append(timed(fused_excl))
+        if group:
+            tg.append(timed(fused_group))
+            th.append(timed(heads_merge))
         if i < nb:
             tb.append(timed(base))
     scores, rows, _, _ = fused()
@@ -108,6 +149,17 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0) -> None:
         extra = {"exclude": exclude, "excl_ms": round(xm, 4), "excl_min_ms": round(min(tx), 4),
                  "excl_max_ms": round(max(tx), 4), "excl_reps": len(tx), "excl_over_fused": round(xm / fm, 4),
                  "excl_over_fused_hi": round(max(tx) / min(tf), 4), "excl_check_rows_equal": round(x_same, 4)}
+    if group:
+        g_scores, g_rows, _, _ = fused_group()
+        m_scores, m_rows = heads_merge()
+        g_same = float(((g_rows == m_rows) & (g_scores == m_scores)).float().mean())
+        gm, hm = statistics.median(tg), statistics.median(th)
+        extra.update({"group": group, "U": Q // group, "group_ms": round(gm, 4), "group_min_ms": round(min(tg), 4),
+                      "group_max_ms": round(max(tg), 4), "group_reps": len(tg),
+                      "heads_ms": round(hm, 4), "heads_min_ms": round(min(th), 4), "heads_max_ms": round(max(th), 4),
+                      "group_over_fused": round(gm / fm, 4), "group_over_fused_hi": round(max(tg) / min(tf), 4),
+                      "group_over_heads": round(gm / hm, 4), "group_over_heads_hi": round(max(tg) / min(th), 4),
+                      "group_check_rows_equal": round(g_same, 4)})
     print(json.dumps({
         "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
         "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
@@ -128,20 +180,25 @@ def main() -> int:
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--exclude", type=int, default=0,
                     help="also time the call with X random excluded rows per query (1..1024), in the same loop")
+    ap.add_argument("--group", type=int, default=0,
+                    help="also time the grouped call with G queries per user (2..8), the G plain calls and their merge")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
     if not 0 <= a.exclude <= 1024:
         raise SystemExit("--exclude takes 0 (off) or 1..1024 rows per query")
+    if a.group and not 2 <= a.group <= 8:
+        raise SystemExit("--group takes 0 (off) or 2..8 queries per user")
     if a.child:
-        child(a.child, a.n_items, a.k, a.reps, a.exclude)
+        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group)
         return 0
     for name in a.shapes.split(","):
         if name not in SHAPES:
             raise SystemExit(f"unknown shape {name}")
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
-                                 "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude)],
+                                 "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
+                                 "--group", str(a.group)],
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
