@@ -892,6 +892,29 @@ int64_t lthm_retrieve_group_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k,
  * otherwise d->ws_bytes must cover lthm_retrieve_group_ws_bytes */
 int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
                              void* stream);
+/* Tag filters: the k best rows among those a query may be shown.
+ *   tags    int32 [N]: one word per catalogue row, read as 32 independent bits (bit 31 is an
+ *           ordinary bit; only the bit pattern matters)
+ *   filter  int32 [Q, 3] (with groups [U, 3], one per user): (all, any, none).  Row j is eligible
+ *           for query q iff
+ *             (tags[j] & all) == all  &&  (any == 0 || (tags[j] & any) != 0)  &&  (tags[j] & none) == 0
+ * An ineligible row is treated exactly as an excluded row: it is scored as -inf, takes no slot
+ * and never counts in rank; where fewer than k rows remain the tail is -inf / -1; order and tie
+ * rule are unchanged.  The target is never filtered as a target: target_score is the plain dot
+ * (with groups the best of the plain dots) and
+ *   rank = #{j != target, j eligible, j not excluded : s_j > s_target}.
+ * The filter (0, 0, 0) gives the bits of the call without tags; an unsatisfiable filter
+ * (all & none != 0) gives an empty list and rank 0 for a valid target.  Filters compose with
+ * exclusion and with groups.  The outputs stay a pure function of the inputs.  Both arrays are
+ * read with 4-byte loads (4-byte aligned), tags never at or past N. */
+typedef struct lthm_retrieve_tags {
+  const int32_t* tags;
+  const int32_t* filter;
+} lthm_retrieve_tags;
+/* t == NULL is lthm_retrieve_topk_group(d, x, g, stream); with t both pointers must be non-null.
+ * The workspace is the group call's: lthm_retrieve_group_ws_bytes (with g == NULL, G = 1). */
+int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                            const lthm_retrieve_tags* t, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -31,6 +31,13 @@
 // accumulator element over those lanes, and the group's first lane (the leader) alone counts,
 // masks, filters and appends, for the user: lists, targets, keys and counts are per user.  The
 // other lanes of a group are inert the way the queries past Q are.
+//
+// Tags (lthm_retrieve_topk_tags): the catalogue carries one 32-bit attribute word per row and
+// every query (user) a filter (all, any, none); a row that fails its query's filter is scored as
+// -inf exactly as an excluded row is.  retr_topk_k<EXCL, GP, true> stages the 64 tag words of
+// tile i + 1 with the image of tile i + 1 (one more LDS-DMA of wave 0, retired by the same wait
+// and barrier), reads its 16 rows' words back as four broadcast 16-byte LDS reads, and masks the
+// accumulator next to the exclusion mask.  The instantiations without tags hold none of this.
 #include "mfma.hpp"
 
 #include <climits>
@@ -63,8 +70,14 @@ struct RetrShared {
   int flag[3];       // flag[i % 3]: tile i pushed some query past RT_LIM
 };
 static_assert(sizeof(RetrShared) <= 160 * 1024, "LDS budget");
+// retr_topk_k<.., .., true>: the tag words of the two images' rows behind the plain layout
+struct RetrSharedTags : RetrShared {
+  alignas(16) int tag[2][RT_IT];  // a lane reads four words at once
+};
+static_assert(sizeof(RetrSharedTags) <= 160 * 1024, "LDS budget");
 
 __device__ __attribute__((aligned(16))) unsigned char retr_zero_row[256];
+__device__ int retr_zero_tag;  // the tag of a row at or past the slab's end
 
 __device__ __forceinline__ u64 retr_key(float s, int row) {
   uint32_t u = __float_as_uint(s + 0.f);  // -0 -> +0: equal scores get equal images
@@ -126,7 +139,15 @@ struct RetrGroupArgs : RetrExclArgs {
   int64_t U;
 };
 template <bool EXCL, int GP>
-using RetrTopkArgs = std::conditional_t<(GP > 1), RetrGroupArgs, std::conditional_t<EXCL, RetrExclArgs, RetrArgs>>;
+using RetrBaseArgs = std::conditional_t<(GP > 1), RetrGroupArgs, std::conditional_t<EXCL, RetrExclArgs, RetrArgs>>;
+// retr_topk_k<EXCL, GP, true>: the arguments of <EXCL, GP> and the tags behind them
+template <class Base>
+struct RetrTagArgs : Base {
+  const int* tags;  // [N]
+  const int* filt;  // [Q, 3] (GP > 1: [U, 3]): all, any, none
+};
+template <bool EXCL, int GP, bool TAGS>
+using RetrTopkArgs = std::conditional_t<TAGS, RetrTagArgs<RetrBaseArgs<EXCL, GP>>, RetrBaseArgs<EXCL, GP>>;
 
 // The maximum of x over the GP adjacent lanes of a group, in every lane of it: xor distances 1
 // and 2 as DPP quad permutes ([1,0,3,2], [2,3,0,1]); then all four lanes of a quad hold the
@@ -301,9 +322,15 @@ __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ 
 // (lead) owns user uq = q / GP: it alone has a threshold, a target, a list cursor and a
 // candidate buffer (those of its own slot ql), after every lane of the group took the group's
 // maximum of its accumulator.
-template <bool EXCL, int GP = 1>
-__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
-  __shared__ __attribute__((aligned(16))) RetrShared sh;
+//
+// TAGS: row j passes the lane's filter iff (tag & (all | none)) == all and (any == 0 or
+// tag & any != 0); the lane keeps fm = all | none, fw = all, fy = any and yz = (any == 0), so that
+// the any term is ((tag & fy) | yz) != 0.  An unsatisfiable filter (all & none != 0) becomes
+// fm = 0, fw = 1, which no tag passes.  A lane that is no leader keeps the neutral filter: it is
+// inert already.
+template <bool EXCL, int GP = 1, bool TAGS = false>
+__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS> a) {
+  __shared__ __attribute__((aligned(16))) std::conditional_t<TAGS, RetrSharedTags, RetrShared> sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
   const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
@@ -365,6 +392,18 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
       nx = *xp;
     }
   }
+  int fm = 0, fw = 0, fy = 0;
+  int yz = 1;
+  if constexpr (TAGS) {
+    if (lead) {
+      const int* fp = a.filt + uq * 3;
+      const int fall = fp[0], fnone = fp[2];
+      fy = fp[1];
+      yz = fy == 0;
+      fm = (fall & fnone) ? 0 : (fall | fnone);
+      fw = (fall & fnone) ? 1 : fall;
+    }
+  }
   int roff[8];
 #pragma unroll
   for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
@@ -382,6 +421,13 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
       const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
                                      : (const void*)(retr_zero_row + 16 * (lane & 15));
       glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+    if constexpr (TAGS) {
+      // wave 0, lane l: the tag of the image's row l; never a read at or past row_hi <= N
+      if (w == 0) {
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+      }
     }
   };
   retire_loads();
@@ -406,6 +452,15 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
       __syncthreads();
     }
     const unsigned char* img = sh.img[i & 1];
+    // TAGS: the lane's rows are four runs of four consecutive tag words, the same in all 32
+    // lanes of a wave half (broadcast reads): element 4 j + c is image row 32 ih + 4 hh + 8 j + c.
+    // Read ahead of the MFMAs, used behind them.
+    int4 t4[4];
+    if constexpr (TAGS) {
+      const int4* tp = reinterpret_cast<const int4*>(sh.tag[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
+    }
     f32x16 acc = {};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -438,6 +493,18 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP> a) {
 #pragma unroll
         for (int v = 0; v < 16; ++v)
           if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    if constexpr (TAGS) {
+      // two compares and one select per element: an ineligible row scores -inf like an excluded one
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int tw[4] = {t4[j].x, t4[j].y, t4[j].z, t4[j].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const bool bad = ((tw[c] & fm) != fw) | (((tw[c] & fy) | yz) == 0);
+          acc[4 * j + c] = bad ? -INFINITY : acc[4 * j + c];
+        }
       }
     }
     float mx = acc[0];
@@ -596,8 +663,20 @@ void retr_launch_group(int gp, dim3 grid, hipStream_t s, const RetrGroupArgs& a)
   else hipLaunchKernelGGL((retr_topk_k<EXCL, 8>), grid, dim3(256), 0, s, a);
 }
 
-// lthm_retrieve_topk_group with G >= 2: d->Q users of G queries each
-int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G, void* stream) {
+template <bool EXCL>
+void retr_launch_group_tags(int gp, dim3 grid, hipStream_t s, const RetrGroupArgs& a, const lthm_retrieve_tags* t) {
+  RetrTagArgs<RetrGroupArgs> ta;
+  static_cast<RetrGroupArgs&>(ta) = a;
+  ta.tags = t->tags;
+  ta.filt = t->filter;
+  if (gp == 2) hipLaunchKernelGGL((retr_topk_k<EXCL, 2, true>), grid, dim3(256), 0, s, ta);
+  else if (gp == 4) hipLaunchKernelGGL((retr_topk_k<EXCL, 4, true>), grid, dim3(256), 0, s, ta);
+  else hipLaunchKernelGGL((retr_topk_k<EXCL, 8, true>), grid, dim3(256), 0, s, ta);
+}
+
+// lthm_retrieve_topk_group / _tags with G >= 2: d->Q users of G queries each
+int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G,
+                           const lthm_retrieve_tags* t, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
@@ -606,6 +685,7 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   const int64_t need = lthm_retrieve_group_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
   const int64_t U = d->Q, N = d->N;
@@ -651,9 +731,11 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
-    retr_launch_group<true>(gp, tgrid, s, a);
+    if (t) retr_launch_group_tags<true>(gp, tgrid, s, a, t);
+    else retr_launch_group<true>(gp, tgrid, s, a);
   } else {
-    retr_launch_group<false>(gp, tgrid, s, a);
+    if (t) retr_launch_group_tags<false>(gp, tgrid, s, a, t);
+    else retr_launch_group<false>(gp, tgrid, s, a);
   }
   LTHM_CHECK_LAUNCH();
   hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, U, N,
@@ -662,8 +744,9 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   return 0;
 }
 
-// the plain and the excluding entry points: x == nullptr is the plain call
-int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
+// the plain, the excluding and the filtering entry points: x == nullptr and t == nullptr is the
+// plain call
+int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
@@ -671,6 +754,7 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* 
   LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   const int64_t need = x ? lthm_retrieve_excl_ws_bytes(d->Q, d->N, d->k, d->slab_rows, x->X)
                          : lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
@@ -715,7 +799,21 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* 
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
-    hipLaunchKernelGGL(retr_topk_k<true>, tgrid, dim3(256), 0, s, a);
+    if (t) {
+      RetrTagArgs<RetrExclArgs> ta;
+      static_cast<RetrExclArgs&>(ta) = a;
+      ta.tags = t->tags;
+      ta.filt = t->filter;
+      hipLaunchKernelGGL((retr_topk_k<true, 1, true>), tgrid, dim3(256), 0, s, ta);
+    } else {
+      hipLaunchKernelGGL(retr_topk_k<true>, tgrid, dim3(256), 0, s, a);
+    }
+  } else if (t) {
+    RetrTagArgs<RetrArgs> ta;
+    static_cast<RetrArgs&>(ta) = a;
+    ta.tags = t->tags;
+    ta.filt = t->filter;
+    hipLaunchKernelGGL((retr_topk_k<false, 1, true>), tgrid, dim3(256), 0, s, ta);
   } else {
     hipLaunchKernelGGL(retr_topk_k<false>, tgrid, dim3(256), 0, s, static_cast<const RetrArgs&>(a));
   }
@@ -728,14 +826,22 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* 
 
 }  // namespace
 
-extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) { return retr_launch(d, nullptr, stream); }
+extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
+  return retr_launch(d, nullptr, nullptr, stream);
+}
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
-  return retr_launch(d, x, stream);
+  return retr_launch(d, x, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, stream);
-  return retr_launch_group_call(d, x, g->G, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, nullptr, stream);
+}
+
+extern "C" int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                       const lthm_retrieve_group* g, const lthm_retrieve_tags* t, void* stream) {
+  if (!g || g->G == 1) return retr_launch(d, x, t, stream);
+  return retr_launch_group_call(d, x, g->G, t, stream);
 }

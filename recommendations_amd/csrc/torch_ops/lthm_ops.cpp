@@ -19,6 +19,7 @@
 //   lthm::retrieve_topk full-catalogue top-K        (build-defined, csrc/retrieve.hip; forward only)
 //   lthm::retrieve_topk_excl  the same without each query's listed rows
 //   lthm::retrieve_topk_group the same for users of several queries, by the best score over them
+//   lthm::retrieve_topk_tags  any of the above among the rows whose tag word passes the query's filter
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -473,9 +474,11 @@ std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor
 }
 
 // q [U, G, 128]: an item's score is its best over the user's G <= 8 queries; exclude_rows is one
-// list per user (int32 [U, X]) or None
-std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
-                                                    const c10::optional<Tensor>& exclude_rows) {
+// list per user (int32 [U, X]) or None; tags (int32 [N]) and filter (int32 [U, 3]) are both null
+// or both given
+std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
+                                                    const c10::optional<Tensor>& exclude_rows, const Tensor* tags_,
+                                                    const Tensor* filter_) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
@@ -496,6 +499,19 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q_, const Tens
                 "exclude_rows takes 1..1024 rows per user, got ", exclude_rows->size(1));
     TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
     xr = exclude_rows->contiguous();
+  }
+  Tensor tg, tf;
+  if (tags_) {
+    on_gpu(*tags_, "tags");
+    on_gpu(*filter_, "tag_filter");
+    TORCH_CHECK(tags_->scalar_type() == at::kInt && tags_->dim() == 1 && tags_->size(0) == N,
+                "tags must be int32 [N], one word per catalogue row");
+    TORCH_CHECK(filter_->scalar_type() == at::kInt && filter_->dim() == 2 && filter_->size(0) == U && filter_->size(1) == 3,
+                "tag_filter must be int32 [Q, 3] = (all, any, none), one row per query (per user for a 3-D q)");
+    TORCH_CHECK(tags_->device() == items.device() && filter_->device() == items.device(),
+                "tags and tag_filter must be on the catalogue's device");
+    tg = tags_->contiguous();
+    tf = filter_->contiguous();
   }
   const int64_t need = lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
   TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
@@ -521,8 +537,29 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q_, const Tens
   }
   lthm_retrieve_group g = {};
   g.G = (int32_t)G;
-  hip_ok(lthm_retrieve_topk_group(&d, excl ? &x : nullptr, &g, cur_stream()), "lthm_retrieve_topk_group");
+  if (tags_) {
+    lthm_retrieve_tags t = {};
+    t.tags = tg.data_ptr<int32_t>();
+    t.filter = tf.data_ptr<int32_t>();
+    hip_ok(lthm_retrieve_topk_tags(&d, excl ? &x : nullptr, &g, &t, cur_stream()), "lthm_retrieve_topk_tags");
+  } else {
+    hip_ok(lthm_retrieve_topk_group(&d, excl ? &x : nullptr, &g, cur_stream()), "lthm_retrieve_topk_group");
+  }
   return std::make_tuple(scores, rows);
+}
+
+std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                    const c10::optional<Tensor>& exclude_rows) {
+  return retrieve_topk_group_impl(q, items, k, normalize_q, exclude_rows, nullptr, nullptr);
+}
+
+// q [Q, 128] or [U, G, 128]; a 2-D q is a group of one query
+std::tuple<Tensor, Tensor> retrieve_topk_tags_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                   const c10::optional<Tensor>& exclude_rows, const Tensor& tags,
+                                                   const Tensor& tag_filter) {
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "q must be [Q, 128] or [U, G, 128]");
+  return retrieve_topk_group_impl(q.dim() == 2 ? q.unsqueeze(1) : q, items, k, normalize_q, exclude_rows, &tags,
+                                  &tag_filter);
 }
 
 int64_t abi_version() { return lthm_abi_version(); }
@@ -549,6 +586,9 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_topk_group(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows=None) -> "
       "(Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_tags(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor tags, "
+      "Tensor tag_filter) -> (Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -561,6 +601,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk", &retrieve_topk_cuda);
   m.impl("retrieve_topk_excl", &retrieve_topk_excl_cuda);
   m.impl("retrieve_topk_group", &retrieve_topk_group_cuda);
+  m.impl("retrieve_topk_tags", &retrieve_topk_tags_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -1653,8 +1653,29 @@ RETRIEVE_MIN_SLAB_ROWS = 64   # RT_IT: the smallest (and the granularity of) sla
 RETRIEVE_MAX_EXCLUDE = 1024   # RT_XMAX: the longest exclusion list of a query
 
 
+def _retrieve_tags(who: str, tags, tag_filter, items, n_filters: int, per: str):
+    """The lthm_retrieve_tags of a call, or None without tags: tags int32 [N] and tag_filter
+    int32 [n_filters, 3], contiguous, on the catalogue's device, both or neither."""
+    from ._lib import STRUCTS
+    _check((tags is None) == (tag_filter is None), f"{who} takes tags and tag_filter together or neither")
+    if tags is None:
+        return None
+    N = items.shape[0]
+    _check(tags.dtype == torch.int32 and tags.dim() == 1 and tags.shape[0] == N,
+           f"tags must be int32 [N], one word per catalogue row (got {tags.dtype} {tuple(tags.shape)}, N={N})")
+    _check(tag_filter.dtype == torch.int32 and tag_filter.dim() == 2 and tuple(tag_filter.shape) == (n_filters, 3),
+           f"tag_filter must be int32 [{per}, 3] = (all, any, none), one row per {'user' if per == 'U' else 'query'} "
+           f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, {per}={n_filters})")
+    _check(tags.is_contiguous() and tag_filter.is_contiguous(), "tags and tag_filter must be contiguous")
+    _check(tags.device == items.device and tag_filter.device == items.device,
+           "tags and tag_filter must be on the catalogue's device")
+    t = STRUCTS["lthm_retrieve_tags"]()
+    t.tags, t.filter = ptr(tags), ptr(tag_filter)
+    return t
+
+
 def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
-                  exclude_rows=None):
+                  exclude_rows=None, tags=None, tag_filter=None):
     """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
 
     q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
@@ -1667,7 +1688,14 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     scored as -inf: it takes none of the k slots (the tail is -inf / -1 where fewer than k rows
     remain) and does not count in rank.  The target is never excluded as a target: target_score
     stays the plain dot, and rank counts the non-excluded rows other than the target scoring
-    above it, also for a target inside its own list."""
+    above it, also for a target inside its own list.
+
+    tags int32 [N] and tag_filter int32 [Q, 3] = (all, any, none), together or neither: row j is
+    eligible for query q iff (tags[j] & all) == all and (any == 0 or tags[j] & any != 0) and
+    tags[j] & none == 0, the words read as 32 independent bits.  An ineligible row is treated
+    exactly as an excluded one, and the target is never filtered as a target: rank counts the
+    eligible, non-excluded rows other than the target scoring above its plain dot.  The filter
+    (0, 0, 0) gives the bits of the call without tags."""
     import ctypes
     from ._lib import STRUCTS
     require_gpu(q, items, target_rows, exclude_rows)
@@ -1705,7 +1733,16 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     d.workspace, d.ws_bytes = ptr(ws), need
     d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = Q, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8)
-    if exclude_rows is None:
+    t = _retrieve_tags("retrieve_topk", tags, tag_filter, items, Q, "Q")
+    if t is not None:
+        x = None
+        if exclude_rows is not None:
+            x = STRUCTS["lthm_retrieve_excl"]()
+            x.rows, x.X = ptr(exclude_rows), X
+        call("lthm_retrieve_topk_tags", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
+             ctypes.addressof(t), stream(), _key="retr_topk_tags_k", _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
+             _bytes=nbytes + 4.0 * Q * X + 4.0 * N + 12.0 * Q)
+    elif exclude_rows is None:
         call("lthm_retrieve_topk", ctypes.addressof(d), stream(), _key="retr_topk_k",
              _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
     else:
@@ -1720,7 +1757,7 @@ RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
 
 
 def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
-                        exclude_rows=None):
+                        exclude_rows=None, tags=None, tag_filter=None):
     """retrieve_topk for users with several queries each: an item's score is its best over the
     user's queries, s[u, j] = max_g s_g[u, j], with s_g the score retrieve_topk gives query
     (u, g) (csrc/retrieve.hip, retr_topk_k<EXCL, GP>).
@@ -1732,7 +1769,8 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     is the best of the user's plain target dots and rank = #{j != target, j not excluded :
     s[u, j] > target_score[u]} (-1 where the target is no catalogue row).  The outputs do not
     depend on the order of a user's queries; G = 1 is retrieve_topk on q[:, 0].  Which query
-    attained a score is not reported."""
+    attained a score is not reported.  tags int32 [N] and tag_filter int32 [U, 3], one filter per
+    user, are retrieve_topk's: an ineligible row is -inf for the user, like an excluded one."""
     import ctypes
     from ._lib import STRUCTS
     require_gpu(q, items, target_rows, exclude_rows)
@@ -1776,7 +1814,14 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
         x.rows, x.X = ptr(exclude_rows), X
     g = STRUCTS["lthm_retrieve_group"]()
     g.G = G
-    call("lthm_retrieve_topk_group", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
-         ctypes.addressof(g), stream(), _key="retr_topk_group_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
-         _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X))
+    nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
+    t = _retrieve_tags("retrieve_topk_group", tags, tag_filter, items, U, "U")
+    if t is not None:
+        call("lthm_retrieve_topk_tags", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
+             ctypes.addressof(g), ctypes.addressof(t), stream(), _key="retr_topk_group_tags_k",
+             _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * N + 12.0 * U)
+    else:
+        call("lthm_retrieve_topk_group", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
+             ctypes.addressof(g), stream(), _key="retr_topk_group_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH,
+             _unit="flop", _bytes=nbytes)
     return scores, rows, rank, tscore

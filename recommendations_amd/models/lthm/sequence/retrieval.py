@@ -7,13 +7,19 @@ the loss normalises both (wrapper.py:118-119) and ranks by their dot product.  A
 scored against all of them (``K.retrieve_topk``, csrc/retrieve.hip) instead of against the
 in-batch negatives only.
 
-File format: safetensors with the two tensors ``ids`` / ``emb`` and a ``format`` metadata
-string, in the style of item_artifact.py.  Loading executes nothing from the file.
+File format: safetensors with the two tensors ``ids`` / ``emb``, an optional third ``tags``, and
+a ``format`` metadata string, in the style of item_artifact.py.  Loading executes nothing from
+the file.
+
+Tags: a catalogue may carry one int32 word per item, read as 32 independent attribute bits (in
+stock, category, market, ...).  A query's filter (all, any, none) then restricts its top-K and
+its rank to the items whose word has every ``all`` bit, some ``any`` bit (if any is non-zero) and
+no ``none`` bit, inside the kernel (``K.retrieve_topk``'s ``tags`` / ``tag_filter``).
 """
 from __future__ import annotations
 
 import json
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
@@ -24,11 +30,44 @@ FORMAT = "lthm-item-catalogue-v1"
 WIDTH = K.RETRIEVE_WIDTH
 
 
+def _bits32(v, n: int, name: str, device) -> torch.Tensor:
+    """An int or an integer tensor [n] (or scalar) of values in -2^31 .. 2^32 - 1 as int64 [n]
+    holding the int32 value with the same low 32 bits."""
+    if isinstance(v, torch.Tensor):
+        if v.dtype not in (torch.int32, torch.int64, torch.uint8, torch.int16, torch.int8) or v.dim() > 1:
+            raise ValueError(f"{name} must be an int or an integer tensor [{n}] (got {v.dtype} {tuple(v.shape)})")
+        t = v.to(device=device, dtype=torch.int64).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(n)
+        if t.numel() != n:
+            raise ValueError(f"{name} must hold one value or {n} (got {t.numel()})")
+    else:
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int or an integer tensor (got {type(v).__name__})")
+        t = torch.full((n,), v, dtype=torch.int64, device=device)
+    if bool(((t < -(1 << 31)) | (t > (1 << 32) - 1)).any()):
+        raise ValueError(f"{name} must lie in 0..2^32-1 (or be an int32 bit pattern)")
+    t = t & 0xFFFFFFFF
+    return torch.where(t >= (1 << 31), t - (1 << 32), t)
+
+
+def make_tag_filter(n: int, tag_all: Union[int, torch.Tensor] = 0, tag_any: Union[int, torch.Tensor] = 0,
+                    tag_none: Union[int, torch.Tensor] = 0, device=None) -> torch.Tensor:
+    """The int32 [n, 3] filter (all, any, none) of n queries from Python ints or integer tensors
+    [n] (one value serves every query).  Values are 32-bit masks in 0..2^32-1 and wrap to the
+    int32 with the same bits, so bit 31 is ``1 << 31``."""
+    if n < 1:
+        raise ValueError("make_tag_filter takes n >= 1")
+    cols = [_bits32(v, n, name, device) for v, name in ((tag_all, "tag_all"), (tag_any, "tag_any"), (tag_none, "tag_none"))]
+    return torch.stack(cols, dim=1).to(torch.int32).contiguous()
+
+
 class ItemCatalogue:
     """``ids`` int64 [N], strictly ascending (so unique) and without the pad id 0; ``emb`` bf16
-    [N, 128], row i the normalised candidate vector of ``ids[i]``."""
+    [N, 128], row i the normalised candidate vector of ``ids[i]``; ``tags`` int32 [N] or None,
+    row i the 32 attribute bits of ``ids[i]``."""
 
-    def __init__(self, ids: torch.Tensor, emb: torch.Tensor):
+    def __init__(self, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None):
         if ids.dtype != torch.int64 or ids.dim() != 1:
             raise ValueError(f"catalogue ids must be int64 [N] (got {ids.dtype} {tuple(ids.shape)})")
         if emb.dtype != torch.bfloat16 or emb.dim() != 2 or emb.shape[1] != WIDTH:
@@ -43,23 +82,50 @@ class ItemCatalogue:
         if ids.shape[0] > 1 and not bool((ids[1:] > ids[:-1]).all()):
             raise ValueError("catalogue ids must be strictly ascending (sorted, no duplicates); "
                              "ItemCatalogue.from_embeddings sorts")
+        if tags is not None:
+            if tags.dtype != torch.int32 or tags.dim() != 1 or tags.shape[0] != ids.shape[0]:
+                raise ValueError(f"catalogue tags must be int32 [N], one word per id "
+                                 f"(got {tags.dtype} {tuple(tags.shape)}, N={ids.shape[0]})")
+            if tags.device != ids.device:
+                raise ValueError("catalogue tags must live on the device of ids and embeddings")
+            tags = tags.contiguous()
         self.ids = ids.contiguous()
         self.emb = emb.contiguous()
+        self.tags = tags
 
     def __len__(self) -> int:
         return self.ids.shape[0]
 
     @classmethod
-    def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor) -> "ItemCatalogue":
+    def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor,
+                        tags: Optional[torch.Tensor] = None) -> "ItemCatalogue":
         """From ids in any order and their (already normalised, bf16) vectors: rows are sorted
-        by id.  Duplicate ids are refused, as is id 0."""
+        by id, and ``tags`` (int32 [N], given in the order of ``ids``) move with them.  Duplicate
+        ids are refused, as is id 0."""
         if ids.dim() != 1 or emb.dim() != 2 or ids.shape[0] != emb.shape[0]:
             raise ValueError("from_embeddings takes ids [N] and emb [N, 128]")
+        if tags is not None and (tags.dim() != 1 or tags.shape[0] != ids.shape[0]):
+            raise ValueError("from_embeddings takes tags [N], one word per id")
         order = torch.argsort(ids, stable=True)
-        return cls(ids[order], emb[order.to(emb.device)])
+        return cls(ids[order], emb[order.to(emb.device)], None if tags is None else tags[order.to(tags.device)])
 
     def to(self, device) -> "ItemCatalogue":
-        return ItemCatalogue(self.ids.to(device), self.emb.to(device))
+        return ItemCatalogue(self.ids.to(device), self.emb.to(device),
+                             None if self.tags is None else self.tags.to(device))
+
+    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
+        """The filter "the same value as the target in the masked bit field": per target t the
+        row (tags[t] & mask, 0, ~tags[t] & mask) of an int32 [Q, 3] filter.  ``mask`` is a 32-bit
+        mask in 0..2^32-1.  A target the catalogue does not hold gets (0, 0, 0)."""
+        if self.tags is None:
+            raise ValueError("filter_like needs a catalogue with tags")
+        if target_ids.dim() != 1:
+            raise ValueError("filter_like takes target ids [Q]")
+        rows = self.rows_of(target_ids).long()
+        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
+        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
+        m = torch.where(rows >= 0, m, torch.zeros_like(m))
+        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
 
     def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
         """Catalogue row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
@@ -69,7 +135,8 @@ class ItemCatalogue:
         return rows.to(torch.int32).view(ids.shape)
 
     def topk(self, q: torch.Tensor, k: int, *, normalize_q: bool = True, target_ids: Optional[torch.Tensor] = None,
-             slab_rows: int = 0, exclude_ids: Optional[torch.Tensor] = None):
+             slab_rows: int = 0, exclude_ids: Optional[torch.Tensor] = None,
+             tag_filter: Optional[torch.Tensor] = None):
         """The k best items per query: (item_ids int64 [Q, k], scores f32 [Q, k], rank, target_score).
         Empty slots (N < k) hold id 0 and score -inf.  With ``target_ids`` [Q], ``rank`` is each
         query's count of items scoring strictly above its target (-1 where the catalogue does
@@ -79,7 +146,13 @@ class ItemCatalogue:
         ``exclude_rows``).  Ids the catalogue does not hold, and the pad id 0, exclude nothing.
         A 3-D ``q`` [U, G, 128] (G <= 8) holds G queries per user: an item's score is its best
         over them (``K.retrieve_topk_group``), and the outputs, ``target_ids`` [U] and
-        ``exclude_ids`` [U, X] are per user."""
+        ``exclude_ids`` [U, X] are per user.
+        ``tag_filter`` int32 [Q, 3] ([U, 3] with a 3-D ``q``) = (all, any, none) restricts query q
+        to the items whose tag word passes it (see ``make_tag_filter`` and ``filter_like``): the others
+        take no slot and do not count in ``rank``, exactly like excluded items.  The catalogue
+        must carry tags."""
+        if tag_filter is not None and self.tags is None:
+            raise ValueError("tag_filter given, but this catalogue carries no tags")
         tr = self.rows_of(target_ids).contiguous() if target_ids is not None else None
         xr = None
         if exclude_ids is not None:
@@ -88,14 +161,17 @@ class ItemCatalogue:
             xr = self.rows_of(exclude_ids).contiguous()  # -1 for unknown ids and for 0, which no catalogue holds
         call = K.retrieve_topk_group if q.dim() == 3 else K.retrieve_topk
         scores, rows, rank, tscore = call(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
-                                          slab_rows=slab_rows, exclude_rows=xr)
+                                          slab_rows=slab_rows, exclude_rows=xr,
+                                          tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter)
         item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
         return item_ids, scores, rank, tscore
 
     def save(self, path: str) -> None:
         from safetensors.torch import save_file
-        save_file({"ids": self.ids.detach().cpu().contiguous(), "emb": self.emb.detach().cpu().contiguous()}, path,
-                  metadata={"format": FORMAT})
+        tensors = {"ids": self.ids.detach().cpu().contiguous(), "emb": self.emb.detach().cpu().contiguous()}
+        if self.tags is not None:
+            tensors["tags"] = self.tags.detach().cpu().contiguous()
+        save_file(tensors, path, metadata={"format": FORMAT})
 
     @classmethod
     def load(cls, path: str, *, device=None) -> "ItemCatalogue":
@@ -105,16 +181,19 @@ class ItemCatalogue:
             if meta.get("format") != FORMAT:
                 raise ValueError(f"{path}: not an item catalogue (metadata {json.dumps(meta)})")
             ids, emb = f.get_tensor("ids"), f.get_tensor("emb")
-        cat = cls(ids, emb)
+            tags = f.get_tensor("tags") if "tags" in f.keys() else None
+        cat = cls(ids, emb, tags)
         return cat.to(device) if device is not None else cat
 
 
 @torch.no_grad()
-def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536) -> ItemCatalogue:
+def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Optional[torch.Tensor] = None) -> ItemCatalogue:
     """The catalogue of ``ids`` under ``wrapper``'s current weights: per chunk, the item
     embedding module and the product tower on a [1, n] id row (the training kernels), then
     F.normalize to bf16 as the loss does (``K.rownorm``).  A row therefore equals the
-    normalised ``current_token_emb`` row a forward produces for that id."""
+    normalised ``current_token_emb`` row a forward produces for that id.  ``tags`` (int32, one
+    word per entry of ``ids``) follow the ids through the sort and the de-duplication; an id given
+    twice with different tags is refused."""
     from ....commons.layers import RowShardedKShiftEmbedding
     enc = wrapper._model
     if isinstance(enc.product_emb_module, RowShardedKShiftEmbedding) and world_size() > 1:
@@ -124,6 +203,10 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536) -> ItemCatal
     if chunk < 1:
         raise ValueError("chunk must be positive")
     dev = next(wrapper.parameters()).device
+    if tags is not None:
+        if tags.dtype != torch.int32 or tags.shape != ids.shape:
+            raise ValueError(f"build_catalogue takes int32 tags, one per id (got {tags.dtype} {tuple(tags.shape)})")
+        tags = unique_tags(ids.to(dev), tags.to(dev))
     ids = torch.unique(ids.to(dev))  # sorted ascending
     if bool((ids == 0).any()):
         raise ValueError("catalogue ids must not hold 0, the pad id")
@@ -132,4 +215,16 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536) -> ItemCatal
         row = ids[lo:lo + chunk].view(1, -1).contiguous()
         _, prod, _ = enc.product_tower(row, enc.product_emb_module(row))
         out[lo:lo + row.numel()] = K.rownorm(prod.reshape(-1, WIDTH).contiguous())[0]
-    return ItemCatalogue(ids, out)
+    return ItemCatalogue(ids, out, tags)
+
+
+def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:
+    """The tags of ``torch.unique(ids)``, row for row: ``tags[i]`` belongs to ``ids[i]``, and an
+    id that occurs more than once must carry one tag word."""
+    uniq, inv = torch.unique(ids, return_inverse=True)  # sorted ascending, as build_catalogue sorts
+    out = torch.empty(uniq.numel(), dtype=tags.dtype, device=tags.device)
+    out[inv] = tags  # of duplicates any one occurrence lands; the check below makes them equal
+    if not bool((out[inv] == tags).all()):
+        bad = ids[out[inv] != tags][0].item()
+        raise ValueError(f"build_catalogue: id {bad} is given more than once with different tags")
+    return out

@@ -346,7 +346,8 @@ class LTHMModelWrapper(BaseModelWrapper):
 
     @torch.no_grad()
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
-                 exclude_history: bool = False, heads: Optional[Sequence[int]] = None) -> Dict[str, torch.Tensor]:
+                 exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
+                 tag_all=None, tag_any=None, tag_none=None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -355,7 +356,11 @@ class LTHMModelWrapper(BaseModelWrapper):
         back (T <= 1024): the k best items it has not interacted with.  With ``heads`` (1 to 8
         distinct head indices; ``head`` is then ignored) the queries are
         ``next_token_emb[:, -1, heads]`` and an item is scored by its best match over them: the k
-        items the sequence is most likely to touch at any of those lookahead offsets."""
+        items the sequence is most likely to touch at any of those lookahead offsets.  With
+        ``tag_all`` / ``tag_any`` / ``tag_none`` (each an int or an int tensor [B] of 32-bit masks;
+        the catalogue must carry tags) sequence b gets only items whose tag word has every
+        ``tag_all`` bit, some ``tag_any`` bit and no ``tag_none`` bit: the k best items that may
+        be shown.  The filter composes with ``exclude_history`` and ``heads``."""
         if heads is not None:
             heads = [int(h) for h in heads]
             n_heads = len(self._lookahead)
@@ -376,12 +381,19 @@ class LTHMModelWrapper(BaseModelWrapper):
             if seen.shape[1] > K.RETRIEVE_MAX_EXCLUDE:
                 raise ValueError(f"exclude_history takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens "
                                  f"(T = {seen.shape[1]})")
-        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen)
+        filt = None
+        if tag_all is not None or tag_any is not None or tag_none is not None:
+            from .retrieval import make_tag_filter
+            if catalogue.tags is None:
+                raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
+            filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
+                                   0 if tag_none is None else tag_none, device=q.device)
+        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt)
         return {"item_ids": item_ids, "scores": scores}
 
     @torch.no_grad()
     def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0,
-                          exclude_seen: bool = False) -> Dict[str, float]:
+                          exclude_seen: bool = False, same_tags_mask: Optional[int] = None) -> Dict[str, float]:
         """Hit rate and hit position of one forward against the whole catalogue: the in-batch
         metrics of wrapper.py:228-238 with every catalogue item as a negative.  Queries are the
         positions t whose target ``current_token_ids[:, t + lookahead[head]]`` is a non-pad
@@ -391,12 +403,19 @@ class LTHMModelWrapper(BaseModelWrapper):
         With ``exclude_seen`` the query at (b, t) ranks its target among the items sequence b has
         not seen up to t: the rows of ``current_token_ids[b, :t + 1]`` do not count (a target
         that is itself among them is still ranked, over the remaining rows).  The keys then end
-        in ``_unseen``.  T <= 1024; the lists are built for at most 16,384 queries at a time."""
+        in ``_unseen``.  T <= 1024; the lists are built for at most 16,384 queries at a time.
+
+        With ``same_tags_mask`` (an int, a 32-bit mask; the catalogue must carry tags) every query
+        ranks its target among the items that agree with the target on the masked tag bits, say
+        the items of the target's own category: whether the model finds the item once it has the
+        category.  The keys then take the suffix ``_tagged``, after ``_unseen`` when both are on."""
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])
         L = ids.shape[1] - off
-        sfx = "_unseen" if exclude_seen else ""
+        sfx = ("_unseen" if exclude_seen else "") + ("_tagged" if same_tags_mask is not None else "")
+        if same_tags_mask is not None and catalogue.tags is None:
+            raise ValueError("same_tags_mask given, but this catalogue carries no tags")
         res: Dict[str, float] = {"catalogue_queries" + sfx: 0}
         if L <= 0:
             return res
@@ -409,8 +428,13 @@ class LTHMModelWrapper(BaseModelWrapper):
         if q.dtype not in (torch.float32, torch.bfloat16):
             q = q.float()
         trow = rows[keep].contiguous()
+        tags = filt = None
+        if same_tags_mask is not None:
+            tags = catalogue.tags
+            filt = catalogue.filter_like(catalogue.ids[trow.long()], same_tags_mask)
         if not exclude_seen:
-            _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=trow)
+            _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=trow,
+                                            tags=tags, tag_filter=filt)
         else:
             T = ids.shape[1]
             if T > K.RETRIEVE_MAX_EXCLUDE:
@@ -423,7 +447,8 @@ class LTHMModelWrapper(BaseModelWrapper):
                 b, t = bi[lo:lo + 16384], ti[lo:lo + 16384]
                 xr = torch.where(col[None, :] <= t[:, None], seen[b], torch.full_like(seen[b], -1)).contiguous()
                 ranks.append(K.retrieve_topk(q[lo:lo + 16384], catalogue.emb, 1, normalize_q=True,
-                                             target_rows=trow[lo:lo + 16384], exclude_rows=xr)[2])
+                                             target_rows=trow[lo:lo + 16384], exclude_rows=xr, tags=tags,
+                                             tag_filter=None if filt is None else filt[lo:lo + 16384])[2])
             rank = torch.cat(ranks)
         pos = rank.float()
         res["catalogue_queries" + sfx] = n

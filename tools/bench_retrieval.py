@@ -2,7 +2,7 @@
 ``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
 
     python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
-                                    [--group G]
+                                    [--group G] [--tags P]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -24,6 +24,13 @@ shape stops the run.  One JSON line per shape:
                           of U queries and a merge of the G lists with torch sorts on the device
                           (heads_*): group_over_fused and group_over_heads on the medians (_hi /
                           _lo: the worst pairing), group_check_rows_equal against that merge
+  tags_* (--tags P)       random tags such that a fraction P of the rows is eligible for every query
+                          (bit 0 set with probability P, every query's filter (1, 0, 0)): the filtered
+                          call timed next to the plain one, tags_over_fused on the medians (_hi: the
+                          worst pairing), its rows against a torch top-k with the ineligible rows at
+                          -inf.  With --exclude also the excluding + filtered call (xtags_*, over the
+                          plain call), with --group the grouped + filtered call (gtags_*, over the
+                          plain and over the grouped call)
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -59,7 +66,7 @@ def merge_heads(lists, k):
     return sc.gather(1, o), rw.gather(1, o)
 
 
-def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0) -> None:
+def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0, tags_p: float = -1.0) -> None:
     import torch
     from recommendations_amd import kernels as K
     Q = SHAPES[name]
@@ -95,6 +102,31 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
     def heads_merge():
         return merge_heads([K.retrieve_topk(qh, items, k, normalize_q=False)[:2] for qh in q_heads], k)
 
+    tags = filt = filt_u = None
+    if tags_p >= 0:
+        tags = (torch.rand(N, generator=g, device=dev) < tags_p).to(torch.int32)
+        tags |= torch.randint(0, 1 << 30, (N,), generator=g, device=dev, dtype=torch.int32) << 1  # noise above bit 0
+        filt = torch.tensor([[1, 0, 0]], dtype=torch.int32, device=dev).repeat(Q, 1).contiguous()
+        if group:
+            filt_u = filt[:Q // group].contiguous()
+
+    def fused_tags():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False, tags=tags, tag_filter=filt)
+
+    def fused_excl_tags():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False, exclude_rows=xr, tags=tags, tag_filter=filt)
+
+    def fused_group_tags():
+        return K.retrieve_topk_group(q_grp, items, k, normalize_q=False, tags=tags, tag_filter=filt_u)
+
+    extras = []  # (key, function, times): the tagged calls of this run
+    if tags is not None:
+        extras.append(("tags", fused_tags, []))
+        if exclude:
+            extras.append(("xtags", fused_excl_tags, []))
+        if group:
+            extras.append(("gtags", fused_group_tags, []))
+
     def base():
         out = []
         for lo in range(0, Q, BASE_CHUNK):
@@ -117,6 +149,8 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
         if group:
             fused_group()
             heads_merge()
+        for _, fn, _ in extras:
+            fn()
         base()
     torch.cuda.synchronize()
     tf, tx, tb, tg, th = [], [], [], [], []
@@ -127,6 +161,8 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
         if group:
             tg.append(timed(fused_group))
             th.append(timed(heads_merge))
+        for _, fn, times in extras:
+            times.append(timed(fn))
         if i < nb:
             tb.append(timed(base))
     scores, rows, _, _ = fused()
@@ -160,6 +196,25 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
                       "group_over_fused": round(gm / fm, 4), "group_over_fused_hi": round(max(tg) / min(tf), 4),
                       "group_over_heads": round(gm / hm, 4), "group_over_heads_hi": round(max(tg) / min(th), 4),
                       "group_check_rows_equal": round(g_same, 4)})
+    if tags is not None:
+        t_rows = fused_tags()[1]
+        sref = q_bf[:nq].float() @ items.float().T
+        sref[:, (tags & 1) == 0] = float("-inf")
+        tref = sref.topk(k)
+        t_same = float((torch.where(tref.values > float("-inf"), tref.indices, torch.full_like(tref.indices, -1))
+                        == t_rows[:nq].long()).float().mean())
+        extra.update({"tags_p": tags_p, "tags_eligible": int((tags & 1).sum()), "tags_check_rows_equal": round(t_same, 4)})
+        for key, _, times in extras:
+            med = statistics.median(times)
+            extra.update({f"{key}_ms": round(med, 4), f"{key}_min_ms": round(min(times), 4),
+                          f"{key}_max_ms": round(max(times), 4), f"{key}_reps": len(times),
+                          f"{key}_over_fused": round(med / fm, 4), f"{key}_over_fused_hi": round(max(times) / min(tf), 4)})
+        if group:
+            extra.update({"gtags_over_group": round(extra["gtags_ms"] / statistics.median(tg), 4),
+                          "gtags_over_group_hi": round(extra["gtags_max_ms"] / min(tg), 4)})
+        if exclude:
+            extra.update({"xtags_over_excl": round(extra["xtags_ms"] / statistics.median(tx), 4),
+                          "xtags_over_excl_hi": round(extra["xtags_max_ms"] / min(tx), 4)})
     print(json.dumps({
         "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
         "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
@@ -182,6 +237,8 @@ def main() -> int:
                     help="also time the call with X random excluded rows per query (1..1024), in the same loop")
     ap.add_argument("--group", type=int, default=0,
                     help="also time the grouped call with G queries per user (2..8), the G plain calls and their merge")
+    ap.add_argument("--tags", type=float, default=-1.0,
+                    help="also time the filtered call with random tags, a fraction P (0..1) of the rows eligible")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -189,8 +246,10 @@ def main() -> int:
         raise SystemExit("--exclude takes 0 (off) or 1..1024 rows per query")
     if a.group and not 2 <= a.group <= 8:
         raise SystemExit("--group takes 0 (off) or 2..8 queries per user")
+    if a.tags != -1.0 and not 0.0 <= a.tags <= 1.0:
+        raise SystemExit("--tags takes a fraction in 0..1")
     if a.child:
-        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group)
+        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags)
         return 0
     for name in a.shapes.split(","):
         if name not in SHAPES:
@@ -198,7 +257,7 @@ def main() -> int:
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
-                                 "--group", str(a.group)],
+                                 "--group", str(a.group), "--tags", str(a.tags)],
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
