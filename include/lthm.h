@@ -915,6 +915,29 @@ typedef struct lthm_retrieve_tags {
  * The workspace is the group call's: lthm_retrieve_group_ws_bytes (with g == NULL, G = 1). */
 int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
                             const lthm_retrieve_tags* t, void* stream);
+/* Cursors: the k best rows strictly after a position of the total order (score descending, row
+ * ascending), for "the next k" and for lists longer than one call returns.
+ *   after_score  f32 [Q] (with groups [U], one cursor per user)
+ *   after_row    int32 [Q] or [U]; any int32
+ * Row j with f32 score s_j (with groups the best over the user's queries; -0 equals +0) is
+ * eligible iff
+ *             s_j < after_score  ||  (s_j == after_score && j > after_row)
+ * A row that is not eligible is treated exactly as an excluded row: it is scored as -inf, takes no
+ * slot and never counts in rank; target_score stays the plain dot; where fewer than k eligible
+ * rows remain the tail is -inf / -1.  after_score = +inf admits every finite-scored row (the bits
+ * of the call without a cursor); -inf or NaN admits none, so the (-inf, -1) tail of an exhausted
+ * list is a valid cursor.  after_row = -1 admits the whole tie run at after_score, a value >= N
+ * none of it.  A list's last (score, row) as the next call's cursor yields the following k rows
+ * of the same order, whatever slab_rows or Q either call used.  Cursors compose with exclusion,
+ * groups and tag filters.  Both arrays are read with 4-byte loads. */
+typedef struct lthm_retrieve_cursor {
+  const float* after_score;
+  const int32_t* after_row;
+} lthm_retrieve_cursor;
+/* c == NULL is lthm_retrieve_topk_tags(d, x, g, t, stream); with c both pointers must be non-null
+ * and 4-byte aligned.  The workspace is the group call's: lthm_retrieve_group_ws_bytes. */
+int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                             const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

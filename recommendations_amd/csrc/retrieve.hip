@@ -38,6 +38,13 @@
 // tile i + 1 with the image of tile i + 1 (one more LDS-DMA of wave 0, retired by the same wait
 // and barrier), reads its 16 rows' words back as four broadcast 16-byte LDS reads, and masks the
 // accumulator next to the exclusion mask.  The instantiations without tags hold none of this.
+//
+// Cursors (lthm_retrieve_topk_after): a query (user) may start its list behind a position
+// (after_score, after_row) of the total order; a row at or before it is scored as -inf exactly
+// as an excluded row is.  retr_topk_k<true, GP, TAGS, true> keeps the cursor in two registers
+// and masks the accumulator next to the other masks; the instantiations without it hold none of
+// this.  Since a (query, row) score does not depend on the slab cut, a page's last (score, row)
+// as the next call's cursor continues the same order without a gap or a duplicate.
 #include "mfma.hpp"
 
 #include <climits>
@@ -147,7 +154,15 @@ struct RetrTagArgs : Base {
   const int* filt;  // [Q, 3] (GP > 1: [U, 3]): all, any, none
 };
 template <bool EXCL, int GP, bool TAGS>
-using RetrTopkArgs = std::conditional_t<TAGS, RetrTagArgs<RetrBaseArgs<EXCL, GP>>, RetrBaseArgs<EXCL, GP>>;
+using RetrFiltArgs = std::conditional_t<TAGS, RetrTagArgs<RetrBaseArgs<EXCL, GP>>, RetrBaseArgs<EXCL, GP>>;
+// retr_topk_k<EXCL, GP, TAGS, true>: the arguments of <EXCL, GP, TAGS> and the cursors behind them
+template <class Base>
+struct RetrAfterArgs : Base {
+  const float* ascore;  // [Q] (GP > 1: [U])
+  const int* arow;      // [Q] (GP > 1: [U])
+};
+template <bool EXCL, int GP, bool TAGS, bool AFTER>
+using RetrTopkArgs = std::conditional_t<AFTER, RetrAfterArgs<RetrFiltArgs<EXCL, GP, TAGS>>, RetrFiltArgs<EXCL, GP, TAGS>>;
 
 // The maximum of x over the GP adjacent lanes of a group, in every lane of it: xor distances 1
 // and 2 as DPP quad permutes ([1,0,3,2], [2,3,0,1]); then all four lanes of a quad hold the
@@ -328,8 +343,16 @@ __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ 
 // the any term is ((tag & fy) | yz) != 0.  An unsatisfiable filter (all & none != 0) becomes
 // fm = 0, fw = 1, which no tag passes.  A lane that is no leader keeps the neutral filter: it is
 // inert already.
-template <bool EXCL, int GP = 1, bool TAGS = false>
-__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS> a) {
+//
+// AFTER: the lane keeps its query's cursor (cs, cr) and row j with score s is eligible iff
+// s < cs or (s == cs and j > cr), in f32 (so -0 == +0, and a NaN cs admits nothing).  A tile whose
+// lane maximum is below cs costs the maximum and one compare; otherwise every element is tested,
+// the row term as "element offset > cr - rb" with cr - rb clamped to [-1, 32], the offsets being
+// 0..27.  A lane that is no leader keeps cs = +inf, which every finite score is below.  An
+// AFTER instantiation takes a null list (a.xs) as "no exclusion": the cursor call without a list
+// runs the excluding instantiation, whose walk then never starts.
+template <bool EXCL, int GP = 1, bool TAGS = false, bool AFTER = false>
+__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, AFTER> a) {
   __shared__ __attribute__((aligned(16))) std::conditional_t<TAGS, RetrSharedTags, RetrShared> sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
@@ -380,7 +403,7 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS> 
   const int* xp = nullptr;
   int nx = INT_MAX;  // a query past Q excludes nothing and reads nothing
   if constexpr (EXCL) {
-    if (lead) {
+    if (lead && (!AFTER || a.xs != nullptr)) {
       const int* xl = a.xs + uq * a.xstride;
       int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
       while (lo < hi) {
@@ -402,6 +425,14 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS> 
       yz = fy == 0;
       fm = (fall & fnone) ? 0 : (fall | fnone);
       fw = (fall & fnone) ? 1 : fall;
+    }
+  }
+  float cs = INFINITY;  // a query past Q and a slot that is no leader: no cursor
+  int cr = -1;
+  if constexpr (AFTER) {
+    if (lead) {
+      cs = a.ascore[uq];
+      cr = a.arow[uq];
     }
   }
   int roff[8];
@@ -504,6 +535,23 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS> 
         for (int c = 0; c < 4; ++c) {
           const bool bad = ((tw[c] & fm) != fw) | (((tw[c] & fy) | yz) == 0);
           acc[4 * j + c] = bad ? -INFINITY : acc[4 * j + c];
+        }
+      }
+    }
+    if constexpr (AFTER) {
+      // rows at or before the cursor score -inf like an excluded row; !(m < cs) also holds for a
+      // NaN cs, which then fails both terms of every element
+      float m = acc[0];
+#pragma unroll
+      for (int v = 1; v < 16; ++v) m = fmaxf(m, acc[v]);
+      if (!(m < cs)) {
+        const int64_t cd = (int64_t)cr - rb;
+        const int cq = cd < -1 ? -1 : cd > 32 ? 32 : (int)cd;  // element offsets are 0..27
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const float s = acc[v];
+          const bool ok = (s < cs) | ((s == cs) & (8 * (v >> 2) + (v & 3) > cq));
+          acc[v] = ok ? s : -INFINITY;
         }
       }
     }
@@ -674,9 +722,36 @@ void retr_launch_group_tags(int gp, dim3 grid, hipStream_t s, const RetrGroupArg
   else hipLaunchKernelGGL((retr_topk_k<EXCL, 8, true>), grid, dim3(256), 0, s, ta);
 }
 
-// lthm_retrieve_topk_group / _tags with G >= 2: d->Q users of G queries each
+// The cursor call: always an excluding instantiation (a.xs == nullptr without a list), with or
+// without tags
+template <int GP>
+void retr_launch_after(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, const lthm_retrieve_tags* t,
+                       const lthm_retrieve_cursor* c) {
+  if (t) {
+    RetrTopkArgs<true, GP, true, true> ca;
+    static_cast<RetrBaseArgs<true, GP>&>(ca) = a;
+    ca.tags = t->tags;
+    ca.filt = t->filter;
+    ca.ascore = c->after_score;
+    ca.arow = c->after_row;
+    hipLaunchKernelGGL((retr_topk_k<true, GP, true, true>), grid, dim3(256), 0, s, ca);
+  } else {
+    RetrTopkArgs<true, GP, false, true> ca;
+    static_cast<RetrBaseArgs<true, GP>&>(ca) = a;
+    ca.ascore = c->after_score;
+    ca.arow = c->after_row;
+    hipLaunchKernelGGL((retr_topk_k<true, GP, false, true>), grid, dim3(256), 0, s, ca);
+  }
+}
+
+inline bool retr_cursor_ok(const lthm_retrieve_cursor* c) {
+  return !c || (c->after_score && c->after_row && ((uintptr_t)c->after_score & 3) == 0 &&
+                ((uintptr_t)c->after_row & 3) == 0);
+}
+
+// lthm_retrieve_topk_group / _tags / _after with G >= 2: d->Q users of G queries each
 int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G,
-                           const lthm_retrieve_tags* t, void* stream) {
+                           const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
@@ -686,6 +761,7 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
+  LTHM_REQUIRE(retr_cursor_ok(c));
   const int64_t need = lthm_retrieve_group_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
   const int64_t U = d->Q, N = d->N;
@@ -731,6 +807,12 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
+  }
+  if (c) {
+    if (gp == 2) retr_launch_after<2>(tgrid, s, a, t, c);
+    else if (gp == 4) retr_launch_after<4>(tgrid, s, a, t, c);
+    else retr_launch_after<8>(tgrid, s, a, t, c);
+  } else if (x) {
     if (t) retr_launch_group_tags<true>(gp, tgrid, s, a, t);
     else retr_launch_group<true>(gp, tgrid, s, a);
   } else {
@@ -746,7 +828,8 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
 
 // the plain, the excluding and the filtering entry points: x == nullptr and t == nullptr is the
 // plain call
-int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t, void* stream) {
+int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                const lthm_retrieve_cursor* c, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
@@ -755,6 +838,7 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
+  LTHM_REQUIRE(retr_cursor_ok(c));
   const int64_t need = x ? lthm_retrieve_excl_ws_bytes(d->Q, d->N, d->k, d->slab_rows, x->X)
                          : lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
@@ -799,6 +883,10 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
+  }
+  if (c) {
+    retr_launch_after<1>(tgrid, s, a, t, c);
+  } else if (x) {
     if (t) {
       RetrTagArgs<RetrExclArgs> ta;
       static_cast<RetrExclArgs&>(ta) = a;
@@ -827,21 +915,28 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
 }  // namespace
 
 extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
-  return retr_launch(d, nullptr, nullptr, stream);
+  return retr_launch(d, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
-  return retr_launch(d, x, nullptr, stream);
+  return retr_launch(d, x, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, stream);
-  return retr_launch_group_call(d, x, g->G, t, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, t, nullptr, stream);
+}
+
+extern "C" int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
+                                        const lthm_retrieve_cursor* c, void* stream) {
+  if (!g || g->G == 1) return retr_launch(d, x, t, c, stream);
+  return retr_launch_group_call(d, x, g->G, t, c, stream);
 }

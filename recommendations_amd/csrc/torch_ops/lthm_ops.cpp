@@ -20,6 +20,7 @@
 //   lthm::retrieve_topk_excl  the same without each query's listed rows
 //   lthm::retrieve_topk_group the same for users of several queries, by the best score over them
 //   lthm::retrieve_topk_tags  any of the above among the rows whose tag word passes the query's filter
+//   lthm::retrieve_topk_after any of the above strictly behind a (score, row) cursor per query
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -478,7 +479,8 @@ std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor
 // or both given
 std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
                                                     const c10::optional<Tensor>& exclude_rows, const Tensor* tags_,
-                                                    const Tensor* filter_) {
+                                                    const Tensor* filter_, const Tensor* after_scores_ = nullptr,
+                                                    const Tensor* after_rows_ = nullptr) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
@@ -513,6 +515,19 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
     tg = tags_->contiguous();
     tf = filter_->contiguous();
   }
+  Tensor cs, cr;
+  if (after_scores_) {
+    on_gpu(*after_scores_, "after_scores");
+    on_gpu(*after_rows_, "after_rows");
+    TORCH_CHECK(after_scores_->scalar_type() == at::kFloat && after_scores_->dim() == 1 && after_scores_->size(0) == U,
+                "after_scores must be f32 [Q], one cursor per query (per user for a 3-D q)");
+    TORCH_CHECK(after_rows_->scalar_type() == at::kInt && after_rows_->dim() == 1 && after_rows_->size(0) == U,
+                "after_rows must be int32 [Q], one cursor per query (per user for a 3-D q)");
+    TORCH_CHECK(after_scores_->device() == q.device() && after_rows_->device() == q.device(),
+                "after_scores and after_rows must be on the queries' device");
+    cs = after_scores_->contiguous();
+    cr = after_rows_->contiguous();
+  }
   const int64_t need = lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
   TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
   auto scores = at::empty({U, k}, q.options().dtype(at::kFloat));
@@ -537,7 +552,18 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   }
   lthm_retrieve_group g = {};
   g.G = (int32_t)G;
-  if (tags_) {
+  if (after_scores_) {
+    lthm_retrieve_tags t = {};
+    if (tags_) {
+      t.tags = tg.data_ptr<int32_t>();
+      t.filter = tf.data_ptr<int32_t>();
+    }
+    lthm_retrieve_cursor c = {};
+    c.after_score = cs.data_ptr<float>();
+    c.after_row = cr.data_ptr<int32_t>();
+    hip_ok(lthm_retrieve_topk_after(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, &c, cur_stream()),
+           "lthm_retrieve_topk_after");
+  } else if (tags_) {
     lthm_retrieve_tags t = {};
     t.tags = tg.data_ptr<int32_t>();
     t.filter = tf.data_ptr<int32_t>();
@@ -560,6 +586,22 @@ std::tuple<Tensor, Tensor> retrieve_topk_tags_cuda(const Tensor& q, const Tensor
   TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "q must be [Q, 128] or [U, G, 128]");
   return retrieve_topk_group_impl(q.dim() == 2 ? q.unsqueeze(1) : q, items, k, normalize_q, exclude_rows, &tags,
                                   &tag_filter);
+}
+
+// the same behind a cursor per query (per user for a 3-D q); tags and tag_filter are both given or
+// both None; k in 1..128 (a longer list is several calls, each behind the last column of the one
+// before)
+std::tuple<Tensor, Tensor> retrieve_topk_after_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                    const c10::optional<Tensor>& exclude_rows,
+                                                    const c10::optional<Tensor>& tags,
+                                                    const c10::optional<Tensor>& tag_filter, const Tensor& after_scores,
+                                                    const Tensor& after_rows) {
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "q must be [Q, 128] or [U, G, 128]");
+  const bool has_tags = tags.has_value() && tags->defined(), has_filter = tag_filter.has_value() && tag_filter->defined();
+  TORCH_CHECK(has_tags == has_filter, "retrieve_topk_after takes tags and tag_filter together or neither");
+  return retrieve_topk_group_impl(q.dim() == 2 ? q.unsqueeze(1) : q, items, k, normalize_q, exclude_rows,
+                                  has_tags ? &*tags : nullptr, has_tags ? &*tag_filter : nullptr, &after_scores,
+                                  &after_rows);
 }
 
 int64_t abi_version() { return lthm_abi_version(); }
@@ -589,6 +631,9 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_topk_tags(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor tags, "
       "Tensor tag_filter) -> (Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_after(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
+      "Tensor? tag_filter, Tensor after_scores, Tensor after_rows) -> (Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -602,6 +647,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_excl", &retrieve_topk_excl_cuda);
   m.impl("retrieve_topk_group", &retrieve_topk_group_cuda);
   m.impl("retrieve_topk_tags", &retrieve_topk_tags_cuda);
+  m.impl("retrieve_topk_after", &retrieve_topk_after_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -1674,8 +1674,58 @@ def _retrieve_tags(who: str, tags, tag_filter, items, n_filters: int, per: str):
     return t
 
 
+RETRIEVE_MAX_DEEP = 1024      # the longest list of a deep call: 8 passes of RETRIEVE_MAX_K
+
+
+def _retrieve_cursor(who: str, after_scores, after_rows, n: int, per: str, device):
+    """The lthm_retrieve_cursor of a call, or None without a cursor: after_scores f32 [n] and
+    after_rows int32 [n], contiguous, on the queries' device, both or neither."""
+    from ._lib import STRUCTS
+    _check((after_scores is None) == (after_rows is None), f"{who} takes after_scores and after_rows together or neither")
+    if after_scores is None:
+        return None
+    _check(after_scores.dtype == torch.float32 and tuple(after_scores.shape) == (n,),
+           f"after_scores must be f32 [{per}] (got {after_scores.dtype} {tuple(after_scores.shape)}, {per}={n})")
+    _check(after_rows.dtype == torch.int32 and tuple(after_rows.shape) == (n,),
+           f"after_rows must be int32 [{per}] (got {after_rows.dtype} {tuple(after_rows.shape)}, {per}={n})")
+    _check(after_scores.is_contiguous() and after_rows.is_contiguous(), "after_scores and after_rows must be contiguous")
+    _check(after_scores.device == device and after_rows.device == device,
+           "after_scores and after_rows must be on the queries' device")
+    c = STRUCTS["lthm_retrieve_cursor"]()
+    c.after_score, c.after_row = ptr(after_scores), ptr(after_rows)
+    return c
+
+
+def retrieve_deep_passes(k: int):
+    """The per-pass list lengths of a deep call: ceil(k / 128) passes, all of RETRIEVE_MAX_K rows
+    but the last, which takes the rest.  k in 1..RETRIEVE_MAX_DEEP."""
+    k = int(k)
+    _check(1 <= k <= RETRIEVE_MAX_DEEP, f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    full, rest = divmod(k, RETRIEVE_MAX_K)
+    return [RETRIEVE_MAX_K] * full + ([rest] if rest else [])
+
+
+def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows, kw):
+    """k > RETRIEVE_MAX_K as passes of at most RETRIEVE_MAX_K rows: pass i + 1 starts behind the
+    last column of pass i, which stays on the device (an exhausted pass ends in (-inf, -1), the
+    cursor that admits nothing).  rank and target_score are the first pass's, whose cursor is the
+    caller's own."""
+    parts_s, parts_r = [], []
+    rank = tscore = None
+    cs, cr = after_scores, after_rows
+    for i, kp in enumerate(retrieve_deep_passes(k)):
+        s, r, rk, ts = call(q, items, kp, target_rows=target_rows if i == 0 else None, after_scores=cs, after_rows=cr, **kw)
+        if i == 0:
+            rank, tscore = rk, ts
+        parts_s.append(s)
+        parts_r.append(r)
+        cs, cr = s[:, -1].contiguous(), r[:, -1].contiguous()
+    return torch.cat(parts_s, dim=1), torch.cat(parts_r, dim=1), rank, tscore
+
+
 def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
-                  exclude_rows=None, tags=None, tag_filter=None):
+                  exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
+                  deep: bool = False):
     """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
 
     q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
@@ -1695,15 +1745,33 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     tags[j] & none == 0, the words read as 32 independent bits.  An ineligible row is treated
     exactly as an excluded one, and the target is never filtered as a target: rank counts the
     eligible, non-excluded rows other than the target scoring above its plain dot.  The filter
-    (0, 0, 0) gives the bits of the call without tags."""
+    (0, 0, 0) gives the bits of the call without tags.
+
+    after_scores f32 [Q] and after_rows int32 [Q], together or neither: a cursor per query.  Row
+    j with score s is eligible iff s < after_scores[q] or (s == after_scores[q] and j >
+    after_rows[q]), in f32 on the kernel's own score; a row that is not is treated exactly as an
+    excluded one (rank counts eligible rows only, target_score stays the plain dot).  A list's
+    last (score, row) as the next call's cursor yields the following k rows of the same order,
+    whatever slab_rows or Q either call used.  +inf gives the bits of the call without a cursor;
+    -inf or NaN gives an empty list, so the (-inf, -1) tail of an exhausted list ends the paging.
+
+    deep=True lifts the cap on k from 128 to RETRIEVE_MAX_DEEP = 1024: the call runs
+    ceil(k / 128) passes, each behind the last column of the one before (no host sync), and
+    concatenates them; rank and target_score are the first pass's.  A deep list costs one scan of
+    the catalogue per 128 rows.  Without deep, k > 128 is refused as it always was."""
     import ctypes
     from ._lib import STRUCTS
+    if deep and int(k) > RETRIEVE_MAX_K:
+        return _retrieve_deep(retrieve_topk, q, items, k, target_rows, after_scores, after_rows,
+                              dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
+                                   tag_filter=tag_filter))
     require_gpu(q, items, target_rows, exclude_rows)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"retrieve_topk takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
     _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"retrieve_topk takes [Q, {RETRIEVE_WIDTH}] queries")
     Q, N, k = q.shape[0], items.shape[0], int(k)
-    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k}; deep=True takes "
+                                     f"up to {RETRIEVE_MAX_DEEP})")
     _check(N >= 1 and Q >= 1, f"retrieve_topk takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
     need = load().lthm_retrieve_ws_bytes(Q, N, k, int(slab_rows))
     _check(need >= 0, f"retrieve_topk: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
@@ -1734,7 +1802,17 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = Q, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8)
     t = _retrieve_tags("retrieve_topk", tags, tag_filter, items, Q, "Q")
-    if t is not None:
+    c = _retrieve_cursor("retrieve_topk", after_scores, after_rows, Q, "Q", dev)
+    if c is not None:
+        x = None
+        if exclude_rows is not None:
+            x = STRUCTS["lthm_retrieve_excl"]()
+            x.rows, x.X = ptr(exclude_rows), X
+        call("lthm_retrieve_topk_after", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
+             ctypes.addressof(t) if t is not None else None, ctypes.addressof(c), stream(), _key="retr_topk_after_k",
+             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
+             _bytes=nbytes + 4.0 * Q * X + (4.0 * N + 12.0 * Q if t is not None else 0.0) + 8.0 * Q)
+    elif t is not None:
         x = None
         if exclude_rows is not None:
             x = STRUCTS["lthm_retrieve_excl"]()
@@ -1757,7 +1835,8 @@ RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
 
 
 def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
-                        exclude_rows=None, tags=None, tag_filter=None):
+                        exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
+                        deep: bool = False):
     """retrieve_topk for users with several queries each: an item's score is its best over the
     user's queries, s[u, j] = max_g s_g[u, j], with s_g the score retrieve_topk gives query
     (u, g) (csrc/retrieve.hip, retr_topk_k<EXCL, GP>).
@@ -1770,9 +1849,16 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     s[u, j] > target_score[u]} (-1 where the target is no catalogue row).  The outputs do not
     depend on the order of a user's queries; G = 1 is retrieve_topk on q[:, 0].  Which query
     attained a score is not reported.  tags int32 [N] and tag_filter int32 [U, 3], one filter per
-    user, are retrieve_topk's: an ineligible row is -inf for the user, like an excluded one."""
+    user, are retrieve_topk's: an ineligible row is -inf for the user, like an excluded one.
+    after_scores f32 [U] and after_rows int32 [U], one cursor per user on the best-over-queries
+    score, and deep=True (k up to RETRIEVE_MAX_DEEP, one catalogue scan per 128 rows) are
+    retrieve_topk's as well."""
     import ctypes
     from ._lib import STRUCTS
+    if deep and int(k) > RETRIEVE_MAX_K:
+        return _retrieve_deep(retrieve_topk_group, q, items, k, target_rows, after_scores, after_rows,
+                              dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
+                                   tag_filter=tag_filter))
     require_gpu(q, items, target_rows, exclude_rows)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"retrieve_topk_group takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
@@ -1816,7 +1902,13 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     g.G = G
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
     t = _retrieve_tags("retrieve_topk_group", tags, tag_filter, items, U, "U")
-    if t is not None:
+    c = _retrieve_cursor("retrieve_topk_group", after_scores, after_rows, U, "U", dev)
+    if c is not None:
+        call("lthm_retrieve_topk_after", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
+             ctypes.addressof(g), ctypes.addressof(t) if t is not None else None, ctypes.addressof(c), stream(),
+             _key="retr_topk_group_after_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
+             _bytes=nbytes + (4.0 * N + 12.0 * U if t is not None else 0.0) + 8.0 * U)
+    elif t is not None:
         call("lthm_retrieve_topk_tags", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
              ctypes.addressof(g), ctypes.addressof(t), stream(), _key="retr_topk_group_tags_k",
              _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * N + 12.0 * U)

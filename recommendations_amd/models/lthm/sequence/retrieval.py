@@ -134,9 +134,17 @@ class ItemCatalogue:
         rows = torch.where(self.ids[at] == flat, at, torch.full_like(at, -1))
         return rows.to(torch.int32).view(ids.shape)
 
+    def cursor_rows(self, after_ids: torch.Tensor) -> torch.Tensor:
+        """The row cursor of an id cursor (int32, same shape): (number of catalogue ids <=
+        after_id) - 1, so that "row > cursor row" means "id > after_id" whether or not the
+        catalogue holds after_id.  An id below the first gives -1, one above the last N - 1."""
+        flat = after_ids.reshape(-1).to(self.ids.device).contiguous()
+        return (torch.searchsorted(self.ids, flat, right=True) - 1).to(torch.int32).view(after_ids.shape)
+
     def topk(self, q: torch.Tensor, k: int, *, normalize_q: bool = True, target_ids: Optional[torch.Tensor] = None,
              slab_rows: int = 0, exclude_ids: Optional[torch.Tensor] = None,
-             tag_filter: Optional[torch.Tensor] = None):
+             tag_filter: Optional[torch.Tensor] = None, after_scores: Optional[torch.Tensor] = None,
+             after_ids: Optional[torch.Tensor] = None):
         """The k best items per query: (item_ids int64 [Q, k], scores f32 [Q, k], rank, target_score).
         Empty slots (N < k) hold id 0 and score -inf.  With ``target_ids`` [Q], ``rank`` is each
         query's count of items scoring strictly above its target (-1 where the catalogue does
@@ -150,9 +158,23 @@ class ItemCatalogue:
         ``tag_filter`` int32 [Q, 3] ([U, 3] with a 3-D ``q``) = (all, any, none) restricts query q
         to the items whose tag word passes it (see ``make_tag_filter`` and ``filter_like``): the others
         take no slot and do not count in ``rank``, exactly like excluded items.  The catalogue
-        must carry tags."""
+        must carry tags.
+        ``after_scores`` f32 [Q] and ``after_ids`` int64 [Q] ([U] with a 3-D ``q``), together or
+        neither, start every list strictly behind (score, id) in the order (score descending, id
+        ascending): the last column of one page is the cursor of the next, and it stays valid
+        after its item has left the catalogue (``cursor_rows``).  The empty slot (-inf, 0) of an
+        exhausted page gives an empty page.  ``k`` may reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above
+        128 the catalogue is scanned once per 128 rows."""
         if tag_filter is not None and self.tags is None:
             raise ValueError("tag_filter given, but this catalogue carries no tags")
+        if (after_scores is None) != (after_ids is None):
+            raise ValueError("after_scores and after_ids are given together or neither")
+        ar = None
+        if after_ids is not None:
+            if after_ids.dtype != torch.int64 or after_ids.dim() != 1:
+                raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
+            ar = self.cursor_rows(after_ids).contiguous()
+            after_scores = after_scores.contiguous()
         tr = self.rows_of(target_ids).contiguous() if target_ids is not None else None
         xr = None
         if exclude_ids is not None:
@@ -162,7 +184,8 @@ class ItemCatalogue:
         call = K.retrieve_topk_group if q.dim() == 3 else K.retrieve_topk
         scores, rows, rank, tscore = call(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
                                           slab_rows=slab_rows, exclude_rows=xr,
-                                          tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter)
+                                          tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter,
+                                          after_scores=after_scores, after_rows=ar, deep=int(k) > K.RETRIEVE_MAX_K)
         item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
         return item_ids, scores, rank, tscore
 

@@ -347,7 +347,7 @@ class LTHMModelWrapper(BaseModelWrapper):
     @torch.no_grad()
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
                  exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
-                 tag_all=None, tag_any=None, tag_none=None) -> Dict[str, torch.Tensor]:
+                 tag_all=None, tag_any=None, tag_none=None, after=None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -360,7 +360,20 @@ class LTHMModelWrapper(BaseModelWrapper):
         ``tag_all`` / ``tag_any`` / ``tag_none`` (each an int or an int tensor [B] of 32-bit masks;
         the catalogue must carry tags) sequence b gets only items whose tag word has every
         ``tag_all`` bit, some ``tag_any`` bit and no ``tag_none`` bit: the k best items that may
-        be shown.  The filter composes with ``exclude_history`` and ``heads``."""
+        be shown.  The filter composes with ``exclude_history`` and ``heads``.  ``after`` asks for
+        the next page: the dict a previous ``retrieve`` returned (its last column is the cursor)
+        or ``(scores [B], item_ids [B])``; sequence b then gets the k best items strictly behind
+        that position of its list, with every other argument as in the call before.  ``k`` may
+        reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above 128 the catalogue is scanned once per 128
+        rows."""
+        after_scores = after_ids = None
+        if after is not None:
+            if isinstance(after, dict):
+                after_scores, after_ids = after["scores"][:, -1], after["item_ids"][:, -1]
+            else:
+                after_scores, after_ids = after
+            if after_scores.dim() != 1 or after_ids.dim() != 1 or after_ids.dtype != torch.int64:
+                raise ValueError("after takes a retrieve() result or (scores f32 [B], item_ids int64 [B])")
         if heads is not None:
             heads = [int(h) for h in heads]
             n_heads = len(self._lookahead)
@@ -388,7 +401,11 @@ class LTHMModelWrapper(BaseModelWrapper):
                 raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
             filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
                                    0 if tag_none is None else tag_none, device=q.device)
-        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt)
+        if after_scores is not None:
+            after_scores = after_scores.to(device=q.device, dtype=torch.float32).contiguous()
+            after_ids = after_ids.to(q.device).contiguous()
+        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt,
+                                                after_scores=after_scores, after_ids=after_ids)
         return {"item_ids": item_ids, "scores": scores}
 
     @torch.no_grad()

@@ -2,7 +2,7 @@
 ``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
 
     python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
-                                    [--group G] [--tags P]
+                                    [--group G] [--tags P] [--after] [--deep K]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -31,6 +31,12 @@ shape stops the run.  One JSON line per shape:
                           -inf.  With --exclude also the excluding + filtered call (xtags_*, over the
                           plain call), with --group the grouped + filtered call (gtags_*, over the
                           plain and over the grouped call)
+  after_* (--after)       page 2 of k rows (the call with page 1's last (score, row) as its cursor) timed
+                          next to page 1, the plain call: after_over_fused on the medians (_hi: the worst
+                          pairing), its rows against entries k .. 2k - 1 of a torch top-2k
+  deep_* (--deep K)       the deep list of K rows (ceil(K / 128) passes, one catalogue scan each) against
+                          the baseline's top-K (deep_base_*): deep_over_base on the medians (_hi: the worst
+                          pairing), deep_over_fused against the plain call, its rows against a torch top-K
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -66,7 +72,8 @@ def merge_heads(lists, k):
     return sc.gather(1, o), rw.gather(1, o)
 
 
-def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0, tags_p: float = -1.0) -> None:
+def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0, tags_p: float = -1.0,
+          after: bool = False, deep: int = 0) -> None:
     import torch
     from recommendations_amd import kernels as K
     Q = SHAPES[name]
@@ -127,11 +134,32 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
         if group:
             extras.append(("gtags", fused_group_tags, []))
 
-    def base():
+    cur = None
+    if after:  # page 2 behind the last column of page 1
+        p_scores, p_rows, _, _ = fused()
+        cur = (p_scores[:, -1].contiguous(), p_rows[:, -1].contiguous())
+
+    def fused_after():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False, after_scores=cur[0], after_rows=cur[1])
+
+    def fused_deep():
+        return K.retrieve_topk(q_bf, items, deep, normalize_q=False, deep=True)
+
+    def base(kk=k):
         out = []
         for lo in range(0, Q, BASE_CHUNK):
-            out.append((q_bf[lo:lo + BASE_CHUNK] @ items.T).float().topk(k))
+            out.append((q_bf[lo:lo + BASE_CHUNK] @ items.T).float().topk(kk))
         return out
+
+    def base_deep():
+        return base(deep)
+
+    more = []  # (key, function, times, every rep or the baseline's fewer)
+    if after:
+        more.append(("after", fused_after, [], True))
+    if deep:
+        more.append(("deep", fused_deep, [], True))
+        more.append(("deep_base", base_deep, [], False))
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -151,6 +179,8 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
             heads_merge()
         for _, fn, _ in extras:
             fn()
+        for _, fn, _, _ in more:
+            fn()
         base()
     torch.cuda.synchronize()
     tf, tx, tb, tg, th = [], [], [], [], []
@@ -163,6 +193,9 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
             th.append(timed(heads_merge))
         for _, fn, times in extras:
             times.append(timed(fn))
+        for _, fn, times, every in more:
+            if every or i < nb:
+                times.append(timed(fn))
         if i < nb:
             tb.append(timed(base))
     scores, rows, _, _ = fused()
@@ -215,6 +248,27 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
         if exclude:
             extra.update({"xtags_over_excl": round(extra["xtags_ms"] / statistics.median(tx), 4),
                           "xtags_over_excl_hi": round(extra["xtags_max_ms"] / min(tx), 4)})
+    stats = {}
+    for key, _, times, _ in more:
+        stats[key] = statistics.median(times)
+        extra.update({f"{key}_ms": round(stats[key], 4), f"{key}_min_ms": round(min(times), 4),
+                      f"{key}_max_ms": round(max(times), 4), f"{key}_reps": len(times)})
+    if after:
+        # page 2 against entries k .. 2k - 1 of an f32 torch top-2k
+        a_rows = fused_after()[1]
+        ref2 = (q_bf[:nq].float() @ items.float().T).topk(2 * k)
+        a_same = float((a_rows[:nq].long() == ref2.indices[:, k:]).float().mean())
+        extra.update({"after_over_fused": round(stats["after"] / fm, 4),
+                      "after_over_fused_hi": round(extra["after_max_ms"] / min(tf), 4),
+                      "after_check_rows_equal": round(a_same, 4)})
+    if deep:
+        d_rows = fused_deep()[1]
+        refd = (q_bf[:nq].float() @ items.float().T).topk(deep)
+        d_same = float((d_rows[:nq].long() == refd.indices).float().mean())
+        extra.update({"deep": deep, "deep_passes": len(K.retrieve_deep_passes(deep)),
+                      "deep_over_base": round(stats["deep"] / stats["deep_base"], 4),
+                      "deep_over_base_hi": round(extra["deep_max_ms"] / extra["deep_base_min_ms"], 4),
+                      "deep_over_fused": round(stats["deep"] / fm, 4), "deep_check_rows_equal": round(d_same, 4)})
     print(json.dumps({
         "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
         "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
@@ -239,6 +293,10 @@ def main() -> int:
                     help="also time the grouped call with G queries per user (2..8), the G plain calls and their merge")
     ap.add_argument("--tags", type=float, default=-1.0,
                     help="also time the filtered call with random tags, a fraction P (0..1) of the rows eligible")
+    ap.add_argument("--after", action="store_true",
+                    help="also time page 2 (the k rows behind page 1's last column) next to page 1, in the same loop")
+    ap.add_argument("--deep", type=int, default=0,
+                    help="also time the deep list of K rows (129..1024) against the torch baseline's top-K")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -248,8 +306,10 @@ def main() -> int:
         raise SystemExit("--group takes 0 (off) or 2..8 queries per user")
     if a.tags != -1.0 and not 0.0 <= a.tags <= 1.0:
         raise SystemExit("--tags takes a fraction in 0..1")
+    if a.deep and not 129 <= a.deep <= 1024:
+        raise SystemExit("--deep takes 0 (off) or a list length in 129..1024")
     if a.child:
-        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags)
+        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags, a.after, a.deep)
         return 0
     for name in a.shapes.split(","):
         if name not in SHAPES:
@@ -257,7 +317,8 @@ def main() -> int:
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
-                                 "--group", str(a.group), "--tags", str(a.tags)],
+                                 "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep)]
+                                + (["--after"] if a.after else []),
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
