@@ -1057,8 +1057,9 @@ __global__ __launch_bounds__(256) void outcome_fwd_k(const float* __restrict__ x
 using namespace lthm;
 
 extern "C" int lthm_flip_tokens(const int64_t* in, int64_t* out, int64_t B, int32_t T, void* stream) {
-  LTHM_REQUIRE(B >= 0 && T >= 0 && in != out);
-  if (B * T == 0) return 0;
+  LTHM_REQUIRE(B >= 0 && T >= 0);
+  if (B * T == 0) return 0;  // before the aliasing test: two empty tensors both have a null pointer
+  LTHM_REQUIRE(in != out);
   hipLaunchKernelGGL(flip_k, dim3(grid_for(B * T, 256)), dim3(256), 0, (hipStream_t)stream, in, out, B, T);
   LTHM_CHECK_LAUNCH();
   return 0;
