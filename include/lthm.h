@@ -938,6 +938,33 @@ typedef struct lthm_retrieve_cursor {
  * and 4-byte aligned.  The workspace is the group call's: lthm_retrieve_group_ws_bytes. */
 int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
                              const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, void* stream);
+/* Score priors: a per-item bias, weighted per query, added to the score inside the kernel.
+ *   bias    f32 [N]: one word per catalogue row, every value finite
+ *   weight  f32 [Q] (with groups [U], one per user), or NULL for 1 everywhere
+ * The score of row j for query q becomes
+ *             s_j = fmaf(weight[q], bias[j], dot_j)
+ * one f32 fused multiply-add on the f32 score dot_j the calls above give (with groups the best over
+ * the user's queries: the prior is added after the maximum).  Everything else sees s_j and only
+ * s_j: the order and the tie rule (score descending, row ascending), the scores returned, the
+ * cursor test and rank.  A row at -inf (excluded, filtered, behind the cursor) stays at -inf.  The
+ * target is biased the same way, target_score = fmaf(weight[q], bias[target], dot_target), which is
+ * the value written and the value rank counts against:
+ *   rank = #{j != target, j eligible : s_j > target_score};
+ * the target is never excluded or filtered as a target.  weight = 0 and an all-zero bias give the
+ * rows and ranks of the call without a prior, with equal scores (-0 may come back as +0).  A
+ * non-finite weight gives that query an unspecified list and nothing else: weights and biases are
+ * only ever values.  Priors compose with exclusion, groups, tag filters and cursors (a cursor is a
+ * position in the order of the biased scores), and the outputs stay a pure function of the inputs.
+ * Both arrays are read with 4-byte loads (4-byte aligned), bias never at or past N. */
+typedef struct lthm_retrieve_bias {
+  const float* bias;
+  const float* weight;
+} lthm_retrieve_bias;
+/* b == NULL is lthm_retrieve_topk_after(d, x, g, t, c, stream); with b, bias must be non-null and
+ * both pointers 4-byte aligned.  The workspace is the group call's: lthm_retrieve_group_ws_bytes. */
+int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                            const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                            void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

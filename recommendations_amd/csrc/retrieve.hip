@@ -45,6 +45,15 @@
 // and masks the accumulator next to the other masks; the instantiations without it hold none of
 // this.  Since a (query, row) score does not depend on the slab cut, a page's last (score, row)
 // as the next call's cursor continues the same order without a gap or a duplicate.
+//
+// Priors (lthm_retrieve_topk_bias): the catalogue may carry one f32 bias per row and a query (user)
+// a weight, and the score becomes s = fmaf(weight, bias[row], dot), one explicit f32 fma on the
+// MFMA's score, before anything looks at a score.  retr_topk_k<true, GP, TAGS, true, true> stages
+// the 64 bias words of tile i + 1 with its image (one more LDS-DMA, of wave 1, retired by the same
+// wait and barrier), reads its 16 rows' words back as four broadcast 16-byte LDS reads and applies
+// 16 fmas behind the group maximum and ahead of every mask.  retr_bias_target_k gives the target
+// score the same fma between the prep kernel and the scan, so that the value written out is the
+// value counted against.  The instantiations without a prior hold none of this.
 #include "mfma.hpp"
 
 #include <climits>
@@ -82,9 +91,17 @@ struct RetrSharedTags : RetrShared {
   alignas(16) int tag[2][RT_IT];  // a lane reads four words at once
 };
 static_assert(sizeof(RetrSharedTags) <= 160 * 1024, "LDS budget");
+// retr_topk_k<.., .., TAGS, .., true>: the bias words of the two images' rows behind the layout of
+// <.., .., TAGS>
+template <class Base>
+struct RetrSharedBias : Base {
+  alignas(16) float bias[2][RT_IT];  // a lane reads four words at once
+};
+static_assert(sizeof(RetrSharedBias<RetrSharedTags>) <= 160 * 1024, "LDS budget");
 
 __device__ __attribute__((aligned(16))) unsigned char retr_zero_row[256];
 __device__ int retr_zero_tag;  // the tag of a row at or past the slab's end
+__device__ float retr_zero_bias;  // and its bias
 
 __device__ __forceinline__ u64 retr_key(float s, int row) {
   uint32_t u = __float_as_uint(s + 0.f);  // -0 -> +0: equal scores get equal images
@@ -162,7 +179,17 @@ struct RetrAfterArgs : Base {
   const int* arow;      // [Q] (GP > 1: [U])
 };
 template <bool EXCL, int GP, bool TAGS, bool AFTER>
-using RetrTopkArgs = std::conditional_t<AFTER, RetrAfterArgs<RetrFiltArgs<EXCL, GP, TAGS>>, RetrFiltArgs<EXCL, GP, TAGS>>;
+using RetrCursArgs = std::conditional_t<AFTER, RetrAfterArgs<RetrFiltArgs<EXCL, GP, TAGS>>, RetrFiltArgs<EXCL, GP, TAGS>>;
+// retr_topk_k<true, GP, TAGS, true, true>: the arguments of <true, GP, TAGS, true> and the prior
+// behind them
+template <class Base>
+struct RetrBiasArgs : Base {
+  const float* bias;  // [N]
+  const float* bw;    // [Q] (GP > 1: [U]) or null: 1 for everyone
+};
+template <bool EXCL, int GP, bool TAGS, bool AFTER, bool BIAS = false>
+using RetrTopkArgs =
+    std::conditional_t<BIAS, RetrBiasArgs<RetrCursArgs<EXCL, GP, TAGS, AFTER>>, RetrCursArgs<EXCL, GP, TAGS, AFTER>>;
 
 // The maximum of x over the GP adjacent lanes of a group, in every lane of it: xor distances 1
 // and 2 as DPP quad permutes ([1,0,3,2], [2,3,0,1]); then all four lanes of a quad hold the
@@ -323,6 +350,20 @@ __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ 
   if (trow && in && sub == 0) tscore[u] = ok ? best : -INFINITY;
 }
 
+// The prior of the target: tscore[q] = fmaf(weight[q], bias[target], tscore[q]) behind either prep
+// kernel (with groups q is a user and tscore the best of the plain dots), ahead of the scan, which
+// reads it as the score to count against.  No target (-inf) stays -inf; bias is read at rows in
+// [0, N) only.
+__global__ __launch_bounds__(256) void retr_bias_target_k(const int* __restrict__ trow, int64_t Q, int64_t N,
+                                                          const float* __restrict__ bias, const float* __restrict__ bw,
+                                                          float* __restrict__ tscore) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= Q) return;
+  const int tr = trow[q];
+  if (tr < 0 || tr >= N) return;
+  tscore[q] = __builtin_fmaf(bw ? bw[q] : 1.f, bias[tr], tscore[q]);
+}
+
 // ---------------------------------------------------------------- scores + threshold selection
 // Wave w: queries 32 (w & 1) + (lane & 31) of the tile (MFMA columns, so every per-query value
 // is a per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3).
@@ -351,9 +392,17 @@ __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ 
 // 0..27.  A lane that is no leader keeps cs = +inf, which every finite score is below.  An
 // AFTER instantiation takes a null list (a.xs) as "no exclusion": the cursor call without a list
 // runs the excluding instantiation, whose walk then never starts.
-template <bool EXCL, int GP = 1, bool TAGS = false, bool AFTER = false>
-__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, AFTER> a) {
-  __shared__ __attribute__((aligned(16))) std::conditional_t<TAGS, RetrSharedTags, RetrShared> sh;
+//
+// BIAS: the lane keeps its query's weight wq (1 without a.bw) and every accumulator element
+// becomes fmaf(wq, bias of its row, element) behind the partial-tile mask and the group maximum
+// and ahead of the other masks, the count and the filter.  A row past the slab reads the zero word
+// and stays at -inf; a lane that is no leader keeps wq = 0.  BIAS exists for <true, GP, TAGS, true>
+// only and takes a null cursor (a.ascore) as "no cursor", the way AFTER takes a null list.
+template <bool EXCL, int GP = 1, bool TAGS = false, bool AFTER = false, bool BIAS = false>
+__global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, AFTER, BIAS> a) {
+  static_assert(!BIAS || (EXCL && AFTER), "the prior rides on the excluding cursor instantiations");
+  using RetrSharedFilt = std::conditional_t<TAGS, RetrSharedTags, RetrShared>;
+  __shared__ __attribute__((aligned(16))) std::conditional_t<BIAS, RetrSharedBias<RetrSharedFilt>, RetrSharedFilt> sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
   const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
@@ -430,10 +479,14 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
   float cs = INFINITY;  // a query past Q and a slot that is no leader: no cursor
   int cr = -1;
   if constexpr (AFTER) {
-    if (lead) {
+    if (lead && (!BIAS || a.ascore != nullptr)) {
       cs = a.ascore[uq];
       cr = a.arow[uq];
     }
+  }
+  float wq = 0.f;  // a query past Q and a slot that is no leader: no prior
+  if constexpr (BIAS) {
+    if (lead) wq = a.bw ? a.bw[uq] : 1.f;
   }
   int roff[8];
 #pragma unroll
@@ -458,6 +511,14 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
       if (w == 0) {
         const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
         glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+      }
+    }
+    if constexpr (BIAS) {
+      // wave 1, lane l: the bias of the image's row l (wave 0 carries the tags); never a read at
+      // or past row_hi <= N
+      if (w == 1) {
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
       }
     }
   };
@@ -492,6 +553,13 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
 #pragma unroll
       for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
     }
+    // BIAS: the same four runs of the bias words, read the same way
+    float4 b4[4];
+    if constexpr (BIAS) {
+      const float4* bp = reinterpret_cast<const float4*>(sh.bias[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b4[j] = bp[2 * j];
+    }
     f32x16 acc = {};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -508,6 +576,15 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
     if constexpr (GP > 1) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) acc[v] = retr_group_max<GP>(acc[v]);
+    }
+    if constexpr (BIAS) {
+      // the score from here on; a row past the slab is fmaf(wq, 0, -inf) = -inf
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bw4[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[4 * j + c] = __builtin_fmaf(wq, bw4[c], acc[4 * j + c]);
+      }
     }
     if constexpr (EXCL) {
       // the tile's excluded rows, folded into a mask of this lane's own elements (the target's
@@ -749,9 +826,46 @@ inline bool retr_cursor_ok(const lthm_retrieve_cursor* c) {
                 ((uintptr_t)c->after_row & 3) == 0);
 }
 
-// lthm_retrieve_topk_group / _tags / _after with G >= 2: d->Q users of G queries each
+// The call with a prior: always an excluding cursor instantiation (a.xs == nullptr without a
+// list, ascore == nullptr without a cursor), with or without tags
+template <int GP>
+void retr_launch_bias(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, const lthm_retrieve_tags* t,
+                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
+  if (t) {
+    RetrTopkArgs<true, GP, true, true, true> ba;
+    static_cast<RetrBaseArgs<true, GP>&>(ba) = a;
+    ba.tags = t->tags;
+    ba.filt = t->filter;
+    ba.ascore = c ? c->after_score : nullptr;
+    ba.arow = c ? c->after_row : nullptr;
+    ba.bias = b->bias;
+    ba.bw = b->weight;
+    hipLaunchKernelGGL((retr_topk_k<true, GP, true, true, true>), grid, dim3(256), 0, s, ba);
+  } else {
+    RetrTopkArgs<true, GP, false, true, true> ba;
+    static_cast<RetrBaseArgs<true, GP>&>(ba) = a;
+    ba.ascore = c ? c->after_score : nullptr;
+    ba.arow = c ? c->after_row : nullptr;
+    ba.bias = b->bias;
+    ba.bw = b->weight;
+    hipLaunchKernelGGL((retr_topk_k<true, GP, false, true, true>), grid, dim3(256), 0, s, ba);
+  }
+}
+
+inline bool retr_bias_ok(const lthm_retrieve_bias* b) {
+  return !b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0);
+}
+
+// the target's prior, behind the prep kernel that wrote d->target_score
+inline void retr_launch_bias_target(const lthm_retrieve_desc* d, const lthm_retrieve_bias* b, hipStream_t s) {
+  hipLaunchKernelGGL(retr_bias_target_k, dim3((unsigned)((d->Q + 255) / 256)), dim3(256), 0, s, d->target_row, d->Q, d->N,
+                     b->bias, b->weight, d->target_score);
+}
+
+// lthm_retrieve_topk_group / _tags / _after / _bias with G >= 2: d->Q users of G queries each
 int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G,
-                           const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, void* stream) {
+                           const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                           void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
@@ -762,6 +876,7 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   LTHM_REQUIRE(retr_cursor_ok(c));
+  LTHM_REQUIRE(retr_bias_ok(b));
   const int64_t need = lthm_retrieve_group_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
   const int64_t U = d->Q, N = d->N;
@@ -784,6 +899,10 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
     hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
                        d->normalize_q, qn, items, N, d->target_row, d->target_score);
   LTHM_CHECK_LAUNCH();
+  if (b && d->target_row) {
+    retr_launch_bias_target(d, b, s);
+    LTHM_CHECK_LAUNCH();
+  }
   RetrGroupArgs a;
   a.items = items;
   a.qn = qn;
@@ -808,7 +927,11 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
     a.xs = xs;
     a.xstride = X + 1;
   }
-  if (c) {
+  if (b) {
+    if (gp == 2) retr_launch_bias<2>(tgrid, s, a, t, c, b);
+    else if (gp == 4) retr_launch_bias<4>(tgrid, s, a, t, c, b);
+    else retr_launch_bias<8>(tgrid, s, a, t, c, b);
+  } else if (c) {
     if (gp == 2) retr_launch_after<2>(tgrid, s, a, t, c);
     else if (gp == 4) retr_launch_after<4>(tgrid, s, a, t, c);
     else retr_launch_after<8>(tgrid, s, a, t, c);
@@ -829,7 +952,7 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
 // the plain, the excluding and the filtering entry points: x == nullptr and t == nullptr is the
 // plain call
 int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
-                const lthm_retrieve_cursor* c, void* stream) {
+                const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
@@ -839,6 +962,7 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   LTHM_REQUIRE(retr_cursor_ok(c));
+  LTHM_REQUIRE(retr_bias_ok(b));
   const int64_t need = x ? lthm_retrieve_excl_ws_bytes(d->Q, d->N, d->k, d->slab_rows, x->X)
                          : lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
   LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
@@ -859,6 +983,10 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
     hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, Q, d->normalize_q, qn,
                        items, N, d->target_row, d->target_score);
   LTHM_CHECK_LAUNCH();
+  if (b && d->target_row) {
+    retr_launch_bias_target(d, b, s);
+    LTHM_CHECK_LAUNCH();
+  }
   RetrExclArgs a;
   a.items = items;
   a.qn = qn;
@@ -884,7 +1012,9 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
     a.xs = xs;
     a.xstride = X + 1;
   }
-  if (c) {
+  if (b) {
+    retr_launch_bias<1>(tgrid, s, a, t, c, b);
+  } else if (c) {
     retr_launch_after<1>(tgrid, s, a, t, c);
   } else if (x) {
     if (t) {
@@ -915,28 +1045,35 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
 }  // namespace
 
 extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
-  return retr_launch(d, nullptr, nullptr, nullptr, stream);
+  return retr_launch(d, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
-  return retr_launch(d, x, nullptr, nullptr, stream);
+  return retr_launch(d, x, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, t, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, t, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                         const lthm_retrieve_cursor* c, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, c, stream);
-  return retr_launch_group_call(d, x, g->G, t, c, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, t, c, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, t, c, nullptr, stream);
+}
+
+extern "C" int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                       const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
+                                       const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
+  if (!g || g->G == 1) return retr_launch(d, x, t, c, b, stream);
+  return retr_launch_group_call(d, x, g->G, t, c, b, stream);
 }

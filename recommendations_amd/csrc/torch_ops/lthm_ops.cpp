@@ -21,6 +21,7 @@
 //   lthm::retrieve_topk_group the same for users of several queries, by the best score over them
 //   lthm::retrieve_topk_tags  any of the above among the rows whose tag word passes the query's filter
 //   lthm::retrieve_topk_after any of the above strictly behind a (score, row) cursor per query
+//   lthm::retrieve_topk_bias  any of the above on the score fma(weight[q], bias[row], dot)
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -480,7 +481,8 @@ std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor
 std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
                                                     const c10::optional<Tensor>& exclude_rows, const Tensor* tags_,
                                                     const Tensor* filter_, const Tensor* after_scores_ = nullptr,
-                                                    const Tensor* after_rows_ = nullptr) {
+                                                    const Tensor* after_rows_ = nullptr, const Tensor* bias_ = nullptr,
+                                                    const Tensor* bias_weight_ = nullptr) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
@@ -528,6 +530,21 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
     cs = after_scores_->contiguous();
     cr = after_rows_->contiguous();
   }
+  Tensor bs, bw;
+  if (bias_) {
+    on_gpu(*bias_, "bias");
+    TORCH_CHECK(bias_->scalar_type() == at::kFloat && bias_->dim() == 1 && bias_->size(0) == N,
+                "bias must be f32 [N], one word per catalogue row");
+    TORCH_CHECK(bias_->device() == items.device(), "bias must be on the catalogue's device");
+    bs = bias_->contiguous();
+    if (bias_weight_) {
+      on_gpu(*bias_weight_, "bias_weight");
+      TORCH_CHECK(bias_weight_->scalar_type() == at::kFloat && bias_weight_->dim() == 1 && bias_weight_->size(0) == U,
+                  "bias_weight must be f32 [Q], one weight per query (per user for a 3-D q)");
+      TORCH_CHECK(bias_weight_->device() == q.device(), "bias_weight must be on the queries' device");
+      bw = bias_weight_->contiguous();
+    }
+  }
   const int64_t need = lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
   TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
   auto scores = at::empty({U, k}, q.options().dtype(at::kFloat));
@@ -552,7 +569,24 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   }
   lthm_retrieve_group g = {};
   g.G = (int32_t)G;
-  if (after_scores_) {
+  if (bias_) {
+    lthm_retrieve_tags t = {};
+    if (tags_) {
+      t.tags = tg.data_ptr<int32_t>();
+      t.filter = tf.data_ptr<int32_t>();
+    }
+    lthm_retrieve_cursor c = {};
+    if (after_scores_) {
+      c.after_score = cs.data_ptr<float>();
+      c.after_row = cr.data_ptr<int32_t>();
+    }
+    lthm_retrieve_bias b = {};
+    b.bias = bs.data_ptr<float>();
+    b.weight = bias_weight_ ? bw.data_ptr<float>() : nullptr;
+    hip_ok(lthm_retrieve_topk_bias(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, after_scores_ ? &c : nullptr, &b,
+                                   cur_stream()),
+           "lthm_retrieve_topk_bias");
+  } else if (after_scores_) {
     lthm_retrieve_tags t = {};
     if (tags_) {
       t.tags = tg.data_ptr<int32_t>();
@@ -604,6 +638,28 @@ std::tuple<Tensor, Tensor> retrieve_topk_after_cuda(const Tensor& q, const Tenso
                                   &after_rows);
 }
 
+// the same on the score fma(bias_weight[q], bias[row], dot); tags and tag_filter, and after_scores
+// and after_rows, are both given or both None; bias_weight None is 1 for every query
+std::tuple<Tensor, Tensor> retrieve_topk_bias_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                   const c10::optional<Tensor>& exclude_rows,
+                                                   const c10::optional<Tensor>& tags,
+                                                   const c10::optional<Tensor>& tag_filter,
+                                                   const c10::optional<Tensor>& after_scores,
+                                                   const c10::optional<Tensor>& after_rows, const Tensor& bias,
+                                                   const c10::optional<Tensor>& bias_weight) {
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "q must be [Q, 128] or [U, G, 128]");
+  const bool has_tags = tags.has_value() && tags->defined(), has_filter = tag_filter.has_value() && tag_filter->defined();
+  TORCH_CHECK(has_tags == has_filter, "retrieve_topk_bias takes tags and tag_filter together or neither");
+  const bool has_cs = after_scores.has_value() && after_scores->defined();
+  const bool has_cr = after_rows.has_value() && after_rows->defined();
+  TORCH_CHECK(has_cs == has_cr, "retrieve_topk_bias takes after_scores and after_rows together or neither");
+  const bool has_w = bias_weight.has_value() && bias_weight->defined();
+  return retrieve_topk_group_impl(q.dim() == 2 ? q.unsqueeze(1) : q, items, k, normalize_q, exclude_rows,
+                                  has_tags ? &*tags : nullptr, has_tags ? &*tag_filter : nullptr,
+                                  has_cs ? &*after_scores : nullptr, has_cs ? &*after_rows : nullptr, &bias,
+                                  has_w ? &*bias_weight : nullptr);
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -634,6 +690,10 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_topk_after(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
       "Tensor? tag_filter, Tensor after_scores, Tensor after_rows) -> (Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_bias(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
+      "Tensor? tag_filter, Tensor? after_scores, Tensor? after_rows, Tensor bias, Tensor? bias_weight=None) -> "
+      "(Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -648,6 +708,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_group", &retrieve_topk_group_cuda);
   m.impl("retrieve_topk_tags", &retrieve_topk_tags_cuda);
   m.impl("retrieve_topk_after", &retrieve_topk_after_cuda);
+  m.impl("retrieve_topk_bias", &retrieve_topk_bias_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

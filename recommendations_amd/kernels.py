@@ -1696,6 +1696,35 @@ def _retrieve_cursor(who: str, after_scores, after_rows, n: int, per: str, devic
     return c
 
 
+def _retrieve_bias(who: str, bias, bias_weight, items, n: int, per: str, device):
+    """(the lthm_retrieve_bias of a call, the weight tensor it points at) or (None, None) without
+    a prior: bias f32 [N], contiguous, on the catalogue's device; bias_weight None (1 for everyone),
+    a Python number (one weight for everyone) or f32 [n], contiguous, on the queries' device."""
+    from ._lib import STRUCTS
+    if bias is None:
+        _check(bias_weight is None, f"{who} takes a bias_weight only with a bias")
+        return None, None
+    N = items.shape[0]
+    _check(isinstance(bias, torch.Tensor) and bias.dtype == torch.float32 and tuple(bias.shape) == (N,),
+           f"bias must be f32 [N], one word per catalogue row (got {getattr(bias, 'dtype', type(bias).__name__)} "
+           f"{tuple(getattr(bias, 'shape', ()))}, N={N})")
+    _check(bias.is_contiguous(), "bias must be contiguous")
+    _check(bias.device == items.device, "bias must be on the catalogue's device")
+    w = bias_weight
+    if w is not None and not isinstance(w, torch.Tensor):
+        _check(isinstance(w, (int, float)) and not isinstance(w, bool),
+               f"bias_weight must be None, a number or an f32 tensor [{per}] (got {type(w).__name__})")
+        w = torch.full((n,), float(w), dtype=torch.float32, device=device)
+    if w is not None:
+        _check(w.dtype == torch.float32 and tuple(w.shape) == (n,),
+               f"bias_weight must be f32 [{per}] (got {w.dtype} {tuple(w.shape)}, {per}={n})")
+        _check(w.is_contiguous(), "bias_weight must be contiguous")
+        _check(w.device == device, "bias_weight must be on the queries' device")
+    b = STRUCTS["lthm_retrieve_bias"]()
+    b.bias, b.weight = ptr(bias), ptr(w)
+    return b, w
+
+
 def retrieve_deep_passes(k: int):
     """The per-pass list lengths of a deep call: ceil(k / 128) passes, all of RETRIEVE_MAX_K rows
     but the last, which takes the rest.  k in 1..RETRIEVE_MAX_DEEP."""
@@ -1725,7 +1754,7 @@ def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows
 
 def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
                   exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
-                  deep: bool = False):
+                  deep: bool = False, bias=None, bias_weight=None):
     """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
 
     q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
@@ -1758,13 +1787,25 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     deep=True lifts the cap on k from 128 to RETRIEVE_MAX_DEEP = 1024: the call runs
     ceil(k / 128) passes, each behind the last column of the one before (no host sync), and
     concatenates them; rank and target_score are the first pass's.  A deep list costs one scan of
-    the catalogue per 128 rows.  Without deep, k > 128 is refused as it always was."""
+    the catalogue per 128 rows.  Without deep, k > 128 is refused as it always was.
+
+    bias f32 [N] (contiguous, on the catalogue's device, every value finite) and bias_weight None, a
+    number or f32 [Q]: a per-item score prior.  The score of row j for query q becomes
+    fma(w[q], bias[j], dot) in f32, with w = 1 where bias_weight is None, and everything above
+    (order, ties, the scores returned, cursors, rank) sees that score and only it; target_score is
+    biased the same way and is the value rank counts against.  A row at -inf stays at -inf.
+    bias_weight = 0 or an all-zero bias gives the rows and ranks of the call without a prior.  A
+    non-finite weight gives that query an unspecified list.  Every pass of a deep list carries the
+    prior."""
     import ctypes
     from ._lib import STRUCTS
+    _check(bias is not None or bias_weight is None, "retrieve_topk takes a bias_weight only with a bias")
     if deep and int(k) > RETRIEVE_MAX_K:
+        if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
+            bias_weight = _retrieve_bias("retrieve_topk", bias, bias_weight, items, q.shape[0], "Q", q.device)[1]
         return _retrieve_deep(retrieve_topk, q, items, k, target_rows, after_scores, after_rows,
                               dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
-                                   tag_filter=tag_filter))
+                                   tag_filter=tag_filter, bias=bias, bias_weight=bias_weight))
     require_gpu(q, items, target_rows, exclude_rows)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"retrieve_topk takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
@@ -1803,7 +1844,18 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8)
     t = _retrieve_tags("retrieve_topk", tags, tag_filter, items, Q, "Q")
     c = _retrieve_cursor("retrieve_topk", after_scores, after_rows, Q, "Q", dev)
-    if c is not None:
+    b, bw = _retrieve_bias("retrieve_topk", bias, bias_weight, items, Q, "Q", dev)
+    if b is not None:
+        x = None
+        if exclude_rows is not None:
+            x = STRUCTS["lthm_retrieve_excl"]()
+            x.rows, x.X = ptr(exclude_rows), X
+        call("lthm_retrieve_topk_bias", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
+             ctypes.addressof(t) if t is not None else None, ctypes.addressof(c) if c is not None else None,
+             ctypes.addressof(b), stream(), _key="retr_topk_bias_k", _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
+             _bytes=nbytes + 4.0 * Q * X + (4.0 * N + 12.0 * Q if t is not None else 0.0)
+             + (8.0 * Q if c is not None else 0.0) + 4.0 * N + (4.0 * Q if bw is not None else 0.0))
+    elif c is not None:
         x = None
         if exclude_rows is not None:
             x = STRUCTS["lthm_retrieve_excl"]()
@@ -1836,7 +1888,7 @@ RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
 
 def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
                         exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
-                        deep: bool = False):
+                        deep: bool = False, bias=None, bias_weight=None):
     """retrieve_topk for users with several queries each: an item's score is its best over the
     user's queries, s[u, j] = max_g s_g[u, j], with s_g the score retrieve_topk gives query
     (u, g) (csrc/retrieve.hip, retr_topk_k<EXCL, GP>).
@@ -1852,13 +1904,18 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     user, are retrieve_topk's: an ineligible row is -inf for the user, like an excluded one.
     after_scores f32 [U] and after_rows int32 [U], one cursor per user on the best-over-queries
     score, and deep=True (k up to RETRIEVE_MAX_DEEP, one catalogue scan per 128 rows) are
-    retrieve_topk's as well."""
+    retrieve_topk's as well.  So are bias f32 [N] and bias_weight (None, a number or f32 [U], one
+    weight per user): the prior is added to the best-over-queries score, fma(w[u], bias[j],
+    max_g s_g[u, j]), which equals the best biased score since the fma is monotone in the dot."""
     import ctypes
     from ._lib import STRUCTS
+    _check(bias is not None or bias_weight is None, "retrieve_topk_group takes a bias_weight only with a bias")
     if deep and int(k) > RETRIEVE_MAX_K:
+        if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
+            bias_weight = _retrieve_bias("retrieve_topk_group", bias, bias_weight, items, q.shape[0], "U", q.device)[1]
         return _retrieve_deep(retrieve_topk_group, q, items, k, target_rows, after_scores, after_rows,
                               dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
-                                   tag_filter=tag_filter))
+                                   tag_filter=tag_filter, bias=bias, bias_weight=bias_weight))
     require_gpu(q, items, target_rows, exclude_rows)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"retrieve_topk_group takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
@@ -1903,7 +1960,15 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
     t = _retrieve_tags("retrieve_topk_group", tags, tag_filter, items, U, "U")
     c = _retrieve_cursor("retrieve_topk_group", after_scores, after_rows, U, "U", dev)
-    if c is not None:
+    b, bw = _retrieve_bias("retrieve_topk_group", bias, bias_weight, items, U, "U", dev)
+    if b is not None:
+        call("lthm_retrieve_topk_bias", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
+             ctypes.addressof(g), ctypes.addressof(t) if t is not None else None,
+             ctypes.addressof(c) if c is not None else None, ctypes.addressof(b), stream(),
+             _key="retr_topk_group_bias_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
+             _bytes=nbytes + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0)
+             + 4.0 * N + (4.0 * U if bw is not None else 0.0))
+    elif c is not None:
         call("lthm_retrieve_topk_after", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
              ctypes.addressof(g), ctypes.addressof(t) if t is not None else None, ctypes.addressof(c), stream(),
              _key="retr_topk_group_after_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",

@@ -7,14 +7,19 @@ the loss normalises both (wrapper.py:118-119) and ranks by their dot product.  A
 scored against all of them (``K.retrieve_topk``, csrc/retrieve.hip) instead of against the
 in-batch negatives only.
 
-File format: safetensors with the two tensors ``ids`` / ``emb``, an optional third ``tags``, and
-a ``format`` metadata string, in the style of item_artifact.py.  Loading executes nothing from
-the file.
+File format: safetensors with the two tensors ``ids`` / ``emb``, the optional ``tags`` and
+``bias``, and a ``format`` metadata string, in the style of item_artifact.py.  Loading executes
+nothing from the file.
 
 Tags: a catalogue may carry one int32 word per item, read as 32 independent attribute bits (in
 stock, category, market, ...).  A query's filter (all, any, none) then restricts its top-K and
 its rank to the items whose word has every ``all`` bit, some ``any`` bit (if any is non-zero) and
 no ``none`` bit, inside the kernel (``K.retrieve_topk``'s ``tags`` / ``tag_filter``).
+
+Bias: a catalogue may carry one finite f32 per item, a score prior (popularity, freshness, a
+sponsored lift, a demotion).  A query's score for item j is then fma(w, bias[j], q . e_j) with a
+weight w per query (1 unless told otherwise), inside the kernel (``K.retrieve_topk``'s ``bias`` /
+``bias_weight``): the order, the cursors and the ranks are those of the biased scores.
 """
 from __future__ import annotations
 
@@ -65,9 +70,11 @@ def make_tag_filter(n: int, tag_all: Union[int, torch.Tensor] = 0, tag_any: Unio
 class ItemCatalogue:
     """``ids`` int64 [N], strictly ascending (so unique) and without the pad id 0; ``emb`` bf16
     [N, 128], row i the normalised candidate vector of ``ids[i]``; ``tags`` int32 [N] or None,
-    row i the 32 attribute bits of ``ids[i]``."""
+    row i the 32 attribute bits of ``ids[i]``; ``bias`` f32 [N] or None, row i the score prior of
+    ``ids[i]``, every value finite (checked here, with one sync)."""
 
-    def __init__(self, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None):
+    def __init__(self, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None,
+                 bias: Optional[torch.Tensor] = None):
         if ids.dtype != torch.int64 or ids.dim() != 1:
             raise ValueError(f"catalogue ids must be int64 [N] (got {ids.dtype} {tuple(ids.shape)})")
         if emb.dtype != torch.bfloat16 or emb.dim() != 2 or emb.shape[1] != WIDTH:
@@ -89,29 +96,43 @@ class ItemCatalogue:
             if tags.device != ids.device:
                 raise ValueError("catalogue tags must live on the device of ids and embeddings")
             tags = tags.contiguous()
+        if bias is not None:
+            if bias.dtype != torch.float32 or bias.dim() != 1 or bias.shape[0] != ids.shape[0]:
+                raise ValueError(f"catalogue bias must be f32 [N], one word per id "
+                                 f"(got {bias.dtype} {tuple(bias.shape)}, N={ids.shape[0]})")
+            if bias.device != ids.device:
+                raise ValueError("catalogue bias must live on the device of ids and embeddings")
+            if not bool(torch.isfinite(bias).all()):
+                raise ValueError("catalogue bias must be finite (it holds NaN or +-inf)")
+            bias = bias.contiguous()
         self.ids = ids.contiguous()
         self.emb = emb.contiguous()
         self.tags = tags
+        self.bias = bias
 
     def __len__(self) -> int:
         return self.ids.shape[0]
 
     @classmethod
-    def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor,
-                        tags: Optional[torch.Tensor] = None) -> "ItemCatalogue":
+    def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None,
+                        bias: Optional[torch.Tensor] = None) -> "ItemCatalogue":
         """From ids in any order and their (already normalised, bf16) vectors: rows are sorted
-        by id, and ``tags`` (int32 [N], given in the order of ``ids``) move with them.  Duplicate
-        ids are refused, as is id 0."""
+        by id, and ``tags`` (int32 [N]) and ``bias`` (f32 [N]), given in the order of ``ids``, move
+        with them.  Duplicate ids are refused, as is id 0."""
         if ids.dim() != 1 or emb.dim() != 2 or ids.shape[0] != emb.shape[0]:
             raise ValueError("from_embeddings takes ids [N] and emb [N, 128]")
         if tags is not None and (tags.dim() != 1 or tags.shape[0] != ids.shape[0]):
             raise ValueError("from_embeddings takes tags [N], one word per id")
+        if bias is not None and (bias.dim() != 1 or bias.shape[0] != ids.shape[0]):
+            raise ValueError("from_embeddings takes bias [N], one word per id")
         order = torch.argsort(ids, stable=True)
-        return cls(ids[order], emb[order.to(emb.device)], None if tags is None else tags[order.to(tags.device)])
+        return cls(ids[order], emb[order.to(emb.device)], None if tags is None else tags[order.to(tags.device)],
+                   None if bias is None else bias[order.to(bias.device)])
 
     def to(self, device) -> "ItemCatalogue":
         return ItemCatalogue(self.ids.to(device), self.emb.to(device),
-                             None if self.tags is None else self.tags.to(device))
+                             None if self.tags is None else self.tags.to(device),
+                             None if self.bias is None else self.bias.to(device))
 
     def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
         """The filter "the same value as the target in the masked bit field": per target t the
@@ -144,7 +165,8 @@ class ItemCatalogue:
     def topk(self, q: torch.Tensor, k: int, *, normalize_q: bool = True, target_ids: Optional[torch.Tensor] = None,
              slab_rows: int = 0, exclude_ids: Optional[torch.Tensor] = None,
              tag_filter: Optional[torch.Tensor] = None, after_scores: Optional[torch.Tensor] = None,
-             after_ids: Optional[torch.Tensor] = None):
+             after_ids: Optional[torch.Tensor] = None,
+             bias_weight: Union[None, float, torch.Tensor] = None):
         """The k best items per query: (item_ids int64 [Q, k], scores f32 [Q, k], rank, target_score).
         Empty slots (N < k) hold id 0 and score -inf.  With ``target_ids`` [Q], ``rank`` is each
         query's count of items scoring strictly above its target (-1 where the catalogue does
@@ -164,9 +186,15 @@ class ItemCatalogue:
         ascending): the last column of one page is the cursor of the next, and it stays valid
         after its item has left the catalogue (``cursor_rows``).  The empty slot (-inf, 0) of an
         exhausted page gives an empty page.  ``k`` may reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above
-        128 the catalogue is scanned once per 128 rows."""
+        128 the catalogue is scanned once per 128 rows.
+        A catalogue that carries a ``bias`` scores item j as fma(w, bias[j], q . e_j): ``scores``,
+        the order, ``target_score``, ``rank`` and the cursors are those of the biased scores.
+        ``bias_weight`` is w: None for 1, a number, or f32 [Q] ([U] with a 3-D ``q``), one weight
+        per query.  A catalogue without a bias refuses a weight."""
         if tag_filter is not None and self.tags is None:
             raise ValueError("tag_filter given, but this catalogue carries no tags")
+        if bias_weight is not None and self.bias is None:
+            raise ValueError("bias_weight given, but this catalogue carries no bias")
         if (after_scores is None) != (after_ids is None):
             raise ValueError("after_scores and after_ids are given together or neither")
         ar = None
@@ -185,7 +213,8 @@ class ItemCatalogue:
         scores, rows, rank, tscore = call(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
                                           slab_rows=slab_rows, exclude_rows=xr,
                                           tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter,
-                                          after_scores=after_scores, after_rows=ar, deep=int(k) > K.RETRIEVE_MAX_K)
+                                          after_scores=after_scores, after_rows=ar, deep=int(k) > K.RETRIEVE_MAX_K,
+                                          bias=self.bias, bias_weight=bias_weight)
         item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
         return item_ids, scores, rank, tscore
 
@@ -194,6 +223,8 @@ class ItemCatalogue:
         tensors = {"ids": self.ids.detach().cpu().contiguous(), "emb": self.emb.detach().cpu().contiguous()}
         if self.tags is not None:
             tensors["tags"] = self.tags.detach().cpu().contiguous()
+        if self.bias is not None:
+            tensors["bias"] = self.bias.detach().cpu().contiguous()
         save_file(tensors, path, metadata={"format": FORMAT})
 
     @classmethod
@@ -205,18 +236,21 @@ class ItemCatalogue:
                 raise ValueError(f"{path}: not an item catalogue (metadata {json.dumps(meta)})")
             ids, emb = f.get_tensor("ids"), f.get_tensor("emb")
             tags = f.get_tensor("tags") if "tags" in f.keys() else None
-        cat = cls(ids, emb, tags)
+            bias = f.get_tensor("bias") if "bias" in f.keys() else None
+        cat = cls(ids, emb, tags, bias)
         return cat.to(device) if device is not None else cat
 
 
 @torch.no_grad()
-def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Optional[torch.Tensor] = None) -> ItemCatalogue:
+def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Optional[torch.Tensor] = None,
+                    bias: Optional[torch.Tensor] = None) -> ItemCatalogue:
     """The catalogue of ``ids`` under ``wrapper``'s current weights: per chunk, the item
     embedding module and the product tower on a [1, n] id row (the training kernels), then
     F.normalize to bf16 as the loss does (``K.rownorm``).  A row therefore equals the
     normalised ``current_token_emb`` row a forward produces for that id.  ``tags`` (int32, one
     word per entry of ``ids``) follow the ids through the sort and the de-duplication; an id given
-    twice with different tags is refused."""
+    twice with different tags is refused.  ``bias`` (f32, one word per entry of ``ids``) follows
+    them the same way, under the same rule."""
     from ....commons.layers import RowShardedKShiftEmbedding
     enc = wrapper._model
     if isinstance(enc.product_emb_module, RowShardedKShiftEmbedding) and world_size() > 1:
@@ -230,6 +264,10 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
         if tags.dtype != torch.int32 or tags.shape != ids.shape:
             raise ValueError(f"build_catalogue takes int32 tags, one per id (got {tags.dtype} {tuple(tags.shape)})")
         tags = unique_tags(ids.to(dev), tags.to(dev))
+    if bias is not None:
+        if bias.dtype != torch.float32 or bias.shape != ids.shape:
+            raise ValueError(f"build_catalogue takes f32 bias, one per id (got {bias.dtype} {tuple(bias.shape)})")
+        bias = unique_bias(ids.to(dev), bias.to(dev))
     ids = torch.unique(ids.to(dev))  # sorted ascending
     if bool((ids == 0).any()):
         raise ValueError("catalogue ids must not hold 0, the pad id")
@@ -238,7 +276,7 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
         row = ids[lo:lo + chunk].view(1, -1).contiguous()
         _, prod, _ = enc.product_tower(row, enc.product_emb_module(row))
         out[lo:lo + row.numel()] = K.rownorm(prod.reshape(-1, WIDTH).contiguous())[0]
-    return ItemCatalogue(ids, out, tags)
+    return ItemCatalogue(ids, out, tags, bias)
 
 
 def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:
@@ -250,4 +288,18 @@ def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:
     if not bool((out[inv] == tags).all()):
         bad = ids[out[inv] != tags][0].item()
         raise ValueError(f"build_catalogue: id {bad} is given more than once with different tags")
+    return out
+
+
+def unique_bias(ids: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """The bias of ``torch.unique(ids)``, row for row, as ``unique_tags`` does for tags: an id that
+    occurs more than once must carry one bias (compared as bits, so -0 and +0 differ and a NaN is
+    left for ``ItemCatalogue`` to refuse)."""
+    uniq, inv = torch.unique(ids, return_inverse=True)
+    out = torch.empty(uniq.numel(), dtype=bias.dtype, device=bias.device)
+    out[inv] = bias
+    same = out[inv].view(torch.int32) == bias.view(torch.int32)
+    if not bool(same.all()):
+        bad = ids[~same][0].item()
+        raise ValueError(f"build_catalogue: id {bad} is given more than once with different biases")
     return out

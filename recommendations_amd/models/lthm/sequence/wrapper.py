@@ -347,7 +347,8 @@ class LTHMModelWrapper(BaseModelWrapper):
     @torch.no_grad()
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
                  exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
-                 tag_all=None, tag_any=None, tag_none=None, after=None) -> Dict[str, torch.Tensor]:
+                 tag_all=None, tag_any=None, tag_none=None, after=None,
+                 bias_weight=None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -365,7 +366,10 @@ class LTHMModelWrapper(BaseModelWrapper):
         or ``(scores [B], item_ids [B])``; sequence b then gets the k best items strictly behind
         that position of its list, with every other argument as in the call before.  ``k`` may
         reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above 128 the catalogue is scanned once per 128
-        rows."""
+        rows.  A catalogue that carries a bias scores item j as fma(w, bias[j], q . e_j);
+        ``bias_weight`` is w, None for 1, a number or f32 [B], one weight per sequence (a
+        catalogue without a bias refuses it).  The scores returned are the biased ones, so
+        ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again."""
         after_scores = after_ids = None
         if after is not None:
             if isinstance(after, dict):
@@ -404,13 +408,17 @@ class LTHMModelWrapper(BaseModelWrapper):
         if after_scores is not None:
             after_scores = after_scores.to(device=q.device, dtype=torch.float32).contiguous()
             after_ids = after_ids.to(q.device).contiguous()
+        if isinstance(bias_weight, torch.Tensor):
+            bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
         item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt,
-                                                after_scores=after_scores, after_ids=after_ids)
+                                                after_scores=after_scores, after_ids=after_ids,
+                                                bias_weight=bias_weight)
         return {"item_ids": item_ids, "scores": scores}
 
     @torch.no_grad()
     def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0,
-                          exclude_seen: bool = False, same_tags_mask: Optional[int] = None) -> Dict[str, float]:
+                          exclude_seen: bool = False, same_tags_mask: Optional[int] = None,
+                          bias_weight: Optional[float] = None) -> Dict[str, float]:
         """Hit rate and hit position of one forward against the whole catalogue: the in-batch
         metrics of wrapper.py:228-238 with every catalogue item as a negative.  Queries are the
         positions t whose target ``current_token_ids[:, t + lookahead[head]]`` is a non-pad
@@ -425,14 +433,27 @@ class LTHMModelWrapper(BaseModelWrapper):
         With ``same_tags_mask`` (an int, a 32-bit mask; the catalogue must carry tags) every query
         ranks its target among the items that agree with the target on the masked tag bits, say
         the items of the target's own category: whether the model finds the item once it has the
-        category.  The keys then take the suffix ``_tagged``, after ``_unseen`` when both are on."""
+        category.  The keys then take the suffix ``_tagged``, after ``_unseen`` when both are on.
+
+        With ``bias_weight`` (a float; the catalogue must carry a bias) every score, the target's
+        included, is fma(bias_weight, bias[j], q . e_j): the hit position under the prior.  The
+        keys then take the suffix ``_biased``, after ``_unseen`` / ``_tagged``.  Without it the
+        metrics are those of the plain dot, whether or not the catalogue carries a bias."""
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])
         L = ids.shape[1] - off
-        sfx = ("_unseen" if exclude_seen else "") + ("_tagged" if same_tags_mask is not None else "")
+        sfx = ("_unseen" if exclude_seen else "") + ("_tagged" if same_tags_mask is not None else "") \
+            + ("_biased" if bias_weight is not None else "")
         if same_tags_mask is not None and catalogue.tags is None:
             raise ValueError("same_tags_mask given, but this catalogue carries no tags")
+        bias = None
+        if bias_weight is not None:
+            if isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float)):
+                raise ValueError(f"bias_weight takes a float (got {type(bias_weight).__name__})")
+            if catalogue.bias is None:
+                raise ValueError("bias_weight given, but this catalogue carries no bias")
+            bias, bias_weight = catalogue.bias, float(bias_weight)
         res: Dict[str, float] = {"catalogue_queries" + sfx: 0}
         if L <= 0:
             return res
@@ -451,7 +472,7 @@ class LTHMModelWrapper(BaseModelWrapper):
             filt = catalogue.filter_like(catalogue.ids[trow.long()], same_tags_mask)
         if not exclude_seen:
             _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=trow,
-                                            tags=tags, tag_filter=filt)
+                                            tags=tags, tag_filter=filt, bias=bias, bias_weight=bias_weight)
         else:
             T = ids.shape[1]
             if T > K.RETRIEVE_MAX_EXCLUDE:
@@ -465,7 +486,8 @@ class LTHMModelWrapper(BaseModelWrapper):
                 xr = torch.where(col[None, :] <= t[:, None], seen[b], torch.full_like(seen[b], -1)).contiguous()
                 ranks.append(K.retrieve_topk(q[lo:lo + 16384], catalogue.emb, 1, normalize_q=True,
                                              target_rows=trow[lo:lo + 16384], exclude_rows=xr, tags=tags,
-                                             tag_filter=None if filt is None else filt[lo:lo + 16384])[2])
+                                             tag_filter=None if filt is None else filt[lo:lo + 16384],
+                                             bias=bias, bias_weight=bias_weight)[2])
             rank = torch.cat(ranks)
         pos = rank.float()
         res["catalogue_queries" + sfx] = n

@@ -2,7 +2,7 @@
 ``(q_bf16 @ items.T).float().topk(k)`` on the same device and inputs.
 
     python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
-                                    [--group G] [--tags P] [--after] [--deep K]
+                                    [--group G] [--tags P] [--after] [--deep K] [--bias]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -37,6 +37,10 @@ shape stops the run.  One JSON line per shape:
   deep_* (--deep K)       the deep list of K rows (ceil(K / 128) passes, one catalogue scan each) against
                           the baseline's top-K (deep_base_*): deep_over_base on the medians (_hi: the worst
                           pairing), deep_over_fused against the plain call, its rows against a torch top-K
+  bias_* (--bias)         the call with a random f32 bias per row (uniform in [-0.05, 0.05], the scale of
+                          the scores' spread) and weight 1, timed next to the plain one: bias_over_fused on
+                          the medians (_hi: the worst pairing), its rows against a torch top-k of
+                          scores + bias
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -73,7 +77,7 @@ def merge_heads(lists, k):
 
 
 def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0, tags_p: float = -1.0,
-          after: bool = False, deep: int = 0) -> None:
+          after: bool = False, deep: int = 0, bias: bool = False) -> None:
     import torch
     from recommendations_amd import kernels as K
     Q = SHAPES[name]
@@ -145,6 +149,13 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
     def fused_deep():
         return K.retrieve_topk(q_bf, items, deep, normalize_q=False, deep=True)
 
+    bias_t = None
+    if bias:
+        bias_t = (torch.rand(N, generator=g, device=dev) - 0.5) * 0.1
+
+    def fused_bias():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False, bias=bias_t)
+
     def base(kk=k):
         out = []
         for lo in range(0, Q, BASE_CHUNK):
@@ -160,6 +171,8 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
     if deep:
         more.append(("deep", fused_deep, [], True))
         more.append(("deep_base", base_deep, [], False))
+    if bias:
+        more.append(("bias", fused_bias, [], True))
 
     def timed(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -269,6 +282,14 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
                       "deep_over_base": round(stats["deep"] / stats["deep_base"], 4),
                       "deep_over_base_hi": round(extra["deep_max_ms"] / extra["deep_base_min_ms"], 4),
                       "deep_over_fused": round(stats["deep"] / fm, 4), "deep_check_rows_equal": round(d_same, 4)})
+    if bias:
+        # the biased rows against an f32 torch top-k of scores + bias
+        b_rows = fused_bias()[1]
+        refb = (q_bf[:nq].float() @ items.float().T + bias_t[None, :]).topk(k)
+        b_same = float((b_rows[:nq].long() == refb.indices).float().mean())
+        extra.update({"bias_over_fused": round(stats["bias"] / fm, 4),
+                      "bias_over_fused_hi": round(extra["bias_max_ms"] / min(tf), 4),
+                      "bias_check_rows_equal": round(b_same, 4)})
     print(json.dumps({
         "shape": name, "Q": Q, "N": N, "k": k, "bound": "hbm" if t_mem >= t_mm else "mfma", "floor_ms": round(floor_ms, 4),
         "fused_ms": round(fm, 4), "fused_min_ms": round(min(tf), 4), "fused_max_ms": round(max(tf), 4), "fused_reps": len(tf),
@@ -297,6 +318,8 @@ def main() -> int:
                     help="also time page 2 (the k rows behind page 1's last column) next to page 1, in the same loop")
     ap.add_argument("--deep", type=int, default=0,
                     help="also time the deep list of K rows (129..1024) against the torch baseline's top-K")
+    ap.add_argument("--bias", action="store_true",
+                    help="also time the call with a random f32 bias per row and weight 1 next to the plain call")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -309,7 +332,7 @@ def main() -> int:
     if a.deep and not 129 <= a.deep <= 1024:
         raise SystemExit("--deep takes 0 (off) or a list length in 129..1024")
     if a.child:
-        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags, a.after, a.deep)
+        child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags, a.after, a.deep, a.bias)
         return 0
     for name in a.shapes.split(","):
         if name not in SHAPES:
@@ -318,7 +341,7 @@ def main() -> int:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep)]
-                                + (["--after"] if a.after else []),
+                                + (["--after"] if a.after else []) + (["--bias"] if a.bias else []),
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
