@@ -965,6 +965,28 @@ typedef struct lthm_retrieve_bias {
 int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
                             const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
                             void* stream);
+/* Deep lists: up to 1024 rows per query from one scan of the catalogue (the calls above stop at
+ * k = 128).  For 129 <= d->k <= 1024 the four outputs are, bit for bit, what a caller of
+ * lthm_retrieve_topk_bias gets who pages: ceil(k / 128) calls, each behind the last (score, row)
+ * of the one before, concatenated, with rank and target_score those of the first call (whose
+ * cursor is the caller's own).  That is: the k first eligible rows under (score descending, row
+ * ascending) on the score of the calls above (the f32 dot, the best over a group, the prior), a row
+ * being ineligible (-inf) when it is excluded, fails its tag filter or lies at or before the
+ * cursor; -1 / -inf where fewer than k rows are eligible.  x, g, t, c and b compose as above and
+ * each may be NULL.  The outputs are a pure function of the inputs (no global atomics; they depend
+ * neither on slab_rows nor on Q), and a non-finite weight gives that query an unspecified list and
+ * nothing else.
+ *   workspace  lthm_retrieve_deep_ws_bytes(Q, G, N, k, slab_rows, X) bytes (X = 0: no list): the
+ *              queries, nslab x Q x stride keys of 8 bytes with stride = 2048 (or max(k, slab_rows)
+ *              for a slab_rows below 2048), nslab x Q counts and the sorted lists
+ * lthm_retrieve_deep_ws_bytes takes k in 1..1024 and returns lthm_retrieve_group_ws_bytes for
+ * k <= 128; -1 for what it refuses (k outside 1..1024, G outside 1..8, X outside 0..1024, a
+ * slab_rows that is no multiple of 64).  With d->k <= 128, lthm_retrieve_topk_deep is exactly
+ * lthm_retrieve_topk_bias(d, x, g, t, c, b, stream). */
+int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows, int64_t X);
+int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                            const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                            void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

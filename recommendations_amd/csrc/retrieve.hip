@@ -715,6 +715,432 @@ __global__ __launch_bounds__(256) void retr_merge_k(const u64* __restrict__ keys
   }
 }
 
+// ---------------------------------------------------------------- deep lists: 128 < k <= 1024 in one scan
+// retr_deep_topk_k is retr_topk_k<true, GP, TAGS, true, true> (the tile loop, the masks and the
+// count are its text) with the candidate keys in the workspace instead of LDS: 64 queries of
+// RD_CAP keys are 1 MiB.  Each (slab, query or user) owns `stride` key slots in global memory
+// (RD_CAP, or max(k, slab_rows) for a slab shorter than RD_CAP, which can never hold more), and
+// only the block of that (slab, query tile) ever touches them.  The per-query count, tau and the
+// flags stay in LDS.  An append takes its slot from the LDS counter and writes the key with an
+// ordinary vector store; the barrier at the top of the next tile (workgroup release / acquire:
+// the stores have left the wave, and all waves of a block share one L1) orders it ahead of the
+// prune, which one wave runs per flagged query: the n <= RD_CAP keys into the wave's own LDS
+// buffer, a bitonic sort (descending, padded with key 0 to a power of two), the first k back to
+// the query's slots, tau from key k - 1.  All keys are distinct, so the sorted list, and with it
+// the result, does not depend on the order in which slots were handed out.  A null list, a null
+// cursor and a null bias are "none": the walk never starts, cs stays +inf, and the bias words
+// are neither staged nor applied.
+constexpr int RD_KMAX = 1024;            // largest k
+constexpr int RD_CAP = 2048;             // candidate slots per (slab, query): a power of two, the sort's size
+constexpr int RD_LIM = RD_CAP - RT_IT;   // a query's count at the start of every tile is <= RD_LIM
+// The same invariant as above, with 960 free slots behind a full list: a prune leaves at most
+// k <= RD_KMAX keys, a tile appends at most RT_IT per query, and a query above RD_LIM is pruned
+// before the next tile.
+static_assert(RD_KMAX <= RD_LIM, "a pruned buffer must have a whole item tile of free slots");
+static_assert(RD_LIM + RT_IT <= RD_CAP, "a tile's appends must fit behind the limit");
+static_assert(RD_LIM - RD_KMAX >= RD_KMAX / 2, "a full list must absorb many appends between two sorts");
+static_assert((RD_CAP & (RD_CAP - 1)) == 0 && RD_CAP >= 512, "the sort takes a power of two, four pairs per lane");
+
+struct RetrDeepShared {
+  unsigned char img[2][RT_IT * 256];
+  u64 sort[4][RD_CAP];  // one buffer per wave
+  float tau[RT_QT];
+  int cnt[RT_QT];
+  int pc[RT_QT];
+  int flag[3];
+  alignas(16) int tag[2][RT_IT];
+  alignas(16) float bias[2][RT_IT];
+};
+static_assert(sizeof(RetrDeepShared) <= 100 * 1024, "LDS budget: the images, four sort buffers and change");
+
+template <int GP, bool TAGS>
+struct RetrDeepArgs : RetrTopkArgs<true, GP, TAGS, true, true> {
+  int stride;  // key slots per (slab, query or user): keys is [nslab, Q or U, stride]
+};
+
+// One wave sorts buf[0, P) descending, P a power of two in 512..RD_CAP: a bitonic network, four
+// compare-exchanges per lane and step (all four pairs read, then written).  A wave's LDS
+// accesses complete in order, so a step sees the step before it.
+__device__ __forceinline__ void retr_deep_sort(u64* buf, int P, int lane) {
+  for (int len = 2; len <= P; len <<= 1) {
+    for (int j = len >> 1; j > 0; j >>= 1) {
+      for (int t0 = lane; t0 < (P >> 1); t0 += 256) {
+        int lo[4];
+        u64 x[4], y[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int t = t0 + 64 * u;  // < P / 2: P / 2 is a multiple of 256
+          lo[u] = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+          x[u] = buf[lo[u]];
+          y[u] = buf[lo[u] | j];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if ((x[u] < y[u]) == ((lo[u] & len) == 0)) {
+            buf[lo[u]] = y[u];
+            buf[lo[u] | j] = x[u];
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
+// One wave: the n keys of g[0, n) sorted descending into buf, the first min(n, k) of them back
+// to g (with fill: key 0 behind them up to k).  Returns min(n, k).
+__device__ __forceinline__ int retr_deep_prune(u64* g, u64* buf, int n, int k, bool fill, int lane) {
+  int P = 512;
+  while (P < n) P <<= 1;  // n <= stride <= RD_CAP
+  for (int idx = lane; idx < P; idx += 64) buf[idx] = idx < n ? g[idx] : 0ull;
+  __builtin_amdgcn_wave_barrier();
+  if (n > 1) retr_deep_sort(buf, P, lane);
+  const int m = n < k ? n : k;
+  const int top = fill ? k : m;
+  for (int idx = lane; idx < top; idx += 64) g[idx] = idx < m ? buf[idx] : 0ull;
+  return m;
+}
+
+template <int GP, bool TAGS>
+__global__ __launch_bounds__(256) void retr_deep_topk_k(RetrDeepArgs<GP, TAGS> a) {
+  __shared__ __attribute__((aligned(16))) RetrDeepShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
+  const int slab = blockIdx.y;
+  const int64_t row_lo = (int64_t)slab * a.slab_rows;
+  const int64_t row_hi = row_lo + a.slab_rows < a.N ? row_lo + a.slab_rows : a.N;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const int64_t q = q0 + ql;
+  const bool live = q < a.Q;
+  bool lead = live;
+  int64_t uq = q;
+  if constexpr (GP > 1) {
+    lead = live && (r32 & (GP - 1)) == 0;
+    uq = q / GP;
+  }
+  int64_t nout = a.Q;  // rows of keys and pcnt per slab
+  if constexpr (GP > 1) nout = a.U;
+  const int stride = a.stride;
+  const bool hasb = a.bias != nullptr;  // uniform
+
+  if (tid < RT_QT) {
+    bool first = q0 + tid < a.Q;
+    if constexpr (GP > 1) first = first && (tid & (GP - 1)) == 0;
+    sh.tau[tid] = first ? -INFINITY : INFINITY;
+    sh.cnt[tid] = 0;
+    sh.pc[tid] = 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  {
+    const bf16_t* rp = a.qn + (live ? q : 0) * RT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live) v = *reinterpret_cast<const u32x4*>(rp + 16 * s + 8 * hh);
+      qf[s] = __builtin_bit_cast(bf16x8v, v);
+    }
+  }
+  int tr = -1;
+  float ts = INFINITY;  // no target: nothing counts
+  if (lead && a.trow) {
+    tr = a.trow[uq];
+    if (tr >= 0 && tr < a.N) ts = a.tscore[uq];
+    else tr = -1;
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // no list, a query past Q: excludes nothing and reads nothing
+  if (lead && a.xs != nullptr) {
+    const int* xl = a.xs + uq * a.xstride;
+    int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (xl[mid] < row_lo) lo = mid + 1;
+      else hi = mid;
+    }
+    xp = xl + lo;
+    nx = *xp;
+  }
+  int fm = 0, fw = 0, fy = 0;
+  int yz = 1;
+  if constexpr (TAGS) {
+    if (lead) {
+      const int* fp = a.filt + uq * 3;
+      const int fall = fp[0], fnone = fp[2];
+      fy = fp[1];
+      yz = fy == 0;
+      fm = (fall & fnone) ? 0 : (fall | fnone);
+      fw = (fall & fnone) ? 1 : fall;
+    }
+  }
+  float cs = INFINITY;  // no cursor, a query past Q, a slot that is no leader
+  int cr = -1;
+  if (lead && a.ascore != nullptr) {
+    cs = a.ascore[uq];
+    cr = a.arow[uq];
+  }
+  float wq = 0.f;
+  if (lead && hasb) wq = a.bw ? a.bw[uq] : 1.f;
+  // the leader's key slots; a lane that is no leader never appends (its tau is +inf)
+  u64* const kbuf = a.keys + ((int64_t)slab * nout + (lead ? uq : 0)) * stride;
+  int roff[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
+
+  const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 4 * j;
+      const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 15));
+      glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+    if constexpr (TAGS) {
+      if (w == 0) {
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+      }
+    }
+    if (hasb && w == 1) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+      glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
+    }
+  };
+  retire_loads();
+  stage(0);
+  int above = 0;
+  for (int i = 0; i < ntile; ++i) {
+    // the key stores of tile i - 1 count in vmcnt like the DMA: this wait retires both
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;
+    if (sh.flag[(i + 2) % 3]) {  // tile i - 1 pushed a query past the limit
+      for (int pq = w * GP; pq < RT_QT; pq += 4 * GP) {
+        int n = sh.cnt[pq];
+        if (n > RD_LIM) {
+          n = n < stride ? n : stride;
+          u64* g = a.keys + ((int64_t)slab * nout + (q0 + pq) / GP) * stride;
+          const int m = retr_deep_prune(g, sh.sort[w], n, a.k, false, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.sort[w][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    int4 t4[4];
+    if constexpr (TAGS) {
+      const int4* tp = reinterpret_cast<const int4*>(sh.tag[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
+    }
+    float4 b4[4] = {};
+    if (hasb) {
+      const float4* bp = reinterpret_cast<const float4*>(sh.bias[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b4[j] = bp[2 * j];
+    }
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const bf16x8v af = frag_at(img + roff[s]);
+      acc = mfma32(af, qf[s], acc);
+    }
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if constexpr (GP > 1) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[v] = retr_group_max<GP>(acc[v]);
+    }
+    if (hasb) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bw4[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) acc[4 * j + c] = __builtin_fmaf(wq, bw4[c], acc[4 * j + c]);
+      }
+    }
+    {
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    if constexpr (TAGS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int tw[4] = {t4[j].x, t4[j].y, t4[j].z, t4[j].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const bool bad = ((tw[c] & fm) != fw) | (((tw[c] & fy) | yz) == 0);
+          acc[4 * j + c] = bad ? -INFINITY : acc[4 * j + c];
+        }
+      }
+    }
+    {
+      float m = acc[0];
+#pragma unroll
+      for (int v = 1; v < 16; ++v) m = fmaxf(m, acc[v]);
+      if (!(m < cs)) {
+        const int64_t cd = (int64_t)cr - rb;
+        const int cq = cd < -1 ? -1 : cd > 32 ? 32 : (int)cd;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const float s = acc[v];
+          const bool ok = (s < cs) | ((s == cs) & (8 * (v >> 2) + (v & 3) > cq));
+          acc[v] = ok ? s : -INFINITY;
+        }
+      }
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      above += acc[v] > ts ? 1 : 0;
+      mx = fmaxf(mx, acc[v]);
+    }
+    const int64_t rel = (int64_t)tr - rb;
+    if (tr >= 0 && rel >= 0 && rel < 32 && !(rel & 4)) {
+      const int vt = (int)(((rel >> 3) << 2) | (rel & 3));
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (v == vt && acc[v] > ts) --above;
+    }
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (lead && slot < stride) kbuf[slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RD_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  above += __shfl_xor(above, 32, 64);
+  if (hh == 0 && live && above) atomicAdd(&sh.pc[ql], above);
+  __syncthreads();  // the last tile's appends have left their waves
+  // the slab's k best of every query, sorted, in the first k of its slots; empty slots are key 0
+  for (int pq = w * GP; pq < RT_QT; pq += 4 * GP) {
+    if (q0 + pq >= a.Q) break;
+    int n = sh.cnt[pq];
+    n = n < stride ? n : stride;
+    u64* g = a.keys + ((int64_t)slab * nout + (q0 + pq) / GP) * stride;
+    retr_deep_prune(g, sh.sort[w], n, a.k, true, lane);
+  }
+  if constexpr (GP == 1) {
+    if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+  } else {
+    if (a.trow && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
+      a.pcnt[(int64_t)slab * nout + (q0 + tid) / GP] = sh.pc[tid];
+  }
+}
+
+// The merge of the slabs' lists, one wave per query.  A is the best list so far (n keys, sorted,
+// in LDS) and B a slab's list (nb keys, sorted, in LDS); all keys are distinct, so the rank of
+// a_i in the union is i + #{b > a_i}, found by binary search, and the same for B.  Every lane
+// takes its keys and their ranks into registers, then the keys of rank < k are written at their
+// rank into A: a wave's LDS accesses complete in order, so every read precedes these writes.
+__global__ __launch_bounds__(256) void retr_deep_merge_k(const u64* __restrict__ keys, int stride,
+                                                         const int* __restrict__ pcnt, const int* __restrict__ trow,
+                                                         int64_t Q, int64_t N, int nslab, int k,
+                                                         float* __restrict__ scores, int* __restrict__ rows,
+                                                         int* __restrict__ rank) {
+  __shared__ u64 sbuf[4][2][RD_KMAX];
+  static_assert(sizeof(sbuf) <= 64 * 1024, "LDS budget");
+  constexpr int PL = RD_KMAX / 64;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t q = (int64_t)blockIdx.x * 4 + w;
+  if (q >= Q) return;  // whole waves; no block barrier below
+  u64* A = sbuf[w][0];
+  u64* B = sbuf[w][1];
+  int n = 0;
+  for (int s = 0; s < nslab; ++s) {
+    const u64* src = keys + ((int64_t)s * Q + q) * stride;
+    if (n == k && src[0] < A[k - 1]) continue;  // nothing in this list reaches the k best
+    int nb = 0;
+    for (int idx = lane; idx < 64 * ((k + 63) / 64); idx += 64) {
+      const u64 key = idx < k ? src[idx] : 0ull;
+      if (key) B[idx] = key;  // sorted, the empty slots at the end: the keys are B[0, nb)
+      nb += __popcll(__ballot(key != 0ull));
+    }
+    __builtin_amdgcn_wave_barrier();
+    u64 ka[PL] = {}, kb[PL] = {};
+    int ra[PL], rb[PL];
+#pragma unroll
+    for (int j = 0; j < PL; ++j) {
+      const int idx = lane + 64 * j;
+      ra[j] = rb[j] = k;  // not written
+      if (64 * j < n) {   // uniform
+        const u64 key = idx < n ? A[idx] : 0ull;
+        int lo = 0, hi = nb;  // #{b > key}: B is descending
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (B[mid] > key) lo = mid + 1;
+          else hi = mid;
+        }
+        ka[j] = key;
+        if (idx < n) ra[j] = idx + lo;
+      }
+      if (64 * j < nb) {
+        const u64 key = idx < nb ? B[idx] : 0ull;
+        int lo = 0, hi = n;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (A[mid] > key) lo = mid + 1;
+          else hi = mid;
+        }
+        kb[j] = key;
+        if (idx < nb) rb[j] = idx + lo;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < PL; ++j) {
+      if (ra[j] < k) A[ra[j]] = ka[j];
+      if (rb[j] < k) A[rb[j]] = kb[j];
+    }
+    __builtin_amdgcn_wave_barrier();
+    n = n + nb < k ? n + nb : k;
+  }
+  for (int idx = lane; idx < k; idx += 64) {
+    const bool has = idx < n;
+    const u64 key = has ? A[idx] : 0ull;
+    scores[q * k + idx] = has ? retr_key_score(key) : -INFINITY;
+    rows[q * k + idx] = has ? retr_key_row(key) : -1;
+  }
+  if (rank) {
+    const int tr = trow[q];
+    int c = 0;
+    for (int s = lane; s < nslab; s += 64) c += pcnt[(int64_t)s * Q + q];  // integers: any order, one sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) rank[q] = (tr >= 0 && tr < N) ? c : -1;
+  }
+}
+
 constexpr int64_t RETR_MAX_SLABS = 65535;  // grid.y
 
 // rows per slab (a multiple of the item tile), or -1 for sizes the kernels do not take
@@ -1076,4 +1502,156 @@ extern "C" int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_r
                                        const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
   if (!g || g->G == 1) return retr_launch(d, x, t, c, b, stream);
   return retr_launch_group_call(d, x, g->G, t, c, b, stream);
+}
+
+// ---------------------------------------------------------------- deep lists: host side
+namespace {
+
+// rows per slab of a deep call, or -1: retr_slab_rows' rule with a longer shortest slab (a slab
+// much shorter than k only pads lists); an explicit multiple of the item tile is honoured
+int64_t retr_deep_slab_rows(int64_t S, int64_t N, int64_t slab_rows) {
+  if (S < 1 || S >= (1ll << 31) || N < 1 || N >= (1ll << 31)) return -1;
+  int64_t sr = slab_rows;
+  if (sr == 0) {
+    const int64_t nqt = (S + RT_QT - 1) / RT_QT;
+    const int64_t want = nqt >= 256 ? 1 : (256 + nqt - 1) / nqt;
+    sr = (N + want - 1) / want;
+    if (sr < 4 * RD_KMAX) sr = 4 * RD_KMAX;
+    sr = (sr + RT_IT - 1) / RT_IT * RT_IT;
+  }
+  if (sr < RT_IT || sr % RT_IT != 0) return -1;
+  if ((N + sr - 1) / sr > RETR_MAX_SLABS) return -1;
+  return sr;
+}
+
+// key slots per (slab, query or user): a slab shorter than RD_CAP never holds more keys than rows
+inline int64_t retr_deep_stride(int64_t sr, int k) { return sr >= RD_CAP ? RD_CAP : (sr > k ? sr : k); }
+
+template <int GP>
+void retr_launch_deep(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, int stride, const lthm_retrieve_tags* t,
+                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
+  if (t) {
+    RetrDeepArgs<GP, true> da;
+    static_cast<RetrBaseArgs<true, GP>&>(da) = a;
+    da.tags = t->tags;
+    da.filt = t->filter;
+    da.ascore = c ? c->after_score : nullptr;
+    da.arow = c ? c->after_row : nullptr;
+    da.bias = b ? b->bias : nullptr;
+    da.bw = b ? b->weight : nullptr;
+    da.stride = stride;
+    hipLaunchKernelGGL((retr_deep_topk_k<GP, true>), grid, dim3(256), 0, s, da);
+  } else {
+    RetrDeepArgs<GP, false> da;
+    static_cast<RetrBaseArgs<true, GP>&>(da) = a;
+    da.ascore = c ? c->after_score : nullptr;
+    da.arow = c ? c->after_row : nullptr;
+    da.bias = b ? b->bias : nullptr;
+    da.bw = b ? b->weight : nullptr;
+    da.stride = stride;
+    hipLaunchKernelGGL((retr_deep_topk_k<GP, false>), grid, dim3(256), 0, s, da);
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
+                                               int64_t X) {
+  if (k <= RT_KMAX) return lthm_retrieve_group_ws_bytes(U, G, N, k, slab_rows, X);
+  if (k > RD_KMAX || G < 1 || G > RT_GMAX || X < 0 || X > RT_XMAX || slab_rows < 0) return -1;
+  if (U < 1 || U >= (1ll << 31)) return -1;
+  const int64_t S = U * retr_gp(G);
+  const int64_t sr = retr_deep_slab_rows(S, N, slab_rows);
+  if (sr < 0) return -1;
+  const int64_t nslab = (N + sr - 1) / sr;
+  return up256(S * RT_D * 2) + up256(nslab * U * retr_deep_stride(sr, k) * 8) + up256(nslab * U * 4) +
+         (X ? up256(U * (X + 1) * 4) : 0);
+}
+
+extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                       const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
+                                       const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
+  LTHM_REQUIRE(d != nullptr);
+  if (d->k <= RT_KMAX) return lthm_retrieve_topk_bias(d, x, g, t, c, b, stream);
+  const int G = g ? g->G : 1;
+  LTHM_REQUIRE(G >= 1 && G <= RT_GMAX);
+  LTHM_REQUIRE(d->k <= RD_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
+  LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
+  LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
+  LTHM_REQUIRE(retr_cursor_ok(c));
+  LTHM_REQUIRE(retr_bias_ok(b));
+  const int64_t need = lthm_retrieve_deep_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
+  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
+  const int64_t U = d->Q, N = d->N;
+  const int gp = retr_gp(G);
+  const int64_t S = U * gp;
+  const int64_t sr = retr_deep_slab_rows(S, N, d->slab_rows);
+  const int64_t nslab = (N + sr - 1) / sr;
+  const int64_t stride = retr_deep_stride(sr, d->k);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)d->workspace;
+  bf16_t* qn = (bf16_t*)ws;
+  u64* keys = (u64*)(ws + up256(S * RT_D * 2));
+  int* pcnt = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * stride * 8));
+  int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * stride * 8) + up256(nslab * U * 4));
+  const bf16_t* items = (const bf16_t*)d->items;
+  const unsigned pgrid = (unsigned)((U + 15) / 16);
+  // the prep kernels of the k <= 128 calls: the plain one for G = 1, the slots for G >= 2
+  if (G == 1) {
+    if (d->q_dtype == LTHM_BF16)
+      hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, d->normalize_q, qn,
+                         items, N, d->target_row, d->target_score);
+    else
+      hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, d->normalize_q, qn,
+                         items, N, d->target_row, d->target_score);
+  } else {
+    if (d->q_dtype == LTHM_BF16)
+      hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
+                         d->normalize_q, qn, items, N, d->target_row, d->target_score);
+    else
+      hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
+                         d->normalize_q, qn, items, N, d->target_row, d->target_score);
+  }
+  LTHM_CHECK_LAUNCH();
+  if (b && d->target_row) {
+    retr_launch_bias_target(d, b, s);
+    LTHM_CHECK_LAUNCH();
+  }
+  RetrGroupArgs a;
+  a.items = items;
+  a.qn = qn;
+  a.trow = d->target_row;
+  a.tscore = d->target_score;
+  a.keys = keys;
+  a.pcnt = pcnt;
+  a.Q = S;
+  a.N = N;
+  a.slab_rows = sr;
+  a.k = d->k;
+  a.xs = nullptr;
+  a.xstride = 0;
+  a.U = U;
+  if (x) {
+    const int X = (int)x->X;
+    int P = 1;
+    while (P < X) P <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)U), dim3(256), 0, s, x->rows, X, P, N, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+  }
+  const dim3 tgrid((unsigned)((S + RT_QT - 1) / RT_QT), (unsigned)nslab);
+  if (gp == 1) retr_launch_deep<1>(tgrid, s, static_cast<const RetrExclArgs&>(a), (int)stride, t, c, b);
+  else if (gp == 2) retr_launch_deep<2>(tgrid, s, a, (int)stride, t, c, b);
+  else if (gp == 4) retr_launch_deep<4>(tgrid, s, a, (int)stride, t, c, b);
+  else retr_launch_deep<8>(tgrid, s, a, (int)stride, t, c, b);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_deep_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, (int)stride, pcnt,
+                     d->target_row, U, N, (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+  LTHM_CHECK_LAUNCH();
+  return 0;
 }

@@ -22,6 +22,7 @@
 //   lthm::retrieve_topk_tags  any of the above among the rows whose tag word passes the query's filter
 //   lthm::retrieve_topk_after any of the above strictly behind a (score, row) cursor per query
 //   lthm::retrieve_topk_bias  any of the above on the score fma(weight[q], bias[row], dot)
+//   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -482,14 +483,15 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
                                                     const c10::optional<Tensor>& exclude_rows, const Tensor* tags_,
                                                     const Tensor* filter_, const Tensor* after_scores_ = nullptr,
                                                     const Tensor* after_rows_ = nullptr, const Tensor* bias_ = nullptr,
-                                                    const Tensor* bias_weight_ = nullptr) {
+                                                    const Tensor* bias_weight_ = nullptr, bool deep = false) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
               "items must be a bf16 [N, 128] catalogue");
   TORCH_CHECK(q_.dim() == 3 && q_.size(2) == 128, "q must be [U, G, 128]");
   TORCH_CHECK(q_.size(1) >= 1 && q_.size(1) <= 8, "retrieve_topk_group takes 1..8 queries per user, got ", q_.size(1));
-  TORCH_CHECK(k >= 1 && k <= 128, "k must be in 1..128, got ", k);
+  // deep: lthm_retrieve_topk_deep, every part of which may be absent
+  TORCH_CHECK(k >= 1 && k <= (deep ? 1024 : 128), "k must be in 1..", deep ? 1024 : 128, ", got ", k);
   TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk_group takes a non-empty catalogue and user set");
   auto q = q_.contiguous(), items = items_.contiguous();
   const int64_t U = q.size(0), G = q.size(1), N = items.size(0);
@@ -545,7 +547,8 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
       bw = bias_weight_->contiguous();
     }
   }
-  const int64_t need = lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
+  const int64_t need = deep ? lthm_retrieve_deep_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0)
+                            : lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
   TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
   auto scores = at::empty({U, k}, q.options().dtype(at::kFloat));
   auto rows = at::empty({U, k}, q.options().dtype(at::kInt));
@@ -569,7 +572,26 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   }
   lthm_retrieve_group g = {};
   g.G = (int32_t)G;
-  if (bias_) {
+  if (deep) {
+    lthm_retrieve_tags t = {};
+    if (tags_) {
+      t.tags = tg.data_ptr<int32_t>();
+      t.filter = tf.data_ptr<int32_t>();
+    }
+    lthm_retrieve_cursor c = {};
+    if (after_scores_) {
+      c.after_score = cs.data_ptr<float>();
+      c.after_row = cr.data_ptr<int32_t>();
+    }
+    lthm_retrieve_bias b = {};
+    if (bias_) {
+      b.bias = bs.data_ptr<float>();
+      b.weight = bias_weight_ ? bw.data_ptr<float>() : nullptr;
+    }
+    hip_ok(lthm_retrieve_topk_deep(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, after_scores_ ? &c : nullptr,
+                                   bias_ ? &b : nullptr, cur_stream()),
+           "lthm_retrieve_topk_deep");
+  } else if (bias_) {
     lthm_retrieve_tags t = {};
     if (tags_) {
       t.tags = tg.data_ptr<int32_t>();
@@ -660,6 +682,31 @@ std::tuple<Tensor, Tensor> retrieve_topk_bias_cuda(const Tensor& q, const Tensor
                                   has_w ? &*bias_weight : nullptr);
 }
 
+// k in 1..1024 from one scan of the catalogue; every optional tensor may be None (tags with
+// tag_filter, after_scores with after_rows, bias_weight only with bias)
+std::tuple<Tensor, Tensor> retrieve_topk_deep_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                   const c10::optional<Tensor>& exclude_rows,
+                                                   const c10::optional<Tensor>& tags,
+                                                   const c10::optional<Tensor>& tag_filter,
+                                                   const c10::optional<Tensor>& after_scores,
+                                                   const c10::optional<Tensor>& after_rows,
+                                                   const c10::optional<Tensor>& bias,
+                                                   const c10::optional<Tensor>& bias_weight) {
+  TORCH_CHECK(q.dim() == 2 || q.dim() == 3, "q must be [Q, 128] or [U, G, 128]");
+  const bool has_tags = tags.has_value() && tags->defined(), has_filter = tag_filter.has_value() && tag_filter->defined();
+  TORCH_CHECK(has_tags == has_filter, "retrieve_topk_deep takes tags and tag_filter together or neither");
+  const bool has_cs = after_scores.has_value() && after_scores->defined();
+  const bool has_cr = after_rows.has_value() && after_rows->defined();
+  TORCH_CHECK(has_cs == has_cr, "retrieve_topk_deep takes after_scores and after_rows together or neither");
+  const bool has_b = bias.has_value() && bias->defined();
+  const bool has_w = bias_weight.has_value() && bias_weight->defined();
+  TORCH_CHECK(has_b || !has_w, "retrieve_topk_deep takes a bias_weight only with a bias");
+  return retrieve_topk_group_impl(q.dim() == 2 ? q.unsqueeze(1) : q, items, k, normalize_q, exclude_rows,
+                                  has_tags ? &*tags : nullptr, has_tags ? &*tag_filter : nullptr,
+                                  has_cs ? &*after_scores : nullptr, has_cs ? &*after_rows : nullptr,
+                                  has_b ? &*bias : nullptr, has_w ? &*bias_weight : nullptr, true);
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -694,6 +741,10 @@ TORCH_LIBRARY(lthm, m) {
       "retrieve_topk_bias(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
       "Tensor? tag_filter, Tensor? after_scores, Tensor? after_rows, Tensor bias, Tensor? bias_weight=None) -> "
       "(Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_topk_deep(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
+      "Tensor? tag_filter, Tensor? after_scores, Tensor? after_rows, Tensor? bias, Tensor? bias_weight=None) -> "
+      "(Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -709,6 +760,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_tags", &retrieve_topk_tags_cuda);
   m.impl("retrieve_topk_after", &retrieve_topk_after_cuda);
   m.impl("retrieve_topk_bias", &retrieve_topk_bias_cuda);
+  m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -1674,7 +1674,7 @@ def _retrieve_tags(who: str, tags, tag_filter, items, n_filters: int, per: str):
     return t
 
 
-RETRIEVE_MAX_DEEP = 1024      # the longest list of a deep call: 8 passes of RETRIEVE_MAX_K
+RETRIEVE_MAX_DEEP = 1024      # the longest list of a deep call (RD_KMAX): one scan, or 8 pages of RETRIEVE_MAX_K
 
 
 def _retrieve_cursor(who: str, after_scores, after_rows, n: int, per: str, device):
@@ -1726,16 +1726,87 @@ def _retrieve_bias(who: str, bias, bias_weight, items, n: int, per: str, device)
 
 
 def retrieve_deep_passes(k: int):
-    """The per-pass list lengths of a deep call: ceil(k / 128) passes, all of RETRIEVE_MAX_K rows
-    but the last, which takes the rest.  k in 1..RETRIEVE_MAX_DEEP."""
+    """The per-pass list lengths of a paged deep call (deep="paged"): ceil(k / 128) passes, all of
+    RETRIEVE_MAX_K rows but the last, which takes the rest.  k in 1..RETRIEVE_MAX_DEEP."""
     k = int(k)
     _check(1 <= k <= RETRIEVE_MAX_DEEP, f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
     full, rest = divmod(k, RETRIEVE_MAX_K)
     return [RETRIEVE_MAX_K] * full + ([rest] if rest else [])
 
 
+def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, slab_rows, exclude_rows, tags, tag_filter,
+                        after_scores, after_rows, bias, bias_weight):
+    """RETRIEVE_MAX_K < k <= RETRIEVE_MAX_DEEP in one scan of the catalogue: lthm_retrieve_topk_deep
+    (csrc/retrieve.hip, retr_deep_topk_k and retr_deep_merge_k).  q [Q, 128] (who = retrieve_topk)
+    or [U, G, 128]; everything else as the caller documents it."""
+    import ctypes
+    from ._lib import STRUCTS
+    grouped = who == "retrieve_topk_group"
+    per = "U" if grouped else "Q"
+    k = int(k)
+    _check(RETRIEVE_MAX_K < k <= RETRIEVE_MAX_DEEP, f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    require_gpu(q, items, target_rows, exclude_rows)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    if grouped:
+        _check(q.dim() == 3 and q.shape[2] == RETRIEVE_WIDTH,
+               f"{who} takes [U, G, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+        G = q.shape[1]
+        _check(1 <= G <= RETRIEVE_MAX_GROUP, f"{who} takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
+    else:
+        _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries")
+        G = 1
+    U, N = q.shape[0], items.shape[0]
+    _check(N >= 1 and U >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, {per}={U})")
+    X = 0
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == U,
+               f"exclude_rows must be int32 [{per}, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, {per}={U})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows (got {X})")
+        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
+        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
+    if target_rows is not None:
+        _check(target_rows.dtype == torch.int32 and target_rows.shape == (U,), f"target_rows must be int32 [{per}]")
+    need = load().lthm_retrieve_deep_ws_bytes(U, G, N, k, int(slab_rows), X)
+    _check(need >= 0, f"{who}: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
+                      f"that cuts N={N} into at most 65535 slabs ({per}={U} G={G} k={k} X={X})")
+    q = q.contiguous()
+    dev = q.device
+    scores = torch.empty((U, k), dtype=torch.float32, device=dev)
+    rows = torch.empty((U, k), dtype=torch.int32, device=dev)
+    rank = tscore = None
+    if target_rows is not None:
+        rank = torch.empty(U, dtype=torch.int32, device=dev)
+        tscore = torch.empty(U, dtype=torch.float32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    d = STRUCTS["lthm_retrieve_desc"]()
+    d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
+    d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
+    d.workspace, d.ws_bytes = ptr(ws), need
+    d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = U, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
+    x = None
+    if exclude_rows is not None:
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
+    g = None
+    if grouped:
+        g = STRUCTS["lthm_retrieve_group"]()
+        g.G = G
+    t = _retrieve_tags(who, tags, tag_filter, items, U, per)
+    c = _retrieve_cursor(who, after_scores, after_rows, U, per, dev)
+    b, bw = _retrieve_bias(who, bias, bias_weight, items, U, per, dev)
+    addr = lambda o: ctypes.addressof(o) if o is not None else None
+    call("lthm_retrieve_topk_deep", addr(d), addr(x), addr(g), addr(t), addr(c), addr(b), stream(),
+         _key="retr_deep_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
+         _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
+         + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0)
+         + (4.0 * N if b is not None else 0.0) + (4.0 * U if bw is not None else 0.0))
+    return scores, rows, rank, tscore
+
+
 def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows, kw):
-    """k > RETRIEVE_MAX_K as passes of at most RETRIEVE_MAX_K rows: pass i + 1 starts behind the
+    """deep="paged": k > RETRIEVE_MAX_K as passes of at most RETRIEVE_MAX_K rows: pass i + 1 starts behind the
     last column of pass i, which stays on the device (an exhausted pass ends in (-inf, -1), the
     cursor that admits nothing).  rank and target_score are the first pass's, whose cursor is the
     caller's own."""
@@ -1784,10 +1855,13 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     whatever slab_rows or Q either call used.  +inf gives the bits of the call without a cursor;
     -inf or NaN gives an empty list, so the (-inf, -1) tail of an exhausted list ends the paging.
 
-    deep=True lifts the cap on k from 128 to RETRIEVE_MAX_DEEP = 1024: the call runs
-    ceil(k / 128) passes, each behind the last column of the one before (no host sync), and
-    concatenates them; rank and target_score are the first pass's.  A deep list costs one scan of
-    the catalogue per 128 rows.  Without deep, k > 128 is refused as it always was.
+    deep=True lifts the cap on k from 128 to RETRIEVE_MAX_DEEP = 1024: one call of
+    lthm_retrieve_topk_deep, which selects the whole list in a single scan of the catalogue.
+    deep="paged" gives the same bits the way a caller of the k <= 128 entries gets them:
+    ceil(k / 128) passes, each behind the last column of the one before (no host sync),
+    concatenated, one catalogue scan per 128 rows; rank and target_score are the first pass's,
+    whose cursor is the caller's own, and the single scan returns those.  Without deep, k > 128 is
+    refused as it always was.
 
     bias f32 [N] (contiguous, on the catalogue's device, every value finite) and bias_weight None, a
     number or f32 [Q]: a per-item score prior.  The score of row j for query q becomes
@@ -1795,12 +1869,16 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     (order, ties, the scores returned, cursors, rank) sees that score and only it; target_score is
     biased the same way and is the value rank counts against.  A row at -inf stays at -inf.
     bias_weight = 0 or an all-zero bias gives the rows and ranks of the call without a prior.  A
-    non-finite weight gives that query an unspecified list.  Every pass of a deep list carries the
-    prior."""
+    non-finite weight gives that query an unspecified list.  A deep list carries the prior, in
+    every pass where it is paged."""
     import ctypes
     from ._lib import STRUCTS
     _check(bias is not None or bias_weight is None, "retrieve_topk takes a bias_weight only with a bias")
     if deep and int(k) > RETRIEVE_MAX_K:
+        _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk takes deep=False, True or "paged" (got {deep!r})')
+        if deep != "paged":
+            return _retrieve_deep_scan("retrieve_topk", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
+                                       tag_filter, after_scores, after_rows, bias, bias_weight)
         if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
             bias_weight = _retrieve_bias("retrieve_topk", bias, bias_weight, items, q.shape[0], "Q", q.device)[1]
         return _retrieve_deep(retrieve_topk, q, items, k, target_rows, after_scores, after_rows,
@@ -1903,14 +1981,18 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     attained a score is not reported.  tags int32 [N] and tag_filter int32 [U, 3], one filter per
     user, are retrieve_topk's: an ineligible row is -inf for the user, like an excluded one.
     after_scores f32 [U] and after_rows int32 [U], one cursor per user on the best-over-queries
-    score, and deep=True (k up to RETRIEVE_MAX_DEEP, one catalogue scan per 128 rows) are
-    retrieve_topk's as well.  So are bias f32 [N] and bias_weight (None, a number or f32 [U], one
+    score, and deep=True (k up to RETRIEVE_MAX_DEEP in one catalogue scan; deep="paged": one scan per
+    128 rows) are retrieve_topk's as well.  So are bias f32 [N] and bias_weight (None, a number or f32 [U], one
     weight per user): the prior is added to the best-over-queries score, fma(w[u], bias[j],
     max_g s_g[u, j]), which equals the best biased score since the fma is monotone in the dot."""
     import ctypes
     from ._lib import STRUCTS
     _check(bias is not None or bias_weight is None, "retrieve_topk_group takes a bias_weight only with a bias")
     if deep and int(k) > RETRIEVE_MAX_K:
+        _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk_group takes deep=False, True or "paged" (got {deep!r})')
+        if deep != "paged":
+            return _retrieve_deep_scan("retrieve_topk_group", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
+                                       tag_filter, after_scores, after_rows, bias, bias_weight)
         if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
             bias_weight = _retrieve_bias("retrieve_topk_group", bias, bias_weight, items, q.shape[0], "U", q.device)[1]
         return _retrieve_deep(retrieve_topk_group, q, items, k, target_rows, after_scores, after_rows,

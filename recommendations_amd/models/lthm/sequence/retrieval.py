@@ -186,7 +186,7 @@ class ItemCatalogue:
         ascending): the last column of one page is the cursor of the next, and it stays valid
         after its item has left the catalogue (``cursor_rows``).  The empty slot (-inf, 0) of an
         exhausted page gives an empty page.  ``k`` may reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above
-        128 the catalogue is scanned once per 128 rows.
+        128 the list still comes from a single scan of the catalogue (the deep selection kernel).
         A catalogue that carries a ``bias`` scores item j as fma(w, bias[j], q . e_j): ``scores``,
         the order, ``target_score``, ``rank`` and the cursors are those of the biased scores.
         ``bias_weight`` is w: None for 1, a number, or f32 [Q] ([U] with a 3-D ``q``), one weight

@@ -365,8 +365,8 @@ class LTHMModelWrapper(BaseModelWrapper):
         the next page: the dict a previous ``retrieve`` returned (its last column is the cursor)
         or ``(scores [B], item_ids [B])``; sequence b then gets the k best items strictly behind
         that position of its list, with every other argument as in the call before.  ``k`` may
-        reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above 128 the catalogue is scanned once per 128
-        rows.  A catalogue that carries a bias scores item j as fma(w, bias[j], q . e_j);
+        reach ``K.RETRIEVE_MAX_DEEP`` = 1024; above 128 the list still comes from a single scan
+        of the catalogue.  A catalogue that carries a bias scores item j as fma(w, bias[j], q . e_j);
         ``bias_weight`` is w, None for 1, a number or f32 [B], one weight per sequence (a
         catalogue without a bias refuses it).  The scores returned are the biased ones, so
         ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again."""

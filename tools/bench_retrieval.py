@@ -34,9 +34,14 @@ shape stops the run.  One JSON line per shape:
   after_* (--after)       page 2 of k rows (the call with page 1's last (score, row) as its cursor) timed
                           next to page 1, the plain call: after_over_fused on the medians (_hi: the worst
                           pairing), its rows against entries k .. 2k - 1 of a torch top-2k
-  deep_* (--deep K)       the deep list of K rows (ceil(K / 128) passes, one catalogue scan each) against
-                          the baseline's top-K (deep_base_*): deep_over_base on the medians (_hi: the worst
-                          pairing), deep_over_fused against the plain call, its rows against a torch top-K
+  deep_* (--deep K)       the deep list of K rows, deep=True (one catalogue scan: deep_ms = deep_scan_ms),
+                          against deep="paged" (deep_paged_*: ceil(K / 128) passes, one catalogue scan each)
+                          and the baseline's top-K (deep_base_*), all in the same loop: deep_scan_over_paged on
+                          the medians (_hi: the worst pairing, scan max / paged min; faster only if < 1),
+                          deep_over_base (_hi), deep_over_fused against the plain call;
+                          deep_check_rows_equal: the fraction of the single scan's (score bits, rows) of all
+                          queries equal to the paged arm's (1.0: the same lists); deep_check_rows_equal_torch:
+                          its rows of the first queries against an f32 torch top-K
   bias_* (--bias)         the call with a random f32 bias per row (uniform in [-0.05, 0.05], the scale of
                           the scores' spread) and weight 1, timed next to the plain one: bias_over_fused on
                           the medians (_hi: the worst pairing), its rows against a torch top-k of
@@ -149,6 +154,9 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
     def fused_deep():
         return K.retrieve_topk(q_bf, items, deep, normalize_q=False, deep=True)
 
+    def fused_deep_paged():
+        return K.retrieve_topk(q_bf, items, deep, normalize_q=False, deep="paged")
+
     bias_t = None
     if bias:
         bias_t = (torch.rand(N, generator=g, device=dev) - 0.5) * 0.1
@@ -170,6 +178,7 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
         more.append(("after", fused_after, [], True))
     if deep:
         more.append(("deep", fused_deep, [], True))
+        more.append(("deep_paged", fused_deep_paged, [], True))
         more.append(("deep_base", base_deep, [], False))
     if bias:
         more.append(("bias", fused_bias, [], True))
@@ -275,13 +284,20 @@ def child(name: str, N: int, k: int, reps: int, exclude: int = 0, group: int = 0
                       "after_over_fused_hi": round(extra["after_max_ms"] / min(tf), 4),
                       "after_check_rows_equal": round(a_same, 4)})
     if deep:
-        d_rows = fused_deep()[1]
+        d_scores, d_rows = fused_deep()[:2]
+        p_scores, p_rows = fused_deep_paged()[:2]
+        d_same = float(((d_rows == p_rows) & (d_scores.view(torch.int32) == p_scores.view(torch.int32))).float().mean())
         refd = (q_bf[:nq].float() @ items.float().T).topk(deep)
-        d_same = float((d_rows[:nq].long() == refd.indices).float().mean())
+        t_same = float((d_rows[:nq].long() == refd.indices).float().mean())
         extra.update({"deep": deep, "deep_passes": len(K.retrieve_deep_passes(deep)),
+                      "deep_scan_ms": extra["deep_ms"], "deep_scan_min_ms": extra["deep_min_ms"],
+                      "deep_scan_max_ms": extra["deep_max_ms"],
+                      "deep_scan_over_paged": round(stats["deep"] / stats["deep_paged"], 4),
+                      "deep_scan_over_paged_hi": round(extra["deep_max_ms"] / extra["deep_paged_min_ms"], 4),
                       "deep_over_base": round(stats["deep"] / stats["deep_base"], 4),
                       "deep_over_base_hi": round(extra["deep_max_ms"] / extra["deep_base_min_ms"], 4),
-                      "deep_over_fused": round(stats["deep"] / fm, 4), "deep_check_rows_equal": round(d_same, 4)})
+                      "deep_over_fused": round(stats["deep"] / fm, 4), "deep_check_rows_equal": round(d_same, 4),
+                      "deep_check_rows_equal_torch": round(t_same, 4)})
     if bias:
         # the biased rows against an f32 torch top-k of scores + bias
         b_rows = fused_bias()[1]
@@ -317,7 +333,7 @@ def main() -> int:
     ap.add_argument("--after", action="store_true",
                     help="also time page 2 (the k rows behind page 1's last column) next to page 1, in the same loop")
     ap.add_argument("--deep", type=int, default=0,
-                    help="also time the deep list of K rows (129..1024) against the torch baseline's top-K")
+                    help="also time the deep list of K rows (129..1024), single-scan and paged, against the torch baseline's top-K")
     ap.add_argument("--bias", action="store_true",
                     help="also time the call with a random f32 bias per row and weight 1 next to the plain call")
     ap.add_argument("--step-timeout", type=int, default=240)
