@@ -987,6 +987,49 @@ int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, 
 int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
                             const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
                             void* stream);
+/* Sharded catalogues: the rows of one catalogue held as S shards (on one device or on many), each
+ * scanned on its own, the shards' lists merged.  A row's score is a function of (query, row,
+ * prior) alone and ties break by item id, so the list over the union is the merge of the lists.
+ *
+ * lthm_retrieve_target_score: out[q] = the target_score that lthm_retrieve_topk_bias /
+ * lthm_retrieve_topk_deep return for the same inputs, bit for bit (the plain f32 dot of the two
+ * bf16 rows, the best over a group of G queries, then fmaf(weight[q], bias[target], .) where bias is
+ * non-NULL; weight NULL is 1), from the same kernels, without a scan of the catalogue.  Where
+ * target_row[q] is outside [0, N) it writes NaN ("this shard does not hold the target").
+ *   q  f32 / bf16 [Q, 128], or [U, G, 128] with G >= 2 and Q = U; target_row int32 [Q]; out f32 [Q]
+ *   workspace  lthm_retrieve_target_score_ws_bytes(Q, G) bytes, 16-byte aligned (-1 for Q < 1 or
+ *              G outside 1..8) */
+int64_t lthm_retrieve_target_score_ws_bytes(int64_t Q, int32_t G);
+int lthm_retrieve_target_score(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q,
+                               int32_t G, const int32_t* target_row, const float* bias, const float* weight, float* out,
+                               int64_t Q, void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_topk_shard: one entry for k in 1..1024 (lthm_retrieve_topk_deep's dispatch and
+ * workspace, lthm_retrieve_deep_ws_bytes).  s == NULL is exactly lthm_retrieve_topk_deep(d, x, g, t,
+ * c, b, stream).  With s the target's score comes from the caller:
+ *   target_score_in  f32 [Q] ([U] with groups), 4-byte aligned; NaN: the query has no target
+ * d->target_score must be NULL and d->rank is required; d->target_row may be NULL or hold -1 where
+ * this shard does not hold the target.  Nothing is read from items for the target, and
+ *   rank[q] = #{j eligible, j != target_row[q] : s_j > target_score_in[q]},
+ * or -1 where target_score_in[q] is NaN.  Eligible is what it is above: not excluded, passing the
+ * tag filter, behind the cursor.  scores and rows are those of the call without s. */
+typedef struct lthm_retrieve_shard {
+  const float* target_score_in;
+} lthm_retrieve_shard;
+int lthm_retrieve_topk_shard(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                             const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                             const lthm_retrieve_shard* s, void* stream);
+/* lthm_retrieve_merge_shards: the k first entries of the union of S lists per query.
+ *   scores  f32 [S, Q, k], ids int64 [S, Q, k]: list (s, q) sorted by (score descending, id
+ *           ascending), its empty slots (-inf, 0) at the end; ids distinct across the lists of one
+ *           query; no NaN; -0 equals +0 (it is returned as +0, as the scans return it)
+ *   ranks   int32 [S, Q] or NULL
+ *   out_scores f32 [Q, k], out_ids int64 [Q, k]: the union's first k in that order, then (-inf, 0)
+ *   out_rank   int64 [Q] (with ranks): -1 if any of the query's S entries is -1, else their sum
+ * 1 <= S <= 64, 1 <= k <= 1024.  Each entry is placed at its rank in the union (binary searches, no
+ * sort and no atomics), so the outputs are a pure function of the inputs.  A pair that occurs in two
+ * lists breaks the contract but not the call: both copies are returned, the lower list's first. */
+int lthm_retrieve_merge_shards(const float* scores, const int64_t* ids, const int32_t* ranks, int32_t S, int64_t Q,
+                               int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_rank, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -103,15 +103,17 @@ __device__ __attribute__((aligned(16))) unsigned char retr_zero_row[256];
 __device__ int retr_zero_tag;  // the tag of a row at or past the slab's end
 __device__ float retr_zero_bias;  // and its bias
 
-__device__ __forceinline__ u64 retr_key(float s, int row) {
+// the order-preserving integer image of a score, and back
+__device__ __forceinline__ uint32_t retr_image(float s) {
   uint32_t u = __float_as_uint(s + 0.f);  // -0 -> +0: equal scores get equal images
   u ^= (uint32_t)((int32_t)u >> 31) | 0x80000000u;
-  return ((u64)u << 32) | (uint32_t)~row;
+  return u;
 }
-__device__ __forceinline__ float retr_key_score(u64 key) {
-  const uint32_t o = (uint32_t)(key >> 32);
+__device__ __forceinline__ float retr_image_score(uint32_t o) {
   return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu));
 }
+__device__ __forceinline__ u64 retr_key(float s, int row) { return ((u64)retr_image(s) << 32) | (uint32_t)~row; }
+__device__ __forceinline__ float retr_key_score(u64 key) { return retr_image_score((uint32_t)(key >> 32)); }
 __device__ __forceinline__ int retr_key_row(u64 key) { return (int)~(uint32_t)key; }
 
 // One wave sorts buf[0, n) (distinct keys, n <= 64 PL) descending and keeps the first k:
@@ -147,6 +149,7 @@ struct RetrArgs {
   int* pcnt;            // [nslab, Q]
   int64_t Q, N, slab_rows;
   int k;
+  int shard;  // tscore is the caller's, for every query, whatever trow says (lthm_retrieve_topk_shard)
 };
 
 constexpr int RT_XMAX = 1024;  // longest exclusion list of a query
@@ -243,12 +246,14 @@ __global__ __launch_bounds__(256) void retr_excl_prep_k(const int* __restrict__ 
 }
 
 // ---------------------------------------------------------------- queries -> bf16, target score
-// 16 lanes per query, 8 contiguous elements per lane (rownorm_v8_k's arithmetic for D = 128)
+// 16 lanes per query, 8 contiguous elements per lane (rownorm_v8_k's arithmetic for D = 128).
+// miss is the target score of a query without a target: -inf in the retrieval calls, NaN in
+// lthm_retrieve_target_score.
 template <typename TQ>
 __global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int64_t Q, int normalize,
                                                    bf16_t* __restrict__ qn, const bf16_t* __restrict__ items,
                                                    int64_t N, const int* __restrict__ trow,
-                                                   float* __restrict__ tscore) {
+                                                   float* __restrict__ tscore, float miss) {
   const int sub = threadIdx.x & 15;
   const int64_t r0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   const bool in = r0 < Q;
@@ -287,7 +292,7 @@ __global__ __launch_bounds__(256) void retr_prep_k(const TQ* __restrict__ q, int
     }
 #pragma unroll
     for (int o = 8; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
-    if (in && sub == 0) tscore[r] = ok ? dot : -INFINITY;
+    if (in && sub == 0) tscore[r] = ok ? dot : miss;
   }
 }
 
@@ -298,7 +303,8 @@ template <typename TQ>
 __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ q, int64_t U, int G, int GP,
                                                          int normalize, bf16_t* __restrict__ qn,
                                                          const bf16_t* __restrict__ items, int64_t N,
-                                                         const int* __restrict__ trow, float* __restrict__ tscore) {
+                                                         const int* __restrict__ trow, float* __restrict__ tscore,
+                                                         float miss) {
   const int sub = threadIdx.x & 15;
   const int64_t u0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   const bool in = u0 < U;
@@ -347,13 +353,13 @@ __global__ __launch_bounds__(256) void retr_prep_group_k(const TQ* __restrict__ 
       best = fmaxf(best, dot);
     }
   }
-  if (trow && in && sub == 0) tscore[u] = ok ? best : -INFINITY;
+  if (trow && in && sub == 0) tscore[u] = ok ? best : miss;
 }
 
 // The prior of the target: tscore[q] = fmaf(weight[q], bias[target], tscore[q]) behind either prep
 // kernel (with groups q is a user and tscore the best of the plain dots), ahead of the scan, which
-// reads it as the score to count against.  No target (-inf) stays -inf; bias is read at rows in
-// [0, N) only.
+// reads it as the score to count against.  No target (-inf, or the NaN of
+// lthm_retrieve_target_score) stays what it is; bias is read at rows in [0, N) only.
 __global__ __launch_bounds__(256) void retr_bias_target_k(const int* __restrict__ trow, int64_t Q, int64_t N,
                                                           const float* __restrict__ bias, const float* __restrict__ bw,
                                                           float* __restrict__ tscore) {
@@ -444,10 +450,12 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
   }
   int tr = -1;
   float ts = INFINITY;  // no target: nothing counts
-  if (lead && a.trow) {
-    tr = a.trow[uq];
-    if (tr >= 0 && tr < a.N) ts = a.tscore[uq];
-    else tr = -1;
+  if (lead && (a.trow || a.shard)) {
+    if (a.trow) tr = a.trow[uq];
+    if (tr < 0 || tr >= a.N) tr = -1;
+    // shard: the score to count against is the caller's also where the target lives elsewhere (a
+    // NaN, "no target", is above nothing and nothing is above it)
+    if (tr >= 0 || a.shard) ts = a.tscore[uq];
   }
   const int* xp = nullptr;
   int nx = INT_MAX;  // a query past Q excludes nothing and reads nothing
@@ -669,9 +677,9 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
     for (int idx = lane; idx < a.k; idx += 64) out[idx] = idx < m ? sh.cand[pq][idx] : 0ull;
   }
   if constexpr (GP == 1) {
-    if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+    if ((a.trow || a.shard) && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
   } else {
-    if (a.trow && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
+    if ((a.trow || a.shard) && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
       a.pcnt[(int64_t)slab * nout + (q0 + tid) / GP] = sh.pc[tid];
   }
 }
@@ -681,7 +689,7 @@ __global__ __launch_bounds__(256) void retr_topk_k(RetrTopkArgs<EXCL, GP, TAGS, 
 __global__ __launch_bounds__(256) void retr_merge_k(const u64* __restrict__ keys, const int* __restrict__ pcnt,
                                                     const int* __restrict__ trow, int64_t Q, int64_t N, int nslab,
                                                     int k, float* __restrict__ scores, int* __restrict__ rows,
-                                                    int* __restrict__ rank) {
+                                                    int* __restrict__ rank, const float* __restrict__ tsin) {
   __shared__ u64 sbuf[4][2 * RT_KMAX];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t q = (int64_t)blockIdx.x * 4 + w;
@@ -706,12 +714,19 @@ __global__ __launch_bounds__(256) void retr_merge_k(const u64* __restrict__ keys
     rows[q * k + idx] = has ? retr_key_row(key) : -1;
   }
   if (rank) {
-    const int tr = trow[q];
     int c = 0;
     for (int s = lane; s < nslab; s += 64) c += pcnt[(int64_t)s * Q + q];  // integers: any order, one sum
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) rank[q] = (tr >= 0 && tr < N) ? c : -1;
+    // tsin (lthm_retrieve_topk_shard): a query has a target iff its given score is no NaN
+    bool has;
+    if (tsin) {
+      has = !(tsin[q] != tsin[q]);
+    } else {
+      const int tr = trow[q];
+      has = tr >= 0 && tr < N;
+    }
+    if (lane == 0) rank[q] = has ? c : -1;
   }
 }
 
@@ -846,10 +861,12 @@ __global__ __launch_bounds__(256) void retr_deep_topk_k(RetrDeepArgs<GP, TAGS> a
   }
   int tr = -1;
   float ts = INFINITY;  // no target: nothing counts
-  if (lead && a.trow) {
-    tr = a.trow[uq];
-    if (tr >= 0 && tr < a.N) ts = a.tscore[uq];
-    else tr = -1;
+  if (lead && (a.trow || a.shard)) {
+    if (a.trow) tr = a.trow[uq];
+    if (tr < 0 || tr >= a.N) tr = -1;
+    // shard: the score to count against is the caller's also where the target lives elsewhere (a
+    // NaN, "no target", is above nothing and nothing is above it)
+    if (tr >= 0 || a.shard) ts = a.tscore[uq];
   }
   const int* xp = nullptr;
   int nx = INT_MAX;  // no list, a query past Q: excludes nothing and reads nothing
@@ -1051,9 +1068,9 @@ __global__ __launch_bounds__(256) void retr_deep_topk_k(RetrDeepArgs<GP, TAGS> a
     retr_deep_prune(g, sh.sort[w], n, a.k, true, lane);
   }
   if constexpr (GP == 1) {
-    if (a.trow && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
+    if ((a.trow || a.shard) && tid < RT_QT && q0 + tid < a.Q) a.pcnt[(int64_t)slab * a.Q + q0 + tid] = sh.pc[tid];
   } else {
-    if (a.trow && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
+    if ((a.trow || a.shard) && tid < RT_QT && q0 + tid < a.Q && (tid & (GP - 1)) == 0)
       a.pcnt[(int64_t)slab * nout + (q0 + tid) / GP] = sh.pc[tid];
   }
 }
@@ -1067,7 +1084,7 @@ __global__ __launch_bounds__(256) void retr_deep_merge_k(const u64* __restrict__
                                                          const int* __restrict__ pcnt, const int* __restrict__ trow,
                                                          int64_t Q, int64_t N, int nslab, int k,
                                                          float* __restrict__ scores, int* __restrict__ rows,
-                                                         int* __restrict__ rank) {
+                                                         int* __restrict__ rank, const float* __restrict__ tsin) {
   __shared__ u64 sbuf[4][2][RD_KMAX];
   static_assert(sizeof(sbuf) <= 64 * 1024, "LDS budget");
   constexpr int PL = RD_KMAX / 64;
@@ -1132,12 +1149,19 @@ __global__ __launch_bounds__(256) void retr_deep_merge_k(const u64* __restrict__
     rows[q * k + idx] = has ? retr_key_row(key) : -1;
   }
   if (rank) {
-    const int tr = trow[q];
     int c = 0;
     for (int s = lane; s < nslab; s += 64) c += pcnt[(int64_t)s * Q + q];  // integers: any order, one sum
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if (lane == 0) rank[q] = (tr >= 0 && tr < N) ? c : -1;
+    // tsin (lthm_retrieve_topk_shard): a query has a target iff its given score is no NaN
+    bool has;
+    if (tsin) {
+      has = !(tsin[q] != tsin[q]);
+    } else {
+      const int tr = trow[q];
+      has = tr >= 0 && tr < N;
+    }
+    if (lane == 0) rank[q] = has ? c : -1;
   }
 }
 
@@ -1278,6 +1302,13 @@ void retr_launch_bias(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a,
   }
 }
 
+// without a shard descriptor a target brings its two outputs; with one the target score is the
+// caller's, d->target_score stays unused (NULL) and every query gets a rank
+inline bool retr_target_ok(const lthm_retrieve_desc* d, const lthm_retrieve_shard* sd) {
+  if (!sd) return !d->target_row || (d->rank && d->target_score);
+  return sd->target_score_in && ((uintptr_t)sd->target_score_in & 3) == 0 && !d->target_score && d->rank;
+}
+
 inline bool retr_bias_ok(const lthm_retrieve_bias* b) {
   return !b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0);
 }
@@ -1291,13 +1322,13 @@ inline void retr_launch_bias_target(const lthm_retrieve_desc* d, const lthm_retr
 // lthm_retrieve_topk_group / _tags / _after / _bias with G >= 2: d->Q users of G queries each
 int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G,
                            const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
-                           void* stream) {
+                           const lthm_retrieve_shard* sd, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
   LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
-  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(retr_target_ok(d, sd));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
@@ -1318,14 +1349,15 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * d->k * 8) + up256(nslab * U * 4));
   const bf16_t* items = (const bf16_t*)d->items;
   const unsigned pgrid = (unsigned)((U + 15) / 16);
+  const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
   if (d->q_dtype == LTHM_BF16)
     hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
-                       d->normalize_q, qn, items, N, d->target_row, d->target_score);
+                       d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
   else
     hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
-                       d->normalize_q, qn, items, N, d->target_row, d->target_score);
+                       d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
   LTHM_CHECK_LAUNCH();
-  if (b && d->target_row) {
+  if (b && ptrow) {
     retr_launch_bias_target(d, b, s);
     LTHM_CHECK_LAUNCH();
   }
@@ -1333,7 +1365,8 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   a.items = items;
   a.qn = qn;
   a.trow = d->target_row;
-  a.tscore = d->target_score;
+  a.tscore = sd ? sd->target_score_in : d->target_score;
+  a.shard = sd ? 1 : 0;
   a.keys = keys;
   a.pcnt = pcnt;
   a.Q = S;
@@ -1370,7 +1403,8 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   }
   LTHM_CHECK_LAUNCH();
   hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, U, N,
-                     (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+                     (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
+                     sd ? sd->target_score_in : nullptr);
   LTHM_CHECK_LAUNCH();
   return 0;
 }
@@ -1378,12 +1412,12 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
 // the plain, the excluding and the filtering entry points: x == nullptr and t == nullptr is the
 // plain call
 int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
-                const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
+                const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, const lthm_retrieve_shard* sd, void* stream) {
   LTHM_REQUIRE(d != nullptr);
   LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
   LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
-  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(retr_target_ok(d, sd));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
@@ -1402,14 +1436,15 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
   int* pcnt = (int*)(ws + up256(Q * RT_D * 2) + up256(nslab * Q * d->k * 8));
   const bf16_t* items = (const bf16_t*)d->items;
   const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
   if (d->q_dtype == LTHM_BF16)
     hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, Q, d->normalize_q, qn,
-                       items, N, d->target_row, d->target_score);
+                       items, N, ptrow, d->target_score, -INFINITY);
   else
     hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, Q, d->normalize_q, qn,
-                       items, N, d->target_row, d->target_score);
+                       items, N, ptrow, d->target_score, -INFINITY);
   LTHM_CHECK_LAUNCH();
-  if (b && d->target_row) {
+  if (b && ptrow) {
     retr_launch_bias_target(d, b, s);
     LTHM_CHECK_LAUNCH();
   }
@@ -1417,7 +1452,8 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
   a.items = items;
   a.qn = qn;
   a.trow = d->target_row;
-  a.tscore = d->target_score;
+  a.tscore = sd ? sd->target_score_in : d->target_score;
+  a.shard = sd ? 1 : 0;
   a.keys = keys;
   a.pcnt = pcnt;
   a.Q = Q;
@@ -1463,7 +1499,8 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
   }
   LTHM_CHECK_LAUNCH();
   hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, Q, N,
-                     (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+                     (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
+                     sd ? sd->target_score_in : nullptr);
   LTHM_CHECK_LAUNCH();
   return 0;
 }
@@ -1471,37 +1508,48 @@ int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const 
 }  // namespace
 
 extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
-  return retr_launch(d, nullptr, nullptr, nullptr, nullptr, stream);
+  return retr_launch(d, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
-  return retr_launch(d, x, nullptr, nullptr, nullptr, stream);
+  return retr_launch(d, x, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, t, nullptr, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, t, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                         const lthm_retrieve_cursor* c, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, c, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, t, c, nullptr, stream);
+  if (!g || g->G == 1) return retr_launch(d, x, t, c, nullptr, nullptr, stream);
+  return retr_launch_group_call(d, x, g->G, t, c, nullptr, nullptr, stream);
 }
+
+namespace {
+
+// lthm_retrieve_topk_bias, and with sd the k <= 128 half of lthm_retrieve_topk_shard
+int retr_topk_any(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                  const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                  const lthm_retrieve_shard* sd, void* stream) {
+  if (!g || g->G == 1) return retr_launch(d, x, t, c, b, sd, stream);
+  return retr_launch_group_call(d, x, g->G, t, c, b, sd, stream);
+}
+
+}  // namespace
 
 extern "C" int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                        const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, c, b, stream);
-  return retr_launch_group_call(d, x, g->G, t, c, b, stream);
+  return retr_topk_any(d, x, g, t, c, b, nullptr, stream);
 }
 
 // ---------------------------------------------------------------- deep lists: host side
@@ -1568,17 +1616,20 @@ extern "C" int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, 
          (X ? up256(U * (X + 1) * 4) : 0);
 }
 
-extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
-                                       const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
-                                       const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
+namespace {
+
+// lthm_retrieve_topk_deep, and with sd lthm_retrieve_topk_shard
+int retr_topk_deep_any(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+                       const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                       const lthm_retrieve_shard* sd, void* stream) {
   LTHM_REQUIRE(d != nullptr);
-  if (d->k <= RT_KMAX) return lthm_retrieve_topk_bias(d, x, g, t, c, b, stream);
+  if (d->k <= RT_KMAX) return retr_topk_any(d, x, g, t, c, b, sd, stream);
   const int G = g ? g->G : 1;
   LTHM_REQUIRE(G >= 1 && G <= RT_GMAX);
   LTHM_REQUIRE(d->k <= RD_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
   LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
-  LTHM_REQUIRE(!d->target_row || (d->rank && d->target_score));
+  LTHM_REQUIRE(retr_target_ok(d, sd));
   LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
@@ -1600,24 +1651,25 @@ extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_r
   int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * stride * 8) + up256(nslab * U * 4));
   const bf16_t* items = (const bf16_t*)d->items;
   const unsigned pgrid = (unsigned)((U + 15) / 16);
+  const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
   // the prep kernels of the k <= 128 calls: the plain one for G = 1, the slots for G >= 2
   if (G == 1) {
     if (d->q_dtype == LTHM_BF16)
       hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, d->normalize_q, qn,
-                         items, N, d->target_row, d->target_score);
+                         items, N, ptrow, d->target_score, -INFINITY);
     else
       hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, d->normalize_q, qn,
-                         items, N, d->target_row, d->target_score);
+                         items, N, ptrow, d->target_score, -INFINITY);
   } else {
     if (d->q_dtype == LTHM_BF16)
       hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
-                         d->normalize_q, qn, items, N, d->target_row, d->target_score);
+                         d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
     else
       hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
-                         d->normalize_q, qn, items, N, d->target_row, d->target_score);
+                         d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
   }
   LTHM_CHECK_LAUNCH();
-  if (b && d->target_row) {
+  if (b && ptrow) {
     retr_launch_bias_target(d, b, s);
     LTHM_CHECK_LAUNCH();
   }
@@ -1625,7 +1677,8 @@ extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_r
   a.items = items;
   a.qn = qn;
   a.trow = d->target_row;
-  a.tscore = d->target_score;
+  a.tscore = sd ? sd->target_score_in : d->target_score;
+  a.shard = sd ? 1 : 0;
   a.keys = keys;
   a.pcnt = pcnt;
   a.Q = S;
@@ -1651,7 +1704,207 @@ extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_r
   else retr_launch_deep<8>(tgrid, s, a, (int)stride, t, c, b);
   LTHM_CHECK_LAUNCH();
   hipLaunchKernelGGL(retr_deep_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, (int)stride, pcnt,
-                     d->target_row, U, N, (int)nslab, d->k, d->scores, d->rows, d->target_row ? d->rank : nullptr);
+                     d->target_row, U, N, (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
+                     sd ? sd->target_score_in : nullptr);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                       const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
+                                       const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
+  return retr_topk_deep_any(d, x, g, t, c, b, nullptr, stream);
+}
+
+// ---------------------------------------------------------------- sharded catalogues
+// lthm_retrieve_topk_shard is the scan above with the caller's target scores (RetrArgs::shard);
+// lthm_retrieve_target_score is the prep kernels' target dot alone; retr_shard_merge_k merges the
+// lists that S shards return for one query.
+//
+// Merge by rank: a (score, id) pair does not fit the 64-bit key, so an entry is compared as
+// (score image, id): a precedes b iff image_a > image_b, or the images are equal and id_a < id_b
+// (or the pairs are equal, which the contract rules out, and a's list comes first: so that also
+// then the positions below are a permutation and every output slot is written once).  The output
+// position of entry i of list s is i plus, for every other list, the number of its entries that
+// precede this one: one binary search per list over that list's filled prefix, cut short at the
+// k - pos entries that can still matter, and given up once pos reaches k.  No sort, no atomics, no
+// slot hand-out: the result is a pure function of the inputs.
+//
+// A team (one wave of a block for S k <= 1024, else the block) owns one query.  The lists are staged
+// in LDS as images and ids (12 bytes per entry) when they fit CAP entries per team, and searched
+// in global memory otherwise (CAP = 0).  Every index is below S k and every write below k,
+// whatever the lists hold.
+namespace lthm {
+namespace {
+
+constexpr int RS_SMAX = 64;    // most lists
+constexpr uint32_t RS_EMPTY = 0x007fffffu;  // retr_image(-inf): an entry at or below it is an empty slot
+
+template <int TEAM, int CAP>
+__global__ __launch_bounds__(256) void retr_shard_merge_k(const float* __restrict__ scores,
+                                                          const int64_t* __restrict__ ids,
+                                                          const int* __restrict__ ranks, int64_t Q, int S, int k,
+                                                          float* __restrict__ out_scores, int64_t* __restrict__ out_ids,
+                                                          int64_t* __restrict__ out_rank) {
+  constexpr int NT = 256 / TEAM;  // queries of a block
+  constexpr bool LDS = CAP > 0;
+  __shared__ uint32_t simg[LDS ? NT * CAP : 1];
+  __shared__ int64_t sid[LDS ? NT * CAP : 1];
+  __shared__ int slen[NT][RS_SMAX];
+  static_assert(sizeof(simg) + sizeof(sid) + sizeof(slen) <= 160 * 1024, "LDS budget");
+  const int team = threadIdx.x / TEAM, t = threadIdx.x % TEAM;
+  const int64_t q0 = (int64_t)blockIdx.x * NT + team;
+  const bool live = q0 < Q;
+  const int64_t q = live ? q0 : Q - 1;  // a team past Q reads the last query and writes nothing
+  const int n = S * k;                  // <= 65536
+  uint32_t* const im = simg + (LDS ? team * CAP : 0);
+  int64_t* const idl = sid + (LDS ? team * CAP : 0);
+  // entry i of list s
+  auto src = [&](int s, int i) { return ((int64_t)s * Q + q) * k + i; };
+  auto img_at = [&](int s, int i) { return LDS ? im[s * k + i] : retr_image(scores[src(s, i)]); };
+  auto id_at = [&](int s, int i) { return LDS ? idl[s * k + i] : ids[src(s, i)]; };
+  if constexpr (LDS) {
+    for (int e = t; e < n; e += TEAM) {
+      const int s = e / k, i = e - s * k;
+      im[e] = retr_image(scores[src(s, i)]);
+      idl[e] = ids[src(s, i)];
+    }
+    __syncthreads();
+  }
+  // the filled prefix of every list: the first empty slot of a descending list
+  for (int s = t; s < S; s += TEAM) {
+    int lo = 0, hi = k;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (img_at(s, mid) > RS_EMPTY) lo = mid + 1;
+      else hi = mid;
+    }
+    slen[team][s] = lo;
+  }
+  __syncthreads();
+  for (int e = t; e < n; e += TEAM) {
+    const int s = e / k, i = e - s * k;
+    if (i >= slen[team][s]) continue;
+    const uint32_t ei = img_at(s, i);
+    const int64_t eid = id_at(s, i);
+    int pos = i;
+    for (int o = 0; o < S && pos < k; ++o) {
+      if (o == s) continue;
+      int lo = 0, hi = slen[team][o];
+      if (hi > k - pos) hi = k - pos;  // k - pos predecessors already put this entry past the list
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const uint32_t mi = img_at(o, mid);
+        bool before = mi > ei;
+        if (mi == ei) {
+          const int64_t mid_id = id_at(o, mid);
+          before = mid_id < eid || (mid_id == eid && o < s);
+        }
+        if (before) lo = mid + 1;
+        else hi = mid;
+      }
+      pos += lo;
+    }
+    if (live && pos < k) {
+      out_scores[q * k + pos] = retr_image_score(ei);
+      out_ids[q * k + pos] = eid;
+    }
+  }
+  int total = 0;
+  for (int s = 0; s < S; ++s) total += slen[team][s];
+  for (int p = (total < k ? total : k) + t; p < k; p += TEAM) {
+    if (live) {
+      out_scores[q * k + p] = -INFINITY;
+      out_ids[q * k + p] = 0;
+    }
+  }
+  if (ranks && live && t == 0) {
+    int64_t c = 0;
+    bool none = false;
+    for (int s = 0; s < S; ++s) {
+      const int r = ranks[(int64_t)s * Q + q];
+      none = none || r == -1;
+      c += r;
+    }
+    out_rank[q] = none ? -1 : c;
+  }
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int64_t lthm_retrieve_target_score_ws_bytes(int64_t Q, int32_t G) {
+  if (Q < 1 || Q >= (1ll << 31) || G < 1 || G > RT_GMAX) return -1;
+  return up256(Q * retr_gp(G) * RT_D * 2);
+}
+
+extern "C" int lthm_retrieve_target_score(const void* items, int64_t N, const void* q, int32_t q_dtype,
+                                          int32_t normalize_q, int32_t G, const int32_t* target_row, const float* bias,
+                                          const float* weight, float* out, int64_t Q, void* workspace, int64_t ws_bytes,
+                                          void* stream) {
+  LTHM_REQUIRE(items && q && target_row && out && workspace);
+  LTHM_REQUIRE(N >= 1 && N < (1ll << 31));
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)weight & 3) == 0 && (bias || !weight));
+  const int64_t need = lthm_retrieve_target_score_ws_bytes(Q, G);
+  LTHM_REQUIRE(need >= 0 && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  bf16_t* qn = (bf16_t*)workspace;  // the prep kernels' other output, not used here
+  const bf16_t* it = (const bf16_t*)items;
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  const float miss = __builtin_nanf("");
+  if (G == 1) {
+    if (q_dtype == LTHM_BF16)
+      hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn, it, N,
+                         target_row, out, miss);
+    else
+      hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn, it, N,
+                         target_row, out, miss);
+  } else {
+    if (q_dtype == LTHM_BF16)
+      hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, G, retr_gp(G),
+                         normalize_q, qn, it, N, target_row, out, miss);
+    else
+      hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, G, retr_gp(G),
+                         normalize_q, qn, it, N, target_row, out, miss);
+  }
+  LTHM_CHECK_LAUNCH();
+  if (bias) {
+    hipLaunchKernelGGL(retr_bias_target_k, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, target_row, Q, N, bias,
+                       weight, out);
+    LTHM_CHECK_LAUNCH();
+  }
+  return 0;
+}
+
+extern "C" int lthm_retrieve_topk_shard(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
+                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
+                                        const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+                                        const lthm_retrieve_shard* s, void* stream) {
+  return retr_topk_deep_any(d, x, g, t, c, b, s, stream);
+}
+
+extern "C" int lthm_retrieve_merge_shards(const float* scores, const int64_t* ids, const int32_t* ranks, int32_t S,
+                                          int64_t Q, int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_rank,
+                                          void* stream) {
+  LTHM_REQUIRE(S >= 1 && S <= RS_SMAX && k >= 1 && k <= RD_KMAX && Q >= 1 && Q < (1ll << 31));
+  LTHM_REQUIRE(scores && ids && out_scores && out_ids && (!ranks || out_rank));
+  LTHM_REQUIRE(((uintptr_t)scores & 3) == 0 && ((uintptr_t)ids & 7) == 0 && ((uintptr_t)ranks & 3) == 0);
+  LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0 && ((uintptr_t)out_rank & 7) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = S * k;
+  if (n <= 1024)
+    hipLaunchKernelGGL((retr_shard_merge_k<64, 1024>), dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, st, scores, ids, ranks,
+                       Q, S, k, out_scores, out_ids, out_rank);
+  else if (n <= 8192)
+    hipLaunchKernelGGL((retr_shard_merge_k<256, 8192>), dim3((unsigned)Q), dim3(256), 0, st, scores, ids, ranks, Q, S, k,
+                       out_scores, out_ids, out_rank);
+  else
+    hipLaunchKernelGGL((retr_shard_merge_k<256, 0>), dim3((unsigned)Q), dim3(256), 0, st, scores, ids, ranks, Q, S, k,
+                       out_scores, out_ids, out_rank);
   LTHM_CHECK_LAUNCH();
   return 0;
 }

@@ -23,6 +23,7 @@
 //   lthm::retrieve_topk_after any of the above strictly behind a (score, row) cursor per query
 //   lthm::retrieve_topk_bias  any of the above on the score fma(weight[q], bias[row], dot)
 //   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
+//   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -707,6 +708,35 @@ std::tuple<Tensor, Tensor> retrieve_topk_deep_cuda(const Tensor& q, const Tensor
                                   has_b ? &*bias : nullptr, has_w ? &*bias_weight : nullptr, true);
 }
 
+// scores f32 [S, Q, k], ids int64 [S, Q, k], ranks int32 [S, Q] or None: the merge of the lists that
+// the shards of one catalogue return (rank: an empty tensor without ranks)
+std::tuple<Tensor, Tensor, Tensor> retrieve_merge_shards_cuda(const Tensor& scores_, const Tensor& ids_,
+                                                              const c10::optional<Tensor>& ranks_) {
+  TORCH_CHECK(scores_.dim() == 3 && scores_.scalar_type() == at::kFloat, "scores must be f32 [S, Q, k]");
+  TORCH_CHECK(ids_.scalar_type() == at::kLong && ids_.sizes() == scores_.sizes(), "ids must be int64 [S, Q, k]");
+  TORCH_CHECK(ids_.device() == scores_.device(), "scores and ids must be on one device");
+  const int64_t S = scores_.size(0), Q = scores_.size(1), k = scores_.size(2);
+  TORCH_CHECK(S >= 1 && S <= 64, "retrieve_merge_shards takes 1..64 lists per query (got S=", S, ")");
+  TORCH_CHECK(k >= 1 && k <= 1024, "retrieve_merge_shards takes k in 1..1024 (got ", k, ")");
+  TORCH_CHECK(Q >= 1, "retrieve_merge_shards takes at least one query");
+  const Tensor scores = scores_.contiguous(), ids = ids_.contiguous();
+  const bool has_r = ranks_.has_value() && ranks_->defined();
+  Tensor ranks, out_rank = at::empty({has_r ? Q : 0}, ids.options());
+  if (has_r) {
+    TORCH_CHECK(ranks_->scalar_type() == at::kInt && ranks_->dim() == 2 && ranks_->size(0) == S && ranks_->size(1) == Q &&
+                    ranks_->device() == scores.device(),
+                "ranks must be int32 [S, Q] on the scores' device");
+    ranks = ranks_->contiguous();
+  }
+  Tensor out_scores = at::empty({Q, k}, scores.options()), out_ids = at::empty({Q, k}, ids.options());
+  hip_ok(lthm_retrieve_merge_shards(scores.data_ptr<float>(), ids.data_ptr<int64_t>(),
+                                    has_r ? ranks.data_ptr<int32_t>() : nullptr, (int32_t)S, Q, (int32_t)k,
+                                    out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(),
+                                    has_r ? out_rank.data_ptr<int64_t>() : nullptr, cur_stream()),
+         "lthm_retrieve_merge_shards");
+  return {out_scores, out_ids, out_rank};
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -745,6 +775,7 @@ TORCH_LIBRARY(lthm, m) {
       "retrieve_topk_deep(Tensor q, Tensor items, int k, bool normalize_q, Tensor? exclude_rows, Tensor? tags, "
       "Tensor? tag_filter, Tensor? after_scores, Tensor? after_rows, Tensor? bias, Tensor? bias_weight=None) -> "
       "(Tensor scores, Tensor rows)");
+  m.def("retrieve_merge_shards(Tensor scores, Tensor ids, Tensor? ranks=None) -> (Tensor scores, Tensor ids, Tensor rank)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -761,6 +792,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_after", &retrieve_topk_after_cuda);
   m.impl("retrieve_topk_bias", &retrieve_topk_bias_cuda);
   m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
+  m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -150,6 +150,26 @@ def all_gather_rows(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def all_gather_stack(t: torch.Tensor, group=None) -> torch.Tensor:
+    """t from every rank of ``group`` (None: the world) as [ranks, *t.shape], in rank order, on t's
+    device; every rank passes the same shape."""
+    ws = dist.get_world_size(group) if dist.is_initialized() else 1
+    if ws == 1:
+        return t.unsqueeze(0)
+    # gathered as the concatenation along dim 0 (the one layout every backend takes), viewed as a stack
+    out = torch.empty((ws * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    dist.all_gather_into_tensor(out, t.contiguous(), group=group)
+    return out.view((ws,) + tuple(t.shape))
+
+
+def all_reduce_max(t: torch.Tensor, group=None) -> torch.Tensor:
+    """The elementwise maximum of t over the ranks of ``group`` (None: the world), in a new tensor."""
+    t = t.contiguous().clone()
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return t
+
+
 def gather_sparse_grads(ids: torch.Tensor, gy: torch.Tensor, out: Optional[torch.Tensor] = None,
                         norms: Optional[torch.Tensor] = None):
     """Replicated-table DP backward input: every rank's (ids, pooled gradient) pairs

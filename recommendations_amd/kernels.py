@@ -1735,17 +1735,20 @@ def retrieve_deep_passes(k: int):
 
 
 def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, slab_rows, exclude_rows, tags, tag_filter,
-                        after_scores, after_rows, bias, bias_weight):
+                        after_scores, after_rows, bias, bias_weight, target_scores=None):
     """RETRIEVE_MAX_K < k <= RETRIEVE_MAX_DEEP in one scan of the catalogue: lthm_retrieve_topk_deep
     (csrc/retrieve.hip, retr_deep_topk_k and retr_deep_merge_k).  q [Q, 128] (who = retrieve_topk)
-    or [U, G, 128]; everything else as the caller documents it."""
+    or [U, G, 128]; everything else as the caller documents it.  With target_scores (f32 [Q] or [U])
+    the call is lthm_retrieve_topk_shard, for every k in 1..RETRIEVE_MAX_DEEP: the scan of one shard
+    of a catalogue, which counts rank against the given scores."""
     import ctypes
     from ._lib import STRUCTS
     grouped = who == "retrieve_topk_group"
     per = "U" if grouped else "Q"
     k = int(k)
-    _check(RETRIEVE_MAX_K < k <= RETRIEVE_MAX_DEEP, f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
-    require_gpu(q, items, target_rows, exclude_rows)
+    _check((RETRIEVE_MAX_K if target_scores is None else 0) < k <= RETRIEVE_MAX_DEEP,
+           f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    require_gpu(q, items, target_rows, exclude_rows, target_scores)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
     if grouped:
@@ -1779,6 +1782,15 @@ def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, sl
     if target_rows is not None:
         rank = torch.empty(U, dtype=torch.int32, device=dev)
         tscore = torch.empty(U, dtype=torch.float32, device=dev)
+    sh = None
+    if target_scores is not None:
+        _check(target_scores.dtype == torch.float32 and tuple(target_scores.shape) == (U,),
+               f"target_scores must be f32 [{per}] (got {target_scores.dtype} {tuple(target_scores.shape)}, {per}={U})")
+        _check(target_scores.device == dev, "target_scores must be on the queries' device")
+        rank = torch.empty(U, dtype=torch.int32, device=dev)
+        tscore = None  # the call writes none: the caller's are the target scores
+        sh = STRUCTS["lthm_retrieve_shard"]()
+        sh.target_score_in = ptr(target_scores)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     d = STRUCTS["lthm_retrieve_desc"]()
     d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
@@ -1797,12 +1809,81 @@ def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, sl
     c = _retrieve_cursor(who, after_scores, after_rows, U, per, dev)
     b, bw = _retrieve_bias(who, bias, bias_weight, items, U, per, dev)
     addr = lambda o: ctypes.addressof(o) if o is not None else None
+    nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X) \
+        + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0) \
+        + (4.0 * N if b is not None else 0.0) + (4.0 * U if bw is not None else 0.0)
+    if sh is not None:
+        call("lthm_retrieve_topk_shard", addr(d), addr(x), addr(g), addr(t), addr(c), addr(b), addr(sh), stream(),
+             _key="retr_shard_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * U)
+        return scores, rows, rank, target_scores
     call("lthm_retrieve_topk_deep", addr(d), addr(x), addr(g), addr(t), addr(c), addr(b), stream(),
-         _key="retr_deep_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
-         _bytes=float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
-         + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0)
-         + (4.0 * N if b is not None else 0.0) + (4.0 * U if bw is not None else 0.0))
+         _key="retr_deep_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
     return scores, rows, rank, tscore
+
+
+def retrieve_target_score(q, items, target_rows, *, normalize_q: bool = True, bias=None, bias_weight=None):
+    """The target_score that retrieve_topk (q [Q, 128]) or retrieve_topk_group (q [U, G, 128]) returns
+    for the same arguments, bit for bit, without a scan of the catalogue (lthm_retrieve_target_score:
+    the same prep kernels).  f32 [Q] or [U]; NaN where target_rows (int32) is outside [0, N): this
+    shard of a catalogue does not hold the query's target."""
+    require_gpu(q, items, target_rows)
+    who = "retrieve_target_score"
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() in (2, 3) and q.shape[-1] == RETRIEVE_WIDTH,
+           f"{who} takes [Q, {RETRIEVE_WIDTH}] or [U, G, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    U, N = q.shape[0], items.shape[0]
+    G = q.shape[1] if q.dim() == 3 else 1
+    per = "U" if q.dim() == 3 else "Q"
+    _check(1 <= G <= RETRIEVE_MAX_GROUP, f"{who} takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
+    _check(N >= 1 and U >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, {per}={U})")
+    _check(target_rows.dtype == torch.int32 and target_rows.shape == (U,), f"target_rows must be int32 [{per}]")
+    dev = q.device
+    bw = None
+    if bias is not None or bias_weight is not None:
+        bw = _retrieve_bias(who, bias, bias_weight, items, U, per, dev)[1]
+    need = load().lthm_retrieve_target_score_ws_bytes(U, G)
+    _check(need >= 0, f"{who}: no workspace size for {per}={U} G={G}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(U, dtype=torch.float32, device=dev)
+    call("lthm_retrieve_target_score", ptr(items), N, ptr(q), dcode(q), int(bool(normalize_q)), G, ptr(target_rows),
+         ptr(bias), ptr(bw), ptr(out), U, ptr(ws), need, stream(), _key="retr_target_score",
+         _work=float(q.numel() * q.element_size() + U * (RETRIEVE_WIDTH * 2 + 8)), _unit="byte")
+    return out
+
+
+RETRIEVE_MAX_SHARDS = 64      # RS_SMAX: the most lists of one merge
+
+
+def retrieve_merge_shards(scores, ids, ranks=None):
+    """The k first entries of the union of S lists per query (lthm_retrieve_merge_shards,
+    retr_shard_merge_k).  scores f32 [S, Q, k] and ids int64 [S, Q, k]: every list sorted by (score
+    descending, id ascending) with its empty slots (-inf, 0) at the end, ids distinct across the
+    lists of one query; ranks int32 [S, Q] or None.  1 <= S <= 64, 1 <= k <= 1024.  Returns (scores
+    f32 [Q, k], ids int64 [Q, k], rank int64 [Q] | None): rank is -1 where any shard's is, else the
+    sum.  -0 equals +0 and comes back as +0.  A pure function of the inputs."""
+    require_gpu(scores, ids, ranks)
+    _check(scores.dim() == 3 and scores.dtype == torch.float32,
+           f"retrieve_merge_shards takes f32 scores [S, Q, k] (got {scores.dtype} {tuple(scores.shape)})")
+    _check(ids.dtype == torch.int64 and ids.shape == scores.shape,
+           f"retrieve_merge_shards takes int64 ids of the scores' shape (got {ids.dtype} {tuple(ids.shape)})")
+    S, Q, k = scores.shape
+    _check(1 <= S <= RETRIEVE_MAX_SHARDS, f"retrieve_merge_shards takes 1..{RETRIEVE_MAX_SHARDS} lists per query (got S={S})")
+    _check(1 <= k <= RETRIEVE_MAX_DEEP, f"retrieve_merge_shards takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    _check(Q >= 1, "retrieve_merge_shards takes at least one query")
+    _check(ids.device == scores.device, "scores and ids must be on one device")
+    dev = scores.device
+    out_rank = None
+    if ranks is not None:
+        _check(ranks.dtype == torch.int32 and tuple(ranks.shape) == (S, Q),
+               f"ranks must be int32 [S, Q] (got {ranks.dtype} {tuple(ranks.shape)})")
+        _check(ranks.device == dev, "ranks must be on the scores' device")
+        out_rank = torch.empty(Q, dtype=torch.int64, device=dev)
+    out_scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    call("lthm_retrieve_merge_shards", ptr(scores), ptr(ids), ptr(ranks), S, Q, k, ptr(out_scores), ptr(out_ids),
+         ptr(out_rank), stream(), _key="retr_shard_merge_k", _work=float(12 * S * Q * k + 12 * Q * k), _unit="byte")
+    return out_scores, out_ids, out_rank
 
 
 def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows, kw):
@@ -1825,7 +1906,7 @@ def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows
 
 def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
                   exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
-                  deep: bool = False, bias=None, bias_weight=None):
+                  deep: bool = False, bias=None, bias_weight=None, target_scores=None):
     """The k catalogue rows with the largest dot product per query (csrc/retrieve.hip).
 
     q f32 / bf16 [Q, 128]; items bf16 [N, 128] (normalised rows); target_rows int32 [Q] or None.
@@ -1870,10 +1951,24 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     biased the same way and is the value rank counts against.  A row at -inf stays at -inf.
     bias_weight = 0 or an all-zero bias gives the rows and ranks of the call without a prior.  A
     non-finite weight gives that query an unspecified list.  A deep list carries the prior, in
-    every pass where it is paged."""
+    every pass where it is paged.
+
+    target_scores f32 [Q]: the catalogue is one shard of a larger one and these are the targets'
+    scores, wherever the targets live (lthm_retrieve_topk_shard; retrieve_target_score computes
+    them on the shard that holds the target).  rank[q] then counts the eligible rows other than
+    target_rows[q] (None, or -1 where this shard does not hold the target) that score strictly above
+    target_scores[q], for every query, -1 where target_scores[q] is NaN; scores and rows are those
+    of the call without it, and the target_score returned is the tensor given.  deep="paged" does
+    not take it."""
     import ctypes
     from ._lib import STRUCTS
     _check(bias is not None or bias_weight is None, "retrieve_topk takes a bias_weight only with a bias")
+    if target_scores is not None:
+        _check(deep != "paged", 'retrieve_topk takes target_scores with deep=False or True, not "paged"')
+        _check(deep or int(k) <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k}; deep=True takes "
+                                                 f"up to {RETRIEVE_MAX_DEEP})")
+        return _retrieve_deep_scan("retrieve_topk", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
+                                   tag_filter, after_scores, after_rows, bias, bias_weight, target_scores=target_scores)
     if deep and int(k) > RETRIEVE_MAX_K:
         _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk takes deep=False, True or "paged" (got {deep!r})')
         if deep != "paged":
@@ -1966,7 +2061,7 @@ RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
 
 def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
                         exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
-                        deep: bool = False, bias=None, bias_weight=None):
+                        deep: bool = False, bias=None, bias_weight=None, target_scores=None):
     """retrieve_topk for users with several queries each: an item's score is its best over the
     user's queries, s[u, j] = max_g s_g[u, j], with s_g the score retrieve_topk gives query
     (u, g) (csrc/retrieve.hip, retr_topk_k<EXCL, GP>).
@@ -1984,10 +2079,17 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     score, and deep=True (k up to RETRIEVE_MAX_DEEP in one catalogue scan; deep="paged": one scan per
     128 rows) are retrieve_topk's as well.  So are bias f32 [N] and bias_weight (None, a number or f32 [U], one
     weight per user): the prior is added to the best-over-queries score, fma(w[u], bias[j],
-    max_g s_g[u, j]), which equals the best biased score since the fma is monotone in the dot."""
+    max_g s_g[u, j]), which equals the best biased score since the fma is monotone in the dot.
+    target_scores f32 [U], the targets' scores for one shard of a catalogue, is retrieve_topk's too."""
     import ctypes
     from ._lib import STRUCTS
     _check(bias is not None or bias_weight is None, "retrieve_topk_group takes a bias_weight only with a bias")
+    if target_scores is not None:
+        _check(deep != "paged", 'retrieve_topk_group takes target_scores with deep=False or True, not "paged"')
+        _check(deep or int(k) <= RETRIEVE_MAX_K, f"retrieve_topk_group takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+        return _retrieve_deep_scan("retrieve_topk_group", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows,
+                                   tags, tag_filter, after_scores, after_rows, bias, bias_weight,
+                                   target_scores=target_scores)
     if deep and int(k) > RETRIEVE_MAX_K:
         _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk_group takes deep=False, True or "paged" (got {deep!r})')
         if deep != "paged":

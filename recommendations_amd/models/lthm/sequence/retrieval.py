@@ -20,16 +20,23 @@ Bias: a catalogue may carry one finite f32 per item, a score prior (popularity, 
 sponsored lift, a demotion).  A query's score for item j is then fma(w, bias[j], q . e_j) with a
 weight w per query (1 unless told otherwise), inside the kernel (``K.retrieve_topk``'s ``bias`` /
 ``bias_weight``): the order, the cursors and the ranks are those of the biased scores.
+
+Shards: a ``ShardedItemCatalogue`` holds the items as several ``ItemCatalogue``s with disjoint ids,
+on this process's devices and, with a process group, on the other ranks' (the row-sharded item
+table of C3: ``build_catalogue(..., shard=(rank, world))``).  Its ``topk`` returns, bit for bit, what
+one catalogue over the union returns: every shard is scanned on its own against the target's score
+(``K.retrieve_target_score``, ``K.retrieve_topk(target_scores=)``) and the lists are merged on the
+device (``K.retrieve_merge_shards``).
 """
 from __future__ import annotations
 
 import json
-from typing import Optional, Union
+from typing import List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from .... import kernels as K
-from ....distributed import world_size
+from ....distributed import all_gather_stack, all_reduce_max, world_size
 
 FORMAT = "lthm-item-catalogue-v1"
 WIDTH = K.RETRIEVE_WIDTH
@@ -112,6 +119,59 @@ class ItemCatalogue:
 
     def __len__(self) -> int:
         return self.ids.shape[0]
+
+    @property
+    def has_tags(self) -> bool:
+        return self.tags is not None
+
+    @property
+    def has_bias(self) -> bool:
+        return self.bias is not None
+
+    def take(self, rows: torch.Tensor) -> "ItemCatalogue":
+        """The catalogue of some of the rows: a bool mask [N] or an integer index tensor (any order,
+        no row twice).  Tags and bias move with the rows; at least one row must remain."""
+        if rows.dtype == torch.bool:
+            if rows.shape != self.ids.shape:
+                raise ValueError(f"take: a mask must be bool [N] (got {tuple(rows.shape)}, N={len(self)})")
+            idx = rows.to(self.ids.device).nonzero(as_tuple=True)[0]
+        else:
+            if rows.dim() != 1 or rows.is_floating_point():
+                raise ValueError(f"take: an index must be an integer tensor [n] (got {rows.dtype} {tuple(rows.shape)})")
+            idx = torch.sort(rows.to(device=self.ids.device, dtype=torch.int64))[0]
+            if idx.numel() and (int(idx[0]) < 0 or int(idx[-1]) >= len(self)):
+                raise ValueError(f"take: rows must lie in 0..{len(self) - 1}")
+            if idx.numel() > 1 and bool((idx[1:] == idx[:-1]).any()):
+                raise ValueError("take: a row is named twice")
+        if idx.numel() < 1:
+            raise ValueError("take: no row remains, and a catalogue is never empty")
+        return ItemCatalogue(self.ids[idx], self.emb[idx], None if self.tags is None else self.tags[idx],
+                             None if self.bias is None else self.bias[idx])
+
+    def split(self, n: int) -> List["ItemCatalogue"]:
+        """n shards of contiguous id ranges: shard i holds rows [i N // n, (i + 1) N // n), so none
+        is empty.  n > N is refused."""
+        N = len(self)
+        if not 1 <= int(n) <= N:
+            raise ValueError(f"split takes 1..N shards (got n={n}, N={N}): a shard is never empty")
+        n = int(n)
+        dev = self.ids.device
+        return [self.take(torch.arange(i * N // n, (i + 1) * N // n, device=dev)) for i in range(n)]
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of ``ids``: the catalogue holds this id."""
+        return self.rows_of(ids) >= 0
+
+    def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, exclude_ids: Optional[torch.Tensor] = None,
+                     tag_filter: Optional[torch.Tensor] = None, bias_weight: Optional[float] = None) -> torch.Tensor:
+        """The hit position of every query's target (``catalogue_metrics``): the number of eligible
+        items scoring strictly above it, -1 where the catalogue does not hold the target; one
+        ``K.retrieve_topk`` with k = 1.  The prior counts only where ``bias_weight`` is given: without
+        it the scores are the plain dots, whether or not the catalogue carries a bias."""
+        xr = None if exclude_ids is None else self.rows_of(exclude_ids).contiguous()
+        return K.retrieve_topk(q, self.emb, 1, normalize_q=True, target_rows=self.rows_of(target_ids).contiguous(),
+                               exclude_rows=xr, tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter,
+                               bias=self.bias if bias_weight is not None else None, bias_weight=bias_weight)[2]
 
     @classmethod
     def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None,
@@ -241,20 +301,228 @@ class ItemCatalogue:
         return cat.to(device) if device is not None else cat
 
 
+class ShardedItemCatalogue:
+    """One catalogue held as shards: ``local_shards`` are the ``ItemCatalogue``s of this process (on
+    one device or on several; disjoint ids, checked here), and with ``group`` the catalogue also
+    covers the shards of the group's other ranks.  All shards agree on carrying tags and on carrying
+    a bias.  At most ``K.RETRIEVE_MAX_SHARDS`` = 64 shards in all.
+
+    With a ``group`` the constructor, ``topk``, ``filter_like``, ``holds``, ``target_ranks`` and
+    ``validate`` are collectives: every rank calls them, with the same queries, and every rank gets
+    the full result.  Disjointness across ranks is not checked here; ``validate()`` does it."""
+
+    def __init__(self, local_shards: Sequence[ItemCatalogue], group=None):
+        shards = list(local_shards)
+        if not shards or not all(isinstance(s, ItemCatalogue) for s in shards):
+            raise ValueError("ShardedItemCatalogue takes one or more ItemCatalogue shards")
+        if len({s.has_tags for s in shards}) != 1:
+            raise ValueError("the shards of a catalogue all carry tags, or none does")
+        if len({s.has_bias for s in shards}) != 1:
+            raise ValueError("the shards of a catalogue all carry a bias, or none does")
+        dev = shards[0].ids.device
+        ids = torch.sort(torch.cat([s.ids.to(dev) for s in shards]))[0]
+        if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+            bad = int(ids[1:][ids[1:] == ids[:-1]][0])
+            raise ValueError(f"the shards of a catalogue hold disjoint ids (id {bad} is in two of them)")
+        self.shards = shards
+        self.group = group
+        self.device = dev
+        self._total = int(ids.numel())
+        self._pad_to = len(shards)       # local lists per rank in a gather
+        self._max_items = self._total    # most items of one rank
+        n_all = len(shards)
+        if group is not None:
+            mine = torch.tensor([len(shards), self._total, int(shards[0].has_tags), int(shards[0].has_bias)],
+                                dtype=torch.int64, device=dev)
+            every = all_gather_stack(mine, group).cpu()
+            if bool((every[:, 2] != every[0, 2]).any()) or bool((every[:, 3] != every[0, 3]).any()):
+                raise ValueError("the shards of a catalogue all carry tags / a bias, or none does (the ranks disagree)")
+            self._pad_to = int(every[:, 0].max())
+            self._total = int(every[:, 1].sum())
+            self._max_items = int(every[:, 1].max())
+            n_all = self._pad_to * every.shape[0]  # the merge sees every rank's lists padded to the longest
+        if n_all > K.RETRIEVE_MAX_SHARDS:
+            raise ValueError(f"a sharded catalogue takes at most {K.RETRIEVE_MAX_SHARDS} shards (got {n_all})")
+
+    def __len__(self) -> int:
+        return self._total
+
+    @property
+    def has_tags(self) -> bool:
+        return self.shards[0].has_tags
+
+    @property
+    def has_bias(self) -> bool:
+        return self.shards[0].has_bias
+
+    def validate(self) -> None:
+        """Disjointness of the ids across the ranks of the group: one all-gather of every rank's ids
+        (padded with 0, which no catalogue holds, to the longest), one sort."""
+        dev = self.device
+        ids = torch.cat([s.ids.to(dev) for s in self.shards])
+        if self.group is not None:
+            pad = torch.zeros(self._max_items, dtype=torch.int64, device=dev)
+            pad[:ids.numel()] = ids
+            ids = all_gather_stack(pad, self.group).reshape(-1)
+            ids = ids[ids != 0]
+        ids = torch.sort(ids)[0]
+        if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+            bad = int(ids[1:][ids[1:] == ids[:-1]][0])
+            raise ValueError(f"the shards of a catalogue hold disjoint ids (id {bad} is in two of them)")
+
+    def _reduce_max(self, t: torch.Tensor) -> torch.Tensor:
+        return t if self.group is None else all_reduce_max(t, self.group)
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of ``ids``: some shard holds this id."""
+        dev = self.device
+        found = torch.stack([s.holds(ids).to(dev) for s in self.shards]).any(dim=0)
+        return self._reduce_max(found.to(torch.int32)).bool()
+
+    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
+        """``ItemCatalogue.filter_like`` over the union: the target's tag word comes from the shard
+        that holds it (at most one does: the words and a found flag are MAX-combined)."""
+        if not self.has_tags:
+            raise ValueError("filter_like needs a catalogue with tags")
+        if target_ids.dim() != 1:
+            raise ValueError("filter_like takes target ids [Q]")
+        dev = self.device
+        both = torch.zeros((2, target_ids.numel()), dtype=torch.int64, device=dev)  # found, the word's 32 bits
+        for s in self.shards:
+            rows = s.rows_of(target_ids).long()
+            word = s.tags[rows.clamp(min=0)].long() & 0xFFFFFFFF
+            both = torch.maximum(both, torch.stack([(rows >= 0).long(), torch.where(rows >= 0, word, 0)]).to(dev))
+        both = self._reduce_max(both)
+        found, t = both[0] > 0, both[1]
+        t = torch.where(t >= (1 << 31), t - (1 << 32), t)
+        m = _bits32(mask, t.numel(), "mask", dev)
+        m = torch.where(found, m, torch.zeros_like(m))
+        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+
+    def _scan(self, q, k, normalize_q, target_ids, slab_rows, exclude_ids, tag_filter, after_scores, after_ids,
+              bias_weight, use_bias):
+        if tag_filter is not None and not self.has_tags:
+            raise ValueError("tag_filter given, but this catalogue carries no tags")
+        if bias_weight is not None and not self.has_bias:
+            raise ValueError("bias_weight given, but this catalogue carries no bias")
+        if (after_scores is None) != (after_ids is None):
+            raise ValueError("after_scores and after_ids are given together or neither")
+        if after_ids is not None and (after_ids.dtype != torch.int64 or after_ids.dim() != 1):
+            raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
+        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
+            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+        k = int(k)
+        if not 1 <= k <= K.RETRIEVE_MAX_DEEP:
+            raise ValueError(f"topk takes k in 1..{K.RETRIEVE_MAX_DEEP} (got {k})")
+        home = q.device
+        call = K.retrieve_topk_group if q.dim() == 3 else K.retrieve_topk
+        if isinstance(bias_weight, (int, float)) and not isinstance(bias_weight, bool) and use_bias:
+            bias_weight = torch.full((q.shape[0],), float(bias_weight), dtype=torch.float32, device=home)
+        on = lambda t, dev: None if t is None else t.to(dev).contiguous()
+        # 1, 2: the target's score, from the one shard that holds the target
+        tscore = tscore_out = None
+        trows = [None] * len(self.shards)
+        if target_ids is not None:
+            parts = []
+            for i, s in enumerate(self.shards):
+                dev = s.ids.device
+                trows[i] = s.rows_of(target_ids).contiguous()
+                with torch.cuda.device(dev):
+                    parts.append(K.retrieve_target_score(on(q, dev), s.emb, trows[i], normalize_q=normalize_q,
+                                                         bias=s.bias if use_bias else None,
+                                                         bias_weight=on(bias_weight, dev) if use_bias else None).to(home))
+            ts = torch.stack(parts)
+            ts = torch.where(torch.isnan(ts), torch.full_like(ts, float("-inf")), ts).amax(dim=0)
+            ts = self._reduce_max(ts)  # a real score is finite; -inf: no shard holds the target
+            tscore = torch.where(ts == float("-inf"), torch.full_like(ts, float("nan")), ts).contiguous()
+            tscore_out = ts  # what one catalogue returns: -inf without a target
+        # 3: every local shard's list, its rows as ids
+        ls, li, lr = [], [], []
+        for i, s in enumerate(self.shards):
+            dev = s.ids.device
+            with torch.cuda.device(dev):
+                sc, rows, rank, _ = call(on(q, dev), s.emb, k, normalize_q=normalize_q, target_rows=trows[i],
+                                         slab_rows=slab_rows,
+                                         exclude_rows=None if exclude_ids is None else s.rows_of(exclude_ids).contiguous(),
+                                         tags=s.tags if tag_filter is not None else None, tag_filter=on(tag_filter, dev),
+                                         after_scores=on(after_scores, dev),
+                                         after_rows=None if after_ids is None else s.cursor_rows(after_ids).contiguous(),
+                                         deep=k > K.RETRIEVE_MAX_K, bias=s.bias if use_bias else None,
+                                         bias_weight=on(bias_weight, dev) if use_bias else None,
+                                         target_scores=on(tscore, dev))
+                ids = torch.where(rows >= 0, s.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+            ls.append(sc.to(home))
+            li.append(ids.to(home))
+            if rank is not None:
+                lr.append(rank.to(home))
+        # 4: the lists of every rank, each rank's padded with empty lists to the longest
+        for _ in range(self._pad_to - len(self.shards)):
+            ls.append(torch.full_like(ls[0], float("-inf")))
+            li.append(torch.zeros_like(li[0]))
+            if lr:
+                lr.append(torch.zeros_like(lr[0]))
+        scores, ids = torch.stack(ls), torch.stack(li)
+        ranks = torch.stack(lr) if lr else None
+        if self.group is not None:
+            scores = all_gather_stack(scores, self.group).flatten(0, 1)
+            ids = all_gather_stack(ids, self.group).flatten(0, 1)
+            if ranks is not None:
+                ranks = all_gather_stack(ranks, self.group).flatten(0, 1)
+        # 5
+        with torch.cuda.device(home):
+            out_scores, out_ids, out_rank = K.retrieve_merge_shards(scores.contiguous(), ids.contiguous(),
+                                                                    None if ranks is None else ranks.contiguous())
+        return out_ids, out_scores, out_rank, tscore_out
+
+    def topk(self, q: torch.Tensor, k: int, *, normalize_q: bool = True, target_ids: Optional[torch.Tensor] = None,
+             slab_rows: int = 0, exclude_ids: Optional[torch.Tensor] = None,
+             tag_filter: Optional[torch.Tensor] = None, after_scores: Optional[torch.Tensor] = None,
+             after_ids: Optional[torch.Tensor] = None,
+             bias_weight: Union[None, float, torch.Tensor] = None):
+        """``ItemCatalogue.topk`` over the union of the shards, argument for argument: (item_ids int64
+        [Q, k], scores f32 [Q, k], rank, target_score), bit for bit what one ``ItemCatalogue`` holding
+        every item returns, but for ``rank``, which is int64 here.  ``slab_rows`` goes to every shard's
+        scan.  The outputs are on ``q``'s device."""
+        return self._scan(q, k, normalize_q, target_ids, slab_rows, exclude_ids, tag_filter, after_scores, after_ids,
+                          bias_weight, True)
+
+    def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, exclude_ids: Optional[torch.Tensor] = None,
+                     tag_filter: Optional[torch.Tensor] = None, bias_weight: Optional[float] = None) -> torch.Tensor:
+        """``ItemCatalogue.target_ranks`` over the union of the shards (int64)."""
+        return self._scan(q, 1, True, target_ids, 0, exclude_ids, tag_filter, None, None, bias_weight,
+                          bias_weight is not None)[2]
+
+
+def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:
+    """The slice [lo, hi) of n sorted ids that ``build_catalogue(shard=(rank, world))`` keeps."""
+    return rank * n // world, (rank + 1) * n // world
+
+
 @torch.no_grad()
 def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Optional[torch.Tensor] = None,
-                    bias: Optional[torch.Tensor] = None) -> ItemCatalogue:
+                    bias: Optional[torch.Tensor] = None, shard: Optional[Tuple[int, int]] = None) -> ItemCatalogue:
     """The catalogue of ``ids`` under ``wrapper``'s current weights: per chunk, the item
     embedding module and the product tower on a [1, n] id row (the training kernels), then
     F.normalize to bf16 as the loss does (``K.rownorm``).  A row therefore equals the
     normalised ``current_token_emb`` row a forward produces for that id.  ``tags`` (int32, one
     word per entry of ``ids``) follow the ids through the sort and the de-duplication; an id given
     twice with different tags is refused.  ``bias`` (f32, one word per entry of ``ids``) follows
-    them the same way, under the same rule."""
+    them the same way, under the same rule.
+
+    ``shard = (rank, world)``: this process's part of a catalogue built by ``world`` processes, for a
+    ``ShardedItemCatalogue``.  Every rank passes the same ``ids`` (and ``tags`` / ``bias``) and keeps
+    the slice [rank n // world, (rank + 1) n // world) of the n sorted unique ids.  Every rank makes
+    the same number of chunk calls, since the forward of a row-sharded item table is a collective: a
+    rank whose slice has ended joins the remaining calls with a one-id row whose result it drops.
+    A row-sharded item table at world size > 1 needs ``shard``."""
     from ....commons.layers import RowShardedKShiftEmbedding
     enc = wrapper._model
-    if isinstance(enc.product_emb_module, RowShardedKShiftEmbedding) and world_size() > 1:
-        raise RuntimeError("build_catalogue does not take a row-sharded item table at world size > 1")
+    if shard is None and isinstance(enc.product_emb_module, RowShardedKShiftEmbedding) and world_size() > 1:
+        raise RuntimeError("build_catalogue does not take a row-sharded item table at world size > 1 "
+                           "without shard=(rank, world): every rank then builds its own slice of the catalogue")
+    if shard is not None:
+        if len(shard) != 2 or not 0 <= int(shard[0]) < int(shard[1]):
+            raise ValueError(f"shard takes (rank, world) with 0 <= rank < world (got {shard})")
     if ids.dtype != torch.int64 or ids.dim() != 1 or ids.numel() < 1:
         raise ValueError("build_catalogue takes int64 ids [N], N >= 1")
     if chunk < 1:
@@ -271,12 +539,25 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
     ids = torch.unique(ids.to(dev))  # sorted ascending
     if bool((ids == 0).any()):
         raise ValueError("catalogue ids must not hold 0, the pad id")
+    calls = (ids.numel() + chunk - 1) // chunk
+    if shard is not None:
+        n, (r, w) = ids.numel(), (int(shard[0]), int(shard[1]))
+        if w > n:
+            raise ValueError(f"build_catalogue: {w} shards of {n} ids: a shard is never empty")
+        lo, hi = shard_bounds(n, r, w)
+        spare = ids[:1]  # the row of a call this rank only joins
+        ids = ids[lo:hi]
+        tags = None if tags is None else tags[lo:hi].contiguous()
+        bias = None if bias is None else bias[lo:hi].contiguous()
+        calls = ((n + w - 1) // w + chunk - 1) // chunk  # those of the longest slice, on every rank
     out = torch.empty((ids.numel(), WIDTH), dtype=torch.bfloat16, device=dev)
-    for lo in range(0, ids.numel(), chunk):
-        row = ids[lo:lo + chunk].view(1, -1).contiguous()
+    for i in range(calls):
+        lo = i * chunk
+        row = (ids[lo:lo + chunk] if lo < ids.numel() else spare).view(1, -1).contiguous()
         _, prod, _ = enc.product_tower(row, enc.product_emb_module(row))
-        out[lo:lo + row.numel()] = K.rownorm(prod.reshape(-1, WIDTH).contiguous())[0]
-    return ItemCatalogue(ids, out, tags, bias)
+        if lo < ids.numel():
+            out[lo:lo + row.numel()] = K.rownorm(prod.reshape(-1, WIDTH).contiguous())[0]
+    return ItemCatalogue(ids.contiguous(), out, tags, bias)
 
 
 def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:

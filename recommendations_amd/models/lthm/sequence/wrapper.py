@@ -401,7 +401,7 @@ class LTHMModelWrapper(BaseModelWrapper):
         filt = None
         if tag_all is not None or tag_any is not None or tag_none is not None:
             from .retrieval import make_tag_filter
-            if catalogue.tags is None:
+            if not catalogue.has_tags:
                 raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
             filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
                                    0 if tag_none is None else tag_none, device=q.device)
@@ -445,49 +445,46 @@ class LTHMModelWrapper(BaseModelWrapper):
         L = ids.shape[1] - off
         sfx = ("_unseen" if exclude_seen else "") + ("_tagged" if same_tags_mask is not None else "") \
             + ("_biased" if bias_weight is not None else "")
-        if same_tags_mask is not None and catalogue.tags is None:
+        if same_tags_mask is not None and not catalogue.has_tags:
             raise ValueError("same_tags_mask given, but this catalogue carries no tags")
-        bias = None
         if bias_weight is not None:
             if isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float)):
                 raise ValueError(f"bias_weight takes a float (got {type(bias_weight).__name__})")
-            if catalogue.bias is None:
+            if not catalogue.has_bias:
                 raise ValueError("bias_weight given, but this catalogue carries no bias")
-            bias, bias_weight = catalogue.bias, float(bias_weight)
+            bias_weight = float(bias_weight)
         res: Dict[str, float] = {"catalogue_queries" + sfx: 0}
         if L <= 0:
             return res
-        rows = catalogue.rows_of(ids[:, off:])
-        keep = (mask[:, off:] == 0) & (rows >= 0)
+        tids = ids[:, off:]
+        keep = (mask[:, off:] == 0) & catalogue.holds(tids)
         n = int(keep.sum())
         if n == 0:
             return res
         q = y[:, :L, head][keep].contiguous()
         if q.dtype not in (torch.float32, torch.bfloat16):
             q = q.float()
-        trow = rows[keep].contiguous()
-        tags = filt = None
+        tid = tids[keep].contiguous()
+        filt = None
         if same_tags_mask is not None:
-            tags = catalogue.tags
-            filt = catalogue.filter_like(catalogue.ids[trow.long()], same_tags_mask)
+            filt = catalogue.filter_like(tid, same_tags_mask)
+        # the scans are the catalogue's (target_ranks): one K.retrieve_topk with k = 1 per call for an
+        # ItemCatalogue, one per shard and a merge for a ShardedItemCatalogue
         if not exclude_seen:
-            _, _, rank, _ = K.retrieve_topk(q, catalogue.emb, 1, normalize_q=True, target_rows=trow,
-                                            tags=tags, tag_filter=filt, bias=bias, bias_weight=bias_weight)
+            rank = catalogue.target_ranks(q, tid, tag_filter=filt, bias_weight=bias_weight)
         else:
             T = ids.shape[1]
             if T > K.RETRIEVE_MAX_EXCLUDE:
                 raise ValueError(f"exclude_seen takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens (T = {T})")
-            seen = catalogue.rows_of(ids)  # [B, T]; the pad id and unknown ids are -1
             bi, ti = keep.nonzero(as_tuple=True)  # the order of q's rows
-            col = torch.arange(T, device=seen.device)
+            col = torch.arange(T, device=ids.device)
             ranks = []
-            for lo in range(0, n, 16384):  # an [n, T] int32 list matrix, at most 32 MB at a time at T = 512
+            for lo in range(0, n, 16384):  # an [n, T] list matrix at a time; the pad id 0 and unknown ids exclude nothing
                 b, t = bi[lo:lo + 16384], ti[lo:lo + 16384]
-                xr = torch.where(col[None, :] <= t[:, None], seen[b], torch.full_like(seen[b], -1)).contiguous()
-                ranks.append(K.retrieve_topk(q[lo:lo + 16384], catalogue.emb, 1, normalize_q=True,
-                                             target_rows=trow[lo:lo + 16384], exclude_rows=xr, tags=tags,
-                                             tag_filter=None if filt is None else filt[lo:lo + 16384],
-                                             bias=bias, bias_weight=bias_weight)[2])
+                xi = torch.where(col[None, :] <= t[:, None], ids[b], torch.zeros_like(ids[b])).contiguous()
+                ranks.append(catalogue.target_ranks(q[lo:lo + 16384], tid[lo:lo + 16384], exclude_ids=xi,
+                                                    tag_filter=None if filt is None else filt[lo:lo + 16384],
+                                                    bias_weight=bias_weight))
             rank = torch.cat(ranks)
         pos = rank.float()
         res["catalogue_queries" + sfx] = n
