@@ -1030,6 +1030,35 @@ int lthm_retrieve_topk_shard(const lthm_retrieve_desc* d, const lthm_retrieve_ex
  * lists breaks the contract but not the call: both copies are returned, the lower list's first. */
 int lthm_retrieve_merge_shards(const float* scores, const int64_t* ids, const int32_t* ranks, int32_t S, int64_t Q,
                                int32_t k, float* out_scores, int64_t* out_ids, int64_t* out_rank, void* stream);
+/* Clustered catalogues (an inverted-file index): the catalogue's rows are grouped into L lists and a
+ * query scans only the lists its probe row names.
+ *   items     bf16 [N, 128], list-major: list c is rows [list_off[c], list_off[c + 1]), its ids ascending
+ *   row_ids   int64 [N]: the item id of every row, distinct
+ *   list_off  int64 [L + 1], ascending from 0 to N (an offset outside [0, N] is clamped, never followed)
+ *   q         f32 / bf16 [Q, 128], prepared exactly as the entries above prepare it
+ *   probes    int32 [Q, P], 1 <= P <= 64: the lists of query q; an entry outside [0, L) is ignored
+ *             (-1 pads).  A list named twice in one row breaks the contract but not the call: the
+ *             duplicate rule of lthm_retrieve_merge_shards applies
+ *   x         NULL, or one list of excluded rows per query, in this catalogue's own (clustered) row
+ *             numbering, under the rules of lthm_retrieve_topk_excl
+ *   out_scores f32 [Q, k], out_ids int64 [Q, k], 1 <= k <= 128: the k first, under (score descending,
+ *             id ascending), of the rows that lie in a probed list and are not excluded, then
+ *             (-inf, 0).  A score is, bit for bit, the one lthm_retrieve_topk returns for the same
+ *             (query, item row), wherever the row sits
+ *   workspace lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X) bytes (X = 0: no exclusion), 16-byte
+ *             aligned; -1 for what the call refuses (Q, N or L outside 1..2^31-1, Q P >= 2^31, P
+ *             outside 1..64, k outside 1..128, X outside 0..1024)
+ * The call runs the query preparation, a plan (pairs counted and grouped by list on the device), one
+ * scan in which each block serves up to 64 (query, probe) pairs of one list, and the merge of every
+ * query's P lists, in sequence on `stream`, with no host synchronisation.  The scan's grid is
+ * lthm_retrieve_ivf_grid(Q, P, L) = Q P / 64 + min(L, Q P), an upper bound on the tiles there can be;
+ * the blocks past the true count exit at once.  The outputs are a pure function of the inputs. */
+int64_t lthm_retrieve_ivf_grid(int64_t Q, int32_t P, int64_t L);
+int64_t lthm_retrieve_ivf_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X);
+int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off, int64_t L,
+                           const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q, const int32_t* probes,
+                           int32_t P, int32_t k, const lthm_retrieve_excl* x, float* out_scores, int64_t* out_ids,
+                           void* workspace, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -12,7 +12,8 @@
 // high word, ~row in the low word, so that "a precedes b" in the total order is key_a > key_b
 // and the key 0 is free to mean "empty".  Selection never depends on the order in which the
 // LDS atomics hand out slots (a prune writes each key at its rank), so the result is a pure
-// function of the inputs.  No global atomics anywhere.
+// function of the inputs.  No global atomics in any of these kernels (the plan of the clustered
+// scan at the end of this file counts its pairs with two integer atomics that no output depends on).
 //
 // Exclusion (lthm_retrieve_topk_excl): every query may name up to RT_XMAX catalogue rows that
 // are scored as -inf, so that they take none of the k slots and never count in the rank.
@@ -1907,4 +1908,413 @@ extern "C" int lthm_retrieve_merge_shards(const float* scores, const int64_t* id
                        out_scores, out_ids, out_rank);
   LTHM_CHECK_LAUNCH();
   return 0;
+}
+
+// ---------------------------------------------------------------- clustered catalogues (IVF)
+// lthm_retrieve_ivf_topk: the catalogue's rows are grouped into L lists (rows [list_off[c],
+// list_off[c + 1]), ids ascending inside a list, row_ids[row] the item id) and query q scans only
+// the lists its probe row names, probes[q, 0..P).  A (query, probe slot) pair p = q P + s with a
+// valid list is one MFMA column of one block:
+//   retr_ivf_count_k    cnt[c] = the pairs that probe list c; a pair without a list (an entry
+//                       outside [0, L)) gets its empty k-list written here;
+//   retr_ivf_offsets_k  one block: the exclusive prefix sums of cnt (pair_off) and of
+//                       ceil(cnt / 64) (tile_off); tile_off[L] is the true tile count;
+//   retr_ivf_fill_k     the pair indices grouped by list (pair_idx), and for every tile of up to
+//                       64 pairs of one list the table entry (list, first pair slot, pairs);
+//   retr_ivf_topk_k     block b < tile_off[L] scans the whole list of its tile for the tile's
+//                       pairs: retr_topk_k's tile loop (the 64 x 64 score tile, the queries as B
+//                       fragments, the LDS-DMA images, the keys and the CAP / LIM invariant)
+//                       without a slab cut, a target count or a merge; it writes every pair's
+//                       sorted k-list as (score, id) into scores / ids [P, Q, k], the layout
+//                       retr_shard_merge_k reads, empty slots as (-inf, 0).
+// Nothing comes back to the host in between: the scan's grid is the bound Q P / 64 + min(L, Q P)
+// on the tile count and a block past the count exits before it touches LDS or the DMA.  The two
+// integer atomics of the plan (cnt, fill) decide only which column of which block serves a pair.
+// A column's state (B fragments, threshold, candidates, list cursor) is its own and a prune
+// writes each key at its rank, so every pair's list, and with it the merged result, is a pure
+// function of the inputs.  A list named twice in one probe row is two pairs with two outputs.
+namespace lthm {
+namespace {
+
+struct RetrIvfShared {
+  unsigned char img[2][RT_IT * 256];
+  u64 cand[RT_QT][RT_CAP];
+  float tau[RT_QT];  // current k-th best score of the pair (-inf until k candidates are held)
+  int cnt[RT_QT];    // candidates held
+  int pair[RT_QT];   // the pair of every column
+  int flag[3];       // flag[i % 3]: tile i pushed some pair past RT_LIM
+};
+static_assert(sizeof(RetrIvfShared) <= 160 * 1024, "LDS budget");
+
+struct RetrIvfArgs {
+  const bf16_t* items;      // [N, 128], list-major
+  const bf16_t* qn;         // [Q, 128] queries as the MFMA reads them
+  const int64_t* row_ids;   // [N]
+  const int64_t* list_off;  // [L + 1]
+  const int* tile_off;      // [L + 1]; tile_off[L]: the tiles there are
+  const int4* tab;          // per tile: list, first slot in pair_idx, pairs (1..64)
+  const int* pair_idx;      // [Q P] pairs grouped by list
+  const int* xs;            // EXCL: [Q, xstride] ascending rows; ignored entries and the last one are INT_MAX
+  int xstride;              // X + 1
+  float* scores;            // [P, Q, k]
+  int64_t* ids;             // [P, Q, k]
+  int64_t Q, N;
+  int L, P, k;
+};
+
+__global__ __launch_bounds__(256) void retr_ivf_count_k(const int* __restrict__ probes, int64_t NP, int L, int P,
+                                                        int64_t Q, int k, int* __restrict__ cnt,
+                                                        float* __restrict__ scores, int64_t* __restrict__ ids) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= NP) return;
+  const int c = probes[p];
+  if (c >= 0 && c < L) {
+    atomicAdd(&cnt[c], 1);
+    return;
+  }
+  const int64_t q = p / P, s = p - q * P;
+  const int64_t o = (s * Q + q) * k;
+  for (int i = 0; i < k; ++i) {
+    scores[o + i] = -INFINITY;
+    ids[o + i] = 0;
+  }
+}
+
+// One block: thread t owns lists [t per, (t + 1) per)
+__global__ __launch_bounds__(256) void retr_ivf_offsets_k(const int* __restrict__ cnt, int L, int* __restrict__ pair_off,
+                                                          int* __restrict__ tile_off) {
+  __shared__ int sp[256], st[256];
+  const int tid = threadIdx.x;
+  const int per = (L + 255) / 256;
+  const int64_t lo64 = (int64_t)tid * per;
+  const int lo = lo64 < L ? (int)lo64 : L, hi = lo64 + per < L ? (int)(lo64 + per) : L;
+  int np = 0, nt = 0;
+  for (int c = lo; c < hi; ++c) {
+    const int n = cnt[c];
+    np += n;
+    nt += (n + RT_QT - 1) / RT_QT;
+  }
+  sp[tid] = np;
+  st[tid] = nt;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {
+    const int x = tid >= o ? sp[tid - o] : 0, y = tid >= o ? st[tid - o] : 0;
+    __syncthreads();
+    sp[tid] += x;
+    st[tid] += y;
+    __syncthreads();
+  }
+  int pa = sp[tid] - np, ta = st[tid] - nt;
+  for (int c = lo; c < hi; ++c) {
+    const int n = cnt[c];
+    pair_off[c] = pa;
+    tile_off[c] = ta;
+    pa += n;
+    ta += (n + RT_QT - 1) / RT_QT;
+  }
+  if (tid == 255) {
+    pair_off[L] = sp[255];
+    tile_off[L] = st[255];
+  }
+}
+
+// pos < cnt[c] (the same pairs were counted), so every index is below Q P and every tile below
+// tile_off[L]
+__global__ __launch_bounds__(256) void retr_ivf_fill_k(const int* __restrict__ probes, int64_t NP, int L,
+                                                       const int* __restrict__ cnt, const int* __restrict__ pair_off,
+                                                       const int* __restrict__ tile_off, int* __restrict__ fill,
+                                                       int* __restrict__ pair_idx, int4* __restrict__ tab) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= NP) return;
+  const int c = probes[p];
+  if (c < 0 || c >= L) return;
+  const int pos = atomicAdd(&fill[c], 1);
+  const int base = pair_off[c];
+  pair_idx[base + pos] = (int)p;
+  if ((pos & (RT_QT - 1)) == 0) {
+    const int n = cnt[c] - pos;
+    tab[tile_off[c] + pos / RT_QT] = make_int4(c, base + pos, n < RT_QT ? n : RT_QT, 0);
+  }
+}
+
+// Wave w: columns 32 (w & 1) + (lane & 31) of the tile (one pair each, so every per-pair value is a
+// per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3), as in retr_topk_k.
+// EXCL: the lane walks its query's sorted list of excluded rows (the clustered numbering) from the
+// first entry >= row_lo; entries of other lists lie outside [row_lo, row_hi) and the walk, which
+// stops at the tile's end <= row_hi, never applies them.
+template <bool EXCL>
+__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
+  const int blk = blockIdx.x;
+  if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
+  __shared__ __attribute__((aligned(16))) RetrIvfShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int4 tt = a.tab[blk];
+  const int c = tt.x, pbase = tt.y, np = tt.z;
+  // the caller's offsets, kept inside the catalogue whatever they hold
+  int64_t row_lo = a.list_off[c], row_hi = a.list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > a.N ? a.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const bool live = ql < np;
+  const int64_t q = live ? a.pair_idx[pbase + ql] / a.P : 0;
+
+  if (tid < RT_QT) {
+    // a column without a pair never passes the filter
+    sh.tau[tid] = tid < np ? -INFINITY : INFINITY;
+    sh.cnt[tid] = 0;
+    sh.pair[tid] = tid < np ? a.pair_idx[pbase + tid] : 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  {
+    const bf16_t* rp = a.qn + q * RT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live) v = *reinterpret_cast<const u32x4*>(rp + 16 * s + 8 * hh);
+      qf[s] = __builtin_bit_cast(bf16x8v, v);
+    }
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // a column without a pair excludes nothing and reads nothing
+  if constexpr (EXCL) {
+    if (live) {
+      const int* xl = a.xs + q * a.xstride;
+      int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (xl[mid] < row_lo) lo = mid + 1;
+        else hi = mid;
+      }
+      xp = xl + lo;
+      nx = *xp;
+    }
+  }
+  int roff[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
+
+  // retr_topk_k's staging: wave w brings rows 16 w .. 16 w + 15 of an image with four DMAs of
+  // 4 rows x 256 B; rows at or past row_hi come from the zero row
+  const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 4 * j;
+      const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 15));
+      glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+  };
+  retire_loads();
+  if (ntile > 0) stage(0);
+  for (int i = 0; i < ntile; ++i) {
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;  // last read in tile i - 1, next set in tile i + 1
+    if (sh.flag[(i + 2) % 3]) {              // tile i - 1 pushed a pair past the limit
+      for (int pq = w; pq < RT_QT; pq += 4) {
+        const int n = sh.cnt[pq];
+        if (n > RT_LIM) {
+          const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], n, a.k, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.cand[pq][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const bf16x8v af = frag_at(img + roff[s]);
+      acc = mfma32(af, qf[s], acc);
+    }
+    // first catalogue row of this lane's elements: element v is row rb + 8 (v >> 2) + (v & 3)
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {  // partial tile: the rows past the list never pass
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if constexpr (EXCL) {
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (slot < RT_CAP) sh.cand[ql][slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RT_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // every pair's k best of the list, sorted, as (score, id); empty slots are (-inf, 0)
+  for (int pq = w; pq < np; pq += 4) {
+    const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], sh.cnt[pq], a.k, lane);
+    const int pr = sh.pair[pq];
+    const int64_t pq_q = pr / a.P, pq_s = pr - pq_q * a.P;
+    const int64_t o = (pq_s * a.Q + pq_q) * a.k;
+    for (int idx = lane; idx < a.k; idx += 64) {
+      const bool has = idx < m;
+      const u64 key = has ? sh.cand[pq][idx] : 0ull;
+      a.scores[o + idx] = has ? retr_key_score(key) : -INFINITY;
+      a.ids[o + idx] = has ? a.row_ids[retr_key_row(key)] : 0;
+    }
+  }
+}
+
+// the workspace of one call, in bytes from its start
+struct RetrIvfWs {
+  int64_t qn, cnt, off, pidx, tab, xs, scores, ids, total, grid;
+};
+
+// the scan's grid: sum_c ceil(n_c / 64) <= floor(sum_c n_c / 64) + #{c : n_c > 0} with sum_c n_c <= Q P
+inline int64_t retr_ivf_grid(int64_t Q, int64_t P, int64_t L) {
+  const int64_t np = Q * P;
+  return np / RT_QT + (L < np ? L : np);
+}
+
+bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o) {
+  if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || L < 1 || L >= (1ll << 31)) return false;
+  if (P < 1 || P > RS_SMAX || k < 1 || k > RT_KMAX || X < 0 || X > RT_XMAX) return false;
+  if (Q * P >= (1ll << 31)) return false;
+  o->grid = retr_ivf_grid(Q, P, L);
+  if (o->grid >= (1ll << 31)) return false;
+  int64_t at = 0;
+  o->qn = at, at += up256(Q * RT_D * 2);
+  o->cnt = at, at += up256(2 * L * 4);        // cnt, fill
+  o->off = at, at += up256(2 * (L + 1) * 4);  // pair_off, tile_off
+  o->pidx = at, at += up256(Q * P * 4);
+  o->tab = at, at += up256(o->grid * 16);
+  o->xs = at, at += X ? up256(Q * (X + 1) * 4) : 0;
+  o->scores = at, at += up256(P * Q * k * 4);
+  o->ids = at, at += up256(P * Q * k * 8);
+  o->total = at;
+  return true;
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int64_t lthm_retrieve_ivf_grid(int64_t Q, int32_t P, int64_t L) {
+  if (Q < 1 || P < 1 || L < 1 || Q >= (1ll << 31) || L >= (1ll << 31)) return -1;
+  return retr_ivf_grid(Q, P, L);
+}
+
+extern "C" int64_t lthm_retrieve_ivf_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X) {
+  RetrIvfWs w;
+  return retr_ivf_ws(Q, N, L, P, k, X, &w) ? w.total : -1;
+}
+
+extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
+                                      int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
+                                      const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
+                                      float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
+                                      void* stream) {
+  LTHM_REQUIRE(items && row_ids && list_off && q && probes && out_scores && out_ids && workspace);
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)row_ids & 7) == 0 && ((uintptr_t)list_off & 7) == 0 && ((uintptr_t)probes & 3) == 0);
+  LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  RetrIvfWs wo;
+  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo) && ws_bytes >= wo.total);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  bf16_t* qn = (bf16_t*)(ws + wo.qn);
+  int* cnt = (int*)(ws + wo.cnt);
+  int* fill = cnt + L;
+  int* pair_off = (int*)(ws + wo.off);
+  int* tile_off = pair_off + (L + 1);
+  int* pair_idx = (int*)(ws + wo.pidx);
+  int4* tab = (int4*)(ws + wo.tab);
+  float* lscores = (float*)(ws + wo.scores);
+  int64_t* lids = (int64_t*)(ws + wo.ids);
+  const bf16_t* it = (const bf16_t*)items;
+  const int64_t NP = Q * P;
+  // 1: the queries, by the arithmetic of every other entry
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  if (q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn, it, N,
+                       (const int*)nullptr, (float*)nullptr, -INFINITY);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn, it, N,
+                       (const int*)nullptr, (float*)nullptr, -INFINITY);
+  LTHM_CHECK_LAUNCH();
+  // 2: the plan
+  {
+    const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(2 * L) * 4, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const unsigned ngrid = (unsigned)((NP + 255) / 256);
+  hipLaunchKernelGGL(retr_ivf_count_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, (int)P, Q, (int)k, cnt, lscores,
+                     lids);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_offsets_k, dim3(1), dim3(256), 0, s, cnt, (int)L, pair_off, tile_off);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_fill_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off, fill,
+                     pair_idx, tab);
+  LTHM_CHECK_LAUNCH();
+  // 3: the scan
+  RetrIvfArgs a;
+  a.items = it;
+  a.qn = qn;
+  a.row_ids = row_ids;
+  a.list_off = list_off;
+  a.tile_off = tile_off;
+  a.tab = tab;
+  a.pair_idx = pair_idx;
+  a.xs = nullptr;
+  a.xstride = 0;
+  a.scores = lscores;
+  a.ids = lids;
+  a.Q = Q;
+  a.N = N;
+  a.L = (int)L;
+  a.P = P;
+  a.k = k;
+  if (x) {
+    int* xs = (int*)(ws + wo.xs);
+    const int X = (int)x->X;
+    int XP = 1;
+    while (XP < X) XP <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)Q), dim3(256), 0, s, x->rows, X, XP, N, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+    hipLaunchKernelGGL(retr_ivf_topk_k<true>, dim3((unsigned)wo.grid), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(retr_ivf_topk_k<false>, dim3((unsigned)wo.grid), dim3(256), 0, s, a);
+  }
+  LTHM_CHECK_LAUNCH();
+  // 4: the merge of every query's P lists
+  return lthm_retrieve_merge_shards(lscores, lids, nullptr, P, Q, k, out_scores, out_ids, nullptr, stream);
 }

@@ -24,6 +24,7 @@
 //   lthm::retrieve_topk_bias  any of the above on the score fma(weight[q], bias[row], dot)
 //   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
 //   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
+//   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -737,6 +738,65 @@ std::tuple<Tensor, Tensor, Tensor> retrieve_merge_shards_cuda(const Tensor& scor
   return {out_scores, out_ids, out_rank};
 }
 
+// the scan of a clustered catalogue: items bf16 [N, 128] list-major, row_ids int64 [N], list_off int64
+// [L + 1], probes int32 [Q, P] (P <= 64), exclude_rows int32 [Q, X] in the clustered row numbering or
+// None; (scores f32 [Q, k], ids int64 [Q, k])
+std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q_, const Tensor& items_, const Tensor& row_ids_,
+                                                  const Tensor& list_off_, const Tensor& probes_, int64_t k,
+                                                  bool normalize_q, const c10::optional<Tensor>& exclude_rows) {
+  on_gpu(q_, "q");
+  on_gpu(items_, "items");
+  on_gpu(row_ids_, "row_ids");
+  on_gpu(list_off_, "list_off");
+  on_gpu(probes_, "probes");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
+              "items must be a bf16 [N, 128] catalogue");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128, "q must be [Q, 128]");
+  TORCH_CHECK(k >= 1 && k <= 128, "k must be in 1..128, got ", k);
+  TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_ivf_topk takes a non-empty catalogue and query set");
+  auto q = q_.contiguous(), items = items_.contiguous();
+  const int64_t Q = q.size(0), N = items.size(0);
+  TORCH_CHECK(row_ids_.scalar_type() == at::kLong && row_ids_.dim() == 1 && row_ids_.size(0) == N,
+              "row_ids must be int64 [N], one id per catalogue row");
+  TORCH_CHECK(list_off_.scalar_type() == at::kLong && list_off_.dim() == 1 && list_off_.size(0) >= 2,
+              "list_off must be int64 [L + 1], L >= 1");
+  TORCH_CHECK(probes_.scalar_type() == at::kInt && probes_.dim() == 2 && probes_.size(0) == Q, "probes must be int32 [Q, P]");
+  TORCH_CHECK(probes_.size(1) >= 1 && probes_.size(1) <= 64, "retrieve_ivf_topk takes 1..64 probes per query, got P=",
+              probes_.size(1));
+  TORCH_CHECK(row_ids_.device() == items.device() && list_off_.device() == items.device() &&
+                  probes_.device() == items.device() && q.device() == items.device(),
+              "q, row_ids, list_off and probes must be on the catalogue's device");
+  auto row_ids = row_ids_.contiguous(), list_off = list_off_.contiguous(), probes = probes_.contiguous();
+  const int64_t L = list_off.size(0) - 1, P = probes.size(1);
+  Tensor xr;
+  const bool excl = exclude_rows.has_value() && exclude_rows->defined();
+  if (excl) {
+    on_gpu(*exclude_rows, "exclude_rows");
+    TORCH_CHECK(exclude_rows->scalar_type() == at::kInt && exclude_rows->dim() == 2 && exclude_rows->size(0) == Q,
+                "exclude_rows must be int32 [Q, X]");
+    TORCH_CHECK(exclude_rows->size(1) >= 1 && exclude_rows->size(1) <= 1024,
+                "exclude_rows takes 1..1024 rows per query, got ", exclude_rows->size(1));
+    TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
+    xr = exclude_rows->contiguous();
+  }
+  const int64_t need = lthm_retrieve_ivf_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0);
+  TORCH_CHECK(need >= 0, "retrieve_ivf_topk: unsupported sizes Q=", Q, " N=", N, " L=", L, " P=", P);
+  auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
+  auto ids = at::empty({Q, k}, q.options().dtype(at::kLong));
+  auto ws = at::empty({need}, q.options().dtype(at::kByte));
+  lthm_retrieve_excl x = {};
+  if (excl) {
+    x.rows = xr.data_ptr<int32_t>();
+    x.X = xr.size(1);
+  }
+  hip_ok(lthm_retrieve_ivf_topk(items.data_ptr(), N, row_ids.data_ptr<int64_t>(), list_off.data_ptr<int64_t>(), L,
+                                q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q, probes.data_ptr<int32_t>(), (int32_t)P,
+                                (int32_t)k, excl ? &x : nullptr, scores.data_ptr<float>(), ids.data_ptr<int64_t>(),
+                                ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_ivf_topk");
+  return std::make_tuple(scores, ids);
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -776,6 +836,9 @@ TORCH_LIBRARY(lthm, m) {
       "Tensor? tag_filter, Tensor? after_scores, Tensor? after_rows, Tensor? bias, Tensor? bias_weight=None) -> "
       "(Tensor scores, Tensor rows)");
   m.def("retrieve_merge_shards(Tensor scores, Tensor ids, Tensor? ranks=None) -> (Tensor scores, Tensor ids, Tensor rank)");
+  m.def(
+      "retrieve_ivf_topk(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
+      "bool normalize_q, Tensor? exclude_rows=None) -> (Tensor scores, Tensor ids)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -793,6 +856,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_bias", &retrieve_topk_bias_cuda);
   m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
   m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
+  m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -2166,3 +2166,75 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
              ctypes.addressof(g), stream(), _key="retr_topk_group_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH,
              _unit="flop", _bytes=nbytes)
     return scores, rows, rank, tscore
+
+
+RETRIEVE_MAX_PROBE = RETRIEVE_MAX_SHARDS  # the most lists one query probes: the merge's RS_SMAX
+
+
+def retrieve_ivf_grid(Q: int, P: int, L: int) -> int:
+    """The grid of the clustered scan (lthm_retrieve_ivf_grid): Q P // 64 + min(L, Q P), an upper bound
+    on sum_c ceil(n_c / 64) over the lists' pair counts n_c, whatever they are (sum_c n_c <= Q P)."""
+    n = int(load().lthm_retrieve_ivf_grid(int(Q), int(P), int(L)))
+    _check(n >= 0, f"retrieve_ivf_grid takes Q, P, L >= 1 (got Q={Q} P={P} L={L})")
+    return n
+
+
+def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_q: bool = True, exclude_rows=None):
+    """The k best items per query among the lists the query probes (lthm_retrieve_ivf_topk,
+    csrc/retrieve.hip retr_ivf_topk_k): the scan of a clustered catalogue.
+
+    q f32 / bf16 [Q, 128]; items bf16 [N, 128], list-major (list c is rows list_off[c] ..
+    list_off[c + 1], ids ascending inside a list); row_ids int64 [N], the item id of every row;
+    list_off int64 [L + 1]; probes int32 [Q, P], 1 <= P <= 64, the lists of every query, entries
+    outside [0, L) ignored (-1 pads); exclude_rows int32 [Q, X] or None, rows in this catalogue's own
+    numbering, under retrieve_topk's rules.  Returns (scores f32 [Q, k], ids int64 [Q, k]), 1 <= k <=
+    128: the first k under (score descending, id ascending) of the probed, non-excluded rows, then
+    (-inf, 0); every score has the bits retrieve_topk returns for the same (query, row).  One call:
+    the query preparation, the plan, the scan and the merge run on the device without a host sync."""
+    import ctypes
+    from ._lib import STRUCTS
+    who = "retrieve_ivf_topk"
+    require_gpu(q, items, row_ids, list_off, probes, exclude_rows)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    Q, N, k = q.shape[0], items.shape[0], int(k)
+    _check(1 <= k <= RETRIEVE_MAX_K, f"{who} takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    _check(row_ids.dtype == torch.int64 and tuple(row_ids.shape) == (N,),
+           f"row_ids must be int64 [N], one id per catalogue row (got {row_ids.dtype} {tuple(row_ids.shape)}, N={N})")
+    _check(list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.shape[0] >= 2,
+           f"list_off must be int64 [L + 1], L >= 1 (got {list_off.dtype} {tuple(list_off.shape)})")
+    L = list_off.shape[0] - 1
+    _check(probes.dtype == torch.int32 and probes.dim() == 2 and probes.shape[0] == Q,
+           f"probes must be int32 [Q, P] (got {probes.dtype} {tuple(probes.shape)}, Q={Q})")
+    P = probes.shape[1]
+    _check(1 <= P <= RETRIEVE_MAX_PROBE, f"{who} takes 1..{RETRIEVE_MAX_PROBE} probes per query (got P={P})")
+    _check(row_ids.is_contiguous() and list_off.is_contiguous() and probes.is_contiguous() and items.is_contiguous(),
+           "items, row_ids, list_off and probes must be contiguous")
+    _check(row_ids.device == items.device and list_off.device == items.device,
+           "row_ids and list_off must be on the catalogue's device")
+    _check(probes.device == q.device and q.device == items.device, "q and probes must be on the catalogue's device")
+    X = 0
+    x = None
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == Q,
+               f"exclude_rows must be int32 [Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, Q={Q})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
+        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
+        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
+    need = load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X)
+    _check(need >= 0, f"{who}: no workspace size for Q={Q} N={N} L={L} P={P} k={k} X={X} (Q P must stay below 2^31)")
+    q = q.contiguous()
+    dev = q.device
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("lthm_retrieve_ivf_topk", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q), int(bool(normalize_q)),
+         Q, ptr(probes), P, k, ctypes.addressof(x) if x is not None else None, ptr(scores), ptr(ids), ptr(ws), need,
+         stream(), _key="retr_ivf_topk_k", _work=float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k
+                                                       + 4.0 * Q * (P + X)), _unit="byte")
+    return scores, ids

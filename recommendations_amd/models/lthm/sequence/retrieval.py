@@ -27,6 +27,11 @@ table of C3: ``build_catalogue(..., shard=(rank, world))``).  Its ``topk`` retur
 one catalogue over the union returns: every shard is scanned on its own against the target's score
 (``K.retrieve_target_score``, ``K.retrieve_topk(target_scores=)``) and the lists are merged on the
 device (``K.retrieve_merge_shards``).
+
+Clusters: a ``ClusteredItemCatalogue`` (``ItemCatalogue.cluster`` or ``from_assignment``) holds the
+rows grouped into lists around centroids, and its ``topk`` scans only the ``nprobe`` lists nearest
+to each query (``K.retrieve_ivf_topk``): the exact top-k of the probed lists, with the flat scan's
+score bits, and with ``nprobe`` = L the flat scan's result.
 """
 from __future__ import annotations
 
@@ -298,6 +303,253 @@ class ItemCatalogue:
             tags = f.get_tensor("tags") if "tags" in f.keys() else None
             bias = f.get_tensor("bias") if "bias" in f.keys() else None
         cat = cls(ids, emb, tags, bias)
+        return cat.to(device) if device is not None else cat
+
+    @torch.no_grad()
+    def cluster(self, nlist: int, iters: int = 10, seed: int = 0, sample: Optional[int] = None) -> "ClusteredItemCatalogue":
+        """This catalogue as ``nlist`` lists around centroids found by spherical k-means, on the
+        catalogue's device (the assignments are ``K.retrieve_topk`` calls).  The centroids start as
+        ``nlist`` rows picked by a permutation seeded with ``seed``; with ``sample`` the iterations
+        see only the first ``sample`` rows of that permutation (``nlist <= sample <= N``).  An
+        iteration assigns every row to its best centroid (``K.retrieve_topk`` with k = 1, the rows as
+        queries: ties go to the lower list) and replaces every centroid by the normalised f32 sum of
+        its rows, taken in (list, id) order by a segmented sum, so two builds give the same bits; a
+        list left without rows keeps its centroid.  A last assignment of all rows against the stored
+        centroids fixes the lists."""
+        N = len(self)
+        nlist, iters = int(nlist), int(iters)
+        if not 1 <= nlist <= N:
+            raise ValueError(f"cluster takes 1..N lists (got nlist={nlist}, N={N})")
+        if iters < 0:
+            raise ValueError(f"cluster takes iters >= 0 (got {iters})")
+        if sample is not None and not nlist <= int(sample) <= N:
+            raise ValueError(f"cluster takes nlist <= sample <= N (got sample={sample}, nlist={nlist}, N={N})")
+        dev = self.emb.device
+        perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))  # on the host: one order everywhere
+        centroids = self.emb[perm[:nlist].to(dev)].contiguous()
+        train = self.emb
+        if sample is not None and int(sample) < N:
+            train = self.emb[torch.sort(perm[:int(sample)])[0].to(dev)].contiguous()  # id-ascending, as the catalogue is
+        for _ in range(iters):
+            assign = K.retrieve_topk(train, centroids, 1, normalize_q=False)[1][:, 0].long()
+            order = torch.argsort(assign, stable=True)  # (list, id)
+            counts = torch.bincount(assign, minlength=nlist)
+            sums = torch.segment_reduce(train[order].float(), "sum", lengths=counts, axis=0, unsafe=True)
+            norm = sums.norm(dim=1, keepdim=True)
+            keep = (counts == 0)[:, None] | (norm == 0)
+            centroids = torch.where(keep, centroids, (sums / norm.clamp_min(1e-12)).to(torch.bfloat16)).contiguous()
+        assign = K.retrieve_topk(self.emb, centroids, 1, normalize_q=False)[1][:, 0].long()
+        return ClusteredItemCatalogue.from_assignment(self, centroids, assign)
+
+
+IVF_INDEX = "lthm-ivf-v1"
+
+
+class ClusteredItemCatalogue:
+    """An ``ItemCatalogue`` whose rows are grouped into L lists around centroids (an inverted-file
+    index), so that a query scans the ``nprobe`` lists nearest to it instead of every row
+    (``K.retrieve_ivf_topk``, csrc/retrieve.hip ``retr_ivf_topk_k``).
+
+    ``emb`` bf16 [N, 128], list-major: list c is rows ``list_off[c] .. list_off[c + 1]``, its ids
+    ascending; ``row_ids`` int64 [N], the id of every row (distinct, never 0); ``list_off`` int64
+    [L + 1]; ``centroids`` bf16 [L, 128]; ``tags`` / ``bias`` in the rows' order or None.  Tags and
+    bias are carried for ``to_flat()`` only: the clustered scan scores the plain dot and filters
+    nothing but ``exclude_ids``."""
+
+    def __init__(self, row_ids: torch.Tensor, emb: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
+                 tags: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+        if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or row_ids.shape[0] < 1:
+            raise ValueError(f"clustered row_ids must be int64 [N], N >= 1 (got {row_ids.dtype} {tuple(row_ids.shape)})")
+        N = row_ids.shape[0]
+        if emb.dtype != torch.bfloat16 or emb.dim() != 2 or tuple(emb.shape) != (N, WIDTH):
+            raise ValueError(f"clustered embeddings must be bf16 [N, {WIDTH}] (got {emb.dtype} {tuple(emb.shape)}, N={N})")
+        if centroids.dim() != 2 or centroids.shape[1] != WIDTH or centroids.shape[0] < 1:
+            raise ValueError(f"centroids must be [L, {WIDTH}], L >= 1 (got {tuple(centroids.shape)})")
+        if centroids.dtype != torch.bfloat16:
+            raise ValueError(f"centroids must be bf16, as the catalogue's rows are (got {centroids.dtype})")
+        L = centroids.shape[0]
+        if list_off.dtype != torch.int64 or tuple(list_off.shape) != (L + 1,):
+            raise ValueError(f"list_off must be int64 [L + 1] (got {list_off.dtype} {tuple(list_off.shape)}, L={L})")
+        dev = emb.device
+        if any(t.device != dev for t in (row_ids, list_off, centroids)):
+            raise ValueError("a clustered catalogue's tensors must live on one device")
+        if int(list_off[0]) != 0 or int(list_off[-1]) != N or bool((list_off[1:] < list_off[:-1]).any()):
+            raise ValueError("list_off must ascend from 0 to N")
+        ids, order = torch.sort(row_ids)
+        if bool((ids == 0).any()):
+            raise ValueError("catalogue ids must not hold 0, the pad id")
+        if N > 1 and bool((ids[1:] == ids[:-1]).any()):
+            raise ValueError("catalogue ids must be distinct")
+        if N > 1:
+            inside = torch.ones(N - 1, dtype=torch.bool, device=dev)  # row i and row i + 1 share a list
+            cut = list_off[1:-1]
+            cut = cut[(cut > 0) & (cut < N)]
+            inside[cut - 1] = False
+            if bool((inside & (row_ids[1:] <= row_ids[:-1])).any()):
+                raise ValueError("the ids of a list must ascend")
+        for t, name, dt in ((tags, "tags", torch.int32), (bias, "bias", torch.float32)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (N,) or t.device != dev):
+                raise ValueError(f"clustered {name} must be {dt} [N] on the catalogue's device "
+                                 f"(got {t.dtype} {tuple(t.shape)})")
+        self.row_ids = row_ids.contiguous()
+        self.emb = emb.contiguous()
+        self.list_off = list_off.contiguous()
+        self.centroids = centroids.contiguous()
+        self.tags = None if tags is None else tags.contiguous()
+        self.bias = None if bias is None else bias.contiguous()
+        self._ids = ids.contiguous()      # ascending
+        self._order = order.contiguous()  # the clustered row of every id of _ids
+        self._plain = None                # the flat catalogue without tags and bias, for recall
+
+    @classmethod
+    def from_assignment(cls, catalogue: ItemCatalogue, centroids: torch.Tensor, assign: torch.Tensor) -> "ClusteredItemCatalogue":
+        """From a flat catalogue, caller-given ``centroids`` bf16 [L, 128] and the list of every item,
+        ``assign`` integer [N] in [0, L).  Nothing ties an item to its nearest centroid here: the
+        contract of ``topk`` holds for any assignment."""
+        if not isinstance(catalogue, ItemCatalogue):
+            raise ValueError("from_assignment takes an ItemCatalogue")
+        if centroids.dim() != 2 or centroids.shape[1] != WIDTH or centroids.shape[0] < 1:
+            raise ValueError(f"centroids must be [L, {WIDTH}], L >= 1 (got {tuple(centroids.shape)})")
+        if centroids.dtype != torch.bfloat16:
+            raise ValueError(f"centroids must be bf16, as the catalogue's rows are (got {centroids.dtype})")
+        N, L = len(catalogue), centroids.shape[0]
+        if assign.is_floating_point() or assign.dtype == torch.bool or tuple(assign.shape) != (N,):
+            raise ValueError(f"assign must be an integer tensor [N], one list per item (got {assign.dtype} "
+                             f"{tuple(assign.shape)}, N={N})")
+        dev = catalogue.ids.device
+        assign = assign.to(device=dev, dtype=torch.int64)
+        if bool(((assign < 0) | (assign >= L)).any()):
+            bad = int(assign[(assign < 0) | (assign >= L)][0])
+            raise ValueError(f"assign must lie in 0..{L - 1}, the lists there are (got {bad})")
+        order = torch.argsort(assign, stable=True)  # list-major, id-ascending inside a list
+        counts = torch.bincount(assign, minlength=L)
+        list_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)])
+        return cls(catalogue.ids[order], catalogue.emb[order], list_off, centroids.to(dev),
+                   None if catalogue.tags is None else catalogue.tags[order],
+                   None if catalogue.bias is None else catalogue.bias[order])
+
+    def __len__(self) -> int:
+        return self.row_ids.shape[0]
+
+    @property
+    def nlist(self) -> int:
+        return self.centroids.shape[0]
+
+    @property
+    def has_tags(self) -> bool:
+        return self.tags is not None
+
+    @property
+    def has_bias(self) -> bool:
+        return self.bias is not None
+
+    def list_lengths(self) -> torch.Tensor:
+        """int64 [L]: the rows of every list."""
+        return self.list_off[1:] - self.list_off[:-1]
+
+    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
+        """The clustered row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
+        flat = ids.reshape(-1).to(self._ids.device)
+        at = torch.searchsorted(self._ids, flat).clamp_(max=len(self) - 1)
+        rows = torch.where(self._ids[at] == flat, self._order[at], torch.full_like(at, -1))
+        return rows.to(torch.int32).view(ids.shape)
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        return self.rows_of(ids) >= 0
+
+    def to_flat(self) -> ItemCatalogue:
+        """The id-sorted ``ItemCatalogue`` of the same items, bit for bit the one this was built from."""
+        o = self._order
+        return ItemCatalogue(self._ids, self.emb[o], None if self.tags is None else self.tags[o],
+                             None if self.bias is None else self.bias[o])
+
+    def to(self, device) -> "ClusteredItemCatalogue":
+        return ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
+                                      self.centroids.to(device), None if self.tags is None else self.tags.to(device),
+                                      None if self.bias is None else self.bias.to(device))
+
+    def _check_call(self, k: int, nprobe) -> Tuple[int, int]:
+        if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
+            raise ValueError(f"a clustered catalogue takes nprobe, an int (got {nprobe!r})")
+        if nprobe > K.RETRIEVE_MAX_PROBE:
+            raise ValueError(f"nprobe takes at most {K.RETRIEVE_MAX_PROBE} lists per query (got {nprobe})")
+        if nprobe > self.nlist:
+            raise ValueError(f"nprobe takes at most the {self.nlist} lists there are (got {nprobe})")
+        if nprobe < 1:
+            raise ValueError(f"nprobe takes at least one list (got {nprobe})")
+        k = int(k)
+        if not 1 <= k <= K.RETRIEVE_MAX_K:
+            raise ValueError(f"a clustered catalogue takes k in 1..{K.RETRIEVE_MAX_K} (got {k})")
+        return k, nprobe
+
+    def probe(self, q: torch.Tensor, nprobe: int, *, normalize_q: bool = True) -> torch.Tensor:
+        """int32 [Q, nprobe]: the lists of the nprobe best centroids per query, best first
+        (``K.retrieve_topk`` with the centroids as the catalogue: ties go to the lower list, and the
+        row at nprobe is a prefix of the row at nprobe + 1)."""
+        _, nprobe = self._check_call(1, nprobe)
+        return K.retrieve_topk(q, self.centroids, nprobe, normalize_q=normalize_q)[1]
+
+    def topk(self, q: torch.Tensor, k: int, *, nprobe: int, normalize_q: bool = True,
+             exclude_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores f32 [Q, k], ids int64 [Q, k]): per query the k first, under (score descending, id
+        ascending), of the items that lie in its ``nprobe`` nearest lists and are not among its
+        ``exclude_ids`` (int64 [Q, X], X <= 1024; unknown ids and 0 exclude nothing), then (-inf, 0).
+        Every score has the bits ``ItemCatalogue.topk`` returns for the same (query, item), and with
+        ``nprobe`` = L the whole result is that of ``to_flat().topk`` on a catalogue without a bias.
+        ``nprobe`` in 1..min(L, 64), ``k`` in 1..128, ``q`` [Q, 128]."""
+        k, nprobe = self._check_call(k, nprobe)
+        if q.dim() != 2:
+            raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        xr = None
+        if exclude_ids is not None:
+            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
+                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+            xr = self.rows_of(exclude_ids).contiguous()
+        probes = self.probe(q, nprobe, normalize_q=normalize_q)
+        return K.retrieve_ivf_topk(q, self.emb, self.row_ids, self.list_off, probes, k, normalize_q=normalize_q,
+                                   exclude_rows=xr)
+
+    def recall(self, q: torch.Tensor, k: int, nprobe: int) -> float:
+        """The mean over the queries of the fraction of the flat scan's top-k ids (plain dots, no
+        filter) that ``topk(q, k, nprobe=nprobe)`` returns.  Never decreases in ``nprobe``; 1.0 at L."""
+        if self._plain is None:
+            self._plain = ItemCatalogue(self._ids, self.emb[self._order])
+        want = self._plain.topk(q, k)[0]
+        got = self.topk(q, k, nprobe=nprobe)[1]
+        real = want != 0
+        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
+        return float((hit / real.sum(dim=1).clamp(min=1).double()).mean())
+
+    def save(self, path: str) -> None:
+        """The flat catalogue's file (``ItemCatalogue.load`` reads it as the id-sorted catalogue) with
+        ``row_ids``, ``list_off`` and ``centroids`` beside its tensors."""
+        from safetensors.torch import save_file
+        flat = self.to_flat()
+        tensors = {"ids": flat.ids.detach().cpu().contiguous(), "emb": flat.emb.detach().cpu().contiguous(),
+                   "row_ids": self.row_ids.detach().cpu().contiguous(), "list_off": self.list_off.detach().cpu().contiguous(),
+                   "centroids": self.centroids.detach().cpu().contiguous()}
+        if flat.tags is not None:
+            tensors["tags"] = flat.tags.detach().cpu().contiguous()
+        if flat.bias is not None:
+            tensors["bias"] = flat.bias.detach().cpu().contiguous()
+        save_file(tensors, path, metadata={"format": FORMAT, "index": IVF_INDEX})
+
+    @classmethod
+    def load(cls, path: str, *, device=None) -> "ClusteredItemCatalogue":
+        from safetensors import safe_open
+        with safe_open(path, framework="pt") as f:
+            meta = f.metadata() or {}
+            if meta.get("format") != FORMAT or meta.get("index") != IVF_INDEX:
+                raise ValueError(f"{path}: not a clustered item catalogue (metadata {json.dumps(meta)})")
+            flat = ItemCatalogue(f.get_tensor("ids"), f.get_tensor("emb"),
+                                 f.get_tensor("tags") if "tags" in f.keys() else None,
+                                 f.get_tensor("bias") if "bias" in f.keys() else None)
+            row_ids, list_off, centroids = f.get_tensor("row_ids"), f.get_tensor("list_off"), f.get_tensor("centroids")
+        rows = flat.rows_of(row_ids).long()
+        if row_ids.shape != flat.ids.shape or bool((rows < 0).any()):
+            raise ValueError(f"{path}: row_ids are not the catalogue's ids")
+        cat = cls(row_ids, flat.emb[rows], list_off, centroids, None if flat.tags is None else flat.tags[rows],
+                  None if flat.bias is None else flat.bias[rows])
         return cat.to(device) if device is not None else cat
 
 

@@ -348,7 +348,7 @@ class LTHMModelWrapper(BaseModelWrapper):
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
                  exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
                  tag_all=None, tag_any=None, tag_none=None, after=None,
-                 bias_weight=None) -> Dict[str, torch.Tensor]:
+                 bias_weight=None, nprobe: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -369,7 +369,24 @@ class LTHMModelWrapper(BaseModelWrapper):
         of the catalogue.  A catalogue that carries a bias scores item j as fma(w, bias[j], q . e_j);
         ``bias_weight`` is w, None for 1, a number or f32 [B], one weight per sequence (a
         catalogue without a bias refuses it).  The scores returned are the biased ones, so
-        ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again."""
+        ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again.
+        A ``ClusteredItemCatalogue`` takes ``nprobe`` (1..min(L, 64)): sequence b gets the k best
+        items (k <= 128) of the ``nprobe`` lists nearest to its query, by id ascending among equal
+        scores; ``exclude_history`` composes, every other argument above is refused by name."""
+        from .retrieval import ClusteredItemCatalogue
+        clustered = isinstance(catalogue, ClusteredItemCatalogue)
+        if clustered:
+            given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
+                     "bias_weight": bias_weight}
+            bad = [name for name, v in given.items() if v is not None]
+            if bad:
+                raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
+                                 "use catalogue.to_flat() for it")
+            if nprobe is None:
+                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
+            catalogue._check_call(k, nprobe)
+        elif nprobe is not None:
+            raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
         after_scores = after_ids = None
         if after is not None:
             if isinstance(after, dict):
@@ -410,6 +427,9 @@ class LTHMModelWrapper(BaseModelWrapper):
             after_ids = after_ids.to(q.device).contiguous()
         if isinstance(bias_weight, torch.Tensor):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
+        if clustered:
+            scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)
+            return {"item_ids": item_ids, "scores": scores}
         item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt,
                                                 after_scores=after_scores, after_ids=after_ids,
                                                 bias_weight=bias_weight)
@@ -439,6 +459,9 @@ class LTHMModelWrapper(BaseModelWrapper):
         included, is fma(bias_weight, bias[j], q . e_j): the hit position under the prior.  The
         keys then take the suffix ``_biased``, after ``_unseen`` / ``_tagged``.  Without it the
         metrics are those of the plain dot, whether or not the catalogue carries a bias."""
+        from .retrieval import ClusteredItemCatalogue
+        if isinstance(catalogue, ClusteredItemCatalogue):
+            raise ValueError("catalogue_metrics counts exact ranks, which take the flat scan: pass catalogue.to_flat()")
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])

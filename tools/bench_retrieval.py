@@ -4,6 +4,7 @@
     python tools/bench_retrieval.py [--shapes serving,evaluation] [--reps 20] [--n-items 2000000] [--exclude X]
                                     [--group G] [--tags P] [--after] [--deep K] [--bias]
     python tools/bench_retrieval.py --shards S [--shapes ...] [--reps 20] [--n-items 2000000] [--k 100]
+    python tools/bench_retrieval.py --ivf L [--shapes ...] [--reps 20] [--n-items 2000000] [--k 100]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -56,6 +57,18 @@ the merge kernel alone on the S lists of k rows and on S synthetic full lists of
   merge_floor_ms                   S Q k 12 B read + Q k 12 B written at 8.0 TB/s
   scans_ms                         the S shard scans alone (the sharded call without steps 1, 2, 4, 5)
   check_equal                      the sharded call's four outputs equal the unsharded call's, bit for bit
+--ivf L is a mode of its own too: N items drawn around 4,096 random unit centres (normalize(centre +
+0.7 noise / sqrt(128)); uniform random vectors have no lists worth probing), the queries drawn the same
+way, the catalogue clustered into L lists (ItemCatalogue.cluster, 5 iterations on a sample of 262,144
+rows; build_s is reported, not judged).  One JSON line per nprobe in {1, 8, 32, 64}:
+  flat_ms / ivf_ms            the flat call and ClusteredItemCatalogue.topk (probe scan + the clustered call),
+                              medians (min / max) of the same alternating loop, and ivf_over_flat (_hi: ivf max /
+                              flat min; faster only if < 1)
+  probe_ms, scan_call_ms, merge_ms   the probe scan alone (K.retrieve_topk over the centroids), the one C call
+                              behind it alone (prep, plan, list scan, merge) and the merge launch alone on P lists
+  plan_us, list_scan_us, merge_us    device time of the call's own kernels from one profiled call (the three plan
+                              kernels summed; null where the profiler gives nothing)
+  recall_at_k, rows_per_query the mean fraction of the flat top-k returned, the mean rows a query scans (of N)
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -413,6 +426,100 @@ def child_shards(name: str, N: int, k: int, reps: int, S: int) -> None:
     print(json.dumps(out), flush=True)
 
 
+def child_ivf(name: str, N: int, k: int, reps: int, L: int) -> None:
+    import time
+    import torch
+    from recommendations_amd import _lib
+    from recommendations_amd import kernels as K
+    from recommendations_amd.models.lthm.sequence.retrieval import ItemCatalogue
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    flat = ItemCatalogue(torch.arange(1, N + 1, dtype=torch.int64, device=dev) * 3, items)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    cl = flat.cluster(L, iters=5, seed=0, sample=min(N, 1 << 18))
+    torch.cuda.synchronize()
+    build_s = time.time() - t0
+    lens = cl.list_lengths()
+    print(json.dumps({"shape": name, "mode": "ivf", "drawn": f"{N} unit rows around {C} random unit centres, noise {sigma:.4f} "
+                      "per coordinate; queries drawn the same way", "L": L, "build_s": round(build_s, 2),
+                      "list_len_min": int(lens.min()), "list_len_median": int(lens.median()), "list_len_max": int(lens.max())}),
+          flush=True)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def flat_call():
+        return K.retrieve_topk(q_bf, items, k, normalize_q=False)
+
+    want = flat.topk(q_bf, k, normalize_q=False)[0]
+    for P in (1, 8, 32, 64):
+        if P > L:
+            continue
+        probes = cl.probe(q_bf, P, normalize_q=False)
+        m_s = torch.rand((P, Q, k), generator=g, device=dev).sort(dim=2, descending=True)[0].contiguous()
+        m_i = (torch.arange(P * k, device=dev).view(P, 1, k) + 1).expand(P, Q, k).contiguous()
+        arms = [("flat", flat_call, []),
+                ("ivf", lambda: cl.topk(q_bf, k, nprobe=P, normalize_q=False), []),
+                ("probe", lambda: K.retrieve_topk(q_bf, cl.centroids, P, normalize_q=False), []),
+                ("scan_call", lambda: K.retrieve_ivf_topk(q_bf, cl.emb, cl.row_ids, cl.list_off, probes, k, normalize_q=False), []),
+                ("merge", lambda: K.retrieve_merge_shards(m_s, m_i), [])]
+        for _ in range(2):
+            for _, fn, _ in arms:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for _, fn, times in arms:
+                times.append(timed(fn))
+        out = {"shape": name, "mode": "ivf", "Q": Q, "N": N, "k": k, "L": L, "nprobe": P, "reps": reps}
+        med = {}
+        for key, _, times in arms:
+            med[key] = statistics.median(times)
+            out.update({f"{key}_ms": round(med[key], 4), f"{key}_min_ms": round(min(times), 4), f"{key}_max_ms": round(max(times), 4)})
+        out["ivf_over_flat"] = round(med["ivf"] / med["flat"], 4)
+        out["ivf_over_flat_hi"] = round(max(arms[1][2]) / min(arms[0][2]), 4)
+        parts = {"plan_us": None, "list_scan_us": None, "merge_us": None}
+        try:  # device time of the call's own kernels, from one profiled call
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+                arms[3][1]()
+                torch.cuda.synchronize()
+            tot = {"plan_us": 0.0, "list_scan_us": 0.0, "merge_us": 0.0}
+            for ev in prof.events():
+                dt = float(ev.device_time if hasattr(ev, "device_time") else getattr(ev, "cuda_time", 0.0))
+                if "retr_ivf_topk_k" in ev.name:
+                    tot["list_scan_us"] += dt
+                elif "retr_ivf_" in ev.name:
+                    tot["plan_us"] += dt
+                elif "retr_shard_merge_k" in ev.name:
+                    tot["merge_us"] += dt
+            if tot["list_scan_us"] > 0:
+                parts = {key: round(v, 1) for key, v in tot.items()}
+        except Exception as e:  # the timings above stand without it
+            parts["profile_error"] = repr(e)[:200]
+        out.update(parts)
+        got = cl.topk(q_bf, k, nprobe=P, normalize_q=False)[1]
+        hit = (want[:, :, None] == got[:, None, :]).any(dim=2).float().sum(dim=1) / k
+        out[f"recall_at_{k}"] = round(float(hit.mean()), 4)
+        out["rows_per_query"] = round(float(lens[probes.long()].sum(dim=1).float().mean()), 1)
+        print(json.dumps(out), flush=True)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="serving,evaluation")
@@ -433,6 +540,8 @@ def main() -> int:
                     help="also time the call with a random f32 bias per row and weight 1 next to the plain call")
     ap.add_argument("--shards", type=int, default=0,
                     help="a mode of its own: the catalogue as S shards (1..64) on this device against the unsharded call")
+    ap.add_argument("--ivf", type=int, default=0,
+                    help="a mode of its own: the catalogue clustered into L lists, nprobe in {1, 8, 32, 64}, against the flat call")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -446,8 +555,13 @@ def main() -> int:
         raise SystemExit("--deep takes 0 (off) or a list length in 129..1024")
     if not 0 <= a.shards <= 64:
         raise SystemExit("--shards takes 0 (off) or 1..64 shards")
+    if a.ivf < 0 or (a.ivf and a.shards):
+        raise SystemExit("--ivf takes 0 (off) or a number of lists, and is a mode of its own")
     if a.child and a.shards:
         child_shards(a.child, a.n_items, a.k, a.reps, a.shards)
+        return 0
+    if a.child and a.ivf:
+        child_ivf(a.child, a.n_items, a.k, a.reps, a.ivf)
         return 0
     if a.child:
         child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags, a.after, a.deep, a.bias)
@@ -458,7 +572,8 @@ def main() -> int:
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
-                                 "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards)]
+                                 "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
+                                 "--ivf", str(a.ivf)]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else []),
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
