@@ -1059,6 +1059,40 @@ int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids,
                            const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q, const int32_t* probes,
                            int32_t P, int32_t k, const lthm_retrieve_excl* x, float* out_scores, int64_t* out_ids,
                            void* workspace, int64_t ws_bytes, void* stream);
+/* Diversified lists: greedy maximal-marginal-relevance (MMR) selection of k out of a pool of M
+ * candidates per query, with an optional cap on the selected items of one group.  The pool is a list
+ * any of the calls above returned (lthm_retrieve_topk_deep gives up to 1,024 rows in one scan).
+ *   items    bf16 [N, 128], 16-byte aligned: the flat catalogue the pool's rows index
+ *   rows     int32 [Q, M], scores f32 [Q, M], 1 <= M <= 1024, in any order.  An entry whose row is
+ *            outside [0, N), or whose score is -inf or NaN, is no candidate.  A query's rows are
+ *            distinct; a row named twice breaks the contract but not the call: it is two candidates,
+ *            the one at the lower pool position first where everything else ties
+ *   k        1..128
+ *   lam      f32 [Q], in [0, 1], or NULL: 1 for every query
+ *   groups   int32 [N] or NULL: one key per catalogue row, 0 = no group (never capped); cap >= 1 is
+ *            the most selected items of one non-zero key (ignored without groups)
+ * Per query, with S empty and d_i = 0 for every candidate, k times: among the candidates not yet
+ * selected whose key is 0 or shared by fewer than cap selected items, select the first under
+ * (m descending, row ascending), where
+ *   m_i = fmaf(-(1.0f - lam), d_i, lam * s_i)            (f32, exactly these operations)
+ * and the order is the one integer order of every list here (-0 equals +0); then d_i = fmaxf(d_i,
+ * g_ij) for every candidate, g_ij the f32 dot of the bf16 rows i and j (its summation order is not
+ * part of the contract: exact for integer-valued rows, within 128 2^-24 sum|a b| otherwise).  If no
+ * candidate is eligible the rest of the list is empty.
+ *   out_rows   int32 [Q, k]: the selected rows in selection order, then -1
+ *   out_scores f32 [Q, k]: the caller's score of the selected row, its bits unchanged, then -inf
+ *   out_obj    f32 [Q, k]: m at the moment of selection, then -inf
+ *   workspace  lthm_retrieve_diversify_ws_bytes(Q, M, k) bytes, 16-byte aligned: 0 for every size the
+ *              call takes (the candidates' rows live in registers; workspace may then be NULL), -1
+ *              for Q outside 1..2^31-1, M outside 1..1024, k outside 1..128
+ * With lam = 1 and no groups m_i = s_i, so the result is the first k of the pool under (score
+ * descending, row ascending) whatever order the pool came in.  One block per query, no atomics: every
+ * output is a pure function of the inputs.  Scores are finite or -inf / NaN (+inf is memory-safe, its
+ * objective may be NaN). */
+int64_t lthm_retrieve_diversify_ws_bytes(int64_t Q, int64_t M, int32_t k);
+int lthm_retrieve_diversify(const void* items, int64_t N, const int32_t* rows, const float* scores, int64_t Q, int32_t M,
+                            int32_t k, const float* lam, const int32_t* groups, int32_t cap, int32_t* out_rows,
+                            float* out_scores, float* out_obj, void* workspace, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

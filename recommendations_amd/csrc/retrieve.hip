@@ -2318,3 +2318,195 @@ extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_
   // 4: the merge of every query's P lists
   return lthm_retrieve_merge_shards(lscores, lids, nullptr, P, Q, k, out_scores, out_ids, nullptr, stream);
 }
+
+// ---------------------------------------------------------------- diversified lists (MMR, per-group caps)
+// lthm_retrieve_diversify: greedy maximal-marginal-relevance selection of k out of a pool of M <= 1024
+// candidates per query, with at most `cap` selected items per non-zero group key.  One block of 256
+// threads owns one query; thread t owns the candidates at pool positions t + 256 j, j < CPT = ceil(M /
+// 256) <= 4, and keeps for each its score s, its running maximum similarity d to the selected set, its
+// row, its group key and the key's count among the selected.
+// Where the rows live: the candidates' bf16 rows are gathered ONCE into registers, 64 packed dwords
+// per candidate (256 VGPRs at CPT = 4, inside the 512-register budget of one wave per SIMD that
+// __launch_bounds__(256) gives).  1,024 rows (256 KiB) do not fit the 160 KiB LDS, and a re-read from
+// global memory per step would put k dependent gathers on the critical path.  A step is then
+//   1: every thread's best eligible key (retr_key of the objective, so one integer order decides:
+//      objective descending, row ascending) with its pool position; the wave maximum by shuffles;
+//      one LDS exchange between the four waves (barrier 1);
+//   2: the winner's owner writes the outputs, the winner's row (256 B) and its group key to LDS
+//      (barrier 2);
+//   3: every thread reads the row back as 16 broadcast 16-byte LDS reads (all lanes one address: no
+//      bank conflict), takes CPT x 128 multiply-adds, d = fmaxf(d, dot), and bumps the count of its
+//      candidates that share the winner's non-zero key.
+// Two candidates with equal keys (a row named twice in one pool) are told apart by the pool position,
+// the lower first, so every output is a pure function of the inputs.  No atomics, no workspace.
+// Every gather is guarded by 0 <= row < N and every pool read by position < M; an output index is
+// below Q k.
+namespace lthm {
+namespace {
+
+constexpr int RV_MMAX = 1024;  // the largest pool (RD_KMAX)
+static_assert(RV_MMAX == RD_KMAX, "a deep list is a pool");
+
+struct RetrDivShared {
+  uint4 row[16];  // the winner's bf16 row
+  u64 wkey[4];    // every wave's best key
+  uint32_t wpos[4];  // and its pool position (RV_NONE: the wave has no eligible candidate)
+  int gkey;       // the winner's group key
+  // 16 and 0xffff0000, republished with every winner: the bf16 -> f32 unpacking of the candidates'
+  // rows takes its shift and its mask from here, so that it stays inside the step loop.  With
+  // literal constants the compiler hoists it and holds every row twice over, as 128 f32 (CPT = 4:
+  // 256 VGPRs + 256 AGPRs and 1,292 bytes of scratch per lane)
+  uint32_t shl, himask;
+};
+constexpr uint32_t RV_NONE = 0xffffffffu;
+
+
+template <int CPT>
+__global__ __launch_bounds__(256) void retr_diversify_k(const bf16_t* __restrict__ items, int64_t N,
+                                                        const int* __restrict__ rows, const float* __restrict__ scores,
+                                                        int M, int k, const float* __restrict__ lam,
+                                                        const int* __restrict__ groups, int cap, int* __restrict__ out_rows,
+                                                        float* __restrict__ out_scores, float* __restrict__ out_obj) {
+  __shared__ __attribute__((aligned(16))) RetrDivShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t q = blockIdx.x;
+  const float l = lam ? lam[q] : 1.f;
+  const float nl = -(1.0f - l);
+  uint4 r[CPT][16];
+  float s[CPT], d[CPT];
+  int row[CPT], gk[CPT], gc[CPT];
+  uint32_t avail = 0;  // bit j: candidate j is one and is not yet selected
+#pragma unroll
+  for (int j = 0; j < CPT; ++j) {
+    const int pos = tid + 256 * j;
+    int rw = -1;
+    float sc = -INFINITY;
+    if (pos < M) {
+      rw = rows[q * M + pos];
+      sc = scores[q * M + pos];
+    }
+    const bool ok = rw >= 0 && (int64_t)rw < N && sc == sc && sc != -INFINITY;
+    row[j] = rw;
+    s[j] = sc;
+    d[j] = 0.f;
+    gk[j] = ok && groups ? groups[rw] : 0;
+    gc[j] = 0;
+    avail |= ok ? 1u << j : 0u;
+    const uint4* src = (const uint4*)(items + (int64_t)(ok ? rw : 0) * RT_D);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) r[j][e] = ok ? src[e] : make_uint4(0, 0, 0, 0);
+  }
+  int t = 0;
+  for (; t < k; ++t) {
+    // 1: the best eligible candidate of the thread, the wave, the block
+    u64 bk = 0;
+    uint32_t bp = RV_NONE;
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      const bool el = ((avail >> j) & 1u) && (gk[j] == 0 || gc[j] < cap);
+      const u64 key = retr_key(fmaf(nl, d[j], l * s[j]), row[j]);
+      if (el && key > bk) bk = key, bp = (uint32_t)(tid + 256 * j);  // ascending positions: a tie keeps the lower
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const u64 ok = __shfl_xor(bk, o, 64);
+      const uint32_t op = __shfl_xor(bp, o, 64);
+      if (ok > bk || (ok == bk && op < bp)) bk = ok, bp = op;
+    }
+    if (lane == 0) sh.wkey[w] = bk, sh.wpos[w] = bp;
+    __syncthreads();
+    bk = sh.wkey[0], bp = sh.wpos[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+      const u64 ok = sh.wkey[i];
+      const uint32_t op = sh.wpos[i];
+      if (ok > bk || (ok == bk && op < bp)) bk = ok, bp = op;
+    }
+    if (bp == RV_NONE) break;  // nothing eligible: the same in every thread
+    // 2: the winner's owner publishes it
+    if ((int)(bp & 255u) == tid) {
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) {
+        if ((int)(bp >> 8) == j) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sh.row[e] = r[j][e];
+          sh.gkey = gk[j];
+          sh.shl = 16u, sh.himask = 0xffff0000u;
+          out_rows[q * k + t] = row[j];
+          out_scores[q * k + t] = s[j];
+          out_obj[q * k + t] = fmaf(nl, d[j], l * s[j]);
+          avail &= ~(1u << j);
+        }
+      }
+    }
+    __syncthreads();
+    // 3: the similarity of every own candidate to the winner
+    const int g = sh.gkey;
+    const uint32_t shl = sh.shl, him = sh.himask;
+    float acc[CPT];
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const uint4 wv = sh.row[e];
+      const uint32_t wu[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) {
+        const uint32_t cu[4] = {r[j][e].x, r[j][e].y, r[j][e].z, r[j][e].w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          acc[j] = fmaf(__uint_as_float(cu[c] << shl), __uint_as_float(wu[c] << 16), acc[j]);
+          acc[j] = fmaf(__uint_as_float(cu[c] & him), __uint_as_float(wu[c] & 0xffff0000u), acc[j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) {
+      d[j] = fmaxf(d[j], acc[j]);
+      gc[j] += (g != 0 && gk[j] == g) ? 1 : 0;
+    }
+  }
+  // the empty rest of the list (t is the same in every thread)
+  for (int p = t + tid; p < k; p += 256) {
+    out_rows[q * k + p] = -1;
+    out_scores[q * k + p] = -INFINITY;
+    out_obj[q * k + p] = -INFINITY;
+  }
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int64_t lthm_retrieve_diversify_ws_bytes(int64_t Q, int64_t M, int32_t k) {
+  if (Q < 1 || Q >= (1ll << 31) || M < 1 || M > RV_MMAX || k < 1 || k > RT_KMAX) return -1;
+  return 0;  // the candidates' rows live in registers
+}
+
+extern "C" int lthm_retrieve_diversify(const void* items, int64_t N, const int32_t* rows, const float* scores, int64_t Q,
+                                       int32_t M, int32_t k, const float* lam, const int32_t* groups, int32_t cap,
+                                       int32_t* out_rows, float* out_scores, float* out_obj, void* workspace,
+                                       int64_t ws_bytes, void* stream) {
+  LTHM_REQUIRE(items && rows && scores && out_rows && out_scores && out_obj);
+  LTHM_REQUIRE(N >= 1 && N < (1ll << 31));
+  const int64_t need = lthm_retrieve_diversify_ws_bytes(Q, M, k);
+  LTHM_REQUIRE(need >= 0 && ws_bytes >= need && (workspace || need == 0));
+  LTHM_REQUIRE(!groups || cap >= 1);
+  LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)rows & 3) == 0 && ((uintptr_t)scores & 3) == 0 && ((uintptr_t)lam & 3) == 0 &&
+               ((uintptr_t)groups & 3) == 0);
+  LTHM_REQUIRE(((uintptr_t)out_rows & 3) == 0 && ((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_obj & 3) == 0);
+  hipStream_t s = (hipStream_t)stream;
+  const bf16_t* it = (const bf16_t*)items;
+  const dim3 grid((unsigned)Q), block(256);
+  if (M <= 256)
+    hipLaunchKernelGGL(retr_diversify_k<1>, grid, block, 0, s, it, N, rows, scores, (int)M, (int)k, lam, groups, (int)cap,
+                       out_rows, out_scores, out_obj);
+  else if (M <= 512)
+    hipLaunchKernelGGL(retr_diversify_k<2>, grid, block, 0, s, it, N, rows, scores, (int)M, (int)k, lam, groups, (int)cap,
+                       out_rows, out_scores, out_obj);
+  else
+    hipLaunchKernelGGL(retr_diversify_k<4>, grid, block, 0, s, it, N, rows, scores, (int)M, (int)k, lam, groups, (int)cap,
+                       out_rows, out_scores, out_obj);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}

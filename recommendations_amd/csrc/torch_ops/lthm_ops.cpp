@@ -25,6 +25,7 @@
 //   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
 //   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
 //   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
+//   lthm::retrieve_diversify     greedy MMR selection of k out of a pool per query, with a cap per group
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -797,6 +798,55 @@ std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q_, const Tensor
   return std::make_tuple(scores, ids);
 }
 
+// items bf16 [N, 128], rows int32 [Q, M], scores f32 [Q, M] (M <= 1024), lam f32 [Q] or None (1
+// everywhere), groups int32 [N] or None with cap >= 1; (rows int32 [Q, k], scores f32 [Q, k],
+// objective f32 [Q, k]) in selection order, empty slots (-1, -inf, -inf)
+std::tuple<Tensor, Tensor, Tensor> retrieve_diversify_cuda(const Tensor& items_, const Tensor& rows_, const Tensor& scores_,
+                                                           int64_t k, const c10::optional<Tensor>& lam_,
+                                                           const c10::optional<Tensor>& groups_, int64_t cap) {
+  on_gpu(items_, "items");
+  on_gpu(rows_, "rows");
+  on_gpu(scores_, "scores");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16 && items_.size(0) >= 1,
+              "items must be a bf16 [N, 128] catalogue, N >= 1");
+  TORCH_CHECK(rows_.dim() == 2 && rows_.scalar_type() == at::kInt, "rows must be int32 [Q, M]");
+  TORCH_CHECK(scores_.scalar_type() == at::kFloat && scores_.sizes() == rows_.sizes(), "scores must be f32 [Q, M]");
+  const int64_t N = items_.size(0), Q = rows_.size(0), M = rows_.size(1);
+  TORCH_CHECK(M >= 1 && M <= 1024, "retrieve_diversify takes a pool of 1..1024 candidates (got M=", M, ")");
+  TORCH_CHECK(k >= 1 && k <= 128, "retrieve_diversify takes k in 1..128 (got ", k, ")");
+  TORCH_CHECK(Q >= 1, "retrieve_diversify takes at least one query");
+  TORCH_CHECK(rows_.device() == items_.device() && scores_.device() == items_.device(),
+              "rows and scores must be on the catalogue's device");
+  const Tensor items = items_.contiguous(), rows = rows_.contiguous(), scores = scores_.contiguous();
+  Tensor lam, groups;
+  const bool has_l = lam_.has_value() && lam_->defined(), has_g = groups_.has_value() && groups_->defined();
+  if (has_l) {
+    TORCH_CHECK(lam_->scalar_type() == at::kFloat && lam_->dim() == 1 && lam_->size(0) == Q &&
+                    lam_->device() == items.device(),
+                "lam must be f32 [Q] on the catalogue's device");
+    lam = lam_->contiguous();
+  }
+  if (has_g) {
+    TORCH_CHECK(groups_->scalar_type() == at::kInt && groups_->dim() == 1 && groups_->size(0) == N &&
+                    groups_->device() == items.device(),
+                "groups must be int32 [N] on the catalogue's device");
+    TORCH_CHECK(cap >= 1 && cap <= INT32_MAX, "retrieve_diversify takes cap >= 1 (got ", cap, ")");
+    groups = groups_->contiguous();
+  }
+  const int64_t need = lthm_retrieve_diversify_ws_bytes(Q, M, (int32_t)k);
+  TORCH_CHECK(need >= 0, "retrieve_diversify: unsupported sizes Q=", Q, " M=", M, " k=", k);
+  Tensor out_rows = at::empty({Q, k}, rows.options()), out_scores = at::empty({Q, k}, scores.options()),
+         out_obj = at::empty({Q, k}, scores.options());
+  auto ws = at::empty({need}, rows.options().dtype(at::kByte));
+  hip_ok(lthm_retrieve_diversify(items.data_ptr(), N, rows.data_ptr<int32_t>(), scores.data_ptr<float>(), Q, (int32_t)M,
+                                 (int32_t)k, has_l ? lam.data_ptr<float>() : nullptr,
+                                 has_g ? groups.data_ptr<int32_t>() : nullptr, has_g ? (int32_t)cap : 1,
+                                 out_rows.data_ptr<int32_t>(), out_scores.data_ptr<float>(), out_obj.data_ptr<float>(),
+                                 need ? ws.data_ptr() : nullptr, need, cur_stream()),
+         "lthm_retrieve_diversify");
+  return {out_rows, out_scores, out_obj};
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -839,6 +889,9 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_ivf_topk(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
       "bool normalize_q, Tensor? exclude_rows=None) -> (Tensor scores, Tensor ids)");
+  m.def(
+      "retrieve_diversify(Tensor items, Tensor rows, Tensor scores, int k, Tensor? lam=None, Tensor? groups=None, "
+      "int cap=1) -> (Tensor rows, Tensor scores, Tensor objective)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -857,6 +910,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
   m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
   m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
+  m.impl("retrieve_diversify", &retrieve_diversify_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

@@ -2238,3 +2238,53 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
          stream(), _key="retr_ivf_topk_k", _work=float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k
                                                        + 4.0 * Q * (P + X)), _unit="byte")
     return scores, ids
+
+
+RETRIEVE_MAX_POOL = RETRIEVE_MAX_DEEP  # RV_MMAX: the largest candidate pool of retrieve_diversify (a deep list)
+
+
+def retrieve_diversify(items, rows, scores, k: int, *, lam=None, groups=None, cap: int = 1):
+    """Greedy maximal-marginal-relevance selection of k out of a pool of M candidates per query, with
+    at most `cap` selected items per group (lthm_retrieve_diversify, csrc/retrieve.hip retr_diversify_k).
+
+    items bf16 [N, 128], the flat catalogue; rows int32 [Q, M] and scores f32 [Q, M], 1 <= M <= 1024,
+    the pool in any order (what retrieve_topk returned, deep=True for more than 128): an entry with a
+    row outside [0, N) or a score of -inf or NaN is no candidate.  k in 1..128.  lam f32 [Q] in [0, 1]
+    or None (1 everywhere); groups int32 [N] or None, key 0 = never capped; cap >= 1 (ignored without
+    groups).  k times per query the eligible candidate first under (m descending, row ascending) is
+    selected, m_i = fmaf(-(1 - lam), d_i, lam s_i) with d_i the largest f32 dot of row i with a row
+    selected so far (0 at the start).  Returns (rows int32 [Q, k], scores f32 [Q, k], objective f32
+    [Q, k]) in selection order: the caller's score of every selected row and m at its selection; empty
+    slots are (-1, -inf, -inf).  lam = 1 without groups is the pool's first k under (score descending,
+    row ascending).  One block per query, no host sync, a pure function of the inputs."""
+    who = "retrieve_diversify"
+    require_gpu(items, rows, scores, lam, groups)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(rows.dim() == 2 and rows.dtype == torch.int32, f"{who} takes int32 rows [Q, M] (got {rows.dtype} {tuple(rows.shape)})")
+    _check(scores.dtype == torch.float32 and scores.shape == rows.shape,
+           f"{who} takes f32 scores of the rows' shape (got {scores.dtype} {tuple(scores.shape)})")
+    (Q, M), N, k, cap = rows.shape, items.shape[0], int(k), int(cap)
+    _check(1 <= M <= RETRIEVE_MAX_POOL, f"{who} takes a pool of 1..{RETRIEVE_MAX_POOL} candidates (got M={M})")
+    _check(1 <= k <= RETRIEVE_MAX_K, f"{who} takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    dev = items.device
+    _check(rows.device == dev and scores.device == dev, "rows and scores must be on the catalogue's device")
+    if lam is not None:
+        _check(lam.dtype == torch.float32 and tuple(lam.shape) == (Q,), f"lam must be f32 [Q] (got {lam.dtype} {tuple(lam.shape)}, Q={Q})")
+        _check(lam.device == dev, "lam must be on the catalogue's device")
+    if groups is not None:
+        _check(groups.dtype == torch.int32 and tuple(groups.shape) == (N,),
+               f"groups must be int32 [N], one key per catalogue row (got {groups.dtype} {tuple(groups.shape)}, N={N})")
+        _check(groups.device == dev, "groups must be on the catalogue's device")
+        _check(cap >= 1, f"{who} takes cap >= 1 (got {cap})")
+    need = load().lthm_retrieve_diversify_ws_bytes(Q, M, k)
+    _check(need >= 0, f"{who}: no workspace size for Q={Q} M={M} k={k}")
+    out_rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    out_scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_obj = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    call("lthm_retrieve_diversify", ptr(items), N, ptr(rows), ptr(scores), Q, M, k, ptr(lam), ptr(groups), max(cap, 1),
+         ptr(out_rows), ptr(out_scores), ptr(out_obj), ptr(ws), need, stream(), _key="retr_diversify_k",
+         _work=2.0 * Q * k * M * RETRIEVE_WIDTH, _unit="flop")
+    return out_rows, out_scores, out_obj

@@ -7,8 +7,8 @@ the loss normalises both (wrapper.py:118-119) and ranks by their dot product.  A
 scored against all of them (``K.retrieve_topk``, csrc/retrieve.hip) instead of against the
 in-batch negatives only.
 
-File format: safetensors with the two tensors ``ids`` / ``emb``, the optional ``tags`` and
-``bias``, and a ``format`` metadata string, in the style of item_artifact.py.  Loading executes
+File format: safetensors with the two tensors ``ids`` / ``emb``, the optional ``tags``,
+``bias`` and ``groups``, and a ``format`` metadata string, in the style of item_artifact.py.  Loading executes
 nothing from the file.
 
 Tags: a catalogue may carry one int32 word per item, read as 32 independent attribute bits (in
@@ -20,6 +20,11 @@ Bias: a catalogue may carry one finite f32 per item, a score prior (popularity, 
 sponsored lift, a demotion).  A query's score for item j is then fma(w, bias[j], q . e_j) with a
 weight w per query (1 unless told otherwise), inside the kernel (``K.retrieve_topk``'s ``bias`` /
 ``bias_weight``): the order, the cursors and the ranks are those of the biased scores.
+
+Groups: a catalogue may carry one int32 key per item (brand, seller, parent product; 0 = none).
+``ItemCatalogue.diversify`` re-ranks a list any ``topk`` returned: greedy maximal-marginal-relevance
+selection against the items already chosen, with at most ``group_cap`` chosen items per non-zero key
+(``K.retrieve_diversify``, one block per query on the device).
 
 Shards: a ``ShardedItemCatalogue`` holds the items as several ``ItemCatalogue``s with disjoint ids,
 on this process's devices and, with a process group, on the other ranks' (the row-sharded item
@@ -83,10 +88,11 @@ class ItemCatalogue:
     """``ids`` int64 [N], strictly ascending (so unique) and without the pad id 0; ``emb`` bf16
     [N, 128], row i the normalised candidate vector of ``ids[i]``; ``tags`` int32 [N] or None,
     row i the 32 attribute bits of ``ids[i]``; ``bias`` f32 [N] or None, row i the score prior of
-    ``ids[i]``, every value finite (checked here, with one sync)."""
+    ``ids[i]``, every value finite (checked here, with one sync); ``groups`` int32 [N] or None, row i
+    the group key of ``ids[i]`` (brand, seller, parent product), 0 for an item of no group."""
 
     def __init__(self, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None,
-                 bias: Optional[torch.Tensor] = None):
+                 bias: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None):
         if ids.dtype != torch.int64 or ids.dim() != 1:
             raise ValueError(f"catalogue ids must be int64 [N] (got {ids.dtype} {tuple(ids.shape)})")
         if emb.dtype != torch.bfloat16 or emb.dim() != 2 or emb.shape[1] != WIDTH:
@@ -117,10 +123,18 @@ class ItemCatalogue:
             if not bool(torch.isfinite(bias).all()):
                 raise ValueError("catalogue bias must be finite (it holds NaN or +-inf)")
             bias = bias.contiguous()
+        if groups is not None:
+            if groups.dtype != torch.int32 or groups.dim() != 1 or groups.shape[0] != ids.shape[0]:
+                raise ValueError(f"catalogue groups must be int32 [N], one key per id "
+                                 f"(got {groups.dtype} {tuple(groups.shape)}, N={ids.shape[0]})")
+            if groups.device != ids.device:
+                raise ValueError("catalogue groups must live on the device of ids and embeddings")
+            groups = groups.contiguous()
         self.ids = ids.contiguous()
         self.emb = emb.contiguous()
         self.tags = tags
         self.bias = bias
+        self.groups = groups
 
     def __len__(self) -> int:
         return self.ids.shape[0]
@@ -133,9 +147,13 @@ class ItemCatalogue:
     def has_bias(self) -> bool:
         return self.bias is not None
 
+    @property
+    def has_groups(self) -> bool:
+        return self.groups is not None
+
     def take(self, rows: torch.Tensor) -> "ItemCatalogue":
         """The catalogue of some of the rows: a bool mask [N] or an integer index tensor (any order,
-        no row twice).  Tags and bias move with the rows; at least one row must remain."""
+        no row twice).  Tags, bias and groups move with the rows; at least one row must remain."""
         if rows.dtype == torch.bool:
             if rows.shape != self.ids.shape:
                 raise ValueError(f"take: a mask must be bool [N] (got {tuple(rows.shape)}, N={len(self)})")
@@ -151,7 +169,8 @@ class ItemCatalogue:
         if idx.numel() < 1:
             raise ValueError("take: no row remains, and a catalogue is never empty")
         return ItemCatalogue(self.ids[idx], self.emb[idx], None if self.tags is None else self.tags[idx],
-                             None if self.bias is None else self.bias[idx])
+                             None if self.bias is None else self.bias[idx],
+                             None if self.groups is None else self.groups[idx])
 
     def split(self, n: int) -> List["ItemCatalogue"]:
         """n shards of contiguous id ranges: shard i holds rows [i N // n, (i + 1) N // n), so none
@@ -180,24 +199,28 @@ class ItemCatalogue:
 
     @classmethod
     def from_embeddings(cls, ids: torch.Tensor, emb: torch.Tensor, tags: Optional[torch.Tensor] = None,
-                        bias: Optional[torch.Tensor] = None) -> "ItemCatalogue":
+                        bias: Optional[torch.Tensor] = None, groups: Optional[torch.Tensor] = None) -> "ItemCatalogue":
         """From ids in any order and their (already normalised, bf16) vectors: rows are sorted
-        by id, and ``tags`` (int32 [N]) and ``bias`` (f32 [N]), given in the order of ``ids``, move
-        with them.  Duplicate ids are refused, as is id 0."""
+        by id, and ``tags`` (int32 [N]), ``bias`` (f32 [N]) and ``groups`` (int32 [N]), given in the
+        order of ``ids``, move with them.  Duplicate ids are refused, as is id 0."""
         if ids.dim() != 1 or emb.dim() != 2 or ids.shape[0] != emb.shape[0]:
             raise ValueError("from_embeddings takes ids [N] and emb [N, 128]")
         if tags is not None and (tags.dim() != 1 or tags.shape[0] != ids.shape[0]):
             raise ValueError("from_embeddings takes tags [N], one word per id")
         if bias is not None and (bias.dim() != 1 or bias.shape[0] != ids.shape[0]):
             raise ValueError("from_embeddings takes bias [N], one word per id")
+        if groups is not None and (groups.dim() != 1 or groups.shape[0] != ids.shape[0]):
+            raise ValueError("from_embeddings takes groups [N], one key per id")
         order = torch.argsort(ids, stable=True)
         return cls(ids[order], emb[order.to(emb.device)], None if tags is None else tags[order.to(tags.device)],
-                   None if bias is None else bias[order.to(bias.device)])
+                   None if bias is None else bias[order.to(bias.device)],
+                   None if groups is None else groups[order.to(groups.device)])
 
     def to(self, device) -> "ItemCatalogue":
         return ItemCatalogue(self.ids.to(device), self.emb.to(device),
                              None if self.tags is None else self.tags.to(device),
-                             None if self.bias is None else self.bias.to(device))
+                             None if self.bias is None else self.bias.to(device),
+                             None if self.groups is None else self.groups.to(device))
 
     def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
         """The filter "the same value as the target in the masked bit field": per target t the
@@ -283,6 +306,50 @@ class ItemCatalogue:
         item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
         return item_ids, scores, rank, tscore
 
+    def diversify(self, item_ids: torch.Tensor, scores: torch.Tensor, k: int, *,
+                  lam: Union[float, torch.Tensor] = 1.0, group_cap: Optional[int] = None):
+        """A diversified list of k out of a pool per query: (item_ids int64 [Q, k], scores f32 [Q, k],
+        objective f32 [Q, k]) in selection order (``K.retrieve_diversify``).  ``item_ids`` int64 [Q, M]
+        and ``scores`` f32 [Q, M], M <= ``K.RETRIEVE_MAX_POOL`` = 1024, are a list any catalogue over
+        these items returned (flat, sharded or clustered: all give ids), in any order; an id this
+        catalogue does not hold, the pad id 0 and a score of -inf or NaN are no candidates.  k times
+        the item with the largest ``lam`` * score - (1 - ``lam``) * (its largest dot with an item
+        chosen so far) is chosen, ties to the lower id; ``lam`` is a number or f32 [Q], in [0, 1]:
+        1 keeps the order by score, 0 looks at similarity only.  ``group_cap`` = m keeps at most m
+        chosen items of one non-zero group key and needs a catalogue with groups.  ``scores`` of
+        the result are the pool's own; empty slots hold (0, -inf, -inf)."""
+        if item_ids.dtype != torch.int64 or item_ids.dim() != 2:
+            raise ValueError(f"diversify takes int64 item_ids [Q, M] (got {item_ids.dtype} {tuple(item_ids.shape)})")
+        if scores.dtype != torch.float32 or scores.shape != item_ids.shape:
+            raise ValueError(f"diversify takes f32 scores of the ids' shape (got {scores.dtype} {tuple(scores.shape)})")
+        Q, M = item_ids.shape
+        if not 1 <= M <= K.RETRIEVE_MAX_POOL:
+            raise ValueError(f"diversify takes a pool of 1..{K.RETRIEVE_MAX_POOL} candidates (got M={M})")
+        if not 1 <= int(k) <= K.RETRIEVE_MAX_K:
+            raise ValueError(f"diversify takes k in 1..{K.RETRIEVE_MAX_K} (got {k})")
+        if group_cap is not None:
+            if self.groups is None:
+                raise ValueError("group_cap given, but this catalogue carries no groups")
+            if isinstance(group_cap, bool) or not isinstance(group_cap, int) or group_cap < 1:
+                raise ValueError(f"group_cap takes an int >= 1 (got {group_cap!r})")
+        dev = self.emb.device
+        if isinstance(lam, torch.Tensor):
+            if lam.dim() != 1 or lam.shape[0] != Q or not lam.is_floating_point():
+                raise ValueError(f"lam must be a number or a float tensor [Q] (got {lam.dtype} {tuple(lam.shape)}, Q={Q})")
+            lam_t = lam.detach().to(torch.float32).cpu()
+            if not bool(((lam_t >= 0) & (lam_t <= 1)).all()):  # NaN fails as well
+                raise ValueError("lam must lie in [0, 1] for every query")
+            lam_t = lam_t.to(dev).contiguous()
+        else:
+            if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= float(lam) <= 1.0:
+                raise ValueError(f"lam must lie in [0, 1] (got {lam!r})")
+            lam_t = None if float(lam) == 1.0 else torch.full((Q,), float(lam), dtype=torch.float32, device=dev)
+        rows, sc, obj = K.retrieve_diversify(self.emb, self.rows_of(item_ids).contiguous(), scores.to(dev).contiguous(),
+                                             int(k), lam=lam_t, groups=self.groups if group_cap is not None else None,
+                                             cap=group_cap if group_cap is not None else 1)
+        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+        return ids, sc, obj
+
     def save(self, path: str) -> None:
         from safetensors.torch import save_file
         tensors = {"ids": self.ids.detach().cpu().contiguous(), "emb": self.emb.detach().cpu().contiguous()}
@@ -290,6 +357,8 @@ class ItemCatalogue:
             tensors["tags"] = self.tags.detach().cpu().contiguous()
         if self.bias is not None:
             tensors["bias"] = self.bias.detach().cpu().contiguous()
+        if self.groups is not None:
+            tensors["groups"] = self.groups.detach().cpu().contiguous()
         save_file(tensors, path, metadata={"format": FORMAT})
 
     @classmethod
@@ -302,7 +371,8 @@ class ItemCatalogue:
             ids, emb = f.get_tensor("ids"), f.get_tensor("emb")
             tags = f.get_tensor("tags") if "tags" in f.keys() else None
             bias = f.get_tensor("bias") if "bias" in f.keys() else None
-        cat = cls(ids, emb, tags, bias)
+            groups = f.get_tensor("groups") if "groups" in f.keys() else None
+        cat = cls(ids, emb, tags, bias, groups)
         return cat.to(device) if device is not None else cat
 
     @torch.no_grad()
@@ -354,7 +424,8 @@ class ClusteredItemCatalogue:
     ascending; ``row_ids`` int64 [N], the id of every row (distinct, never 0); ``list_off`` int64
     [L + 1]; ``centroids`` bf16 [L, 128]; ``tags`` / ``bias`` in the rows' order or None.  Tags and
     bias are carried for ``to_flat()`` only: the clustered scan scores the plain dot and filters
-    nothing but ``exclude_ids``."""
+    nothing but ``exclude_ids``.  Groups are not carried: a clustered list is diversified against
+    the flat catalogue it was built from (``ItemCatalogue.diversify`` takes its ids)."""
 
     def __init__(self, row_ids: torch.Tensor, emb: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
                  tags: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -557,7 +628,9 @@ class ShardedItemCatalogue:
     """One catalogue held as shards: ``local_shards`` are the ``ItemCatalogue``s of this process (on
     one device or on several; disjoint ids, checked here), and with ``group`` the catalogue also
     covers the shards of the group's other ranks.  All shards agree on carrying tags and on carrying
-    a bias.  At most ``K.RETRIEVE_MAX_SHARDS`` = 64 shards in all.
+    a bias.  At most ``K.RETRIEVE_MAX_SHARDS`` = 64 shards in all.  The merged catalogue carries no
+    groups, whatever its shards hold: its lists are diversified against a flat catalogue over the
+    same items (``ItemCatalogue.diversify`` takes the ids ``topk`` returns).
 
     With a ``group`` the constructor, ``topk``, ``filter_like``, ``holds``, ``target_ranks`` and
     ``validate`` are collectives: every rank calls them, with the same queries, and every rank gets
@@ -752,17 +825,19 @@ def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:
 
 @torch.no_grad()
 def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Optional[torch.Tensor] = None,
-                    bias: Optional[torch.Tensor] = None, shard: Optional[Tuple[int, int]] = None) -> ItemCatalogue:
+                    bias: Optional[torch.Tensor] = None, shard: Optional[Tuple[int, int]] = None,
+                    groups: Optional[torch.Tensor] = None) -> ItemCatalogue:
     """The catalogue of ``ids`` under ``wrapper``'s current weights: per chunk, the item
     embedding module and the product tower on a [1, n] id row (the training kernels), then
     F.normalize to bf16 as the loss does (``K.rownorm``).  A row therefore equals the
     normalised ``current_token_emb`` row a forward produces for that id.  ``tags`` (int32, one
     word per entry of ``ids``) follow the ids through the sort and the de-duplication; an id given
     twice with different tags is refused.  ``bias`` (f32, one word per entry of ``ids``) follows
-    them the same way, under the same rule.
+    them the same way, under the same rule, and so do ``groups`` (int32, one key per entry of ``ids``,
+    0 = no group: ``ItemCatalogue.diversify``'s ``group_cap``).
 
     ``shard = (rank, world)``: this process's part of a catalogue built by ``world`` processes, for a
-    ``ShardedItemCatalogue``.  Every rank passes the same ``ids`` (and ``tags`` / ``bias``) and keeps
+    ``ShardedItemCatalogue``.  Every rank passes the same ``ids`` (and ``tags`` / ``bias`` / ``groups``) and keeps
     the slice [rank n // world, (rank + 1) n // world) of the n sorted unique ids.  Every rank makes
     the same number of chunk calls, since the forward of a row-sharded item table is a collective: a
     rank whose slice has ended joins the remaining calls with a one-id row whose result it drops.
@@ -788,6 +863,10 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
         if bias.dtype != torch.float32 or bias.shape != ids.shape:
             raise ValueError(f"build_catalogue takes f32 bias, one per id (got {bias.dtype} {tuple(bias.shape)})")
         bias = unique_bias(ids.to(dev), bias.to(dev))
+    if groups is not None:
+        if groups.dtype != torch.int32 or groups.shape != ids.shape:
+            raise ValueError(f"build_catalogue takes int32 groups, one per id (got {groups.dtype} {tuple(groups.shape)})")
+        groups = unique_groups(ids.to(dev), groups.to(dev))
     ids = torch.unique(ids.to(dev))  # sorted ascending
     if bool((ids == 0).any()):
         raise ValueError("catalogue ids must not hold 0, the pad id")
@@ -801,6 +880,7 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
         ids = ids[lo:hi]
         tags = None if tags is None else tags[lo:hi].contiguous()
         bias = None if bias is None else bias[lo:hi].contiguous()
+        groups = None if groups is None else groups[lo:hi].contiguous()
         calls = ((n + w - 1) // w + chunk - 1) // chunk  # those of the longest slice, on every rank
     out = torch.empty((ids.numel(), WIDTH), dtype=torch.bfloat16, device=dev)
     for i in range(calls):
@@ -809,7 +889,7 @@ def build_catalogue(wrapper, ids: torch.Tensor, chunk: int = 65536, tags: Option
         _, prod, _ = enc.product_tower(row, enc.product_emb_module(row))
         if lo < ids.numel():
             out[lo:lo + row.numel()] = K.rownorm(prod.reshape(-1, WIDTH).contiguous())[0]
-    return ItemCatalogue(ids.contiguous(), out, tags, bias)
+    return ItemCatalogue(ids.contiguous(), out, tags, bias, groups)
 
 
 def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:
@@ -821,6 +901,18 @@ def unique_tags(ids: torch.Tensor, tags: torch.Tensor) -> torch.Tensor:
     if not bool((out[inv] == tags).all()):
         bad = ids[out[inv] != tags][0].item()
         raise ValueError(f"build_catalogue: id {bad} is given more than once with different tags")
+    return out
+
+
+def unique_groups(ids: torch.Tensor, groups: torch.Tensor) -> torch.Tensor:
+    """The group keys of ``torch.unique(ids)``, row for row, as ``unique_tags`` does for tags: an id
+    that occurs more than once must carry one key."""
+    uniq, inv = torch.unique(ids, return_inverse=True)
+    out = torch.empty(uniq.numel(), dtype=groups.dtype, device=groups.device)
+    out[inv] = groups
+    if not bool((out[inv] == groups).all()):
+        bad = ids[out[inv] != groups][0].item()
+        raise ValueError(f"build_catalogue: id {bad} is given more than once with different groups")
     return out
 
 

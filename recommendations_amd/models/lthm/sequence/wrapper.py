@@ -348,7 +348,8 @@ class LTHMModelWrapper(BaseModelWrapper):
     def retrieve(self, batch: Dict[str, torch.Tensor], catalogue, k: int, head: int = 0,
                  exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
                  tag_all=None, tag_any=None, tag_none=None, after=None,
-                 bias_weight=None, nprobe: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                 bias_weight=None, nprobe: Optional[int] = None, diversity: Optional[float] = None,
+                 pool: Optional[int] = None, group_cap: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -372,12 +373,20 @@ class LTHMModelWrapper(BaseModelWrapper):
         ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again.
         A ``ClusteredItemCatalogue`` takes ``nprobe`` (1..min(L, 64)): sequence b gets the k best
         items (k <= 128) of the ``nprobe`` lists nearest to its query, by id ascending among equal
-        scores; ``exclude_history`` composes, every other argument above is refused by name."""
-        from .retrieval import ClusteredItemCatalogue
+        scores; ``exclude_history`` composes, every other argument above is refused by name.
+        ``diversity`` = lambda in [0, 1] and / or ``group_cap`` = m (alone it means lambda = 1; the
+        catalogue must carry groups) ask a flat ``ItemCatalogue`` for a diversified list: the call
+        retrieves ``pool`` items (default min(8 k, 1024); k <= ``pool`` <= 1024, k <= 128; above 128
+        by the deep scan) exactly as above, with ``exclude_history``, ``heads``, ``tag_*`` and
+        ``bias_weight`` in force, and returns the k that ``ItemCatalogue.diversify`` selects from
+        them, in selection order: ``scores`` are the pool's own and ``objective`` f32 [B, k] is the
+        value each item was selected at.  ``after`` is refused with them: a cursor has no meaning in
+        a re-ordered list.  Sharded and clustered catalogues refuse them."""
+        from .retrieval import ClusteredItemCatalogue, ItemCatalogue
         clustered = isinstance(catalogue, ClusteredItemCatalogue)
         if clustered:
             given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
-                     "bias_weight": bias_weight}
+                     "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
             bad = [name for name, v in given.items() if v is not None]
             if bad:
                 raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
@@ -387,6 +396,28 @@ class LTHMModelWrapper(BaseModelWrapper):
             catalogue._check_call(k, nprobe)
         elif nprobe is not None:
             raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
+        diversify = diversity is not None or group_cap is not None
+        if diversify:
+            if not isinstance(catalogue, ItemCatalogue):
+                raise ValueError("diversity / group_cap take a flat ItemCatalogue: a sharded or clustered list is "
+                                 "diversified with ItemCatalogue.diversify on a flat catalogue over the same items")
+            if after is not None:
+                raise ValueError("after given with diversity / group_cap: a cursor has no meaning in a re-ordered list")
+            if diversity is not None and (isinstance(diversity, bool) or not isinstance(diversity, (int, float))
+                                          or not 0.0 <= float(diversity) <= 1.0):
+                raise ValueError(f"diversity takes lambda in [0, 1] (got {diversity!r})")
+            if group_cap is not None and not catalogue.has_groups:
+                raise ValueError("group_cap given, but this catalogue carries no groups")
+            if group_cap is not None and (isinstance(group_cap, bool) or not isinstance(group_cap, int) or group_cap < 1):
+                raise ValueError(f"group_cap takes an int >= 1 (got {group_cap!r})")
+            if not 1 <= int(k) <= K.RETRIEVE_MAX_K:
+                raise ValueError(f"a diversified list takes k in 1..{K.RETRIEVE_MAX_K} (got {k})")
+            if pool is None:
+                pool = min(8 * int(k), K.RETRIEVE_MAX_POOL)
+            if isinstance(pool, bool) or not isinstance(pool, int) or not int(k) <= pool <= K.RETRIEVE_MAX_POOL:
+                raise ValueError(f"pool takes k..{K.RETRIEVE_MAX_POOL} candidates (got pool={pool!r}, k={k})")
+        elif pool is not None:
+            raise ValueError("pool given without diversity or group_cap")
         after_scores = after_ids = None
         if after is not None:
             if isinstance(after, dict):
@@ -430,9 +461,13 @@ class LTHMModelWrapper(BaseModelWrapper):
         if clustered:
             scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)
             return {"item_ids": item_ids, "scores": scores}
-        item_ids, scores, _, _ = catalogue.topk(q, k, normalize_q=True, exclude_ids=seen, tag_filter=filt,
-                                                after_scores=after_scores, after_ids=after_ids,
+        item_ids, scores, _, _ = catalogue.topk(q, pool if diversify else k, normalize_q=True, exclude_ids=seen,
+                                                tag_filter=filt, after_scores=after_scores, after_ids=after_ids,
                                                 bias_weight=bias_weight)
+        if diversify:
+            item_ids, scores, obj = catalogue.diversify(item_ids, scores, k, lam=1.0 if diversity is None else float(diversity),
+                                                        group_cap=group_cap)
+            return {"item_ids": item_ids, "scores": scores, "objective": obj}
         return {"item_ids": item_ids, "scores": scores}
 
     @torch.no_grad()

@@ -69,6 +69,14 @@ rows; build_s is reported, not judged).  One JSON line per nprobe in {1, 8, 32, 
   plan_us, list_scan_us, merge_us    device time of the call's own kernels from one profiled call (the three plan
                               kernels summed; null where the profiler gives nothing)
   recall_at_k, rows_per_query the mean fraction of the flat top-k returned, the mean rows a query scans (of N)
+--diversify is a mode of its own too: Q = 256 queries, N unit rows drawn as --ivf draws them, the pool the deep
+scan's own first M rows for M in {512, 1024}, k = 100 by default, lam = 0.7.  One JSON line per M:
+  kernel_ms / torch_ms        K.retrieve_diversify and a torch greedy loop on the device over the gathered
+                              [Q, M, 128] f32 rows (k steps of mask, argmax, gather, batched dot, maximum), medians
+                              (min / max) of the same alternating loop, and kernel_over_torch (_hi: kernel max /
+                              torch min; faster only if < 1)
+  fma_per_s                   Q k M 128 multiply-adds over the kernel's median
+  same_rows                   the fraction of list slots where the two agree (near-ties may fall either way)
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -520,6 +528,69 @@ def child_ivf(name: str, N: int, k: int, reps: int, L: int) -> None:
         print(json.dumps(out), flush=True)
 
 
+def child_diversify(N: int, k: int, reps: int) -> None:
+    import torch
+    from recommendations_amd import kernels as K
+    Q, lam_v = 256, 0.7
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    lam = torch.full((Q,), lam_v, dtype=torch.float32, device=dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    for M in (512, 1024):
+        sc, rw, _, _ = K.retrieve_topk(q_bf, items, M, normalize_q=False, deep=True)
+        sc, rw = sc.contiguous(), rw.contiguous()
+
+        def torch_greedy():
+            X = items[rw.long()].float()  # [Q, M, 128]: the gather is part of the baseline, as it is of the kernel
+            d = torch.zeros_like(sc)
+            taken = torch.zeros_like(sc, dtype=torch.bool)
+            out = torch.empty((Q, k), dtype=torch.int64, device=dev)
+            ar = torch.arange(Q, device=dev)
+            for t in range(k):
+                m = (lam_v * sc - (1.0 - lam_v) * d).masked_fill(taken, float("-inf"))
+                j = m.argmax(dim=1)
+                out[:, t] = j
+                taken[ar, j] = True
+                d = torch.maximum(d, torch.bmm(X, X[ar, j][:, :, None])[:, :, 0])
+            return rw.gather(1, out)
+
+        arms = [("kernel", lambda: K.retrieve_diversify(items, rw, sc, k, lam=lam), []), ("torch", torch_greedy, [])]
+        for _ in range(2):
+            for _, fn, _ in arms:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for _, fn, times in arms:
+                times.append(timed(fn))
+        out = {"mode": "diversify", "Q": Q, "N": N, "M": M, "k": k, "lam": lam_v, "reps": reps}
+        med = {}
+        for key, _, times in arms:
+            med[key] = statistics.median(times)
+            out.update({f"{key}_ms": round(med[key], 4), f"{key}_min_ms": round(min(times), 4), f"{key}_max_ms": round(max(times), 4)})
+        out["kernel_over_torch"] = round(med["kernel"] / med["torch"], 4)
+        out["kernel_over_torch_hi"] = round(max(arms[0][2]) / min(arms[1][2]), 4)
+        out["fma_per_s"] = round(Q * k * M * 128 / (med["kernel"] * 1e-3), 0)
+        out["same_rows"] = round(float((arms[0][1]()[0].long() == torch_greedy()).float().mean()), 4)
+        print(json.dumps(out), flush=True)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="serving,evaluation")
@@ -542,6 +613,8 @@ def main() -> int:
                     help="a mode of its own: the catalogue as S shards (1..64) on this device against the unsharded call")
     ap.add_argument("--ivf", type=int, default=0,
                     help="a mode of its own: the catalogue clustered into L lists, nprobe in {1, 8, 32, 64}, against the flat call")
+    ap.add_argument("--diversify", action="store_true",
+                    help="a mode of its own: K.retrieve_diversify on pools of 512 and 1,024 against a torch greedy loop")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -557,6 +630,11 @@ def main() -> int:
         raise SystemExit("--shards takes 0 (off) or 1..64 shards")
     if a.ivf < 0 or (a.ivf and a.shards):
         raise SystemExit("--ivf takes 0 (off) or a number of lists, and is a mode of its own")
+    if a.diversify and (a.ivf or a.shards or not 1 <= a.k <= 128):
+        raise SystemExit("--diversify is a mode of its own and takes --k in 1..128")
+    if a.child and a.diversify:
+        child_diversify(a.n_items, a.k, a.reps)
+        return 0
     if a.child and a.shards:
         child_shards(a.child, a.n_items, a.k, a.reps, a.shards)
         return 0
@@ -566,7 +644,7 @@ def main() -> int:
     if a.child:
         child(a.child, a.n_items, a.k, a.reps, a.exclude, a.group, a.tags, a.after, a.deep, a.bias)
         return 0
-    for name in a.shapes.split(","):
+    for name in ["serving"] if a.diversify else a.shapes.split(","):
         if name not in SHAPES:
             raise SystemExit(f"unknown shape {name}")
         try:
@@ -574,7 +652,8 @@ def main() -> int:
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
                                  "--ivf", str(a.ivf)]
-                                + (["--after"] if a.after else []) + (["--bias"] if a.bias else []),
+                                + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
+                                + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
         except subprocess.TimeoutExpired:
             print(json.dumps({"shape": name, "error": f"no result within {a.step_timeout} s"}), flush=True)
