@@ -1093,6 +1093,39 @@ int64_t lthm_retrieve_diversify_ws_bytes(int64_t Q, int64_t M, int32_t k);
 int lthm_retrieve_diversify(const void* items, int64_t N, const int32_t* rows, const float* scores, int64_t Q, int32_t M,
                             int32_t k, const float* lam, const int32_t* groups, int32_t cap, int32_t* out_rows,
                             float* out_scores, float* out_obj, void* workspace, int64_t ws_bytes, void* stream);
+/* e4m3 catalogues: a cheap approximate scan for a shortlist, then exact scores for the shortlist.
+ * Quantiser: a bf16 row x[0..127] with a = max |x_k| becomes 128 OCP e4m3fn codes and one f32
+ * scale.  e = 0 for a = 0, otherwise the largest integer with a 2^e <= 448, clamped to [-64, 64];
+ * code_k = the round-to-nearest-even, saturating e4m3fn conversion of the (exact) f32 product
+ * x_k 2^e; scale = 2^-e; the row stands for code_k scale.  On the CPU this is
+ * (x.float() * 2.0**e).to(torch.float8_e4m3fn), and the device equals it bit for bit.  A row with
+ * a non-finite element gets unspecified codes.
+ *   items  bf16 [N, 128], 16-byte aligned; codes uint8 [N, 128], 16-byte aligned; scale f32 [N] */
+int lthm_catalogue_quantize_q8(const void* items, int64_t N, uint8_t* codes, float* scale, void* stream);
+/* The shortlist: the M first rows (1 <= M <= 1024) under (s^ descending, row ascending), where
+ *   s^[q, j] = acc (scale_q scale_j),  acc = the f32 MFMA accumulation of cq_k c_jk from zero,
+ * and (cq, scale_q) is the quantiser applied to the bf16 row that lthm_retrieve_topk forms from q
+ * (normalize_q included).  Both multiplies are explicit f32 operations by powers of two.  x may be
+ * NULL; otherwise it follows lthm_retrieve_topk_excl's rules (an excluded row scores -inf).  Where
+ * fewer than M rows are eligible the tail is -inf / -1.  The outputs are a pure function of the
+ * inputs: no global atomics, no dependence on slab_rows (a multiple of 64, or 0), Q or slot order.
+ *   workspace  lthm_retrieve_q8_ws_bytes(Q, N, M, slab_rows, X) bytes (X = 0: no list), 16-byte
+ *              aligned; -1 for M outside 1..1024, X outside 0..1024, slab_rows that is no multiple
+ *              of 64, and Q or N outside 1..2^31-1 */
+int64_t lthm_retrieve_q8_ws_bytes(int64_t Q, int64_t N, int32_t M, int32_t slab_rows, int64_t X);
+int lthm_retrieve_q8_topk(const uint8_t* codes, const float* scale, int64_t N, const void* q, int32_t q_dtype,
+                          int32_t normalize_q, int64_t Q, int32_t M, int32_t slab_rows, const lthm_retrieve_excl* x,
+                          float* out_scores, int32_t* out_rows, void* workspace, int64_t ws_bytes, void* stream);
+/* Re-scoring: rows int32 [Q, M] (1 <= M <= 1024, any order) names catalogue rows per query.  Every
+ * entry in [0, N) gets the score whose f32 bits lthm_retrieve_topk returns for that (query, row);
+ * an entry outside [0, N) is no candidate; a row named twice appears twice.  out_scores / out_rows
+ * [Q, k], 1 <= k <= M: the k first under (score descending, row ascending), then -inf / -1.
+ *   workspace  lthm_retrieve_rescore_ws_bytes(Q, M, k) bytes, 16-byte aligned; -1 for Q outside
+ *              1..2^31-1, M outside 1..1024, k outside 1..M */
+int64_t lthm_retrieve_rescore_ws_bytes(int64_t Q, int32_t M, int32_t k);
+int lthm_retrieve_rescore(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
+                          const int32_t* rows, int32_t M, int32_t k, float* out_scores, int32_t* out_rows,
+                          void* workspace, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

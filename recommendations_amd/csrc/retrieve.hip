@@ -2510,3 +2510,495 @@ extern "C" int lthm_retrieve_diversify(const void* items, int64_t N, const int32
   LTHM_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------- e4m3 catalogues: scan codes, re-score in bf16
+// A row x[0..127] (bf16) with a = max |x_k| is stored as 128 OCP e4m3fn codes and one f32 scale:
+// e = the largest integer with a 2^e <= 448 (clamped to [-64, 64]; 0 for a zero row), code_k =
+// e4m3(x_k 2^e) (the product is exact in f32), scale = 2^-e.  The approximate score of a query
+// (quantised the same way from the bf16 row that retr_prep_k forms) against a row is
+//   s^[q, j] = acc (scale_q scale_j),   acc = sum_k cq_k c_jk  (f32 MFMA accumulation from zero),
+// two explicit f32 multiplies by powers of two.
+//   retr_q8_quant_k   16 lanes per row: amax by integer maximum of the bf16 magnitudes, the
+//                     exponent from the f32 exponent and significand bits, cvt_pk_fp8_f32;
+//   retr_q8_topk_k    retr_deep_topk_k<1, false>'s tile loop, keys-in-workspace selection, flagged
+//                     bitonic prune and slab lists over 64 x 128 B images; the codes of a fragment
+//                     become bf16 in registers (exactly: an e4m3 value has four significand bits) and
+//                     feed the flat scan's eight v_mfma_f32_32x32x16_bf16 per wave and tile, whose
+//                     accumulation is the f32 chain the contract names (the block-scaled
+//                     v_mfma_scale_f32_32x32x64_f8f6f4 sums its 64 products more coarsely: measured
+//                     2^-15.3 of sum|a b| against the chain's 2^-17); the 64 row
+//                     scales of tile i + 1 ride with its image the way the bias words do; the slabs'
+//                     lists go through retr_deep_merge_k;
+//   retr_rescore_k    one block per query: 32 listed rows at a time as A rows gathered from the bf16
+//                     catalogue, the query in every B column, the flat scan's eight-step
+//                     v_mfma_f32_32x32x16_bf16 chain, keys sorted in LDS by retr_deep_sort.
+// The queries go through retr_prep_k itself (no target) and then through retr_q8_quant_k: a query's
+// codes are the catalogue's rule applied to the bf16 row, so no second prep kernel exists.
+//
+// The e4m3 image: chunk ch (16 B) of row r at r 128 + ((ch ^ ((r >> 1) & 7)) << 4).  A 256-B bank
+// row holds two image rows of eight slots; the 16 lanes of one ds_read_b128 group read one chunk
+// of the rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} (+ 32 for the upper lanes), whose even
+// (and odd) members have eight distinct (r >> 1) & 7: 16 distinct slots, no conflict, for either
+// chunk of a fragment.
+namespace lthm {
+namespace {
+
+constexpr int RQ_ROWB = 128;  // bytes of a row of codes
+
+// 16 e4m3 codes (four words) as two bf16 fragments of eight, in byte order: v_cvt_pk_f32_fp8 and
+// v_cvt_pk_bf16_f32, both exact here
+__device__ __forceinline__ void retr_q8_frags(const u32x4& c, bf16x8v& f0, bf16x8v& f1) {
+  u32x4 w[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[i], true);
+    w[i >> 1][2 * (i & 1)] = pack_bf16x2(lo[0], lo[1]);
+    w[i >> 1][2 * (i & 1) + 1] = pack_bf16x2(hi[0], hi[1]);
+  }
+  f0 = __builtin_bit_cast(bf16x8v, w[0]);
+  f1 = __builtin_bit_cast(bf16x8v, w[1]);
+}
+
+struct RetrQ8Shared {
+  unsigned char img[2][RT_IT * RQ_ROWB];
+  u64 sort[4][RD_CAP];  // one buffer per wave
+  float tau[RT_QT];
+  int cnt[RT_QT];
+  int flag[3];
+  alignas(16) float scl[2][RT_IT];
+};
+static_assert(sizeof(RetrQ8Shared) <= 96 * 1024, "LDS budget: the images, four sort buffers and change");
+
+struct RetrQ8Args {
+  const unsigned char* codes;  // [N, 128] e4m3fn
+  const float* scale;          // [N]
+  const unsigned char* cq;     // [Q, 128] the queries' codes
+  const float* sq;             // [Q]
+  u64* keys;                   // [nslab, Q, stride]
+  const int* xs;               // [Q, xstride] ascending (EXCL)
+  int64_t Q, N, slab_rows;
+  int k, stride, xstride;
+};
+
+// 16 lanes per row, 8 contiguous elements per lane
+__global__ __launch_bounds__(256) void retr_q8_quant_k(const bf16_t* __restrict__ x, int64_t R,
+                                                       unsigned char* __restrict__ codes, float* __restrict__ scale) {
+  const int sub = threadIdx.x & 15;
+  const int64_t r0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+  const bool in = r0 < R;
+  const int64_t r = in ? r0 : R - 1;  // every lane takes part in the group maximum
+  const u32x4 w = *reinterpret_cast<const u32x4*>(x + r * RT_D + 8 * sub);
+  // the magnitudes as integers: their order is the order of the values
+  uint32_t am = 0u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t lo = w[i] & 0x7fffu, hi = (w[i] >> 16) & 0x7fffu;
+    am = am > lo ? am : lo;
+    am = am > hi ? am : hi;
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    const uint32_t other = (uint32_t)__shfl_xor((int)am, o, 64);
+    am = am > other ? am : other;
+  }
+  // a = 1.f 2^(E - 127) = m 2^p with m = 1.f / 2, p = E - 126: m <= 0.875 iff the seven significand
+  // bits are <= 0x60.  A subnormal a (E = 0) has p <= -126 and lands on the upper clamp.
+  int e = 0;
+  if (am != 0u) {
+    const int E = (int)(am >> 7);
+    e = ((am & 0x7fu) <= 0x60u ? 135 : 134) - E;
+    if (E == 0) e = 64;
+    e = e < -64 ? -64 : e > 64 ? 64 : e;
+  }
+  const float up = __uint_as_float((uint32_t)(127 + e) << 23);
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = fminf(fmaxf(__uint_as_float(w[i] << 16) * up, -448.f), 448.f);
+    v[2 * i + 1] = fminf(fmaxf(__uint_as_float(w[i] & 0xffff0000u) * up, -448.f), 448.f);
+  }
+  u32x2 c;
+  c[0] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+  c[0] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], (int)c[0], true);
+  c[1] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], 0, false);
+  c[1] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], (int)c[1], true);
+  // two lanes' words side by side: the even lane writes 16 bytes
+  u32x4 c4;
+  c4[0] = c[0];
+  c4[1] = c[1];
+  c4[2] = (uint32_t)__shfl_xor((int)c[0], 1, 64);
+  c4[3] = (uint32_t)__shfl_xor((int)c[1], 1, 64);
+  if (in && !(sub & 1)) *reinterpret_cast<u32x4*>(codes + r * RQ_ROWB + 8 * sub) = c4;
+  if (in && sub == 0) scale[r] = __uint_as_float((uint32_t)(127 - e) << 23);
+}
+
+// Wave w: queries 32 (w & 1) + (lane & 31) of the tile, image rows 32 (w >> 1) + 8 (v >> 2) +
+// 4 (lane >> 5) + (v & 3), as in retr_deep_topk_k.  A lane holds row lane & 31, bytes 64 s +
+// 32 (lane >> 5) .. + 31 for s = 0, 1 (chunks 4 s + 2 (lane >> 5) and the next one, two ds_read_b128);
+// MFMA step 4 s + t takes bytes 8 t .. 8 t + 7 of them, for the item rows and the queries alike, so
+// both lane halves together cover every k once and an A element meets the B element of its own k.
+template <bool EXCL>
+__global__ __launch_bounds__(256) void retr_q8_topk_k(RetrQ8Args a) {
+  __shared__ __attribute__((aligned(16))) RetrQ8Shared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int64_t q0 = (int64_t)blockIdx.x * RT_QT;
+  const int slab = blockIdx.y;
+  const int64_t row_lo = (int64_t)slab * a.slab_rows;
+  const int64_t row_hi = row_lo + a.slab_rows < a.N ? row_lo + a.slab_rows : a.N;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const int64_t q = q0 + ql;
+  const bool live = q < a.Q;
+  const int stride = a.stride;
+
+  if (tid < RT_QT) {
+    sh.tau[tid] = q0 + tid < a.Q ? -INFINITY : INFINITY;  // a query past Q never passes the filter
+    sh.cnt[tid] = 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  float sq = 0.f;
+  {
+    const unsigned char* rp = a.cq + (live ? q : 0) * RQ_ROWB;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+      if (live) {
+        lo = *reinterpret_cast<const u32x4*>(rp + 64 * s + 32 * hh);
+        hi = *reinterpret_cast<const u32x4*>(rp + 64 * s + 32 * hh + 16);
+      }
+      retr_q8_frags(lo, qf[4 * s], qf[4 * s + 1]);
+      retr_q8_frags(hi, qf[4 * s + 2], qf[4 * s + 3]);
+    }
+    if (live) sq = a.sq[q];
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // a query past Q excludes nothing and reads nothing
+  if constexpr (EXCL) {
+    if (live) {
+      const int* xl = a.xs + q * a.xstride;
+      int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (xl[mid] < row_lo) lo = mid + 1;
+        else hi = mid;
+      }
+      xp = xl + lo;
+      nx = *xp;
+    }
+  }
+  // a lane that is not live never appends (its tau is +inf)
+  u64* const kbuf = a.keys + ((int64_t)slab * a.Q + (live ? q : 0)) * stride;
+  int roff[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int R = 32 * ih + r32, ch = 4 * (c >> 1) + 2 * hh + (c & 1);
+    roff[c] = R * RQ_ROWB + ((ch ^ ((R >> 1) & 7)) << 4);
+  }
+
+  // wave w stages rows 16 w .. 16 w + 15 of an image with two DMAs of 8 rows x 128 B (lane l: row
+  // 16 w + 8 j + l / 8, slot l % 8, source chunk slot ^ ((row >> 1) & 7) = slot ^ (l / 16) ^ 4 j);
+  // rows at or past row_hi come from the zero row
+  const int srow = 16 * w + (lane >> 3), sch = (lane & 7) ^ (lane >> 4);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 8 * j;
+      const void* src = row < row_hi ? (const void*)(a.codes + row * RQ_ROWB + ((sch ^ (4 * j)) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 7));
+      glds16(src, img + (16 * w + 8 * j) * RQ_ROWB);
+    }
+    // wave 1, lane l: the scale of the image's row l; never a read at or past row_hi <= N
+    if (w == 1) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+      glds4(row < row_hi ? a.scale + row : &retr_zero_bias, sh.scl[t & 1]);
+    }
+  };
+  retire_loads();
+  stage(0);
+  for (int i = 0; i < ntile; ++i) {
+    // the key stores of tile i - 1 count in vmcnt like the DMA: this wait retires both
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;
+    if (sh.flag[(i + 2) % 3]) {  // tile i - 1 pushed a query past the limit
+      for (int pq = w; pq < RT_QT; pq += 4) {
+        int n = sh.cnt[pq];
+        if (n > RD_LIM) {
+          n = n < stride ? n : stride;
+          u64* g = a.keys + ((int64_t)slab * a.Q + q0 + pq) * stride;
+          const int m = retr_deep_prune(g, sh.sort[w], n, a.k, false, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.sort[w][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    // the lane's rows are four runs of four consecutive scale words (broadcast reads): element
+    // 4 j + c is image row 32 ih + 4 hh + 8 j + c
+    float4 s4[4];
+    {
+      const float4* sp = reinterpret_cast<const float4*>(sh.scl[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] = sp[2 * j];
+    }
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(img + roff[2 * s]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(img + roff[2 * s + 1]);
+      bf16x8v af[4];
+      retr_q8_frags(lo, af[0], af[1]);
+      retr_q8_frags(hi, af[2], af[3]);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc = mfma32(af[t], qf[4 * s + t], acc);
+    }
+    // the score from here on: acc (scale_q scale_j), two multiplies by powers of two
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sj[4] = {s4[j].x, s4[j].y, s4[j].z, s4[j].w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[4 * j + c] = acc[4 * j + c] * (sq * sj[c]);
+    }
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {  // partial tile: the rows past the slab never pass
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if constexpr (EXCL) {
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (live && slot < stride) kbuf[slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RD_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  __syncthreads();  // the last tile's appends have left their waves
+  // the slab's k best of every query, sorted, in the first k of its slots; empty slots are key 0
+  for (int pq = w; pq < RT_QT; pq += 4) {
+    if (q0 + pq >= a.Q) break;
+    int n = sh.cnt[pq];
+    n = n < stride ? n : stride;
+    u64* g = a.keys + ((int64_t)slab * a.Q + q0 + pq) * stride;
+    retr_deep_prune(g, sh.sort[w], n, a.k, true, lane);
+  }
+}
+
+// One block per query.  Wave w takes the list entries 32 t .. 32 t + 31 for t = w, w + 4, ..: entry
+// 32 t + (lane & 31) is A row lane & 31 (an entry outside [0, N) reads row 0 and becomes key 0), the
+// query is every B column, so every column of the accumulator holds the 32 scores; lane (r < 16, h)
+// owns element r of its registers: entry 32 t + 8 (r >> 2) + 4 h + (r & 3).
+__global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__ items, int64_t N,
+                                                      const bf16_t* __restrict__ qn, const int* __restrict__ rows,
+                                                      int M, int k, float* __restrict__ scores,
+                                                      int* __restrict__ out_rows) {
+  __shared__ u64 keys[RD_KMAX];
+  __shared__ int srow[RD_KMAX];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5;
+  const int64_t q = blockIdx.x;
+  const int P = M <= 512 ? 512 : RD_KMAX;
+  for (int i = tid; i < P; i += 256) {
+    int r = -1;
+    if (i < M) {
+      r = rows[q * M + i];
+      if (r < 0 || r >= N) r = -1;
+    }
+    srow[i] = r;
+    keys[i] = 0ull;
+  }
+  bf16x8v qf[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s)
+    qf[s] = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(qn + q * RT_D + 16 * s + 8 * hh));
+  __syncthreads();
+  const int ntile = (M + 31) / 32;
+  for (int t = w; t < ntile; t += 4) {
+    const int ar = srow[32 * t + r32];
+    const bf16_t* rp = items + (int64_t)(ar < 0 ? 0 : ar) * RT_D + 8 * hh;
+    u32x4 av[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) av[s] = *reinterpret_cast<const u32x4*>(rp + 16 * s);
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) acc = mfma32(__builtin_bit_cast(bf16x8v, av[s]), qf[s], acc);
+    float mine = 0.f;
+#pragma unroll
+    for (int v = 0; v < 16; ++v)
+      if (r32 == v) mine = acc[v];
+    if (r32 < 16) {
+      const int e = 32 * t + 8 * (r32 >> 2) + 4 * hh + (r32 & 3);
+      const int er = srow[e];
+      if (er >= 0) keys[e] = retr_key(mine, er);
+    }
+  }
+  __syncthreads();
+  if (w == 0 && M > 1) retr_deep_sort(keys, P, lane);
+  __syncthreads();
+  for (int i = tid; i < k; i += 256) {
+    const u64 key = keys[i];
+    scores[q * k + i] = key ? retr_key_score(key) : -INFINITY;
+    out_rows[q * k + i] = key ? retr_key_row(key) : -1;
+  }
+}
+
+// the sizes both q8 entries share: rows per slab and slots per list, or false
+inline bool retr_q8_plan(int64_t Q, int64_t N, int32_t M, int32_t slab_rows, int64_t* sr, int64_t* stride) {
+  if (M < 1 || M > RD_KMAX || slab_rows < 0) return false;
+  *sr = retr_deep_slab_rows(Q, N, slab_rows);
+  if (*sr < 0) return false;
+  *stride = retr_deep_stride(*sr, M);
+  return true;
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int lthm_catalogue_quantize_q8(const void* items, int64_t N, uint8_t* codes, float* scale, void* stream) {
+  LTHM_REQUIRE(items && codes && scale && N >= 1 && N < (1ll << 31));
+  LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)codes & 15) == 0 && ((uintptr_t)scale & 3) == 0);
+  hipLaunchKernelGGL(retr_q8_quant_k, dim3((unsigned)((N + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)items, N, codes, scale);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t lthm_retrieve_q8_ws_bytes(int64_t Q, int64_t N, int32_t M, int32_t slab_rows, int64_t X) {
+  int64_t sr, stride;
+  if (X < 0 || X > RT_XMAX || !retr_q8_plan(Q, N, M, slab_rows, &sr, &stride)) return -1;
+  const int64_t nslab = (N + sr - 1) / sr;
+  return up256(Q * RT_D * 2) + up256(Q * RQ_ROWB) + up256(Q * 4) + up256(nslab * Q * stride * 8) +
+         (X ? up256(Q * (X + 1) * 4) : 0);
+}
+
+extern "C" int lthm_retrieve_q8_topk(const uint8_t* codes, const float* scale, int64_t N, const void* q, int32_t q_dtype,
+                                     int32_t normalize_q, int64_t Q, int32_t M, int32_t slab_rows,
+                                     const lthm_retrieve_excl* x, float* out_scores, int32_t* out_rows, void* workspace,
+                                     int64_t ws_bytes, void* stream) {
+  LTHM_REQUIRE(codes && scale && q && out_scores && out_rows && workspace);
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)codes & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)scale & 3) == 0 && ((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_rows & 3) == 0);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  const int64_t need = lthm_retrieve_q8_ws_bytes(Q, N, M, slab_rows, x ? x->X : 0);
+  LTHM_REQUIRE(need >= 0 && ws_bytes >= need);
+  int64_t sr, stride;
+  retr_q8_plan(Q, N, M, slab_rows, &sr, &stride);
+  const int64_t nslab = (N + sr - 1) / sr;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  bf16_t* qn = (bf16_t*)ws;
+  ws += up256(Q * RT_D * 2);
+  unsigned char* cq = ws;
+  ws += up256(Q * RQ_ROWB);
+  float* sq = (float*)ws;
+  ws += up256(Q * 4);
+  u64* keys = (u64*)ws;
+  ws += up256(nslab * Q * stride * 8);
+  int* xs = (int*)ws;
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  // the flat call's query rows, then the catalogue's quantiser on them
+  if (q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn,
+                       (const bf16_t*)nullptr, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn,
+                       (const bf16_t*)nullptr, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_q8_quant_k, dim3(pgrid), dim3(256), 0, s, (const bf16_t*)qn, Q, cq, sq);
+  LTHM_CHECK_LAUNCH();
+  RetrQ8Args a;
+  a.codes = codes;
+  a.scale = scale;
+  a.cq = cq;
+  a.sq = sq;
+  a.keys = keys;
+  a.xs = nullptr;
+  a.Q = Q;
+  a.N = N;
+  a.slab_rows = sr;
+  a.k = M;
+  a.stride = (int)stride;
+  a.xstride = 0;
+  const dim3 tgrid((unsigned)((Q + RT_QT - 1) / RT_QT), (unsigned)nslab);
+  if (x) {
+    const int X = (int)x->X;
+    int P = 1;
+    while (P < X) P <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)Q), dim3(256), 0, s, x->rows, X, P, N, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+    hipLaunchKernelGGL(retr_q8_topk_k<true>, tgrid, dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(retr_q8_topk_k<false>, tgrid, dim3(256), 0, s, a);
+  }
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_deep_merge_k, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, keys, (int)stride,
+                     (const int*)nullptr, (const int*)nullptr, Q, N, (int)nslab, (int)M, out_scores, out_rows,
+                     (int*)nullptr, (const float*)nullptr);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t lthm_retrieve_rescore_ws_bytes(int64_t Q, int32_t M, int32_t k) {
+  if (Q < 1 || Q >= (1ll << 31) || M < 1 || M > RD_KMAX || k < 1 || k > M) return -1;
+  return up256(Q * RT_D * 2);
+}
+
+extern "C" int lthm_retrieve_rescore(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q,
+                                     int64_t Q, const int32_t* rows, int32_t M, int32_t k, float* out_scores,
+                                     int32_t* out_rows, void* workspace, int64_t ws_bytes, void* stream) {
+  LTHM_REQUIRE(items && q && rows && out_scores && out_rows && workspace);
+  LTHM_REQUIRE(N >= 1 && N < (1ll << 31));
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)rows & 3) == 0 && ((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_rows & 3) == 0);
+  const int64_t need = lthm_retrieve_rescore_ws_bytes(Q, M, k);
+  LTHM_REQUIRE(need >= 0 && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  bf16_t* qn = (bf16_t*)workspace;
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  if (q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn,
+                       (const bf16_t*)items, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn,
+                       (const bf16_t*)items, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_rescore_k, dim3((unsigned)Q), dim3(256), 0, s, (const bf16_t*)items, N, (const bf16_t*)qn, rows,
+                     (int)M, (int)k, out_scores, out_rows);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}

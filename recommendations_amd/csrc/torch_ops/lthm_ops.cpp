@@ -26,6 +26,8 @@
 //   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
 //   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
 //   lthm::retrieve_diversify     greedy MMR selection of k out of a pool per query, with a cap per group
+//   lthm::quantize_catalogue_q8, lthm::retrieve_q8_topk, lthm::retrieve_rescore
+//                                an e4m3 catalogue, its shortlist scan and the exact re-scoring of a list
 #include <ATen/hip/HIPContext.h>
 #include <torch/autograd.h>
 #include <torch/library.h>
@@ -847,6 +849,95 @@ std::tuple<Tensor, Tensor, Tensor> retrieve_diversify_cuda(const Tensor& items_,
   return {out_rows, out_scores, out_obj};
 }
 
+// e4m3 catalogues (lthm_catalogue_quantize_q8, lthm_retrieve_q8_topk, lthm_retrieve_rescore)
+// items bf16 [N, 128] -> (codes uint8 [N, 128], scale f32 [N])
+std::tuple<Tensor, Tensor> quantize_catalogue_q8_cuda(const Tensor& items_) {
+  on_gpu(items_, "items");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16 && items_.size(0) >= 1,
+              "items must be a bf16 [N, 128] catalogue, N >= 1");
+  const Tensor items = items_.contiguous();
+  const int64_t N = items.size(0);
+  Tensor codes = at::empty({N, 128}, items.options().dtype(at::kByte)), scale = at::empty({N}, items.options().dtype(at::kFloat));
+  hip_ok(lthm_catalogue_quantize_q8(items.data_ptr(), N, codes.data_ptr<uint8_t>(), scale.data_ptr<float>(), cur_stream()),
+         "lthm_catalogue_quantize_q8");
+  return {codes, scale};
+}
+
+// q f32 / bf16 [Q, 128], codes uint8 [N, 128], scale f32 [N], pool in 1..1024, exclude_rows int32
+// [Q, X] or None -> (scores f32 [Q, pool], rows int32 [Q, pool]), padded with -inf / -1
+std::tuple<Tensor, Tensor> retrieve_q8_topk_cuda(const Tensor& q_, const Tensor& codes_, const Tensor& scale_, int64_t pool,
+                                                 bool normalize_q, const c10::optional<Tensor>& excl_) {
+  on_gpu(q_, "q");
+  on_gpu(codes_, "codes");
+  on_gpu(scale_, "scale");
+  TORCH_CHECK(codes_.dim() == 2 && codes_.size(1) == 128 && codes_.scalar_type() == at::kByte && codes_.size(0) >= 1,
+              "codes must be uint8 [N, 128], N >= 1");
+  const int64_t N = codes_.size(0);
+  TORCH_CHECK(scale_.scalar_type() == at::kFloat && scale_.dim() == 1 && scale_.size(0) == N, "scale must be f32 [N]");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128 && q_.size(0) >= 1, "q must be [Q, 128], Q >= 1");
+  TORCH_CHECK(pool >= 1 && pool <= 1024, "retrieve_q8_topk takes a pool of 1..1024 rows (got ", pool, ")");
+  TORCH_CHECK(codes_.device() == q_.device() && scale_.device() == q_.device(),
+              "codes and scales must be on the queries' device");
+  const Tensor q = q_.contiguous(), codes = codes_.contiguous(), scale = scale_.contiguous();
+  const int64_t Q = q.size(0);
+  const bool has_x = excl_.has_value() && excl_->defined();
+  Tensor xr;
+  if (has_x) {
+    on_gpu(*excl_, "exclude_rows");
+    TORCH_CHECK(excl_->scalar_type() == at::kInt && excl_->dim() == 2 && excl_->size(0) == Q,
+                "exclude_rows must be int32 [Q, X]");
+    TORCH_CHECK(excl_->size(1) >= 1 && excl_->size(1) <= 1024, "exclude_rows takes 1..1024 rows per query, got ",
+                excl_->size(1));
+    TORCH_CHECK(excl_->device() == q.device(), "exclude_rows must be on the queries' device");
+    xr = excl_->contiguous();
+  }
+  const int64_t need = lthm_retrieve_q8_ws_bytes(Q, N, (int32_t)pool, 0, has_x ? xr.size(1) : 0);
+  TORCH_CHECK(need >= 0, "retrieve_q8_topk: unsupported sizes Q=", Q, " N=", N);
+  auto scores = at::empty({Q, pool}, q.options().dtype(at::kFloat));
+  auto rows = at::empty({Q, pool}, q.options().dtype(at::kInt));
+  auto ws = at::empty({need}, q.options().dtype(at::kByte));
+  lthm_retrieve_excl x = {};
+  if (has_x) {
+    x.rows = xr.data_ptr<int32_t>();
+    x.X = xr.size(1);
+  }
+  hip_ok(lthm_retrieve_q8_topk(codes.data_ptr<uint8_t>(), scale.data_ptr<float>(), N, q.data_ptr(), dcode(q),
+                               normalize_q ? 1 : 0, Q, (int32_t)pool, 0, has_x ? &x : nullptr, scores.data_ptr<float>(),
+                               rows.data_ptr<int32_t>(), ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_q8_topk");
+  return {scores, rows};
+}
+
+// q f32 / bf16 [Q, 128], items bf16 [N, 128], rows int32 [Q, M] (M <= 1024), k in 1..M ->
+// (scores f32 [Q, k], rows int32 [Q, k]): the flat call's bits for the listed rows, sorted
+std::tuple<Tensor, Tensor> retrieve_rescore_cuda(const Tensor& q_, const Tensor& items_, const Tensor& rows_, int64_t k,
+                                                 bool normalize_q) {
+  on_gpu(q_, "q");
+  on_gpu(items_, "items");
+  on_gpu(rows_, "rows");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16 && items_.size(0) >= 1,
+              "items must be a bf16 [N, 128] catalogue, N >= 1");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128 && q_.size(0) >= 1, "q must be [Q, 128], Q >= 1");
+  const int64_t Q = q_.size(0), N = items_.size(0);
+  TORCH_CHECK(rows_.dim() == 2 && rows_.scalar_type() == at::kInt && rows_.size(0) == Q, "rows must be int32 [Q, M]");
+  const int64_t M = rows_.size(1);
+  TORCH_CHECK(M >= 1 && M <= 1024, "retrieve_rescore takes lists of 1..1024 rows (got M=", M, ")");
+  TORCH_CHECK(k >= 1 && k <= M, "retrieve_rescore takes k in 1..M (got k=", k, ", M=", M, ")");
+  TORCH_CHECK(rows_.device() == q_.device() && items_.device() == q_.device(),
+              "rows and the catalogue must be on the queries' device");
+  const Tensor q = q_.contiguous(), items = items_.contiguous(), rows = rows_.contiguous();
+  const int64_t need = lthm_retrieve_rescore_ws_bytes(Q, (int32_t)M, (int32_t)k);
+  TORCH_CHECK(need >= 0, "retrieve_rescore: unsupported sizes Q=", Q, " M=", M, " k=", k);
+  auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
+  auto out_rows = at::empty({Q, k}, rows.options());
+  auto ws = at::empty({need}, rows.options().dtype(at::kByte));
+  hip_ok(lthm_retrieve_rescore(items.data_ptr(), N, q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q, rows.data_ptr<int32_t>(),
+                               (int32_t)M, (int32_t)k, scores.data_ptr<float>(), out_rows.data_ptr<int32_t>(), ws.data_ptr(),
+                               need, cur_stream()),
+         "lthm_retrieve_rescore");
+  return {scores, out_rows};
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -892,6 +983,11 @@ TORCH_LIBRARY(lthm, m) {
   m.def(
       "retrieve_diversify(Tensor items, Tensor rows, Tensor scores, int k, Tensor? lam=None, Tensor? groups=None, "
       "int cap=1) -> (Tensor rows, Tensor scores, Tensor objective)");
+  m.def("quantize_catalogue_q8(Tensor items) -> (Tensor codes, Tensor scale)");
+  m.def(
+      "retrieve_q8_topk(Tensor q, Tensor codes, Tensor scale, int pool, bool normalize_q, Tensor? exclude_rows=None) -> "
+      "(Tensor scores, Tensor rows)");
+  m.def("retrieve_rescore(Tensor q, Tensor items, Tensor rows, int k, bool normalize_q) -> (Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -911,6 +1007,9 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
   m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
   m.impl("retrieve_diversify", &retrieve_diversify_cuda);
+  m.impl("quantize_catalogue_q8", &quantize_catalogue_q8_cuda);
+  m.impl("retrieve_q8_topk", &retrieve_q8_topk_cuda);
+  m.impl("retrieve_rescore", &retrieve_rescore_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

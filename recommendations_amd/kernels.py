@@ -2288,3 +2288,112 @@ def retrieve_diversify(items, rows, scores, k: int, *, lam=None, groups=None, ca
          ptr(out_rows), ptr(out_scores), ptr(out_obj), ptr(ws), need, stream(), _key="retr_diversify_k",
          _work=2.0 * Q * k * M * RETRIEVE_WIDTH, _unit="flop")
     return out_rows, out_scores, out_obj
+
+
+RETRIEVE_Q8_MAX_POOL = RETRIEVE_MAX_DEEP  # the longest shortlist of retrieve_q8_topk and list of retrieve_rescore
+
+
+def quantize_catalogue_q8(items):
+    """A bf16 [N, 128] catalogue as e4m3 codes with one power-of-two scale per row
+    (lthm_catalogue_quantize_q8, csrc/retrieve.hip retr_q8_quant_k).
+
+    With a the largest magnitude of a row, e is the largest integer with a 2^e <= 448 (0 for a zero row,
+    clamped to [-64, 64]), the codes are (x.float() * 2.0**e).to(torch.float8_e4m3fn) and the scale is
+    2^-e, bit for bit.  Returns (codes uint8 [N, 128], scale f32 [N]).  A row with a non-finite element
+    gets unspecified codes."""
+    who = "quantize_catalogue_q8"
+    require_gpu(items)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(items.is_contiguous(), f"{who} takes a contiguous catalogue")
+    N = items.shape[0]
+    _check(N >= 1, f"{who} takes a non-empty catalogue (N={N})")
+    codes = torch.empty((N, RETRIEVE_WIDTH), dtype=torch.uint8, device=items.device)
+    scale = torch.empty(N, dtype=torch.float32, device=items.device)
+    call("lthm_catalogue_quantize_q8", ptr(items), N, ptr(codes), ptr(scale), stream(), _key="retr_q8_quant_k",
+         _bytes=float(N * (RETRIEVE_WIDTH * 3 + 4)))
+    return codes, scale
+
+
+def retrieve_q8_topk(q, codes, scale, pool: int, *, normalize_q: bool = True, exclude_rows=None, slab_rows: int = 0):
+    """The shortlist of an e4m3 catalogue: the `pool` first rows per query under (approximate score
+    descending, row ascending) (lthm_retrieve_q8_topk, csrc/retrieve.hip retr_q8_topk_k).
+
+    q f32 / bf16 [Q, 128]; codes uint8 [N, 128] and scale f32 [N] from quantize_catalogue_q8; pool in
+    1..1024.  The query becomes the bf16 row retrieve_topk forms (normalize_q as there), is quantised by
+    the catalogue's rule, and the score of row j is acc * (scale_q * scale_j) with acc the f32 sum of the
+    128 code products.  exclude_rows int32 [Q, X] follows retrieve_topk's rules.  Returns (scores f32
+    [Q, pool], rows int32 [Q, pool]), padded with -inf / -1; a pure function of the inputs, whatever
+    slab_rows (0, or a multiple of 64)."""
+    import ctypes
+    from ._lib import STRUCTS
+    who = "retrieve_q8_topk"
+    require_gpu(q, codes, scale, exclude_rows)
+    _check(codes.dim() == 2 and codes.shape[1] == RETRIEVE_WIDTH and codes.dtype == torch.uint8,
+           f"{who} takes uint8 [N, {RETRIEVE_WIDTH}] codes (got {codes.dtype} {tuple(codes.shape)})")
+    N = codes.shape[0]
+    _check(scale.dtype == torch.float32 and tuple(scale.shape) == (N,),
+           f"{who} takes f32 [N] scales (got {scale.dtype} {tuple(scale.shape)}, N={N})")
+    _check(codes.is_contiguous() and scale.is_contiguous(), f"{who} takes contiguous codes and scales")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries")
+    Q, M = q.shape[0], int(pool)
+    _check(1 <= M <= RETRIEVE_Q8_MAX_POOL, f"{who} takes a pool of 1..{RETRIEVE_Q8_MAX_POOL} rows (got {M})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    dev = q.device
+    _check(codes.device == dev and scale.device == dev, "codes and scales must be on the queries' device")
+    X = 0
+    x = None
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == Q,
+               f"exclude_rows must be int32 [Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, Q={Q})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
+        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
+        _check(exclude_rows.device == dev, "exclude_rows must be on the queries' device")
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
+    need = load().lthm_retrieve_q8_ws_bytes(Q, N, M, int(slab_rows), X)
+    _check(need >= 0, f"{who}: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
+                      f"that cuts N={N} into at most 65535 slabs")
+    scores = torch.empty((Q, M), dtype=torch.float32, device=dev)
+    rows = torch.empty((Q, M), dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("lthm_retrieve_q8_topk", ptr(codes), ptr(scale), N, ptr(q), dcode(q), int(bool(normalize_q)), Q, M,
+         int(slab_rows), ctypes.addressof(x) if x is not None else None, ptr(scores), ptr(rows), ptr(ws), need, stream(),
+         _key="retr_q8_topk_k", _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
+         _bytes=float(N * (RETRIEVE_WIDTH + 4) + q.numel() * q.element_size() + Q * M * 8) + 4.0 * Q * X)
+    return scores, rows
+
+
+def retrieve_rescore(q, items, rows, k: int, *, normalize_q: bool = True):
+    """Exact scores for a list of rows per query, and the k first of them (lthm_retrieve_rescore,
+    csrc/retrieve.hip retr_rescore_k).
+
+    q f32 / bf16 [Q, 128]; items bf16 [N, 128]; rows int32 [Q, M], 1 <= M <= 1024, in any order; k in
+    1..M.  Every entry in [0, N) gets the f32 bits retrieve_topk returns for that (query, row); an entry
+    outside is no candidate; a row named twice appears twice.  Returns (scores f32 [Q, k], rows int32
+    [Q, k]) under (score descending, row ascending), padded with -inf / -1."""
+    who = "retrieve_rescore"
+    require_gpu(q, items, rows)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries")
+    Q, N, k = q.shape[0], items.shape[0], int(k)
+    _check(rows.dim() == 2 and rows.dtype == torch.int32 and rows.shape[0] == Q,
+           f"{who} takes int32 rows [Q, M] (got {rows.dtype} {tuple(rows.shape)}, Q={Q})")
+    M = rows.shape[1]
+    _check(1 <= M <= RETRIEVE_Q8_MAX_POOL, f"{who} takes lists of 1..{RETRIEVE_Q8_MAX_POOL} rows (got M={M})")
+    _check(1 <= k <= M, f"{who} takes k in 1..M (got k={k}, M={M})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    _check(rows.is_contiguous(), "rows must be contiguous")
+    dev = q.device
+    _check(rows.device == dev and items.device == dev, "rows and the catalogue must be on the queries' device")
+    need = load().lthm_retrieve_rescore_ws_bytes(Q, M, k)
+    _check(need >= 0, f"{who}: no workspace size for Q={Q} M={M} k={k}")
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("lthm_retrieve_rescore", ptr(items), N, ptr(q), dcode(q), int(bool(normalize_q)), Q, ptr(rows), M, k,
+         ptr(scores), ptr(out_rows), ptr(ws), need, stream(), _key="retr_rescore_k",
+         _work=2.0 * Q * M * RETRIEVE_WIDTH, _unit="flop")
+    return scores, out_rows

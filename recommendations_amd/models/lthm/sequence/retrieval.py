@@ -375,6 +375,14 @@ class ItemCatalogue:
         cat = cls(ids, emb, tags, bias, groups)
         return cat.to(device) if device is not None else cat
 
+    def quantize(self, keep_exact: bool = True) -> "QuantizedItemCatalogue":
+        """This catalogue as e4m3 codes with one power-of-two scale per row
+        (``K.quantize_catalogue_q8``, on the catalogue's device), and with ``keep_exact`` the bf16 rows
+        beside them for re-scoring.  Tags, bias and groups are not carried in this version: a quantised
+        catalogue scores plain dots over all rows, and ``quantize()`` drops them."""
+        codes, scale = K.quantize_catalogue_q8(self.emb)
+        return QuantizedItemCatalogue(self.ids, codes, scale, self.emb if keep_exact else None)
+
     @torch.no_grad()
     def cluster(self, nlist: int, iters: int = 10, seed: int = 0, sample: Optional[int] = None) -> "ClusteredItemCatalogue":
         """This catalogue as ``nlist`` lists around centroids found by spherical k-means, on the
@@ -410,6 +418,137 @@ class ItemCatalogue:
             centroids = torch.where(keep, centroids, (sums / norm.clamp_min(1e-12)).to(torch.bfloat16)).contiguous()
         assign = K.retrieve_topk(self.emb, centroids, 1, normalize_q=False)[1][:, 0].long()
         return ClusteredItemCatalogue.from_assignment(self, centroids, assign)
+
+
+Q8_INDEX = "lthm-q8-v1"
+
+
+class QuantizedItemCatalogue:
+    """An ``ItemCatalogue`` stored as OCP e4m3fn codes: ``ids`` int64 [N] (strictly ascending, no 0),
+    ``codes`` uint8 [N, 128] and ``scale`` f32 [N] as ``K.quantize_catalogue_q8`` writes them (row i
+    stands for ``codes[i] * scale[i]``), and ``emb`` bf16 [N, 128] or None, the exact rows.  ``topk`` scans
+    the codes for a shortlist (``K.retrieve_q8_topk``) and, where the exact rows are kept, re-scores the
+    shortlist in bf16 (``K.retrieve_rescore``): the result is the flat list restricted to the shortlist,
+    so it equals ``ItemCatalogue.topk`` whenever the shortlist holds the flat top-k.  Tags, bias and
+    groups are not carried in this version."""
+
+    def __init__(self, ids: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, emb: Optional[torch.Tensor] = None):
+        if ids.dtype != torch.int64 or ids.dim() != 1 or ids.shape[0] < 1:
+            raise ValueError(f"catalogue ids must be int64 [N], N >= 1 (got {ids.dtype} {tuple(ids.shape)})")
+        N = ids.shape[0]
+        if codes.dtype != torch.uint8 or tuple(codes.shape) != (N, WIDTH):
+            raise ValueError(f"catalogue codes must be uint8 [N, {WIDTH}] (got {codes.dtype} {tuple(codes.shape)}, N={N})")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (N,):
+            raise ValueError(f"catalogue scales must be f32 [N] (got {scale.dtype} {tuple(scale.shape)}, N={N})")
+        if emb is not None and (emb.dtype != torch.bfloat16 or tuple(emb.shape) != (N, WIDTH)):
+            raise ValueError(f"catalogue embeddings must be bf16 [N, {WIDTH}] (got {emb.dtype} {tuple(emb.shape)}, N={N})")
+        if codes.device != ids.device or scale.device != ids.device or (emb is not None and emb.device != ids.device):
+            raise ValueError("catalogue ids, codes, scales and embeddings must live on one device")
+        if bool((ids == 0).any()):
+            raise ValueError("catalogue ids must not hold 0, the pad id")
+        if N > 1 and not bool((ids[1:] > ids[:-1]).all()):
+            raise ValueError("catalogue ids must be strictly ascending (sorted, no duplicates)")
+        self.ids = ids.contiguous()
+        self.codes = codes.contiguous()
+        self.scale = scale.contiguous()
+        self.emb = None if emb is None else emb.contiguous()
+
+    def __len__(self) -> int:
+        return self.ids.shape[0]
+
+    @property
+    def keep_exact(self) -> bool:
+        return self.emb is not None
+
+    def to(self, device) -> "QuantizedItemCatalogue":
+        return QuantizedItemCatalogue(self.ids.to(device), self.codes.to(device), self.scale.to(device),
+                                      None if self.emb is None else self.emb.to(device))
+
+    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
+        """Catalogue row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
+        flat = ids.reshape(-1).to(self.ids.device)
+        at = torch.searchsorted(self.ids, flat).clamp_(max=len(self) - 1)
+        rows = torch.where(self.ids[at] == flat, at, torch.full_like(at, -1))
+        return rows.to(torch.int32).view(ids.shape)
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of ``ids``: the catalogue holds this id."""
+        return self.rows_of(ids) >= 0
+
+    def to_flat(self) -> ItemCatalogue:
+        """The exact catalogue (without tags, bias or groups); needs ``keep_exact``."""
+        if self.emb is None:
+            raise ValueError("to_flat needs the exact rows: this catalogue was built with keep_exact=False")
+        return ItemCatalogue(self.ids, self.emb)
+
+    @staticmethod
+    def default_shortlist(k: int) -> int:
+        return min(max(4 * int(k), 128), K.RETRIEVE_Q8_MAX_POOL)
+
+    def topk(self, q: torch.Tensor, k: int, *, shortlist: Optional[int] = None, rescore: bool = True,
+             normalize_q: bool = True, exclude_ids: Optional[torch.Tensor] = None,
+             slab_rows: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(item_ids int64 [Q, k], scores f32 [Q, k]).  The ``shortlist`` first rows under the
+        approximate e4m3 scores (default min(max(4 k, 128), 1024); in k..1024) are re-scored with the
+        exact bf16 rows and the k first under (score descending, id ascending) returned: every score
+        has the bits ``ItemCatalogue.topk`` returns for that (query, item).  ``rescore=False`` returns
+        the first k of the shortlist with the approximate scores, the only mode of a catalogue built
+        with ``keep_exact=False``.  ``exclude_ids`` int64 [Q, X] (X <= 1024) as in ``ItemCatalogue.topk``.
+        Empty slots hold id 0 and score -inf.  ``k`` in 1..1024, ``q`` [Q, 128]."""
+        k = int(k)
+        if not 1 <= k <= K.RETRIEVE_Q8_MAX_POOL:
+            raise ValueError(f"a quantised catalogue takes k in 1..{K.RETRIEVE_Q8_MAX_POOL} (got {k})")
+        M = self.default_shortlist(k) if shortlist is None else int(shortlist)
+        if not k <= M <= K.RETRIEVE_Q8_MAX_POOL:
+            raise ValueError(f"shortlist must lie in k..{K.RETRIEVE_Q8_MAX_POOL} (got shortlist={M}, k={k})")
+        if rescore and self.emb is None:
+            raise ValueError("rescore=True needs the exact rows: this catalogue was built with keep_exact=False "
+                             "(pass rescore=False)")
+        if q.dim() != 2:
+            raise ValueError(f"a quantised catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        xr = None
+        if exclude_ids is not None:
+            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
+                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+            xr = self.rows_of(exclude_ids).contiguous()
+        scores, rows = K.retrieve_q8_topk(q, self.codes, self.scale, M, normalize_q=normalize_q, exclude_rows=xr,
+                                          slab_rows=slab_rows)
+        if rescore:
+            scores, rows = K.retrieve_rescore(q, self.emb, rows, k, normalize_q=normalize_q)
+        else:
+            scores, rows = scores[:, :k].contiguous(), rows[:, :k].contiguous()
+        item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+        return item_ids, scores
+
+    def recall(self, q: torch.Tensor, k: int, shortlist: Optional[int] = None) -> float:
+        """The mean over the queries of the fraction of the flat scan's top-k ids that
+        ``topk(q, k, shortlist=shortlist)`` returns; needs ``keep_exact``."""
+        want = self.to_flat().topk(q, k)[0]
+        got = self.topk(q, k, shortlist=shortlist)[0]
+        real = want != 0
+        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
+        return float((hit / real.sum(dim=1).clamp(min=1).double()).mean())
+
+    def save(self, path: str) -> None:
+        """``ItemCatalogue.save``'s container with ``codes`` and ``scale`` beside ``ids`` (and ``emb``
+        where the exact rows are kept: ``ItemCatalogue.load`` then reads the flat catalogue)."""
+        from safetensors.torch import save_file
+        tensors = {"ids": self.ids.detach().cpu().contiguous(), "codes": self.codes.detach().cpu().contiguous(),
+                   "scale": self.scale.detach().cpu().contiguous()}
+        if self.emb is not None:
+            tensors["emb"] = self.emb.detach().cpu().contiguous()
+        save_file(tensors, path, metadata={"format": FORMAT, "index": Q8_INDEX})
+
+    @classmethod
+    def load(cls, path: str, *, device=None) -> "QuantizedItemCatalogue":
+        from safetensors import safe_open
+        with safe_open(path, framework="pt") as f:
+            meta = f.metadata() or {}
+            if meta.get("format") != FORMAT or meta.get("index") != Q8_INDEX:
+                raise ValueError(f"{path}: not a quantised item catalogue (metadata {json.dumps(meta)})")
+            cat = cls(f.get_tensor("ids"), f.get_tensor("codes"), f.get_tensor("scale"),
+                      f.get_tensor("emb") if "emb" in f.keys() else None)
+        return cat.to(device) if device is not None else cat
 
 
 IVF_INDEX = "lthm-ivf-v1"

@@ -349,7 +349,8 @@ class LTHMModelWrapper(BaseModelWrapper):
                  exclude_history: bool = False, heads: Optional[Sequence[int]] = None,
                  tag_all=None, tag_any=None, tag_none=None, after=None,
                  bias_weight=None, nprobe: Optional[int] = None, diversity: Optional[float] = None,
-                 pool: Optional[int] = None, group_cap: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                 pool: Optional[int] = None, group_cap: Optional[int] = None,
+                 shortlist: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -381,9 +382,30 @@ class LTHMModelWrapper(BaseModelWrapper):
         ``bias_weight`` in force, and returns the k that ``ItemCatalogue.diversify`` selects from
         them, in selection order: ``scores`` are the pool's own and ``objective`` f32 [B, k] is the
         value each item was selected at.  ``after`` is refused with them: a cursor has no meaning in
-        a re-ordered list.  Sharded and clustered catalogues refuse them."""
-        from .retrieval import ClusteredItemCatalogue, ItemCatalogue
+        a re-ordered list.  Sharded and clustered catalogues refuse them.
+        A ``QuantizedItemCatalogue`` (``ItemCatalogue.quantize``) takes ``shortlist`` (None for
+        min(max(4 k, 128), 1024); k..1024): the e4m3 scan's ``shortlist`` best rows are re-scored with the
+        exact rows and the k best returned (k <= 1024), the flat list wherever the shortlist holds it;
+        ``exclude_history`` composes, every other argument above is refused by name.  Any other
+        catalogue refuses ``shortlist``."""
+        from .retrieval import ClusteredItemCatalogue, ItemCatalogue, QuantizedItemCatalogue
         clustered = isinstance(catalogue, ClusteredItemCatalogue)
+        quantized = isinstance(catalogue, QuantizedItemCatalogue)
+        if quantized:
+            given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
+                     "bias_weight": bias_weight, "nprobe": nprobe, "diversity": diversity, "pool": pool,
+                     "group_cap": group_cap}
+            bad = [name for name, v in given.items() if v is not None]
+            if bad:
+                raise ValueError(f"retrieve with a quantised catalogue does not take {', '.join(bad)}: "
+                                 "use catalogue.to_flat() for it")
+            if shortlist is not None and (isinstance(shortlist, bool) or not isinstance(shortlist, int)
+                                          or not int(k) <= shortlist <= K.RETRIEVE_Q8_MAX_POOL):
+                raise ValueError(f"shortlist takes k..{K.RETRIEVE_Q8_MAX_POOL} rows (got shortlist={shortlist!r}, k={k})")
+            if not 1 <= int(k) <= K.RETRIEVE_Q8_MAX_POOL:
+                raise ValueError(f"a quantised catalogue takes k in 1..{K.RETRIEVE_Q8_MAX_POOL} (got {k})")
+        elif shortlist is not None:
+            raise ValueError("shortlist given, but this catalogue is not quantised (ItemCatalogue.quantize builds one)")
         if clustered:
             given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
                      "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
@@ -460,6 +482,10 @@ class LTHMModelWrapper(BaseModelWrapper):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
         if clustered:
             scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)
+            return {"item_ids": item_ids, "scores": scores}
+        if quantized:
+            item_ids, scores = catalogue.topk(q, k, shortlist=shortlist, rescore=catalogue.keep_exact, normalize_q=True,
+                                              exclude_ids=seen)
             return {"item_ids": item_ids, "scores": scores}
         item_ids, scores, _, _ = catalogue.topk(q, pool if diversify else k, normalize_q=True, exclude_ids=seen,
                                                 tag_filter=filt, after_scores=after_scores, after_ids=after_ids,

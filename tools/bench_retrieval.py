@@ -77,6 +77,13 @@ scan's own first M rows for M in {512, 1024}, k = 100 by default, lam = 0.7.  On
                               torch min; faster only if < 1)
   fma_per_s                   Q k M 128 multiply-adds over the kernel's median
   same_rows                   the fraction of list slots where the two agree (near-ties may fall either way)
+--q8 POOL is a mode of its own too: the e4m3 catalogue of the rows --ivf draws.  One JSON line per shape:
+  flat_deep_ms / q8_scan_ms   K.retrieve_topk(k = POOL, deep=True), the bf16 way to such a shortlist, and
+                              K.retrieve_q8_topk(pool = POOL), with q8_scan_over_flat_deep (faster only if < 1)
+  q8_two_stage_ms / flat_ms   the e4m3 scan plus K.retrieve_rescore to k, and the flat call at k, with
+                              q8_two_stage_over_flat; torch_ms is the baseline at k
+  bf16_bytes_per_scan, q8_bytes_per_scan   catalogue bytes one scan reads (256 B and 128 + 4 B per row)
+  recall_at_k (_min)          the mean (least) fraction of the flat top-k the two-stage list returns
 The paths alternate inside the timed loop.  Shapes: serving Q = 256, evaluation Q = 4096
 (baseline chunked over Q so that its score matrix fits), N = 2,000,000, k = 100.
 """
@@ -591,6 +598,70 @@ def child_diversify(N: int, k: int, reps: int) -> None:
         print(json.dumps(out), flush=True)
 
 
+def child_q8(name: str, N: int, k: int, reps: int, pool: int) -> None:
+    """The e4m3 catalogue against the bf16 one, all arms alternating in one loop: the flat deep scan at
+    k = pool (the bf16 way to such a shortlist), the e4m3 scan at pool, the e4m3 scan plus the re-scoring to
+    k, the flat call at k, and the torch baseline."""
+    import torch
+    from recommendations_amd import kernels as K
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    codes, scale = K.quantize_catalogue_q8(items)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def two_stage():
+        rows = K.retrieve_q8_topk(q_bf, codes, scale, pool, normalize_q=False)[1]
+        return K.retrieve_rescore(q_bf, items, rows, k, normalize_q=False)
+
+    def base():
+        return [(q_bf[lo:lo + BASE_CHUNK] @ items.T).float().topk(k) for lo in range(0, Q, BASE_CHUNK)]
+
+    arms = [("flat_deep", lambda: K.retrieve_topk(q_bf, items, pool, normalize_q=False, deep=True), []),
+            ("q8_scan", lambda: K.retrieve_q8_topk(q_bf, codes, scale, pool, normalize_q=False), []),
+            ("q8_two_stage", two_stage, []),
+            ("flat", lambda: K.retrieve_topk(q_bf, items, k, normalize_q=False), []),
+            ("torch", base, [])]
+    for _ in range(2):
+        for _, fn, _ in arms:
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for _, fn, times in arms:
+            times.append(timed(fn))
+    out = {"shape": name, "mode": "q8", "Q": Q, "N": N, "k": k, "pool": pool, "reps": reps,
+           "drawn": f"{N} unit rows around {C} random unit centres, noise {sigma:.4f} per coordinate; queries drawn the same way",
+           "bf16_bytes_per_scan": N * 256, "q8_bytes_per_scan": N * 132}
+    med = {}
+    for key, _, times in arms:
+        med[key] = statistics.median(times)
+        out.update({f"{key}_ms": round(med[key], 4), f"{key}_min_ms": round(min(times), 4), f"{key}_max_ms": round(max(times), 4)})
+    out["q8_scan_over_flat_deep"] = round(med["q8_scan"] / med["flat_deep"], 4)
+    out["q8_two_stage_over_flat"] = round(med["q8_two_stage"] / med["flat"], 4)
+    want = K.retrieve_topk(q_bf, items, k, normalize_q=False)[1]
+    got = two_stage()[1]
+    hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & (want >= 0)[:, :, None].any(dim=2)).float().sum(dim=1) / k
+    out[f"recall_at_{k}"] = round(float(hit.mean()), 4)
+    out[f"recall_at_{k}_min"] = round(float(hit.min()), 4)
+    print(json.dumps(out), flush=True)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="serving,evaluation")
@@ -615,6 +686,8 @@ def main() -> int:
                     help="a mode of its own: the catalogue clustered into L lists, nprobe in {1, 8, 32, 64}, against the flat call")
     ap.add_argument("--diversify", action="store_true",
                     help="a mode of its own: K.retrieve_diversify on pools of 512 and 1,024 against a torch greedy loop")
+    ap.add_argument("--q8", type=int, default=0,
+                    help="a mode of its own: the e4m3 scan at POOL (1..1024) and the two-stage list against the flat calls")
     ap.add_argument("--step-timeout", type=int, default=240)
     ap.add_argument("--child", default=None)
     a = ap.parse_args()
@@ -632,6 +705,11 @@ def main() -> int:
         raise SystemExit("--ivf takes 0 (off) or a number of lists, and is a mode of its own")
     if a.diversify and (a.ivf or a.shards or not 1 <= a.k <= 128):
         raise SystemExit("--diversify is a mode of its own and takes --k in 1..128")
+    if not 0 <= a.q8 <= 1024 or (a.q8 and (a.ivf or a.shards or a.diversify or not 1 <= a.k <= min(a.q8, 128))):
+        raise SystemExit("--q8 takes 0 (off) or a pool of 1..1024, is a mode of its own and takes --k in 1..min(pool, 128)")
+    if a.child and a.q8:
+        child_q8(a.child, a.n_items, a.k, a.reps, a.q8)
+        return 0
     if a.child and a.diversify:
         child_diversify(a.n_items, a.k, a.reps)
         return 0
@@ -651,7 +729,7 @@ def main() -> int:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
-                                 "--ivf", str(a.ivf)]
+                                 "--ivf", str(a.ivf), "--q8", str(a.q8)]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
                                 + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
