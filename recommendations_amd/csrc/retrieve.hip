@@ -1166,48 +1166,18 @@ __global__ __launch_bounds__(256) void retr_deep_merge_k(const u64* __restrict__
   }
 }
 
+// ---------------------------------------------------------------- the scan's host side
+// Every scan entry point is one call of retr_scan: the checks, the plan of the grid and the
+// workspace (RetrPlan), then prep, the target's prior, the sorted lists, the scan and the merge.
+// The workspace is, in this order and each part rounded up to 256 bytes,
+//   qn    [S, 128] bf16     the queries as slots, S = U gp
+//   keys  [nslab, U, stride] u64
+//   pcnt  [nslab, U] int
+//   xs    [U, X + 1] int    only with an exclusion list
+// and the four size queries return the plan's total.
 constexpr int64_t RETR_MAX_SLABS = 65535;  // grid.y
 
-// rows per slab (a multiple of the item tile), or -1 for sizes the kernels do not take
-int64_t retr_slab_rows(int64_t Q, int64_t N, int k, int64_t slab_rows) {
-  if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || k < 1 || k > RT_KMAX) return -1;
-  int64_t sr = slab_rows;
-  if (sr == 0) {
-    // one block per CU: with few query tiles (serving) the catalogue is cut into enough slabs
-    // to fill 256 CUs; with many (evaluation) into few long ones, which prune and merge less
-    const int64_t nqt = (Q + RT_QT - 1) / RT_QT;
-    const int64_t want = nqt >= 256 ? 1 : (256 + nqt - 1) / nqt;
-    sr = (N + want - 1) / want;
-    if (sr < 1024) sr = 1024;
-    sr = (sr + RT_IT - 1) / RT_IT * RT_IT;
-  }
-  if (sr < RT_IT || sr % RT_IT != 0) return -1;
-  if ((N + sr - 1) / sr > RETR_MAX_SLABS) return -1;
-  return sr;
-}
-
 inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
-
-}  // namespace
-}  // namespace lthm
-
-using namespace lthm;
-
-extern "C" int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows) {
-  if (slab_rows < 0) return -1;
-  const int64_t sr = retr_slab_rows(Q, N, k, slab_rows);
-  if (sr < 0) return -1;
-  const int64_t nslab = (N + sr - 1) / sr;
-  return up256(Q * RT_D * 2) + up256(nslab * Q * k * 8) + up256(nslab * Q * 4);
-}
-
-extern "C" int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows, int64_t X) {
-  const int64_t base = lthm_retrieve_ws_bytes(Q, N, k, slab_rows);
-  if (base < 0 || X < 1 || X > RT_XMAX) return -1;
-  return base + up256(Q * (X + 1) * 4);
-}
-
-namespace {
 
 // slots per user: the next power of two of G
 inline int retr_gp(int G) {
@@ -1216,91 +1186,66 @@ inline int retr_gp(int G) {
   return gp;
 }
 
-}  // namespace
-
-extern "C" int64_t lthm_retrieve_group_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
-                                                int64_t X) {
-  if (G < 1 || G > RT_GMAX || X < 0 || X > RT_XMAX || slab_rows < 0) return -1;
-  if (G == 1) return X ? lthm_retrieve_excl_ws_bytes(U, N, k, slab_rows, X) : lthm_retrieve_ws_bytes(U, N, k, slab_rows);
-  if (U < 1 || U >= (1ll << 31)) return -1;
-  const int64_t S = U * retr_gp(G);  // the slab rule sees the query tiles of the padded slots
-  const int64_t sr = retr_slab_rows(S, N, k, slab_rows);
-  if (sr < 0) return -1;
-  const int64_t nslab = (N + sr - 1) / sr;
-  return up256(S * RT_D * 2) + up256(nslab * U * k * 8) + up256(nslab * U * 4) + (X ? up256(U * (X + 1) * 4) : 0);
-}
-
-namespace {
-
-template <bool EXCL>
-void retr_launch_group(int gp, dim3 grid, hipStream_t s, const RetrGroupArgs& a) {
-  if (gp == 2) hipLaunchKernelGGL((retr_topk_k<EXCL, 2>), grid, dim3(256), 0, s, a);
-  else if (gp == 4) hipLaunchKernelGGL((retr_topk_k<EXCL, 4>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((retr_topk_k<EXCL, 8>), grid, dim3(256), 0, s, a);
-}
-
-template <bool EXCL>
-void retr_launch_group_tags(int gp, dim3 grid, hipStream_t s, const RetrGroupArgs& a, const lthm_retrieve_tags* t) {
-  RetrTagArgs<RetrGroupArgs> ta;
-  static_cast<RetrGroupArgs&>(ta) = a;
-  ta.tags = t->tags;
-  ta.filt = t->filter;
-  if (gp == 2) hipLaunchKernelGGL((retr_topk_k<EXCL, 2, true>), grid, dim3(256), 0, s, ta);
-  else if (gp == 4) hipLaunchKernelGGL((retr_topk_k<EXCL, 4, true>), grid, dim3(256), 0, s, ta);
-  else hipLaunchKernelGGL((retr_topk_k<EXCL, 8, true>), grid, dim3(256), 0, s, ta);
-}
-
-// The cursor call: always an excluding instantiation (a.xs == nullptr without a list), with or
-// without tags
-template <int GP>
-void retr_launch_after(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, const lthm_retrieve_tags* t,
-                       const lthm_retrieve_cursor* c) {
-  if (t) {
-    RetrTopkArgs<true, GP, true, true> ca;
-    static_cast<RetrBaseArgs<true, GP>&>(ca) = a;
-    ca.tags = t->tags;
-    ca.filt = t->filter;
-    ca.ascore = c->after_score;
-    ca.arow = c->after_row;
-    hipLaunchKernelGGL((retr_topk_k<true, GP, true, true>), grid, dim3(256), 0, s, ca);
-  } else {
-    RetrTopkArgs<true, GP, false, true> ca;
-    static_cast<RetrBaseArgs<true, GP>&>(ca) = a;
-    ca.ascore = c->after_score;
-    ca.arow = c->after_row;
-    hipLaunchKernelGGL((retr_topk_k<true, GP, false, true>), grid, dim3(256), 0, s, ca);
+// Rows per slab (a multiple of the item tile), or -1 for sizes the kernels do not take.  S counts
+// the query slots.  floor is the shortest slab the rule picks by itself: 1024 rows for k <= RT_KMAX,
+// 4 RD_KMAX for a deep list (a slab much shorter than k only pads lists); an explicit multiple of
+// the item tile is honoured.
+int64_t retr_slab_rows(int64_t S, int64_t N, int64_t slab_rows, int64_t floor) {
+  if (S < 1 || S >= (1ll << 31) || N < 1 || N >= (1ll << 31)) return -1;
+  int64_t sr = slab_rows;
+  if (sr == 0) {
+    // one block per CU: with few query tiles (serving) the catalogue is cut into enough slabs
+    // to fill 256 CUs; with many (evaluation) into few long ones, which prune and merge less
+    const int64_t nqt = (S + RT_QT - 1) / RT_QT;
+    const int64_t want = nqt >= 256 ? 1 : (256 + nqt - 1) / nqt;
+    sr = (N + want - 1) / want;
+    if (sr < floor) sr = floor;
+    sr = (sr + RT_IT - 1) / RT_IT * RT_IT;
   }
+  if (sr < RT_IT || sr % RT_IT != 0) return -1;
+  if ((N + sr - 1) / sr > RETR_MAX_SLABS) return -1;
+  return sr;
+}
+
+// key slots per (slab, query or user) of a deep call: a slab shorter than RD_CAP never holds more
+// keys than rows
+inline int64_t retr_deep_stride(int64_t sr, int k) { return sr >= RD_CAP ? RD_CAP : (sr > k ? sr : k); }
+
+struct RetrPlan {
+  int gp;                             // slots per user
+  bool deep;                          // k > RT_KMAX: retr_deep_topk_k and retr_deep_merge_k
+  int64_t S, sr, nslab, stride;       // slots, rows per slab, slabs, key slots per (slab, user)
+  int64_t qn, keys, pcnt, xs, total;  // byte offsets into the workspace, and its size
+};
+
+// the plan of a scan of U users with G queries each (X = 0: no exclusion list); false for sizes
+// the kernels do not take
+bool retr_plan(int64_t U, int G, int64_t N, int k, int64_t slab_rows, int64_t X, RetrPlan* p) {
+  if (G < 1 || G > RT_GMAX || k < 1 || k > RD_KMAX || X < 0 || X > RT_XMAX || slab_rows < 0) return false;
+  if (U < 1 || U >= (1ll << 31)) return false;
+  p->gp = retr_gp(G);
+  p->deep = k > RT_KMAX;
+  p->S = U * p->gp;  // the slab rule sees the query tiles of the padded slots
+  p->sr = retr_slab_rows(p->S, N, slab_rows, p->deep ? 4 * RD_KMAX : 1024);
+  if (p->sr < 0) return false;
+  p->nslab = (N + p->sr - 1) / p->sr;
+  p->stride = p->deep ? retr_deep_stride(p->sr, k) : k;
+  p->qn = 0;
+  p->keys = p->qn + up256(p->S * RT_D * 2);
+  p->pcnt = p->keys + up256(p->nslab * U * p->stride * 8);
+  p->xs = p->pcnt + up256(p->nslab * U * 4);
+  p->total = p->xs + (X ? up256(U * (X + 1) * 4) : 0);
+  return true;
+}
+
+int64_t retr_plan_bytes(int64_t U, int G, int64_t N, int k, int64_t slab_rows, int64_t X) {
+  RetrPlan p;
+  return retr_plan(U, G, N, k, slab_rows, X, &p) ? p.total : -1;
 }
 
 inline bool retr_cursor_ok(const lthm_retrieve_cursor* c) {
   return !c || (c->after_score && c->after_row && ((uintptr_t)c->after_score & 3) == 0 &&
                 ((uintptr_t)c->after_row & 3) == 0);
-}
-
-// The call with a prior: always an excluding cursor instantiation (a.xs == nullptr without a
-// list, ascore == nullptr without a cursor), with or without tags
-template <int GP>
-void retr_launch_bias(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, const lthm_retrieve_tags* t,
-                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
-  if (t) {
-    RetrTopkArgs<true, GP, true, true, true> ba;
-    static_cast<RetrBaseArgs<true, GP>&>(ba) = a;
-    ba.tags = t->tags;
-    ba.filt = t->filter;
-    ba.ascore = c ? c->after_score : nullptr;
-    ba.arow = c ? c->after_row : nullptr;
-    ba.bias = b->bias;
-    ba.bw = b->weight;
-    hipLaunchKernelGGL((retr_topk_k<true, GP, true, true, true>), grid, dim3(256), 0, s, ba);
-  } else {
-    RetrTopkArgs<true, GP, false, true, true> ba;
-    static_cast<RetrBaseArgs<true, GP>&>(ba) = a;
-    ba.ascore = c ? c->after_score : nullptr;
-    ba.arow = c ? c->after_row : nullptr;
-    ba.bias = b->bias;
-    ba.bw = b->weight;
-    hipLaunchKernelGGL((retr_topk_k<true, GP, false, true, true>), grid, dim3(256), 0, s, ba);
-  }
 }
 
 // without a shard descriptor a target brings its two outputs; with one the target score is the
@@ -1314,19 +1259,74 @@ inline bool retr_bias_ok(const lthm_retrieve_bias* b) {
   return !b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0);
 }
 
-// the target's prior, behind the prep kernel that wrote d->target_score
-inline void retr_launch_bias_target(const lthm_retrieve_desc* d, const lthm_retrieve_bias* b, hipStream_t s) {
-  hipLaunchKernelGGL(retr_bias_target_k, dim3((unsigned)((d->Q + 255) / 256)), dim3(256), 0, s, d->target_row, d->Q, d->N,
-                     b->bias, b->weight, d->target_score);
+// f(std::integral_constant<int, gp>) for gp = 1, 2, 4, 8
+template <class F>
+void retr_with_gp(int gp, F&& f) {
+  if (gp == 1) f(std::integral_constant<int, 1>{});
+  else if (gp == 2) f(std::integral_constant<int, 2>{});
+  else if (gp == 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
 }
 
-// lthm_retrieve_topk_group / _tags / _after / _bias with G >= 2: d->Q users of G queries each
-int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, int G,
-                           const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
-                           const lthm_retrieve_shard* sd, void* stream) {
+// The argument block of one instantiation: the common arguments sliced to the kernel's own base
+// type (a GP = 1 kernel holds no U, a plain one no lists) and the parts it has behind them.  An
+// instantiation that takes a cursor or a prior takes a null one as "none".
+template <bool EXCL, int GP, bool TAGS, bool AFTER, bool BIAS>
+void retr_fill(RetrTopkArgs<EXCL, GP, TAGS, AFTER, BIAS>& r, const RetrGroupArgs& a, const lthm_retrieve_tags* t,
+               const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
+  static_cast<RetrBaseArgs<EXCL, GP>&>(r) = a;
+  if constexpr (TAGS) {
+    r.tags = t->tags;
+    r.filt = t->filter;
+  }
+  if constexpr (AFTER) {
+    r.ascore = c ? c->after_score : nullptr;
+    r.arow = c ? c->after_row : nullptr;
+  }
+  if constexpr (BIAS) {
+    r.bias = b ? b->bias : nullptr;
+    r.bw = b ? b->weight : nullptr;
+  }
+}
+
+template <bool EXCL, int GP, bool TAGS, bool AFTER, bool BIAS>
+void retr_launch_topk(dim3 grid, hipStream_t s, const RetrGroupArgs& a, const lthm_retrieve_tags* t,
+                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
+  RetrTopkArgs<EXCL, GP, TAGS, AFTER, BIAS> r;
+  retr_fill<EXCL, GP, TAGS, AFTER, BIAS>(r, a, t, c, b);
+  hipLaunchKernelGGL((retr_topk_k<EXCL, GP, TAGS, AFTER, BIAS>), grid, dim3(256), 0, s, r);
+}
+
+// The scan kernel of a call.  A deep list has one kernel per (GP, TAGS), which takes every other
+// part as it comes.  For k <= RT_KMAX the instantiation holds only what the call needs: a prior
+// brings the cursor and the lists with it (null where absent), a cursor the lists (a.xs == nullptr
+// without one), and the plain call runs retr_topk_k<false>.
+template <int GP, bool TAGS>
+void retr_launch_scan(const RetrPlan& p, dim3 grid, hipStream_t s, const RetrGroupArgs& a, const lthm_retrieve_tags* t,
+                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
+  if (p.deep) {
+    RetrDeepArgs<GP, TAGS> da;
+    retr_fill<true, GP, TAGS, true, true>(da, a, t, c, b);
+    da.stride = (int)p.stride;
+    hipLaunchKernelGGL((retr_deep_topk_k<GP, TAGS>), grid, dim3(256), 0, s, da);
+  } else if (b) {
+    retr_launch_topk<true, GP, TAGS, true, true>(grid, s, a, t, c, b);
+  } else if (c) {
+    retr_launch_topk<true, GP, TAGS, true, false>(grid, s, a, t, c, b);
+  } else if (a.xs) {
+    retr_launch_topk<true, GP, TAGS, false, false>(grid, s, a, t, c, b);
+  } else {
+    retr_launch_topk<false, GP, TAGS, false, false>(grid, s, a, t, c, b);
+  }
+}
+
+// Every scan entry point: d->Q queries, or with g users of g->G queries each; x, t, c and b are the
+// parts of the call that are present; sd (lthm_retrieve_topk_shard) makes the target scores the
+// caller's.  1 <= d->k <= RD_KMAX.
+int retr_scan(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
+              const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
+              const lthm_retrieve_shard* sd, void* stream) {
   LTHM_REQUIRE(d != nullptr);
-  LTHM_REQUIRE(G >= 2 && G <= RT_GMAX);
-  LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
   LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
   LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
   LTHM_REQUIRE(retr_target_ok(d, sd));
@@ -1335,31 +1335,34 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   LTHM_REQUIRE(retr_cursor_ok(c));
   LTHM_REQUIRE(retr_bias_ok(b));
-  const int64_t need = lthm_retrieve_group_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
-  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
+  const int G = g ? g->G : 1;
   const int64_t U = d->Q, N = d->N;
-  const int gp = retr_gp(G);
-  const int64_t S = U * gp;
-  const int64_t sr = retr_slab_rows(S, N, d->k, d->slab_rows);
-  const int64_t nslab = (N + sr - 1) / sr;
+  RetrPlan p;
+  LTHM_REQUIRE(retr_plan(U, G, N, d->k, d->slab_rows, x ? x->X : 0, &p) && d->ws_bytes >= p.total);
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)d->workspace;
-  bf16_t* qn = (bf16_t*)ws;
-  u64* keys = (u64*)(ws + up256(S * RT_D * 2));
-  int* pcnt = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * d->k * 8));
-  int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * d->k * 8) + up256(nslab * U * 4));
+  bf16_t* qn = (bf16_t*)(ws + p.qn);
+  u64* keys = (u64*)(ws + p.keys);
+  int* pcnt = (int*)(ws + p.pcnt);
   const bf16_t* items = (const bf16_t*)d->items;
-  const unsigned pgrid = (unsigned)((U + 15) / 16);
   const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
-  if (d->q_dtype == LTHM_BF16)
-    hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
-                       d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
-  else
-    hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
-                       d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
+  // queries -> slots: the plain kernel for G = 1, the padded slots for G >= 2
+  auto prep = [&](auto* q) {
+    using TQ = std::remove_const_t<std::remove_pointer_t<decltype(q)>>;
+    const dim3 pgrid((unsigned)((U + 15) / 16));
+    if (G == 1)
+      hipLaunchKernelGGL((retr_prep_k<TQ>), pgrid, dim3(256), 0, s, q, U, d->normalize_q, qn, items, N, ptrow,
+                         d->target_score, -INFINITY);
+    else
+      hipLaunchKernelGGL((retr_prep_group_k<TQ>), pgrid, dim3(256), 0, s, q, U, G, p.gp, d->normalize_q, qn, items, N,
+                         ptrow, d->target_score, -INFINITY);
+  };
+  if (d->q_dtype == LTHM_BF16) prep((const bf16_t*)d->q);
+  else prep((const float*)d->q);
   LTHM_CHECK_LAUNCH();
-  if (b && ptrow) {
-    retr_launch_bias_target(d, b, s);
+  if (b && ptrow) {  // the target's prior, behind the prep kernel that wrote d->target_score
+    hipLaunchKernelGGL(retr_bias_target_k, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, s, ptrow, U, N, b->bias,
+                       b->weight, d->target_score);
     LTHM_CHECK_LAUNCH();
   }
   RetrGroupArgs a;
@@ -1370,353 +1373,108 @@ int retr_launch_group_call(const lthm_retrieve_desc* d, const lthm_retrieve_excl
   a.shard = sd ? 1 : 0;
   a.keys = keys;
   a.pcnt = pcnt;
-  a.Q = S;
+  a.Q = p.S;
   a.N = N;
-  a.slab_rows = sr;
+  a.slab_rows = p.sr;
   a.k = d->k;
   a.xs = nullptr;
   a.xstride = 0;
   a.U = U;
-  const dim3 tgrid((unsigned)((S + RT_QT - 1) / RT_QT), (unsigned)nslab);
   if (x) {
     const int X = (int)x->X;
     int P = 1;
     while (P < X) P <<= 1;
+    int* xs = (int*)(ws + p.xs);
     hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)U), dim3(256), 0, s, x->rows, X, P, N, xs);  // one list per user
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
   }
-  if (b) {
-    if (gp == 2) retr_launch_bias<2>(tgrid, s, a, t, c, b);
-    else if (gp == 4) retr_launch_bias<4>(tgrid, s, a, t, c, b);
-    else retr_launch_bias<8>(tgrid, s, a, t, c, b);
-  } else if (c) {
-    if (gp == 2) retr_launch_after<2>(tgrid, s, a, t, c);
-    else if (gp == 4) retr_launch_after<4>(tgrid, s, a, t, c);
-    else retr_launch_after<8>(tgrid, s, a, t, c);
-  } else if (x) {
-    if (t) retr_launch_group_tags<true>(gp, tgrid, s, a, t);
-    else retr_launch_group<true>(gp, tgrid, s, a);
-  } else {
-    if (t) retr_launch_group_tags<false>(gp, tgrid, s, a, t);
-    else retr_launch_group<false>(gp, tgrid, s, a);
-  }
+  const dim3 tgrid((unsigned)((p.S + RT_QT - 1) / RT_QT), (unsigned)p.nslab);
+  retr_with_gp(p.gp, [&](auto GP) {
+    if (t) retr_launch_scan<decltype(GP)::value, true>(p, tgrid, s, a, t, c, b);
+    else retr_launch_scan<decltype(GP)::value, false>(p, tgrid, s, a, t, c, b);
+  });
   LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, U, N,
-                     (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
-                     sd ? sd->target_score_in : nullptr);
+  const dim3 mgrid((unsigned)((U + 3) / 4));
+  int32_t* rank = (d->target_row || sd) ? d->rank : nullptr;
+  const float* tsin = sd ? sd->target_score_in : nullptr;
+  if (p.deep)
+    hipLaunchKernelGGL(retr_deep_merge_k, mgrid, dim3(256), 0, s, keys, (int)p.stride, pcnt, d->target_row, U, N,
+                       (int)p.nslab, d->k, d->scores, d->rows, rank, tsin);
+  else
+    hipLaunchKernelGGL(retr_merge_k, mgrid, dim3(256), 0, s, keys, pcnt, d->target_row, U, N, (int)p.nslab, d->k,
+                       d->scores, d->rows, rank, tsin);
   LTHM_CHECK_LAUNCH();
   return 0;
 }
 
-// the plain, the excluding and the filtering entry points: x == nullptr and t == nullptr is the
-// plain call
-int retr_launch(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
-                const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, const lthm_retrieve_shard* sd, void* stream) {
-  LTHM_REQUIRE(d != nullptr);
-  LTHM_REQUIRE(d->k >= 1 && d->k <= RT_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
-  LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
-  LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
-  LTHM_REQUIRE(retr_target_ok(d, sd));
-  LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
-  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
-  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
-  LTHM_REQUIRE(retr_cursor_ok(c));
-  LTHM_REQUIRE(retr_bias_ok(b));
-  const int64_t need = x ? lthm_retrieve_excl_ws_bytes(d->Q, d->N, d->k, d->slab_rows, x->X)
-                         : lthm_retrieve_ws_bytes(d->Q, d->N, d->k, d->slab_rows);
-  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
-  const int64_t Q = d->Q, N = d->N;
-  const int64_t sr = retr_slab_rows(Q, N, d->k, d->slab_rows);
-  const int64_t nslab = (N + sr - 1) / sr;
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)d->workspace;
-  bf16_t* qn = (bf16_t*)ws;
-  u64* keys = (u64*)(ws + up256(Q * RT_D * 2));
-  int* pcnt = (int*)(ws + up256(Q * RT_D * 2) + up256(nslab * Q * d->k * 8));
-  const bf16_t* items = (const bf16_t*)d->items;
-  const unsigned pgrid = (unsigned)((Q + 15) / 16);
-  const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
-  if (d->q_dtype == LTHM_BF16)
-    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, Q, d->normalize_q, qn,
-                       items, N, ptrow, d->target_score, -INFINITY);
-  else
-    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, Q, d->normalize_q, qn,
-                       items, N, ptrow, d->target_score, -INFINITY);
-  LTHM_CHECK_LAUNCH();
-  if (b && ptrow) {
-    retr_launch_bias_target(d, b, s);
-    LTHM_CHECK_LAUNCH();
-  }
-  RetrExclArgs a;
-  a.items = items;
-  a.qn = qn;
-  a.trow = d->target_row;
-  a.tscore = sd ? sd->target_score_in : d->target_score;
-  a.shard = sd ? 1 : 0;
-  a.keys = keys;
-  a.pcnt = pcnt;
-  a.Q = Q;
-  a.N = N;
-  a.slab_rows = sr;
-  a.k = d->k;
-  a.xs = nullptr;
-  a.xstride = 0;
-  const dim3 tgrid((unsigned)((Q + RT_QT - 1) / RT_QT), (unsigned)nslab);
-  if (x) {
-    // the sorted lists live behind the plain call's workspace
-    int* xs = (int*)(ws + lthm_retrieve_ws_bytes(Q, N, d->k, d->slab_rows));
-    const int X = (int)x->X;
-    int P = 1;
-    while (P < X) P <<= 1;
-    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)Q), dim3(256), 0, s, x->rows, X, P, N, xs);
-    LTHM_CHECK_LAUNCH();
-    a.xs = xs;
-    a.xstride = X + 1;
-  }
-  if (b) {
-    retr_launch_bias<1>(tgrid, s, a, t, c, b);
-  } else if (c) {
-    retr_launch_after<1>(tgrid, s, a, t, c);
-  } else if (x) {
-    if (t) {
-      RetrTagArgs<RetrExclArgs> ta;
-      static_cast<RetrExclArgs&>(ta) = a;
-      ta.tags = t->tags;
-      ta.filt = t->filter;
-      hipLaunchKernelGGL((retr_topk_k<true, 1, true>), tgrid, dim3(256), 0, s, ta);
-    } else {
-      hipLaunchKernelGGL(retr_topk_k<true>, tgrid, dim3(256), 0, s, a);
-    }
-  } else if (t) {
-    RetrTagArgs<RetrArgs> ta;
-    static_cast<RetrArgs&>(ta) = a;
-    ta.tags = t->tags;
-    ta.filt = t->filter;
-    hipLaunchKernelGGL((retr_topk_k<false, 1, true>), tgrid, dim3(256), 0, s, ta);
-  } else {
-    hipLaunchKernelGGL(retr_topk_k<false>, tgrid, dim3(256), 0, s, static_cast<const RetrArgs&>(a));
-  }
-  LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_merge_k, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, keys, pcnt, d->target_row, Q, N,
-                     (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
-                     sd ? sd->target_score_in : nullptr);
-  LTHM_CHECK_LAUNCH();
-  return 0;
-}
+// the entry points for k <= RT_KMAX refuse a deep list
+inline bool retr_shallow(const lthm_retrieve_desc* d) { return d && d->k <= RT_KMAX; }
 
 }  // namespace
+}  // namespace lthm
+
+using namespace lthm;
+
+extern "C" int64_t lthm_retrieve_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows) {
+  return k > RT_KMAX ? -1 : retr_plan_bytes(Q, 1, N, k, slab_rows, 0);
+}
+
+extern "C" int64_t lthm_retrieve_excl_ws_bytes(int64_t Q, int64_t N, int32_t k, int32_t slab_rows, int64_t X) {
+  return k > RT_KMAX || X < 1 ? -1 : retr_plan_bytes(Q, 1, N, k, slab_rows, X);
+}
+
+extern "C" int64_t lthm_retrieve_group_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
+                                                int64_t X) {
+  return k > RT_KMAX ? -1 : retr_plan_bytes(U, G, N, k, slab_rows, X);
+}
+
+extern "C" int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
+                                               int64_t X) {
+  return retr_plan_bytes(U, G, N, k, slab_rows, X);
+}
 
 extern "C" int lthm_retrieve_topk(const lthm_retrieve_desc* d, void* stream) {
-  return retr_launch(d, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_excl(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, void* stream) {
-  return retr_launch(d, x, nullptr, nullptr, nullptr, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, x, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_group(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, nullptr, nullptr, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, nullptr, nullptr, nullptr, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, x, g, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_tags(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, nullptr, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, t, nullptr, nullptr, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, x, g, t, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int lthm_retrieve_topk_after(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                         const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                         const lthm_retrieve_cursor* c, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, c, nullptr, nullptr, stream);
-  return retr_launch_group_call(d, x, g->G, t, c, nullptr, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, x, g, t, c, nullptr, nullptr, stream);
 }
-
-namespace {
-
-// lthm_retrieve_topk_bias, and with sd the k <= 128 half of lthm_retrieve_topk_shard
-int retr_topk_any(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
-                  const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
-                  const lthm_retrieve_shard* sd, void* stream) {
-  if (!g || g->G == 1) return retr_launch(d, x, t, c, b, sd, stream);
-  return retr_launch_group_call(d, x, g->G, t, c, b, sd, stream);
-}
-
-}  // namespace
 
 extern "C" int lthm_retrieve_topk_bias(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                        const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
-  return retr_topk_any(d, x, g, t, c, b, nullptr, stream);
+  LTHM_REQUIRE(retr_shallow(d));
+  return retr_scan(d, x, g, t, c, b, nullptr, stream);
 }
-
-// ---------------------------------------------------------------- deep lists: host side
-namespace {
-
-// rows per slab of a deep call, or -1: retr_slab_rows' rule with a longer shortest slab (a slab
-// much shorter than k only pads lists); an explicit multiple of the item tile is honoured
-int64_t retr_deep_slab_rows(int64_t S, int64_t N, int64_t slab_rows) {
-  if (S < 1 || S >= (1ll << 31) || N < 1 || N >= (1ll << 31)) return -1;
-  int64_t sr = slab_rows;
-  if (sr == 0) {
-    const int64_t nqt = (S + RT_QT - 1) / RT_QT;
-    const int64_t want = nqt >= 256 ? 1 : (256 + nqt - 1) / nqt;
-    sr = (N + want - 1) / want;
-    if (sr < 4 * RD_KMAX) sr = 4 * RD_KMAX;
-    sr = (sr + RT_IT - 1) / RT_IT * RT_IT;
-  }
-  if (sr < RT_IT || sr % RT_IT != 0) return -1;
-  if ((N + sr - 1) / sr > RETR_MAX_SLABS) return -1;
-  return sr;
-}
-
-// key slots per (slab, query or user): a slab shorter than RD_CAP never holds more keys than rows
-inline int64_t retr_deep_stride(int64_t sr, int k) { return sr >= RD_CAP ? RD_CAP : (sr > k ? sr : k); }
-
-template <int GP>
-void retr_launch_deep(dim3 grid, hipStream_t s, const RetrBaseArgs<true, GP>& a, int stride, const lthm_retrieve_tags* t,
-                      const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b) {
-  if (t) {
-    RetrDeepArgs<GP, true> da;
-    static_cast<RetrBaseArgs<true, GP>&>(da) = a;
-    da.tags = t->tags;
-    da.filt = t->filter;
-    da.ascore = c ? c->after_score : nullptr;
-    da.arow = c ? c->after_row : nullptr;
-    da.bias = b ? b->bias : nullptr;
-    da.bw = b ? b->weight : nullptr;
-    da.stride = stride;
-    hipLaunchKernelGGL((retr_deep_topk_k<GP, true>), grid, dim3(256), 0, s, da);
-  } else {
-    RetrDeepArgs<GP, false> da;
-    static_cast<RetrBaseArgs<true, GP>&>(da) = a;
-    da.ascore = c ? c->after_score : nullptr;
-    da.arow = c ? c->after_row : nullptr;
-    da.bias = b ? b->bias : nullptr;
-    da.bw = b ? b->weight : nullptr;
-    da.stride = stride;
-    hipLaunchKernelGGL((retr_deep_topk_k<GP, false>), grid, dim3(256), 0, s, da);
-  }
-}
-
-}  // namespace
-
-extern "C" int64_t lthm_retrieve_deep_ws_bytes(int64_t U, int32_t G, int64_t N, int32_t k, int32_t slab_rows,
-                                               int64_t X) {
-  if (k <= RT_KMAX) return lthm_retrieve_group_ws_bytes(U, G, N, k, slab_rows, X);
-  if (k > RD_KMAX || G < 1 || G > RT_GMAX || X < 0 || X > RT_XMAX || slab_rows < 0) return -1;
-  if (U < 1 || U >= (1ll << 31)) return -1;
-  const int64_t S = U * retr_gp(G);
-  const int64_t sr = retr_deep_slab_rows(S, N, slab_rows);
-  if (sr < 0) return -1;
-  const int64_t nslab = (N + sr - 1) / sr;
-  return up256(S * RT_D * 2) + up256(nslab * U * retr_deep_stride(sr, k) * 8) + up256(nslab * U * 4) +
-         (X ? up256(U * (X + 1) * 4) : 0);
-}
-
-namespace {
-
-// lthm_retrieve_topk_deep, and with sd lthm_retrieve_topk_shard
-int retr_topk_deep_any(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x, const lthm_retrieve_group* g,
-                       const lthm_retrieve_tags* t, const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
-                       const lthm_retrieve_shard* sd, void* stream) {
-  LTHM_REQUIRE(d != nullptr);
-  if (d->k <= RT_KMAX) return retr_topk_any(d, x, g, t, c, b, sd, stream);
-  const int G = g ? g->G : 1;
-  LTHM_REQUIRE(G >= 1 && G <= RT_GMAX);
-  LTHM_REQUIRE(d->k <= RD_KMAX && d->N >= 1 && d->Q >= 1 && d->slab_rows >= 0);
-  LTHM_REQUIRE(d->items && d->q && d->scores && d->rows && d->workspace);
-  LTHM_REQUIRE(d->q_dtype == LTHM_F32 || d->q_dtype == LTHM_BF16);
-  LTHM_REQUIRE(retr_target_ok(d, sd));
-  LTHM_REQUIRE(((uintptr_t)d->items & 15) == 0 && ((uintptr_t)d->q & 15) == 0 && ((uintptr_t)d->workspace & 15) == 0);
-  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
-  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
-  LTHM_REQUIRE(retr_cursor_ok(c));
-  LTHM_REQUIRE(retr_bias_ok(b));
-  const int64_t need = lthm_retrieve_deep_ws_bytes(d->Q, G, d->N, d->k, d->slab_rows, x ? x->X : 0);
-  LTHM_REQUIRE(need >= 0 && d->ws_bytes >= need);
-  const int64_t U = d->Q, N = d->N;
-  const int gp = retr_gp(G);
-  const int64_t S = U * gp;
-  const int64_t sr = retr_deep_slab_rows(S, N, d->slab_rows);
-  const int64_t nslab = (N + sr - 1) / sr;
-  const int64_t stride = retr_deep_stride(sr, d->k);
-  hipStream_t s = (hipStream_t)stream;
-  unsigned char* ws = (unsigned char*)d->workspace;
-  bf16_t* qn = (bf16_t*)ws;
-  u64* keys = (u64*)(ws + up256(S * RT_D * 2));
-  int* pcnt = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * stride * 8));
-  int* xs = (int*)(ws + up256(S * RT_D * 2) + up256(nslab * U * stride * 8) + up256(nslab * U * 4));
-  const bf16_t* items = (const bf16_t*)d->items;
-  const unsigned pgrid = (unsigned)((U + 15) / 16);
-  const int32_t* ptrow = sd ? nullptr : d->target_row;  // shard: the prep kernel computes no target score
-  // the prep kernels of the k <= 128 calls: the plain one for G = 1, the slots for G >= 2
-  if (G == 1) {
-    if (d->q_dtype == LTHM_BF16)
-      hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, d->normalize_q, qn,
-                         items, N, ptrow, d->target_score, -INFINITY);
-    else
-      hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, d->normalize_q, qn,
-                         items, N, ptrow, d->target_score, -INFINITY);
-  } else {
-    if (d->q_dtype == LTHM_BF16)
-      hipLaunchKernelGGL((retr_prep_group_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)d->q, U, G, gp,
-                         d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
-    else
-      hipLaunchKernelGGL((retr_prep_group_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)d->q, U, G, gp,
-                         d->normalize_q, qn, items, N, ptrow, d->target_score, -INFINITY);
-  }
-  LTHM_CHECK_LAUNCH();
-  if (b && ptrow) {
-    retr_launch_bias_target(d, b, s);
-    LTHM_CHECK_LAUNCH();
-  }
-  RetrGroupArgs a;
-  a.items = items;
-  a.qn = qn;
-  a.trow = d->target_row;
-  a.tscore = sd ? sd->target_score_in : d->target_score;
-  a.shard = sd ? 1 : 0;
-  a.keys = keys;
-  a.pcnt = pcnt;
-  a.Q = S;
-  a.N = N;
-  a.slab_rows = sr;
-  a.k = d->k;
-  a.xs = nullptr;
-  a.xstride = 0;
-  a.U = U;
-  if (x) {
-    const int X = (int)x->X;
-    int P = 1;
-    while (P < X) P <<= 1;
-    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)U), dim3(256), 0, s, x->rows, X, P, N, xs);
-    LTHM_CHECK_LAUNCH();
-    a.xs = xs;
-    a.xstride = X + 1;
-  }
-  const dim3 tgrid((unsigned)((S + RT_QT - 1) / RT_QT), (unsigned)nslab);
-  if (gp == 1) retr_launch_deep<1>(tgrid, s, static_cast<const RetrExclArgs&>(a), (int)stride, t, c, b);
-  else if (gp == 2) retr_launch_deep<2>(tgrid, s, a, (int)stride, t, c, b);
-  else if (gp == 4) retr_launch_deep<4>(tgrid, s, a, (int)stride, t, c, b);
-  else retr_launch_deep<8>(tgrid, s, a, (int)stride, t, c, b);
-  LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_deep_merge_k, dim3((unsigned)((U + 3) / 4)), dim3(256), 0, s, keys, (int)stride, pcnt,
-                     d->target_row, U, N, (int)nslab, d->k, d->scores, d->rows, (d->target_row || sd) ? d->rank : nullptr,
-                     sd ? sd->target_score_in : nullptr);
-  LTHM_CHECK_LAUNCH();
-  return 0;
-}
-
-}  // namespace
 
 extern "C" int lthm_retrieve_topk_deep(const lthm_retrieve_desc* d, const lthm_retrieve_excl* x,
                                        const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                        const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b, void* stream) {
-  return retr_topk_deep_any(d, x, g, t, c, b, nullptr, stream);
+  return retr_scan(d, x, g, t, c, b, nullptr, stream);
 }
 
 // ---------------------------------------------------------------- sharded catalogues
@@ -1885,7 +1643,7 @@ extern "C" int lthm_retrieve_topk_shard(const lthm_retrieve_desc* d, const lthm_
                                         const lthm_retrieve_group* g, const lthm_retrieve_tags* t,
                                         const lthm_retrieve_cursor* c, const lthm_retrieve_bias* b,
                                         const lthm_retrieve_shard* s, void* stream) {
-  return retr_topk_deep_any(d, x, g, t, c, b, s, stream);
+  return retr_scan(d, x, g, t, c, b, s, stream);
 }
 
 extern "C" int lthm_retrieve_merge_shards(const float* scores, const int64_t* ids, const int32_t* ranks, int32_t S,
@@ -2876,7 +2634,7 @@ __global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__
 // the sizes both q8 entries share: rows per slab and slots per list, or false
 inline bool retr_q8_plan(int64_t Q, int64_t N, int32_t M, int32_t slab_rows, int64_t* sr, int64_t* stride) {
   if (M < 1 || M > RD_KMAX || slab_rows < 0) return false;
-  *sr = retr_deep_slab_rows(Q, N, slab_rows);
+  *sr = retr_slab_rows(Q, N, slab_rows, 4 * RD_KMAX);
   if (*sr < 0) return false;
   *stride = retr_deep_stride(*sr, M);
   return true;

@@ -421,69 +421,9 @@ Tensor item_artifact_cuda(const Tensor& ids_, const Tensor& W, int64_t K, int64_
 }
 
 // ---------------------------------------------------------------- full-catalogue top-K (forward only)
-// excl: the exclusion lists (int32 [Q, X]) of retrieve_topk_excl, or null for the plain op
-std::tuple<Tensor, Tensor> retrieve_topk_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
-                                              const Tensor* excl) {
-  on_gpu(q_, "q");
-  on_gpu(items_, "items");
-  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
-              "items must be a bf16 [N, 128] catalogue");
-  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128, "q must be [Q, 128]");
-  TORCH_CHECK(k >= 1 && k <= 128, "k must be in 1..128, got ", k);
-  TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk takes a non-empty catalogue and query set");
-  auto q = q_.contiguous(), items = items_.contiguous();
-  const int64_t Q = q.size(0), N = items.size(0);
-  Tensor xr;
-  if (excl) {
-    on_gpu(*excl, "exclude_rows");
-    TORCH_CHECK(excl->scalar_type() == at::kInt && excl->dim() == 2 && excl->size(0) == Q,
-                "exclude_rows must be int32 [Q, X]");
-    TORCH_CHECK(excl->size(1) >= 1 && excl->size(1) <= 1024, "exclude_rows takes 1..1024 rows per query, got ",
-                excl->size(1));
-    TORCH_CHECK(excl->device() == q.device(), "exclude_rows must be on the queries' device");
-    xr = excl->contiguous();
-  }
-  const int64_t need = excl ? lthm_retrieve_excl_ws_bytes(Q, N, (int32_t)k, 0, xr.size(1))
-                            : lthm_retrieve_ws_bytes(Q, N, (int32_t)k, 0);
-  TORCH_CHECK(need >= 0, "retrieve_topk: unsupported sizes Q=", Q, " N=", N);
-  auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
-  auto rows = at::empty({Q, k}, q.options().dtype(at::kInt));
-  auto ws = at::empty({need}, q.options().dtype(at::kByte));
-  lthm_retrieve_desc d = {};
-  d.items = items.data_ptr();
-  d.q = q.data_ptr();
-  d.scores = scores.data_ptr<float>();
-  d.rows = rows.data_ptr<int32_t>();
-  d.workspace = ws.data_ptr();
-  d.ws_bytes = need;
-  d.Q = Q;
-  d.N = N;
-  d.k = (int32_t)k;
-  d.q_dtype = dcode(q);
-  d.normalize_q = normalize_q ? 1 : 0;
-  if (excl) {
-    lthm_retrieve_excl x = {};
-    x.rows = xr.data_ptr<int32_t>();
-    x.X = xr.size(1);
-    hip_ok(lthm_retrieve_topk_excl(&d, &x, cur_stream()), "lthm_retrieve_topk_excl");
-  } else {
-    hip_ok(lthm_retrieve_topk(&d, cur_stream()), "lthm_retrieve_topk");
-  }
-  return std::make_tuple(scores, rows);
-}
-
-std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q) {
-  return retrieve_topk_impl(q, items, k, normalize_q, nullptr);
-}
-
-std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
-                                                   const Tensor& exclude_rows) {
-  return retrieve_topk_impl(q, items, k, normalize_q, &exclude_rows);
-}
-
-// q [U, G, 128]: an item's score is its best over the user's G <= 8 queries; exclude_rows is one
-// list per user (int32 [U, X]) or None; tags (int32 [N]) and filter (int32 [U, 3]) are both null
-// or both given
+// Every scan op.  q [U, G, 128]: an item's score is its best over the user's G <= 8 queries (the ops
+// unsqueeze a 2-D q to groups of one); exclude_rows is one list per user (int32 [U, X]) or None;
+// tags (int32 [N]) and filter (int32 [U, 3]) are both null or both given, as are the cursor's two
 std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tensor& items_, int64_t k, bool normalize_q,
                                                     const c10::optional<Tensor>& exclude_rows, const Tensor* tags_,
                                                     const Tensor* filter_, const Tensor* after_scores_ = nullptr,
@@ -493,9 +433,9 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   on_gpu(items_, "items");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
               "items must be a bf16 [N, 128] catalogue");
-  TORCH_CHECK(q_.dim() == 3 && q_.size(2) == 128, "q must be [U, G, 128]");
+  TORCH_CHECK(q_.dim() == 3 && q_.size(2) == 128, "q must be [Q, 128] or [U, G, 128]");
   TORCH_CHECK(q_.size(1) >= 1 && q_.size(1) <= 8, "retrieve_topk_group takes 1..8 queries per user, got ", q_.size(1));
-  // deep: lthm_retrieve_topk_deep, every part of which may be absent
+  // the k cap is the op's: 1024 for the deep op, 128 for the others
   TORCH_CHECK(k >= 1 && k <= (deep ? 1024 : 128), "k must be in 1..", deep ? 1024 : 128, ", got ", k);
   TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_topk_group takes a non-empty catalogue and user set");
   auto q = q_.contiguous(), items = items_.contiguous();
@@ -505,9 +445,9 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   if (excl) {
     on_gpu(*exclude_rows, "exclude_rows");
     TORCH_CHECK(exclude_rows->scalar_type() == at::kInt && exclude_rows->dim() == 2 && exclude_rows->size(0) == U,
-                "exclude_rows must be int32 [U, X], one list per user");
+                "exclude_rows must be int32 [Q, X], one list per query (per user for a 3-D q)");
     TORCH_CHECK(exclude_rows->size(1) >= 1 && exclude_rows->size(1) <= 1024,
-                "exclude_rows takes 1..1024 rows per user, got ", exclude_rows->size(1));
+                "exclude_rows takes 1..1024 rows per query (per user for a 3-D q), got ", exclude_rows->size(1));
     TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
     xr = exclude_rows->contiguous();
   }
@@ -552,8 +492,7 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
       bw = bias_weight_->contiguous();
     }
   }
-  const int64_t need = deep ? lthm_retrieve_deep_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0)
-                            : lthm_retrieve_group_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
+  const int64_t need = lthm_retrieve_deep_ws_bytes(U, (int32_t)G, N, (int32_t)k, 0, excl ? xr.size(1) : 0);
   TORCH_CHECK(need >= 0, "retrieve_topk_group: unsupported sizes U=", U, " G=", G, " N=", N);
   auto scores = at::empty({U, k}, q.options().dtype(at::kFloat));
   auto rows = at::empty({U, k}, q.options().dtype(at::kInt));
@@ -570,6 +509,7 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   d.k = (int32_t)k;
   d.q_dtype = dcode(q);
   d.normalize_q = normalize_q ? 1 : 0;
+  // one call, lthm_retrieve_topk_deep, with the parts that are present: it picks the kernels by k and G
   lthm_retrieve_excl x = {};
   if (excl) {
     x.rows = xr.data_ptr<int32_t>();
@@ -577,67 +517,42 @@ std::tuple<Tensor, Tensor> retrieve_topk_group_impl(const Tensor& q_, const Tens
   }
   lthm_retrieve_group g = {};
   g.G = (int32_t)G;
-  if (deep) {
-    lthm_retrieve_tags t = {};
-    if (tags_) {
-      t.tags = tg.data_ptr<int32_t>();
-      t.filter = tf.data_ptr<int32_t>();
-    }
-    lthm_retrieve_cursor c = {};
-    if (after_scores_) {
-      c.after_score = cs.data_ptr<float>();
-      c.after_row = cr.data_ptr<int32_t>();
-    }
-    lthm_retrieve_bias b = {};
-    if (bias_) {
-      b.bias = bs.data_ptr<float>();
-      b.weight = bias_weight_ ? bw.data_ptr<float>() : nullptr;
-    }
-    hip_ok(lthm_retrieve_topk_deep(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, after_scores_ ? &c : nullptr,
-                                   bias_ ? &b : nullptr, cur_stream()),
-           "lthm_retrieve_topk_deep");
-  } else if (bias_) {
-    lthm_retrieve_tags t = {};
-    if (tags_) {
-      t.tags = tg.data_ptr<int32_t>();
-      t.filter = tf.data_ptr<int32_t>();
-    }
-    lthm_retrieve_cursor c = {};
-    if (after_scores_) {
-      c.after_score = cs.data_ptr<float>();
-      c.after_row = cr.data_ptr<int32_t>();
-    }
-    lthm_retrieve_bias b = {};
-    b.bias = bs.data_ptr<float>();
-    b.weight = bias_weight_ ? bw.data_ptr<float>() : nullptr;
-    hip_ok(lthm_retrieve_topk_bias(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, after_scores_ ? &c : nullptr, &b,
-                                   cur_stream()),
-           "lthm_retrieve_topk_bias");
-  } else if (after_scores_) {
-    lthm_retrieve_tags t = {};
-    if (tags_) {
-      t.tags = tg.data_ptr<int32_t>();
-      t.filter = tf.data_ptr<int32_t>();
-    }
-    lthm_retrieve_cursor c = {};
-    c.after_score = cs.data_ptr<float>();
-    c.after_row = cr.data_ptr<int32_t>();
-    hip_ok(lthm_retrieve_topk_after(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, &c, cur_stream()),
-           "lthm_retrieve_topk_after");
-  } else if (tags_) {
-    lthm_retrieve_tags t = {};
+  lthm_retrieve_tags t = {};
+  if (tags_) {
     t.tags = tg.data_ptr<int32_t>();
     t.filter = tf.data_ptr<int32_t>();
-    hip_ok(lthm_retrieve_topk_tags(&d, excl ? &x : nullptr, &g, &t, cur_stream()), "lthm_retrieve_topk_tags");
-  } else {
-    hip_ok(lthm_retrieve_topk_group(&d, excl ? &x : nullptr, &g, cur_stream()), "lthm_retrieve_topk_group");
   }
+  lthm_retrieve_cursor c = {};
+  if (after_scores_) {
+    c.after_score = cs.data_ptr<float>();
+    c.after_row = cr.data_ptr<int32_t>();
+  }
+  lthm_retrieve_bias b = {};
+  if (bias_) {
+    b.bias = bs.data_ptr<float>();
+    b.weight = bias_weight_ ? bw.data_ptr<float>() : nullptr;
+  }
+  hip_ok(lthm_retrieve_topk_deep(&d, excl ? &x : nullptr, &g, tags_ ? &t : nullptr, after_scores_ ? &c : nullptr,
+                                 bias_ ? &b : nullptr, cur_stream()),
+         "lthm_retrieve_topk_deep");
   return std::make_tuple(scores, rows);
 }
 
 std::tuple<Tensor, Tensor> retrieve_topk_group_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
                                                     const c10::optional<Tensor>& exclude_rows) {
   return retrieve_topk_group_impl(q, items, k, normalize_q, exclude_rows, nullptr, nullptr);
+}
+
+// q [Q, 128]: a group of one query
+std::tuple<Tensor, Tensor> retrieve_topk_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q) {
+  TORCH_CHECK(q.dim() == 2, "q must be [Q, 128]");
+  return retrieve_topk_group_impl(q.unsqueeze(1), items, k, normalize_q, c10::nullopt, nullptr, nullptr);
+}
+
+std::tuple<Tensor, Tensor> retrieve_topk_excl_cuda(const Tensor& q, const Tensor& items, int64_t k, bool normalize_q,
+                                                   const Tensor& exclude_rows) {
+  TORCH_CHECK(q.dim() == 2, "q must be [Q, 128]");
+  return retrieve_topk_group_impl(q.unsqueeze(1), items, k, normalize_q, exclude_rows, nullptr, nullptr);
 }
 
 // q [Q, 128] or [U, G, 128]; a 2-D q is a group of one query

@@ -1734,20 +1734,20 @@ def retrieve_deep_passes(k: int):
     return [RETRIEVE_MAX_K] * full + ([rest] if rest else [])
 
 
-def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, slab_rows, exclude_rows, tags, tag_filter,
-                        after_scores, after_rows, bias, bias_weight, target_scores=None):
-    """RETRIEVE_MAX_K < k <= RETRIEVE_MAX_DEEP in one scan of the catalogue: lthm_retrieve_topk_deep
-    (csrc/retrieve.hip, retr_deep_topk_k and retr_deep_merge_k).  q [Q, 128] (who = retrieve_topk)
-    or [U, G, 128]; everything else as the caller documents it.  With target_scores (f32 [Q] or [U])
-    the call is lthm_retrieve_topk_shard, for every k in 1..RETRIEVE_MAX_DEEP: the scan of one shard
-    of a catalogue, which counts rank against the given scores."""
+def _retrieve_scan(who: str, q, items, k: int, kmax: int, normalize_q, target_rows, slab_rows, exclude_rows, tags,
+                   tag_filter, after_scores, after_rows, bias, bias_weight, target_scores):
+    """The one call path of retrieve_topk (q [Q, 128]) and retrieve_topk_group (q [U, G, 128]), which
+    document the arguments: k in 1..kmax from one scan of the catalogue (csrc/retrieve.hip, retr_scan).
+    The call is lthm_retrieve_topk_deep with the parts that are present, which picks the kernels by
+    k and G; with target_scores it is lthm_retrieve_topk_shard, the scan of one shard of a catalogue,
+    which counts rank against the given scores."""
     import ctypes
     from ._lib import STRUCTS
     grouped = who == "retrieve_topk_group"
-    per = "U" if grouped else "Q"
+    per, one = ("U", "user") if grouped else ("Q", "query")
     k = int(k)
-    _check((RETRIEVE_MAX_K if target_scores is None else 0) < k <= RETRIEVE_MAX_DEEP,
-           f"a deep list takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    _check(1 <= k <= kmax, f"{who} takes k in 1..{kmax} (got {k}"
+                           + (f"; deep=True takes up to {RETRIEVE_MAX_DEEP})" if kmax < RETRIEVE_MAX_DEEP else ")"))
     require_gpu(q, items, target_rows, exclude_rows, target_scores)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
@@ -1757,50 +1757,46 @@ def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, sl
         G = q.shape[1]
         _check(1 <= G <= RETRIEVE_MAX_GROUP, f"{who} takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
     else:
-        _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries")
+        _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH,
+               f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
         G = 1
     U, N = q.shape[0], items.shape[0]
-    _check(N >= 1 and U >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, {per}={U})")
-    X = 0
+    _check(N >= 1 and U >= 1, f"{who} takes a non-empty catalogue and at least one {one} (N={N}, {per}={U})")
+    dev = q.device
+    x, X = None, 0
     if exclude_rows is not None:
         _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == U,
-               f"exclude_rows must be int32 [{per}, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, {per}={U})")
+               f"exclude_rows must be int32 [{per}, X], one list per {one} (got {exclude_rows.dtype} "
+               f"{tuple(exclude_rows.shape)}, {per}={U})")
         X = exclude_rows.shape[1]
-        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows (got {X})")
-        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
-        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per {one} (got {X})")
+        _check(exclude_rows.device == dev, "exclude_rows must be on the queries' device")
+        x = STRUCTS["lthm_retrieve_excl"]()
+        x.rows, x.X = ptr(exclude_rows), X
     if target_rows is not None:
         _check(target_rows.dtype == torch.int32 and target_rows.shape == (U,), f"target_rows must be int32 [{per}]")
     need = load().lthm_retrieve_deep_ws_bytes(U, G, N, k, int(slab_rows), X)
     _check(need >= 0, f"{who}: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
                       f"that cuts N={N} into at most 65535 slabs ({per}={U} G={G} k={k} X={X})")
-    q = q.contiguous()
-    dev = q.device
     scores = torch.empty((U, k), dtype=torch.float32, device=dev)
     rows = torch.empty((U, k), dtype=torch.int32, device=dev)
-    rank = tscore = None
-    if target_rows is not None:
-        rank = torch.empty(U, dtype=torch.int32, device=dev)
-        tscore = torch.empty(U, dtype=torch.float32, device=dev)
-    sh = None
+    rank = tscore = sh = None
     if target_scores is not None:
         _check(target_scores.dtype == torch.float32 and tuple(target_scores.shape) == (U,),
                f"target_scores must be f32 [{per}] (got {target_scores.dtype} {tuple(target_scores.shape)}, {per}={U})")
         _check(target_scores.device == dev, "target_scores must be on the queries' device")
-        rank = torch.empty(U, dtype=torch.int32, device=dev)
-        tscore = None  # the call writes none: the caller's are the target scores
+        rank = torch.empty(U, dtype=torch.int32, device=dev)  # the call writes no target score: the caller's are
         sh = STRUCTS["lthm_retrieve_shard"]()
         sh.target_score_in = ptr(target_scores)
+    elif target_rows is not None:
+        rank = torch.empty(U, dtype=torch.int32, device=dev)
+        tscore = torch.empty(U, dtype=torch.float32, device=dev)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     d = STRUCTS["lthm_retrieve_desc"]()
     d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
     d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
     d.workspace, d.ws_bytes = ptr(ws), need
     d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = U, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
-    x = None
-    if exclude_rows is not None:
-        x = STRUCTS["lthm_retrieve_excl"]()
-        x.rows, x.X = ptr(exclude_rows), X
     g = None
     if grouped:
         g = STRUCTS["lthm_retrieve_group"]()
@@ -1808,17 +1804,24 @@ def _retrieve_deep_scan(who: str, q, items, k: int, normalize_q, target_rows, sl
     t = _retrieve_tags(who, tags, tag_filter, items, U, per)
     c = _retrieve_cursor(who, after_scores, after_rows, U, per, dev)
     b, bw = _retrieve_bias(who, bias, bias_weight, items, U, per, dev)
-    addr = lambda o: ctypes.addressof(o) if o is not None else None
+    # the timer's record: the key names the narrowest entry point that takes the call
+    if sh is not None:
+        key = "retr_shard_topk_k"
+    elif k > RETRIEVE_MAX_K:
+        key = "retr_deep_topk_k"
+    else:
+        part = "bias_" if b is not None else "after_" if c is not None else "tags_" if t is not None \
+            else "excl_" if x is not None and not grouped else ""
+        key = f"retr_topk_{'group_' if grouped else ''}{part}k"
     nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X) \
         + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0) \
-        + (4.0 * N if b is not None else 0.0) + (4.0 * U if bw is not None else 0.0)
+        + (4.0 * N if b is not None else 0.0) + (4.0 * U if bw is not None else 0.0) + (4.0 * U if sh is not None else 0.0)
+    parts = [ctypes.addressof(o) if o is not None else None for o in (d, x, g, t, c, b)]
     if sh is not None:
-        call("lthm_retrieve_topk_shard", addr(d), addr(x), addr(g), addr(t), addr(c), addr(b), addr(sh), stream(),
-             _key="retr_shard_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * U)
-        return scores, rows, rank, target_scores
-    call("lthm_retrieve_topk_deep", addr(d), addr(x), addr(g), addr(t), addr(c), addr(b), stream(),
-         _key="retr_deep_topk_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
-    return scores, rows, rank, tscore
+        parts.append(ctypes.addressof(sh))
+    call("lthm_retrieve_topk_shard" if sh is not None else "lthm_retrieve_topk_deep", *parts, stream(),
+         _key=key, _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
+    return scores, rows, rank, target_scores if sh is not None else tscore
 
 
 def retrieve_target_score(q, items, target_rows, *, normalize_q: bool = True, bias=None, bias_weight=None):
@@ -1904,6 +1907,23 @@ def _retrieve_deep(call, q, items, k: int, target_rows, after_scores, after_rows
     return torch.cat(parts_s, dim=1), torch.cat(parts_r, dim=1), rank, tscore
 
 
+def _retrieve_call(fn, q, items, k: int, deep, *, target_rows, after_scores, after_rows, target_scores, **kw):
+    """retrieve_topk or retrieve_topk_group (fn): the deep / "paged" handling, then the scan."""
+    who = fn.__name__
+    bias, bias_weight = kw["bias"], kw["bias_weight"]
+    _check(bias is not None or bias_weight is None, f"{who} takes a bias_weight only with a bias")
+    _check(target_scores is None or deep != "paged", f'{who} takes target_scores with deep=False or True, not "paged"')
+    if target_scores is None and deep and int(k) > RETRIEVE_MAX_K:
+        _check(not isinstance(deep, str) or deep == "paged", f'{who} takes deep=False, True or "paged" (got {deep!r})')
+        if deep == "paged":
+            if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):  # one tensor for all passes
+                per = "U" if fn is retrieve_topk_group else "Q"
+                kw["bias_weight"] = _retrieve_bias(who, bias, bias_weight, items, q.shape[0], per, q.device)[1]
+            return _retrieve_deep(fn, q, items, k, target_rows, after_scores, after_rows, kw)
+    return _retrieve_scan(who, q, items, k, RETRIEVE_MAX_DEEP if deep else RETRIEVE_MAX_K, target_rows=target_rows,
+                          after_scores=after_scores, after_rows=after_rows, target_scores=target_scores, **kw)
+
+
 def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=None, slab_rows: int = 0,
                   exclude_rows=None, tags=None, tag_filter=None, after_scores=None, after_rows=None,
                   deep: bool = False, bias=None, bias_weight=None, target_scores=None):
@@ -1960,100 +1980,10 @@ def retrieve_topk(q, items, k: int, *, normalize_q: bool = True, target_rows=Non
     target_scores[q], for every query, -1 where target_scores[q] is NaN; scores and rows are those
     of the call without it, and the target_score returned is the tensor given.  deep="paged" does
     not take it."""
-    import ctypes
-    from ._lib import STRUCTS
-    _check(bias is not None or bias_weight is None, "retrieve_topk takes a bias_weight only with a bias")
-    if target_scores is not None:
-        _check(deep != "paged", 'retrieve_topk takes target_scores with deep=False or True, not "paged"')
-        _check(deep or int(k) <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k}; deep=True takes "
-                                                 f"up to {RETRIEVE_MAX_DEEP})")
-        return _retrieve_deep_scan("retrieve_topk", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
-                                   tag_filter, after_scores, after_rows, bias, bias_weight, target_scores=target_scores)
-    if deep and int(k) > RETRIEVE_MAX_K:
-        _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk takes deep=False, True or "paged" (got {deep!r})')
-        if deep != "paged":
-            return _retrieve_deep_scan("retrieve_topk", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
-                                       tag_filter, after_scores, after_rows, bias, bias_weight)
-        if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
-            bias_weight = _retrieve_bias("retrieve_topk", bias, bias_weight, items, q.shape[0], "Q", q.device)[1]
-        return _retrieve_deep(retrieve_topk, q, items, k, target_rows, after_scores, after_rows,
-                              dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
-                                   tag_filter=tag_filter, bias=bias, bias_weight=bias_weight))
-    require_gpu(q, items, target_rows, exclude_rows)
-    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
-           f"retrieve_topk takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
-    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"retrieve_topk takes [Q, {RETRIEVE_WIDTH}] queries")
-    Q, N, k = q.shape[0], items.shape[0], int(k)
-    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk takes k in 1..{RETRIEVE_MAX_K} (got {k}; deep=True takes "
-                                     f"up to {RETRIEVE_MAX_DEEP})")
-    _check(N >= 1 and Q >= 1, f"retrieve_topk takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
-    need = load().lthm_retrieve_ws_bytes(Q, N, k, int(slab_rows))
-    _check(need >= 0, f"retrieve_topk: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
-                      f"that cuts N={N} into at most 65535 slabs")
-    X = 0
-    if exclude_rows is not None:
-        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == Q,
-               f"exclude_rows must be int32 [Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, Q={Q})")
-        X = exclude_rows.shape[1]
-        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
-        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
-        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
-        need = load().lthm_retrieve_excl_ws_bytes(Q, N, k, int(slab_rows), X)
-        _check(need >= 0, f"retrieve_topk: no workspace size for Q={Q} N={N} k={k} X={X}")
-    dev = q.device
-    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
-    rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
-    rank = tscore = None
-    if target_rows is not None:
-        _check(target_rows.dtype == torch.int32 and target_rows.shape == (Q,), "target_rows must be int32 [Q]")
-        rank = torch.empty(Q, dtype=torch.int32, device=dev)
-        tscore = torch.empty(Q, dtype=torch.float32, device=dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    d = STRUCTS["lthm_retrieve_desc"]()
-    d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
-    d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
-    d.workspace, d.ws_bytes = ptr(ws), need
-    d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = Q, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
-    nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + Q * k * 8)
-    t = _retrieve_tags("retrieve_topk", tags, tag_filter, items, Q, "Q")
-    c = _retrieve_cursor("retrieve_topk", after_scores, after_rows, Q, "Q", dev)
-    b, bw = _retrieve_bias("retrieve_topk", bias, bias_weight, items, Q, "Q", dev)
-    if b is not None:
-        x = None
-        if exclude_rows is not None:
-            x = STRUCTS["lthm_retrieve_excl"]()
-            x.rows, x.X = ptr(exclude_rows), X
-        call("lthm_retrieve_topk_bias", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
-             ctypes.addressof(t) if t is not None else None, ctypes.addressof(c) if c is not None else None,
-             ctypes.addressof(b), stream(), _key="retr_topk_bias_k", _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
-             _bytes=nbytes + 4.0 * Q * X + (4.0 * N + 12.0 * Q if t is not None else 0.0)
-             + (8.0 * Q if c is not None else 0.0) + 4.0 * N + (4.0 * Q if bw is not None else 0.0))
-    elif c is not None:
-        x = None
-        if exclude_rows is not None:
-            x = STRUCTS["lthm_retrieve_excl"]()
-            x.rows, x.X = ptr(exclude_rows), X
-        call("lthm_retrieve_topk_after", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
-             ctypes.addressof(t) if t is not None else None, ctypes.addressof(c), stream(), _key="retr_topk_after_k",
-             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
-             _bytes=nbytes + 4.0 * Q * X + (4.0 * N + 12.0 * Q if t is not None else 0.0) + 8.0 * Q)
-    elif t is not None:
-        x = None
-        if exclude_rows is not None:
-            x = STRUCTS["lthm_retrieve_excl"]()
-            x.rows, x.X = ptr(exclude_rows), X
-        call("lthm_retrieve_topk_tags", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None, None,
-             ctypes.addressof(t), stream(), _key="retr_topk_tags_k", _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop",
-             _bytes=nbytes + 4.0 * Q * X + 4.0 * N + 12.0 * Q)
-    elif exclude_rows is None:
-        call("lthm_retrieve_topk", ctypes.addressof(d), stream(), _key="retr_topk_k",
-             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes)
-    else:
-        x = STRUCTS["lthm_retrieve_excl"]()
-        x.rows, x.X = ptr(exclude_rows), X
-        call("lthm_retrieve_topk_excl", ctypes.addressof(d), ctypes.addressof(x), stream(), _key="retr_topk_excl_k",
-             _work=2.0 * Q * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * Q * X)
-    return scores, rows, rank, tscore
+    return _retrieve_call(retrieve_topk, q, items, k, deep, normalize_q=normalize_q, target_rows=target_rows,
+                          slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags, tag_filter=tag_filter,
+                          after_scores=after_scores, after_rows=after_rows, bias=bias, bias_weight=bias_weight,
+                          target_scores=target_scores)
 
 
 RETRIEVE_MAX_GROUP = 8        # RT_GMAX: the most queries of one user
@@ -2081,91 +2011,10 @@ def retrieve_topk_group(q, items, k: int, *, normalize_q: bool = True, target_ro
     weight per user): the prior is added to the best-over-queries score, fma(w[u], bias[j],
     max_g s_g[u, j]), which equals the best biased score since the fma is monotone in the dot.
     target_scores f32 [U], the targets' scores for one shard of a catalogue, is retrieve_topk's too."""
-    import ctypes
-    from ._lib import STRUCTS
-    _check(bias is not None or bias_weight is None, "retrieve_topk_group takes a bias_weight only with a bias")
-    if target_scores is not None:
-        _check(deep != "paged", 'retrieve_topk_group takes target_scores with deep=False or True, not "paged"')
-        _check(deep or int(k) <= RETRIEVE_MAX_K, f"retrieve_topk_group takes k in 1..{RETRIEVE_MAX_K} (got {k})")
-        return _retrieve_deep_scan("retrieve_topk_group", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows,
-                                   tags, tag_filter, after_scores, after_rows, bias, bias_weight,
-                                   target_scores=target_scores)
-    if deep and int(k) > RETRIEVE_MAX_K:
-        _check(not isinstance(deep, str) or deep == "paged", f'retrieve_topk_group takes deep=False, True or "paged" (got {deep!r})')
-        if deep != "paged":
-            return _retrieve_deep_scan("retrieve_topk_group", q, items, k, normalize_q, target_rows, slab_rows, exclude_rows, tags,
-                                       tag_filter, after_scores, after_rows, bias, bias_weight)
-        if bias is not None and bias_weight is not None and not isinstance(bias_weight, torch.Tensor):
-            bias_weight = _retrieve_bias("retrieve_topk_group", bias, bias_weight, items, q.shape[0], "U", q.device)[1]
-        return _retrieve_deep(retrieve_topk_group, q, items, k, target_rows, after_scores, after_rows,
-                              dict(normalize_q=normalize_q, slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags,
-                                   tag_filter=tag_filter, bias=bias, bias_weight=bias_weight))
-    require_gpu(q, items, target_rows, exclude_rows)
-    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
-           f"retrieve_topk_group takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
-    _check(q.dim() == 3 and q.shape[2] == RETRIEVE_WIDTH,
-           f"retrieve_topk_group takes [U, G, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
-    U, G, N, k = q.shape[0], q.shape[1], items.shape[0], int(k)
-    _check(1 <= G <= RETRIEVE_MAX_GROUP, f"retrieve_topk_group takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
-    _check(1 <= k <= RETRIEVE_MAX_K, f"retrieve_topk_group takes k in 1..{RETRIEVE_MAX_K} (got {k})")
-    _check(N >= 1 and U >= 1, f"retrieve_topk_group takes a non-empty catalogue and at least one user (N={N}, U={U})")
-    X = 0
-    if exclude_rows is not None:
-        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == U,
-               f"exclude_rows must be int32 [U, X], one list per user (got {exclude_rows.dtype} "
-               f"{tuple(exclude_rows.shape)}, U={U})")
-        X = exclude_rows.shape[1]
-        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per user (got {X})")
-        _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
-    if target_rows is not None:
-        _check(target_rows.dtype == torch.int32 and target_rows.shape == (U,), "target_rows must be int32 [U]")
-    need = load().lthm_retrieve_group_ws_bytes(U, G, N, k, int(slab_rows), X)
-    _check(need >= 0, f"retrieve_topk_group: slab_rows={slab_rows} is not 0 or a multiple of {RETRIEVE_MIN_SLAB_ROWS} "
-                      f"that cuts N={N} into at most 65535 slabs (U={U} G={G} k={k} X={X})")
-    dev = q.device
-    scores = torch.empty((U, k), dtype=torch.float32, device=dev)
-    rows = torch.empty((U, k), dtype=torch.int32, device=dev)
-    rank = tscore = None
-    if target_rows is not None:
-        rank = torch.empty(U, dtype=torch.int32, device=dev)
-        tscore = torch.empty(U, dtype=torch.float32, device=dev)
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    d = STRUCTS["lthm_retrieve_desc"]()
-    d.items, d.q, d.target_row = ptr(items), ptr(q), ptr(target_rows)
-    d.scores, d.rows, d.rank, d.target_score = ptr(scores), ptr(rows), ptr(rank), ptr(tscore)
-    d.workspace, d.ws_bytes = ptr(ws), need
-    d.Q, d.N, d.k, d.q_dtype, d.normalize_q, d.slab_rows = U, N, k, dcode(q), int(bool(normalize_q)), int(slab_rows)
-    x = None
-    if exclude_rows is not None:
-        x = STRUCTS["lthm_retrieve_excl"]()
-        x.rows, x.X = ptr(exclude_rows), X
-    g = STRUCTS["lthm_retrieve_group"]()
-    g.G = G
-    nbytes = float(N * RETRIEVE_WIDTH * 2 + q.numel() * q.element_size() + U * k * 8 + 4.0 * U * X)
-    t = _retrieve_tags("retrieve_topk_group", tags, tag_filter, items, U, "U")
-    c = _retrieve_cursor("retrieve_topk_group", after_scores, after_rows, U, "U", dev)
-    b, bw = _retrieve_bias("retrieve_topk_group", bias, bias_weight, items, U, "U", dev)
-    if b is not None:
-        call("lthm_retrieve_topk_bias", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
-             ctypes.addressof(g), ctypes.addressof(t) if t is not None else None,
-             ctypes.addressof(c) if c is not None else None, ctypes.addressof(b), stream(),
-             _key="retr_topk_group_bias_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
-             _bytes=nbytes + (4.0 * N + 12.0 * U if t is not None else 0.0) + (8.0 * U if c is not None else 0.0)
-             + 4.0 * N + (4.0 * U if bw is not None else 0.0))
-    elif c is not None:
-        call("lthm_retrieve_topk_after", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
-             ctypes.addressof(g), ctypes.addressof(t) if t is not None else None, ctypes.addressof(c), stream(),
-             _key="retr_topk_group_after_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop",
-             _bytes=nbytes + (4.0 * N + 12.0 * U if t is not None else 0.0) + 8.0 * U)
-    elif t is not None:
-        call("lthm_retrieve_topk_tags", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
-             ctypes.addressof(g), ctypes.addressof(t), stream(), _key="retr_topk_group_tags_k",
-             _work=2.0 * U * G * N * RETRIEVE_WIDTH, _unit="flop", _bytes=nbytes + 4.0 * N + 12.0 * U)
-    else:
-        call("lthm_retrieve_topk_group", ctypes.addressof(d), ctypes.addressof(x) if x is not None else None,
-             ctypes.addressof(g), stream(), _key="retr_topk_group_k", _work=2.0 * U * G * N * RETRIEVE_WIDTH,
-             _unit="flop", _bytes=nbytes)
-    return scores, rows, rank, tscore
+    return _retrieve_call(retrieve_topk_group, q, items, k, deep, normalize_q=normalize_q, target_rows=target_rows,
+                          slab_rows=slab_rows, exclude_rows=exclude_rows, tags=tags, tag_filter=tag_filter,
+                          after_scores=after_scores, after_rows=after_rows, bias=bias, bias_weight=bias_weight,
+                          target_scores=target_scores)
 
 
 RETRIEVE_MAX_PROBE = RETRIEVE_MAX_SHARDS  # the most lists one query probes: the merge's RS_SMAX
