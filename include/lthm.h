@@ -1059,6 +1059,48 @@ int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids,
                            const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q, const int32_t* probes,
                            int32_t P, int32_t k, const lthm_retrieve_excl* x, float* out_scores, int64_t* out_ids,
                            void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_ivf_topk_filt: lthm_retrieve_ivf_topk with tag filters, a score prior and a cursor per
+ * query, each under the rules of the flat entries (lthm_retrieve_topk_tags / _bias / _after) and applied
+ * in their order: the prior, then exclusion, the tag filter and the cursor.
+ *   t   NULL, or tags int32 [N] in this catalogue's own (clustered) row numbering and filter int32
+ *       [Q, 3] = (all, any, none); both non-null, 4-byte aligned; tags is never read at or past the end
+ *       of a probed list (<= N).  An ineligible row takes no slot; (0, 0, 0) gives the rows of the call
+ *       without tags and an unsatisfiable filter (all & none != 0) an empty list
+ *   b   NULL, or bias f32 [N] in the clustered numbering (non-null, every value finite) and weight f32
+ *       [Q] or NULL (1 for every query), 4-byte aligned: the score of a row is fmaf(weight[q], bias[row],
+ *       dot) in f32, bit for bit the score lthm_retrieve_topk_bias returns for the same (query, item),
+ *       and the order, the cursor and the scores written see that value only.  weight = 0 or an all-zero
+ *       bias gives the rows of the call without a prior
+ *   c   NULL, or a cursor per query: after_score f32 [Q] (4-byte aligned) and after_id int64 [Q] (8-byte
+ *       aligned), both non-null.  An item with score s and id i is eligible iff s < after_score[q] or
+ *       (s == after_score[q] and i > after_id[q]), in f32: -0 equals +0; +inf gives the rows of the call
+ *       without a cursor; -inf or NaN admits nothing, so the (-inf, 0) tail of an exhausted page gives an
+ *       empty page.  The cursor holds an id, not a row, since ids ascend with the rows inside a list only:
+ *       the call turns it into one cursor row per (query, probed list) by a binary search over that
+ *       list's row_ids, so after_id need not be an id of a probed list, nor of the catalogue.  With the
+ *       same probes, a page's last (score, id) as the next call's cursor yields the following k items
+ * The result is the k first, under (score descending, id ascending), of the rows that lie in a probed
+ * list, are not excluded, pass the filter and lie strictly behind the cursor, then (-inf, 0); with
+ * every list probed it is the flat entry's result for the same arguments.  t, b and c compose with x
+ * and with each other.  With t, b and c all NULL the call is lthm_retrieve_ivf_topk: the same kernels
+ * and the same bits.  Every pointer, alignment and range check is made before any launch.
+ *   workspace lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, P, k, X, has_cursor) bytes: has_cursor = 0 gives
+ *             lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X), has_cursor != 0 adds the Q P cursor rows; -1
+ *             where that is -1
+ * With c the call runs one more kernel ahead of the scan (one thread per pair); nothing else changes:
+ * no host synchronisation, the same grid, and the outputs stay a pure function of the inputs. */
+typedef struct lthm_retrieve_ivf_cursor {
+  const float* after_score;
+  const int64_t* after_id;
+} lthm_retrieve_ivf_cursor;
+int64_t lthm_retrieve_ivf_filt_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X,
+                                        int32_t has_cursor);
+int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
+                                int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
+                                const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
+                                const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
+                                const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
+                                void* workspace, int64_t ws_bytes, void* stream);
 /* Diversified lists: greedy maximal-marginal-relevance (MMR) selection of k out of a pool of M
  * candidates per query, with an optional cap on the selected items of one group.  The pool is a list
  * any of the calls above returned (lthm_retrieve_topk_deep gives up to 1,024 rows in one scan).

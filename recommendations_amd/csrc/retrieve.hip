@@ -1703,6 +1703,16 @@ struct RetrIvfShared {
   int flag[3];       // flag[i % 3]: tile i pushed some pair past RT_LIM
 };
 static_assert(sizeof(RetrIvfShared) <= 160 * 1024, "LDS budget");
+// retr_ivf_topk_k<true, true, TAGS, BIAS>: the tag and the bias words of the two images' rows behind
+// the plain layout, as RetrSharedTags / RetrSharedBias hold them
+struct RetrIvfSharedTags : RetrIvfShared {
+  alignas(16) int tag[2][RT_IT];  // a lane reads four words at once
+};
+template <class Base>
+struct RetrIvfSharedBias : Base {
+  alignas(16) float bias[2][RT_IT];  // a lane reads four words at once
+};
+static_assert(sizeof(RetrIvfSharedBias<RetrIvfSharedTags>) <= 160 * 1024, "LDS budget");
 
 struct RetrIvfArgs {
   const bf16_t* items;      // [N, 128], list-major
@@ -1719,6 +1729,18 @@ struct RetrIvfArgs {
   int64_t Q, N;
   int L, P, k;
 };
+// retr_ivf_topk_k<true, true, TAGS, BIAS> takes the plain arguments and the filters behind them, so
+// that the plain instantiations' argument block is the one they always had
+struct RetrIvfFiltArgs : RetrIvfArgs {
+  const int* tags;      // TAGS: [N], clustered numbering
+  const int* filt;      // TAGS: [Q, 3]: all, any, none
+  const float* bias;    // BIAS: [N], clustered numbering
+  const float* bw;      // BIAS: [Q] or null: 1 for everyone
+  const float* ascore;  // [Q] or null: no cursor
+  const int* crow;      // with ascore: [Q P] the cursor row of every pair (retr_ivf_cursor_k)
+};
+template <bool FILT>
+using RetrIvfScanArgs = std::conditional_t<FILT, RetrIvfFiltArgs, RetrIvfArgs>;
 
 __global__ __launch_bounds__(256) void retr_ivf_count_k(const int* __restrict__ probes, int64_t NP, int L, int P,
                                                         int64_t Q, int k, int* __restrict__ cnt,
@@ -1795,16 +1817,59 @@ __global__ __launch_bounds__(256) void retr_ivf_fill_k(const int* __restrict__ p
   }
 }
 
+// The cursor row of every pair p = q P + s with a list c: inside a list ids ascend with rows, so
+// "id > after_id" is "row > cr" with cr = row_lo + #{rows of the list with row_ids <= after_id} - 1,
+// whether or not the list, or the catalogue, holds after_id (row_lo - 1: every row of the list is
+// behind the id; row_hi - 1: none is).  One thread per pair: an upper bound over row_ids[row_lo,
+// row_hi) in at most 31 steps, on the scan's own clamped offsets.  A pair without a list gets -1,
+// which nothing reads.
+__global__ __launch_bounds__(256) void retr_ivf_cursor_k(const int* __restrict__ probes, int64_t NP, int L, int P,
+                                                         int64_t N, const int64_t* __restrict__ list_off,
+                                                         const int64_t* __restrict__ row_ids,
+                                                         const int64_t* __restrict__ after_ids, int* __restrict__ crow) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= NP) return;
+  const int c = probes[p];
+  if (c < 0 || c >= L) {
+    crow[p] = -1;
+    return;
+  }
+  int64_t row_lo = list_off[c], row_hi = list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > N ? N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > N ? N : row_hi;
+  const int64_t aid = after_ids[p / P];
+  int64_t lo = row_lo, hi = row_hi;  // the first row of [row_lo, row_hi) whose id is above aid
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (row_ids[mid] <= aid) lo = mid + 1;
+    else hi = mid;
+  }
+  crow[p] = (int)(lo - 1);  // row_lo - 1 >= -1 and row_hi - 1 < N < 2^31
+}
+
 // Wave w: columns 32 (w & 1) + (lane & 31) of the tile (one pair each, so every per-pair value is a
 // per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3), as in retr_topk_k.
 // EXCL: the lane walks its query's sorted list of excluded rows (the clustered numbering) from the
 // first entry >= row_lo; entries of other lists lie outside [row_lo, row_hi) and the walk, which
 // stops at the tile's end <= row_hi, never applies them.
-template <bool EXCL>
-__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
+//
+// FILT (with EXCL): retr_topk_k's tags, prior and cursor with its arithmetic, in its order: the
+// partial-tile mask, the prior, exclusion, tags, the cursor, then the threshold and the appends.
+// A null list (a.xs) is "no exclusion" and a null cursor (a.ascore) "no cursor", as retr_topk_k's
+// AFTER / BIAS instantiations take them.  TAGS: wave 0 stages the 64 tag words of tile i + 1 with
+// its image (the zero word for rows at or past row_hi, so never a read at or past row_hi <= N) and a
+// lane reads its 16 rows' words back as four broadcast 16-byte LDS reads ahead of the MFMAs.  BIAS:
+// wave 1 stages the bias words the same way and every element becomes fmaf(wq, bias of its row,
+// element), the score from there on.  The cursor: the pair's score cs and its cursor row cr
+// (retr_ivf_cursor_k), then retr_topk_k's AFTER code unchanged.  The filter, the weight and the
+// cursor are per lane, like every other per-pair value.  <false> and <true> hold none of this.
+template <bool EXCL, bool FILT = false, bool TAGS = false, bool BIAS = false>
+__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) {
+  static_assert(FILT ? EXCL : !(TAGS || BIAS), "tags, prior and cursor ride on the excluding instantiation");
   const int blk = blockIdx.x;
   if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
-  __shared__ __attribute__((aligned(16))) RetrIvfShared sh;
+  using RetrIvfSharedFilt = std::conditional_t<TAGS, RetrIvfSharedTags, RetrIvfShared>;
+  __shared__ __attribute__((aligned(16))) std::conditional_t<BIAS, RetrIvfSharedBias<RetrIvfSharedFilt>, RetrIvfSharedFilt> sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
   const int4 tt = a.tab[blk];
@@ -1839,7 +1904,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
   const int* xp = nullptr;
   int nx = INT_MAX;  // a column without a pair excludes nothing and reads nothing
   if constexpr (EXCL) {
-    if (live) {
+    if (live && (!FILT || a.xs != nullptr)) {
       const int* xl = a.xs + q * a.xstride;
       int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
       while (lo < hi) {
@@ -1849,6 +1914,30 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
       }
       xp = xl + lo;
       nx = *xp;
+    }
+  }
+  int fm = 0, fw = 0, fy = 0;
+  int yz = 1;
+  if constexpr (TAGS) {
+    if (live) {
+      const int* fp = a.filt + q * 3;
+      const int fall = fp[0], fnone = fp[2];
+      fy = fp[1];
+      yz = fy == 0;
+      fm = (fall & fnone) ? 0 : (fall | fnone);
+      fw = (fall & fnone) ? 1 : fall;
+    }
+  }
+  float cs = INFINITY;  // a column without a pair: no cursor
+  int cr = -1;
+  float wq = 0.f;  // a column without a pair: no prior
+  if constexpr (FILT) {
+    if (live && a.ascore != nullptr) {
+      cs = a.ascore[q];
+      cr = a.crow[a.pair_idx[pbase + ql]];
+    }
+    if constexpr (BIAS) {
+      if (live) wq = a.bw ? a.bw[q] : 1.f;
     }
   }
   int roff[8];
@@ -1867,6 +1956,20 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
       const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
                                      : (const void*)(retr_zero_row + 16 * (lane & 15));
       glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+    if constexpr (TAGS) {
+      // wave 0, lane l: the tag of the image's row l; never a read at or past row_hi <= N
+      if (w == 0) {
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+      }
+    }
+    if constexpr (BIAS) {
+      // wave 1, lane l: the bias of the image's row l; never a read at or past row_hi <= N
+      if (w == 1) {
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
+      }
     }
   };
   retire_loads();
@@ -1890,6 +1993,21 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
       __syncthreads();
     }
     const unsigned char* img = sh.img[i & 1];
+    // TAGS / BIAS: element 4 j + c is image row 32 ih + 4 hh + 8 j + c, so the lane's words are four
+    // runs of four, the same in all 32 lanes of a wave half (broadcast reads); read ahead of the
+    // MFMAs, used behind them
+    int4 t4[4];
+    if constexpr (TAGS) {
+      const int4* tp = reinterpret_cast<const int4*>(sh.tag[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
+    }
+    float4 b4[4];
+    if constexpr (BIAS) {
+      const float4* bp = reinterpret_cast<const float4*>(sh.bias[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b4[j] = bp[2 * j];
+    }
     f32x16 acc = {};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -1903,6 +2021,15 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
       for (int v = 0; v < 16; ++v)
         if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
     }
+    if constexpr (BIAS) {
+      // the score from here on; a row past the list is fmaf(wq, 0, -inf) = -inf
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bw4[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[4 * j + e] = __builtin_fmaf(wq, bw4[e], acc[4 * j + e]);
+      }
+    }
     if constexpr (EXCL) {
       const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
       unsigned xm = 0u;
@@ -1915,6 +2042,35 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
 #pragma unroll
         for (int v = 0; v < 16; ++v)
           if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    if constexpr (TAGS) {
+      // two compares and one select per element: an ineligible row scores -inf like an excluded one
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int tw[4] = {t4[j].x, t4[j].y, t4[j].z, t4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool bad = ((tw[e] & fm) != fw) | (((tw[e] & fy) | yz) == 0);
+          acc[4 * j + e] = bad ? -INFINITY : acc[4 * j + e];
+        }
+      }
+    }
+    if constexpr (FILT) {
+      // rows at or before the cursor score -inf like an excluded row; !(m < cs) also holds for a
+      // NaN cs, which then fails both terms of every element.  Without a cursor cs = +inf
+      float m = acc[0];
+#pragma unroll
+      for (int v = 1; v < 16; ++v) m = fmaxf(m, acc[v]);
+      if (!(m < cs)) {
+        const int64_t cd = (int64_t)cr - rb;
+        const int cq = cd < -1 ? -1 : cd > 32 ? 32 : (int)cd;  // element offsets are 0..27
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const float s = acc[v];
+          const bool ok = (s < cs) | ((s == cs) & (8 * (v >> 2) + (v & 3) > cq));
+          acc[v] = ok ? s : -INFINITY;
+        }
       }
     }
     float mx = acc[0];
@@ -1951,7 +2107,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfArgs a) {
 
 // the workspace of one call, in bytes from its start
 struct RetrIvfWs {
-  int64_t qn, cnt, off, pidx, tab, xs, scores, ids, total, grid;
+  int64_t qn, cnt, off, pidx, tab, xs, scores, ids, crow, total, grid;
 };
 
 // the scan's grid: sum_c ceil(n_c / 64) <= floor(sum_c n_c / 64) + #{c : n_c > 0} with sum_c n_c <= Q P
@@ -1960,7 +2116,9 @@ inline int64_t retr_ivf_grid(int64_t Q, int64_t P, int64_t L) {
   return np / RT_QT + (L < np ? L : np);
 }
 
-bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o) {
+// cursor: the pairs' cursor rows behind everything else, so that the call without one has the
+// layout and the size it always had
+bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o, bool cursor = false) {
   if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || L < 1 || L >= (1ll << 31)) return false;
   if (P < 1 || P > RS_SMAX || k < 1 || k > RT_KMAX || X < 0 || X > RT_XMAX) return false;
   if (Q * P >= (1ll << 31)) return false;
@@ -1975,6 +2133,7 @@ bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t 
   o->xs = at, at += X ? up256(Q * (X + 1) * 4) : 0;
   o->scores = at, at += up256(P * Q * k * 4);
   o->ids = at, at += up256(P * Q * k * 8);
+  o->crow = at, at += cursor ? up256(Q * P * 4) : 0;
   o->total = at;
   return true;
 }
@@ -1992,19 +2151,43 @@ extern "C" int64_t lthm_retrieve_ivf_ws_bytes(int64_t Q, int64_t N, int64_t L, i
   return retr_ivf_ws(Q, N, L, P, k, X, &w) ? w.total : -1;
 }
 
+extern "C" int64_t lthm_retrieve_ivf_filt_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X,
+                                                   int32_t has_cursor) {
+  RetrIvfWs w;
+  return retr_ivf_ws(Q, N, L, P, k, X, &w, has_cursor != 0) ? w.total : -1;
+}
+
 extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
                                       int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
                                       const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
                                       float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
                                       void* stream) {
+  return lthm_retrieve_ivf_topk_filt(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, Q, probes, P, k, x, nullptr,
+                                     nullptr, nullptr, out_scores, out_ids, workspace, ws_bytes, stream);
+}
+
+// The one call path of the clustered scan: without t, b and c it launches retr_ivf_topk_k<false> /
+// <true>, as lthm_retrieve_ivf_topk always did; with any of them <true, true, TAGS, BIAS>, which takes
+// a null list and a null cursor as "none".
+extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row_ids,
+                                           const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                                           int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t k,
+                                           const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                                           const lthm_retrieve_bias* b, const lthm_retrieve_ivf_cursor* c,
+                                           float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
+                                           void* stream) {
   LTHM_REQUIRE(items && row_ids && list_off && q && probes && out_scores && out_ids && workspace);
+  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
+  LTHM_REQUIRE(!b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0));
+  LTHM_REQUIRE(!c || (c->after_score && c->after_id && ((uintptr_t)c->after_score & 3) == 0 &&
+                      ((uintptr_t)c->after_id & 7) == 0));
   LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
   LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
   LTHM_REQUIRE(((uintptr_t)row_ids & 7) == 0 && ((uintptr_t)list_off & 7) == 0 && ((uintptr_t)probes & 3) == 0);
   LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   RetrIvfWs wo;
-  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo) && ws_bytes >= wo.total);
+  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo, c != nullptr) && ws_bytes >= wo.total);
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   bf16_t* qn = (bf16_t*)(ws + wo.qn);
@@ -2041,8 +2224,23 @@ extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_
   hipLaunchKernelGGL(retr_ivf_fill_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off, fill,
                      pair_idx, tab);
   LTHM_CHECK_LAUNCH();
-  // 3: the scan
-  RetrIvfArgs a;
+  // 3: the scan (with a cursor, the pairs' cursor rows first: one more kernel of the plan's shape)
+  const bool filt = t || b || c;
+  RetrIvfFiltArgs a;  // the plain instantiations take its base
+  a.tags = t ? t->tags : nullptr;
+  a.filt = t ? t->filter : nullptr;
+  a.bias = b ? b->bias : nullptr;
+  a.bw = b ? b->weight : nullptr;
+  a.ascore = nullptr;
+  a.crow = nullptr;
+  if (c) {
+    int* crow = (int*)(ws + wo.crow);
+    hipLaunchKernelGGL(retr_ivf_cursor_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, (int)P, N, list_off, row_ids,
+                       c->after_id, crow);
+    LTHM_CHECK_LAUNCH();
+    a.ascore = c->after_score;
+    a.crow = crow;
+  }
   a.items = it;
   a.qn = qn;
   a.row_ids = row_ids;
@@ -2068,9 +2266,20 @@ extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_
     LTHM_CHECK_LAUNCH();
     a.xs = xs;
     a.xstride = X + 1;
-    hipLaunchKernelGGL(retr_ivf_topk_k<true>, dim3((unsigned)wo.grid), dim3(256), 0, s, a);
+  }
+  const dim3 grid((unsigned)wo.grid);
+  if (!filt) {
+    const RetrIvfArgs& pa = a;
+    if (x) hipLaunchKernelGGL(retr_ivf_topk_k<true>, grid, dim3(256), 0, s, pa);
+    else hipLaunchKernelGGL(retr_ivf_topk_k<false>, grid, dim3(256), 0, s, pa);
+  } else if (t && b) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, true>), grid, dim3(256), 0, s, a);
+  } else if (t) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, false>), grid, dim3(256), 0, s, a);
+  } else if (b) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, true>), grid, dim3(256), 0, s, a);
   } else {
-    hipLaunchKernelGGL(retr_ivf_topk_k<false>, dim3((unsigned)wo.grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, false>), grid, dim3(256), 0, s, a);
   }
   LTHM_CHECK_LAUNCH();
   // 4: the merge of every query's P lists

@@ -25,6 +25,7 @@
 //   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
 //   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
 //   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
+//   lthm::retrieve_ivf_topk_filt the same with a tag filter, a score prior and an (score, id) cursor per query
 //   lthm::retrieve_diversify     greedy MMR selection of k out of a pool per query, with a cap per group
 //   lthm::quantize_catalogue_q8, lthm::retrieve_q8_topk, lthm::retrieve_rescore
 //                                an e4m3 catalogue, its shortlist scan and the exact re-scoring of a list
@@ -659,9 +660,30 @@ std::tuple<Tensor, Tensor, Tensor> retrieve_merge_shards_cuda(const Tensor& scor
 // the scan of a clustered catalogue: items bf16 [N, 128] list-major, row_ids int64 [N], list_off int64
 // [L + 1], probes int32 [Q, P] (P <= 64), exclude_rows int32 [Q, X] in the clustered row numbering or
 // None; (scores f32 [Q, k], ids int64 [Q, k])
-std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q_, const Tensor& items_, const Tensor& row_ids_,
-                                                  const Tensor& list_off_, const Tensor& probes_, int64_t k,
+std::tuple<Tensor, Tensor> retrieve_ivf_topk_filt_cuda(
+    const Tensor& q_, const Tensor& items_, const Tensor& row_ids_, const Tensor& list_off_, const Tensor& probes_,
+    int64_t k, bool normalize_q, const c10::optional<Tensor>& exclude_rows, const c10::optional<Tensor>& tags_,
+    const c10::optional<Tensor>& tag_filter_, const c10::optional<Tensor>& bias_,
+    const c10::optional<Tensor>& bias_weight_, const c10::optional<Tensor>& after_scores_,
+    const c10::optional<Tensor>& after_ids_);
+
+std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q, const Tensor& items, const Tensor& row_ids,
+                                                  const Tensor& list_off, const Tensor& probes, int64_t k,
                                                   bool normalize_q, const c10::optional<Tensor>& exclude_rows) {
+  return retrieve_ivf_topk_filt_cuda(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, c10::nullopt,
+                                     c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt);
+}
+
+// the same with retrieve_topk's filters, prior and cursor on the probed rows: tags int32 [N] and bias
+// f32 [N] in the clustered row numbering, tag_filter int32 [Q, 3], bias_weight f32 [Q] or None (1),
+// after_scores f32 [Q] with after_ids int64 [Q]; tags with tag_filter, after_scores with after_ids,
+// bias_weight only with bias.  With none of them it is retrieve_ivf_topk's call
+std::tuple<Tensor, Tensor> retrieve_ivf_topk_filt_cuda(
+    const Tensor& q_, const Tensor& items_, const Tensor& row_ids_, const Tensor& list_off_, const Tensor& probes_,
+    int64_t k, bool normalize_q, const c10::optional<Tensor>& exclude_rows, const c10::optional<Tensor>& tags_,
+    const c10::optional<Tensor>& tag_filter_, const c10::optional<Tensor>& bias_,
+    const c10::optional<Tensor>& bias_weight_, const c10::optional<Tensor>& after_scores_,
+    const c10::optional<Tensor>& after_ids_) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   on_gpu(row_ids_, "row_ids");
@@ -697,7 +719,54 @@ std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q_, const Tensor
     TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
     xr = exclude_rows->contiguous();
   }
-  const int64_t need = lthm_retrieve_ivf_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0);
+  const bool has_tags = tags_.has_value() && tags_->defined(), has_filter = tag_filter_.has_value() && tag_filter_->defined();
+  TORCH_CHECK(has_tags == has_filter, "retrieve_ivf_topk_filt takes tags and tag_filter together or neither");
+  const bool has_b = bias_.has_value() && bias_->defined(), has_w = bias_weight_.has_value() && bias_weight_->defined();
+  TORCH_CHECK(has_b || !has_w, "retrieve_ivf_topk_filt takes a bias_weight only with a bias");
+  const bool has_cs = after_scores_.has_value() && after_scores_->defined();
+  const bool has_ci = after_ids_.has_value() && after_ids_->defined();
+  TORCH_CHECK(has_cs == has_ci, "retrieve_ivf_topk_filt takes after_scores and after_ids together or neither");
+  Tensor tags, tag_filter, bias, bias_weight, after_scores, after_ids;
+  if (has_tags) {
+    on_gpu(*tags_, "tags");
+    on_gpu(*tag_filter_, "tag_filter");
+    TORCH_CHECK(tags_->scalar_type() == at::kInt && tags_->dim() == 1 && tags_->size(0) == N &&
+                    tags_->device() == items.device(),
+                "tags must be int32 [N] on the catalogue's device");
+    TORCH_CHECK(tag_filter_->scalar_type() == at::kInt && tag_filter_->dim() == 2 && tag_filter_->size(0) == Q &&
+                    tag_filter_->size(1) == 3 && tag_filter_->device() == q.device(),
+                "tag_filter must be int32 [Q, 3] on the queries' device");
+    tags = tags_->contiguous();
+    tag_filter = tag_filter_->contiguous();
+  }
+  if (has_b) {
+    on_gpu(*bias_, "bias");
+    TORCH_CHECK(bias_->scalar_type() == at::kFloat && bias_->dim() == 1 && bias_->size(0) == N &&
+                    bias_->device() == items.device(),
+                "bias must be f32 [N] on the catalogue's device");
+    bias = bias_->contiguous();
+    if (has_w) {
+      on_gpu(*bias_weight_, "bias_weight");
+      TORCH_CHECK(bias_weight_->scalar_type() == at::kFloat && bias_weight_->dim() == 1 && bias_weight_->size(0) == Q &&
+                      bias_weight_->device() == q.device(),
+                  "bias_weight must be f32 [Q] on the queries' device");
+      bias_weight = bias_weight_->contiguous();
+    }
+  }
+  if (has_cs) {
+    on_gpu(*after_scores_, "after_scores");
+    on_gpu(*after_ids_, "after_ids");
+    TORCH_CHECK(after_scores_->scalar_type() == at::kFloat && after_scores_->dim() == 1 && after_scores_->size(0) == Q &&
+                    after_scores_->device() == q.device(),
+                "after_scores must be f32 [Q] on the queries' device");
+    TORCH_CHECK(after_ids_->scalar_type() == at::kLong && after_ids_->dim() == 1 && after_ids_->size(0) == Q &&
+                    after_ids_->device() == q.device(),
+                "after_ids must be int64 [Q] on the queries' device");
+    after_scores = after_scores_->contiguous();
+    after_ids = after_ids_->contiguous();
+  }
+  const int64_t need =
+      lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0, has_cs ? 1 : 0);
   TORCH_CHECK(need >= 0, "retrieve_ivf_topk: unsupported sizes Q=", Q, " N=", N, " L=", L, " P=", P);
   auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
   auto ids = at::empty({Q, k}, q.options().dtype(at::kLong));
@@ -707,11 +776,27 @@ std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q_, const Tensor
     x.rows = xr.data_ptr<int32_t>();
     x.X = xr.size(1);
   }
-  hip_ok(lthm_retrieve_ivf_topk(items.data_ptr(), N, row_ids.data_ptr<int64_t>(), list_off.data_ptr<int64_t>(), L,
-                                q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q, probes.data_ptr<int32_t>(), (int32_t)P,
-                                (int32_t)k, excl ? &x : nullptr, scores.data_ptr<float>(), ids.data_ptr<int64_t>(),
-                                ws.data_ptr(), need, cur_stream()),
-         "lthm_retrieve_ivf_topk");
+  lthm_retrieve_tags t = {};
+  if (has_tags) {
+    t.tags = tags.data_ptr<int32_t>();
+    t.filter = tag_filter.data_ptr<int32_t>();
+  }
+  lthm_retrieve_bias b = {};
+  if (has_b) {
+    b.bias = bias.data_ptr<float>();
+    b.weight = has_w ? bias_weight.data_ptr<float>() : nullptr;
+  }
+  lthm_retrieve_ivf_cursor c = {};
+  if (has_cs) {
+    c.after_score = after_scores.data_ptr<float>();
+    c.after_id = after_ids.data_ptr<int64_t>();
+  }
+  hip_ok(lthm_retrieve_ivf_topk_filt(items.data_ptr(), N, row_ids.data_ptr<int64_t>(), list_off.data_ptr<int64_t>(), L,
+                                     q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q, probes.data_ptr<int32_t>(),
+                                     (int32_t)P, (int32_t)k, excl ? &x : nullptr, has_tags ? &t : nullptr,
+                                     has_b ? &b : nullptr, has_cs ? &c : nullptr, scores.data_ptr<float>(),
+                                     ids.data_ptr<int64_t>(), ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_ivf_topk_filt");
   return std::make_tuple(scores, ids);
 }
 
@@ -896,6 +981,10 @@ TORCH_LIBRARY(lthm, m) {
       "retrieve_ivf_topk(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
       "bool normalize_q, Tensor? exclude_rows=None) -> (Tensor scores, Tensor ids)");
   m.def(
+      "retrieve_ivf_topk_filt(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
+      "bool normalize_q, Tensor? exclude_rows=None, Tensor? tags=None, Tensor? tag_filter=None, Tensor? bias=None, "
+      "Tensor? bias_weight=None, Tensor? after_scores=None, Tensor? after_ids=None) -> (Tensor scores, Tensor ids)");
+  m.def(
       "retrieve_diversify(Tensor items, Tensor rows, Tensor scores, int k, Tensor? lam=None, Tensor? groups=None, "
       "int cap=1) -> (Tensor rows, Tensor scores, Tensor objective)");
   m.def("quantize_catalogue_q8(Tensor items) -> (Tensor codes, Tensor scale)");
@@ -921,6 +1010,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
   m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
   m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
+  m.impl("retrieve_ivf_topk_filt", &retrieve_ivf_topk_filt_cuda);
   m.impl("retrieve_diversify", &retrieve_diversify_cuda);
   m.impl("quantize_catalogue_q8", &quantize_catalogue_q8_cuda);
   m.impl("retrieve_q8_topk", &retrieve_q8_topk_cuda);

@@ -2028,7 +2028,27 @@ def retrieve_ivf_grid(Q: int, P: int, L: int) -> int:
     return n
 
 
-def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_q: bool = True, exclude_rows=None):
+def _retrieve_ivf_cursor(who: str, after_scores, after_ids, Q: int, device):
+    """The lthm_retrieve_ivf_cursor of a call, or None without a cursor: after_scores f32 [Q] and
+    after_ids int64 [Q], contiguous, on the queries' device, both or neither."""
+    from ._lib import STRUCTS
+    _check((after_scores is None) == (after_ids is None), f"{who} takes after_scores and after_ids together or neither")
+    if after_scores is None:
+        return None
+    _check(after_scores.dtype == torch.float32 and tuple(after_scores.shape) == (Q,),
+           f"after_scores must be f32 [Q] (got {after_scores.dtype} {tuple(after_scores.shape)}, Q={Q})")
+    _check(after_ids.dtype == torch.int64 and tuple(after_ids.shape) == (Q,),
+           f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)}, Q={Q})")
+    _check(after_scores.is_contiguous() and after_ids.is_contiguous(), "after_scores and after_ids must be contiguous")
+    _check(after_scores.device == device and after_ids.device == device,
+           "after_scores and after_ids must be on the queries' device")
+    c = STRUCTS["lthm_retrieve_ivf_cursor"]()
+    c.after_score, c.after_id = ptr(after_scores), ptr(after_ids)
+    return c
+
+
+def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_q: bool = True, exclude_rows=None,
+                      tags=None, tag_filter=None, bias=None, bias_weight=None, after_scores=None, after_ids=None):
     """The k best items per query among the lists the query probes (lthm_retrieve_ivf_topk,
     csrc/retrieve.hip retr_ivf_topk_k): the scan of a clustered catalogue.
 
@@ -2039,11 +2059,19 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     numbering, under retrieve_topk's rules.  Returns (scores f32 [Q, k], ids int64 [Q, k]), 1 <= k <=
     128: the first k under (score descending, id ascending) of the probed, non-excluded rows, then
     (-inf, 0); every score has the bits retrieve_topk returns for the same (query, row).  One call:
-    the query preparation, the plan, the scan and the merge run on the device without a host sync."""
+    the query preparation, the plan, the scan and the merge run on the device without a host sync.
+
+    tags int32 [N] with tag_filter int32 [Q, 3], bias f32 [N] with bias_weight (None, a number or f32
+    [Q]), and after_scores f32 [Q] with after_ids int64 [Q] are retrieve_topk's filters, prior and
+    cursor on the probed rows (lthm_retrieve_ivf_topk_filt): tags and bias in this catalogue's own
+    row order, the cursor an id, since the cursor row differs per list.  The result is the k first
+    of the probed, non-excluded rows that pass the filter and lie strictly behind (after_score,
+    after_id), every score fma(w[q], bias[row], dot) as retrieve_topk returns it; with every list
+    probed it is retrieve_topk's list.  With none of them the call is the one it always was."""
     import ctypes
     from ._lib import STRUCTS
     who = "retrieve_ivf_topk"
-    require_gpu(q, items, row_ids, list_off, probes, exclude_rows)
+    require_gpu(q, items, row_ids, list_off, probes, exclude_rows, tags, tag_filter, bias, after_scores, after_ids)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
     _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
@@ -2075,17 +2103,32 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
         _check(exclude_rows.device == q.device, "exclude_rows must be on the queries' device")
         x = STRUCTS["lthm_retrieve_excl"]()
         x.rows, x.X = ptr(exclude_rows), X
-    need = load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X)
+    dev = q.device
+    t = _retrieve_tags(who, tags, tag_filter, items, Q, "Q")
+    b, bw = _retrieve_bias(who, bias, bias_weight, items, Q, "Q", dev)
+    c = _retrieve_ivf_cursor(who, after_scores, after_ids, Q, dev)
+    filt = t is not None or b is not None or c is not None
+    if filt:
+        need = load().lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, P, k, X, int(c is not None))
+    else:
+        need = load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X)
     _check(need >= 0, f"{who}: no workspace size for Q={Q} N={N} L={L} P={P} k={k} X={X} (Q P must stay below 2^31)")
     q = q.contiguous()
-    dev = q.device
     scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
     ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    call("lthm_retrieve_ivf_topk", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q), int(bool(normalize_q)),
-         Q, ptr(probes), P, k, ctypes.addressof(x) if x is not None else None, ptr(scores), ptr(ids), ptr(ws), need,
-         stream(), _key="retr_ivf_topk_k", _work=float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k
-                                                       + 4.0 * Q * (P + X)), _unit="byte")
+    work = float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k + 4.0 * Q * (P + X))
+    if not filt:
+        call("lthm_retrieve_ivf_topk", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
+             int(bool(normalize_q)), Q, ptr(probes), P, k, ctypes.addressof(x) if x is not None else None, ptr(scores),
+             ptr(ids), ptr(ws), need, stream(), _key="retr_ivf_topk_k", _work=work, _unit="byte")
+        return scores, ids
+    parts = [ctypes.addressof(o) if o is not None else None for o in (x, t, b, c)]
+    work += (12.0 * Q if t is not None else 0.0) + (4.0 * Q if bw is not None else 0.0) \
+        + (12.0 * Q + 4.0 * Q * P if c is not None else 0.0)
+    call("lthm_retrieve_ivf_topk_filt", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
+         int(bool(normalize_q)), Q, ptr(probes), P, k, *parts, ptr(scores), ptr(ids), ptr(ws), need, stream(),
+         _key="retr_ivf_topk_filt_k", _work=work, _unit="byte")
     return scores, ids
 
 

@@ -36,7 +36,9 @@ device (``K.retrieve_merge_shards``).
 Clusters: a ``ClusteredItemCatalogue`` (``ItemCatalogue.cluster`` or ``from_assignment``) holds the
 rows grouped into lists around centroids, and its ``topk`` scans only the ``nprobe`` lists nearest
 to each query (``K.retrieve_ivf_topk``): the exact top-k of the probed lists, with the flat scan's
-score bits, and with ``nprobe`` = L the flat scan's result.
+score bits, and with ``nprobe`` = L the flat scan's result.  Its ``with_filters()`` view scans the same
+lists with the catalogue's tags and bias and behind a (score, id) cursor, under ``ItemCatalogue.topk``'s
+conventions.
 """
 from __future__ import annotations
 
@@ -562,8 +564,9 @@ class ClusteredItemCatalogue:
     ``emb`` bf16 [N, 128], list-major: list c is rows ``list_off[c] .. list_off[c + 1]``, its ids
     ascending; ``row_ids`` int64 [N], the id of every row (distinct, never 0); ``list_off`` int64
     [L + 1]; ``centroids`` bf16 [L, 128]; ``tags`` / ``bias`` in the rows' order or None.  Tags and
-    bias are carried for ``to_flat()`` only: the clustered scan scores the plain dot and filters
-    nothing but ``exclude_ids``.  Groups are not carried: a clustered list is diversified against
+    bias are carried for ``to_flat()`` and for the view ``with_filters()`` returns, whose scan applies
+    them and takes cursors; this catalogue's own scan scores the plain dot and filters nothing but
+    ``exclude_ids``.  Groups are not carried: a clustered list is diversified against
     the flat catalogue it was built from (``ItemCatalogue.diversify`` takes its ids)."""
 
     def __init__(self, row_ids: torch.Tensor, emb: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
@@ -674,9 +677,25 @@ class ClusteredItemCatalogue:
                              None if self.bias is None else self.bias[o])
 
     def to(self, device) -> "ClusteredItemCatalogue":
-        return ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
-                                      self.centroids.to(device), None if self.tags is None else self.tags.to(device),
-                                      None if self.bias is None else self.bias.to(device))
+        out = ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
+                                     self.centroids.to(device), None if self.tags is None else self.tags.to(device),
+                                     None if self.bias is None else self.bias.to(device))
+        return out.with_filters() if self.scans_filters else out
+
+    @property
+    def scans_filters(self) -> bool:
+        """Whether ``topk`` follows the flat catalogue's conventions (tags, bias, cursors): False here,
+        True on the view ``with_filters()`` returns."""
+        return False
+
+    def with_filters(self) -> "FilteredClusteredItemCatalogue":
+        """A view over the same tensors (nothing is copied) whose scan applies the catalogue's tags and
+        bias and takes cursors, as ``ItemCatalogue.topk`` does: see ``FilteredClusteredItemCatalogue``.
+        This catalogue is unchanged.  The flag is not stored by ``save``."""
+        view = object.__new__(FilteredClusteredItemCatalogue)
+        view.__dict__.update(self.__dict__)
+        view._flat = None
+        return view
 
     def _check_call(self, k: int, nprobe) -> Tuple[int, int]:
         if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
@@ -761,6 +780,106 @@ class ClusteredItemCatalogue:
         cat = cls(row_ids, flat.emb[rows], list_off, centroids, None if flat.tags is None else flat.tags[rows],
                   None if flat.bias is None else flat.bias[rows])
         return cat.to(device) if device is not None else cat
+
+
+class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
+    """``ClusteredItemCatalogue.with_filters()``: the same tensors, scanned under the flat catalogue's
+    conventions (``K.retrieve_ivf_topk`` with tags, bias and cursor; csrc/retrieve.hip
+    ``retr_ivf_topk_k<true, true, TAGS, BIAS>``).  A catalogue that carries a bias scores with it, a
+    ``tag_filter`` needs tags, and a cursor is a (score, id) position.  Everything else (``probe``,
+    ``rows_of``, ``to_flat``, ``save``, the limits on ``nprobe`` and ``k``) is the plain catalogue's."""
+
+    @property
+    def scans_filters(self) -> bool:
+        return True
+
+    def with_filters(self) -> "FilteredClusteredItemCatalogue":
+        return self
+
+    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
+        """``ItemCatalogue.filter_like``: per target t the row (tags[t] & mask, 0, ~tags[t] & mask) of an
+        int32 [Q, 3] filter, (0, 0, 0) for a target the catalogue does not hold."""
+        if self.tags is None:
+            raise ValueError("filter_like needs a catalogue with tags")
+        if target_ids.dim() != 1:
+            raise ValueError("filter_like takes target ids [Q]")
+        rows = self.rows_of(target_ids).long()
+        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
+        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
+        m = torch.where(rows >= 0, m, torch.zeros_like(m))
+        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+
+    def _check_filters(self, q, tag_filter, after_scores, after_ids, bias_weight) -> None:
+        if q.dim() != 2:
+            raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        Q = q.shape[0]
+        if tag_filter is not None:
+            if self.tags is None:
+                raise ValueError("tag_filter given, but this catalogue carries no tags")
+            if tag_filter.dtype != torch.int32 or tuple(tag_filter.shape) != (Q, 3):
+                raise ValueError(f"tag_filter must be int32 [Q, 3] = (all, any, none) "
+                                 f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, Q={Q})")
+        if bias_weight is not None:
+            if self.bias is None:
+                raise ValueError("bias_weight given, but this catalogue carries no bias")
+            if isinstance(bias_weight, torch.Tensor):
+                if bias_weight.dtype != torch.float32 or tuple(bias_weight.shape) != (Q,):
+                    raise ValueError(f"bias_weight must be None, a number or f32 [Q] "
+                                     f"(got {bias_weight.dtype} {tuple(bias_weight.shape)}, Q={Q})")
+            elif isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float)):
+                raise ValueError(f"bias_weight must be None, a number or f32 [Q] (got {type(bias_weight).__name__})")
+        if (after_scores is None) != (after_ids is None):
+            raise ValueError("after_scores and after_ids are given together or neither")
+        if after_ids is not None:
+            if after_ids.dtype != torch.int64 or tuple(after_ids.shape) != (Q,):
+                raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
+            if after_scores.dtype != torch.float32 or tuple(after_scores.shape) != (Q,):
+                raise ValueError(f"after_scores must be f32 [Q] (got {after_scores.dtype} {tuple(after_scores.shape)})")
+
+    def topk(self, q: torch.Tensor, k: int, *, nprobe: int, normalize_q: bool = True,
+             exclude_ids: Optional[torch.Tensor] = None, tag_filter: Optional[torch.Tensor] = None,
+             after_scores: Optional[torch.Tensor] = None, after_ids: Optional[torch.Tensor] = None,
+             bias_weight: Union[None, float, torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores f32 [Q, k], ids int64 [Q, k]): per query the k first, under (score descending, id
+        ascending), of the items that lie in its ``nprobe`` nearest lists, are not among its
+        ``exclude_ids``, pass its ``tag_filter`` (int32 [Q, 3] = (all, any, none); the catalogue must
+        carry tags) and lie strictly behind (``after_scores`` f32 [Q], ``after_ids`` int64 [Q]; together
+        or neither), then (-inf, 0).  A catalogue that carries a ``bias`` scores item j as
+        fma(w, bias[j], q . e_j), with ``bias_weight`` = w: None for 1, a number or f32 [Q]; one without
+        refuses a weight.  Every score has the bits ``ItemCatalogue.topk`` returns for the same (query,
+        item) and arguments, and with ``nprobe`` = L the whole result is ``to_flat().topk``'s.  The probes
+        depend on ``q`` only, so with the same ``nprobe`` the last (score, id) of one page as the next
+        page's cursor yields the following k items, and the (-inf, 0) of an exhausted page an empty one."""
+        k, nprobe = self._check_call(k, nprobe)
+        self._check_filters(q, tag_filter, after_scores, after_ids, bias_weight)
+        xr = None
+        if exclude_ids is not None:
+            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
+                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+            xr = self.rows_of(exclude_ids).contiguous()
+        probes = self.probe(q, nprobe, normalize_q=normalize_q)
+        return K.retrieve_ivf_topk(q, self.emb, self.row_ids, self.list_off, probes, k, normalize_q=normalize_q,
+                                   exclude_rows=xr, tags=self.tags if tag_filter is not None else None,
+                                   tag_filter=None if tag_filter is None else tag_filter.contiguous(),
+                                   bias=self.bias, bias_weight=bias_weight,
+                                   after_scores=None if after_scores is None else after_scores.contiguous(),
+                                   after_ids=None if after_ids is None else after_ids.contiguous())
+
+    def recall(self, q: torch.Tensor, k: int, nprobe: int, **filters) -> float:
+        """The mean over the queries of the fraction of ``to_flat().topk(q, k, **filters)``'s ids that
+        ``topk(q, k, nprobe=nprobe, **filters)`` returns (``filters``: ``exclude_ids``, ``tag_filter``,
+        ``after_scores`` / ``after_ids``, ``bias_weight``), over the queries whose flat list is not
+        empty (1.0 where every one is).  Never decreases in ``nprobe``; 1.0 at L."""
+        if self._flat is None:
+            self._flat = self.to_flat()
+        want = self._flat.topk(q, k, **filters)[0]
+        got = self.topk(q, k, nprobe=nprobe, **filters)[1]
+        real = want != 0
+        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
+        n = real.sum(dim=1)
+        if not bool((n > 0).any()):
+            return 1.0
+        return float((hit[n > 0] / n[n > 0].double()).mean())
 
 
 class ShardedItemCatalogue:

@@ -374,7 +374,10 @@ class LTHMModelWrapper(BaseModelWrapper):
         ``after`` pages a biased list with nothing added: pass the same ``bias_weight`` again.
         A ``ClusteredItemCatalogue`` takes ``nprobe`` (1..min(L, 64)): sequence b gets the k best
         items (k <= 128) of the ``nprobe`` lists nearest to its query, by id ascending among equal
-        scores; ``exclude_history`` composes, every other argument above is refused by name.
+        scores; ``exclude_history`` composes, every other argument above is refused by name.  Its
+        ``with_filters()`` view also takes ``tag_all`` / ``tag_any`` / ``tag_none``, ``after`` and
+        ``bias_weight``, with the meaning they have on a flat catalogue, on the probed lists (pass the
+        same ``nprobe`` with ``after``); it still refuses ``heads`` and k > 128.
         ``diversity`` = lambda in [0, 1] and / or ``group_cap`` = m (alone it means lambda = 1; the
         catalogue must carry groups) ask a flat ``ItemCatalogue`` for a diversified list: the call
         retrieves ``pool`` items (default min(8 k, 1024); k <= ``pool`` <= 1024, k <= 128; above 128
@@ -409,6 +412,8 @@ class LTHMModelWrapper(BaseModelWrapper):
         if clustered:
             given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
                      "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
+            if catalogue.scans_filters:  # a with_filters() view scans tags, prior and cursor itself
+                given = {name: given[name] for name in ("heads", "diversity", "pool", "group_cap")}
             bad = [name for name, v in given.items() if v is not None]
             if bad:
                 raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
@@ -480,6 +485,10 @@ class LTHMModelWrapper(BaseModelWrapper):
             after_ids = after_ids.to(q.device).contiguous()
         if isinstance(bias_weight, torch.Tensor):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
+        if clustered and catalogue.scans_filters:
+            scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen, tag_filter=filt,
+                                              after_scores=after_scores, after_ids=after_ids, bias_weight=bias_weight)
+            return {"item_ids": item_ids, "scores": scores}
         if clustered:
             scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)
             return {"item_ids": item_ids, "scores": scores}

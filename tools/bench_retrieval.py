@@ -69,6 +69,18 @@ rows; build_s is reported, not judged).  One JSON line per nprobe in {1, 8, 32, 
   plan_us, list_scan_us, merge_us    device time of the call's own kernels from one profiled call (the three plan
                               kernels summed; null where the profiler gives nothing)
   recall_at_k, rows_per_query the mean fraction of the flat top-k returned, the mean rows a query scans (of N)
+--ivf-filt L is a mode of its own too: the catalogue of --ivf with one random tag bit (half the rows carry it)
+and a random finite bias per row.  One JSON line per nprobe in {1, 8, 32}, four arms in one alternating loop,
+medians (min / max):
+  plain_ms                    ClusteredItemCatalogue.topk, the unfiltered scan (tags and bias ignored)
+  neutral_ms                  the with_filters() view with the filter (0, 0, 0) and weight 0: the cost of the machinery
+  filt_ms                     the view with tag_all = the bit (50 % selective) and weight 1
+  flat_ms                     to_flat().topk with that filter and weight: what the flat path costs
+  neutral_over_plain, filt_over_plain, filt_over_flat (and _hi, the worst pairing: max / min)
+  neutral_equals_plain, filt_equals_flat_on_probed   the arms' outputs checked where the contract makes them equal
+With --baseline-lib PATH (another build of liblthm_hip.so, say the parent commit's) a fifth and sixth arm time the
+one C call lthm_retrieve_ivf_topk of that library and of this one on the same probes (base_scan_call_ms,
+scan_call_ms, scan_call_over_base): the unfiltered path's timing against its parent in the same loop.
 --diversify is a mode of its own too: Q = 256 queries, N unit rows drawn as --ivf draws them, the pool the deep
 scan's own first M rows for M in {512, 1024}, k = 100 by default, lam = 0.7.  One JSON line per M:
   kernel_ms / torch_ms        K.retrieve_diversify and a torch greedy loop on the device over the gathered
@@ -535,6 +547,104 @@ def child_ivf(name: str, N: int, k: int, reps: int, L: int) -> None:
         print(json.dumps(out), flush=True)
 
 
+def child_ivf_filt(name: str, N: int, k: int, reps: int, L: int, baseline_lib: str) -> None:
+    import ctypes
+    import torch
+    from recommendations_amd import _lib
+    from recommendations_amd import kernels as K
+    from recommendations_amd._lib import dcode, ptr, stream
+    from recommendations_amd.models.lthm.sequence.retrieval import ItemCatalogue
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5  # child_ivf's catalogue and queries, drawn the same way
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    tags = torch.randint(0, 2, (N,), generator=g, device=dev).to(torch.int32)
+    bias = (0.05 * torch.randn((N,), generator=g, device=dev)).contiguous()
+    flat = ItemCatalogue(torch.arange(1, N + 1, dtype=torch.int64, device=dev) * 3, items, tags, bias)
+    cl = flat.cluster(L, iters=5, seed=0, sample=min(N, 1 << 18))
+    view = cl.with_filters()
+    flat = cl.to_flat()
+    torch.cuda.synchronize()
+    zero_f = torch.zeros((Q, 3), dtype=torch.int32, device=dev)
+    half_f = torch.tensor([[1, 0, 0]] * Q, dtype=torch.int32, device=dev)
+    zero_w = torch.zeros(Q, dtype=torch.float32, device=dev)
+    one_w = torch.ones(Q, dtype=torch.float32, device=dev)
+    base = ctypes.CDLL(baseline_lib) if baseline_lib else None  # RTLD_LOCAL: its own kernels behind its own entry
+    if base is not None:
+        base.lthm_retrieve_ivf_topk.restype = ctypes.c_int
+        base.lthm_retrieve_ivf_topk.argtypes = _lib.load().lthm_retrieve_ivf_topk.argtypes
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    for P in (1, 8, 32):
+        if P > L:
+            continue
+        probes = cl.probe(q_bf, P, normalize_q=False)
+        need = _lib.load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, 0)
+        sc = torch.empty((Q, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def scan_call(lib):
+            rc = lib.lthm_retrieve_ivf_topk(ptr(cl.emb), N, ptr(cl.row_ids), ptr(cl.list_off), L, ptr(q_bf), dcode(q_bf), 0, Q,
+                                            ptr(probes), P, k, None, ptr(sc), ptr(ids), ptr(ws), need, stream())
+            if rc != 0:
+                raise RuntimeError(f"lthm_retrieve_ivf_topk failed with hip error {rc}")
+
+        arms = [("plain", lambda: cl.topk(q_bf, k, nprobe=P, normalize_q=False), []),
+                ("neutral", lambda: view.topk(q_bf, k, nprobe=P, normalize_q=False, tag_filter=zero_f, bias_weight=zero_w), []),
+                ("filt", lambda: view.topk(q_bf, k, nprobe=P, normalize_q=False, tag_filter=half_f, bias_weight=one_w), []),
+                ("flat", lambda: flat.topk(q_bf, k, normalize_q=False, tag_filter=half_f, bias_weight=one_w), [])]
+        if base is not None:
+            arms += [("base_scan_call", lambda: scan_call(base), []), ("scan_call", lambda: scan_call(_lib.load()), [])]
+        for _ in range(2):
+            for _, fn, _ in arms:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for _, fn, times in arms:
+                times.append(timed(fn))
+        out = {"shape": name, "mode": "ivf_filt", "Q": Q, "N": N, "k": k, "L": L, "nprobe": P, "reps": reps}
+        med, lo_, hi_ = {}, {}, {}
+        for key, _, times in arms:
+            med[key], lo_[key], hi_[key] = statistics.median(times), min(times), max(times)
+            out.update({f"{key}_ms": round(med[key], 4), f"{key}_min_ms": round(lo_[key], 4), f"{key}_max_ms": round(hi_[key], 4)})
+        for a, b in (("neutral", "plain"), ("filt", "plain"), ("filt", "flat")) + ((("scan_call", "base_scan_call"),) if base else ()):
+            tag = "scan_call_over_base" if b == "base_scan_call" else f"{a}_over_{b}"
+            out[tag] = round(med[a] / med[b], 4)
+            out[tag + "_hi"] = round(hi_[a] / lo_[b], 4)
+        p_s, p_i = cl.topk(q_bf, k, nprobe=P, normalize_q=False)
+        n_s, n_i = view.topk(q_bf, k, nprobe=P, normalize_q=False, tag_filter=zero_f, bias_weight=zero_w)
+        out["neutral_equals_plain"] = bool(torch.equal(p_i, n_i) and torch.equal(p_s.view(torch.int32), n_s.view(torch.int32)))
+        # the flat list's entries that lie in a probed list are, in order, the head of the clustered list
+        f_s, f_i = view.topk(q_bf, k, nprobe=P, normalize_q=False, tag_filter=half_f, bias_weight=one_w)
+        w_i, w_s, _, _ = flat.topk(q_bf, k, normalize_q=False, tag_filter=half_f, bias_weight=one_w)
+        lists = torch.bucketize(cl.rows_of(w_i).long().clamp(min=0), cl.list_off[1:], right=True)
+        probed = (lists[:, :, None] == probes.long()[:, None, :]).any(dim=2) & (w_i != 0)
+        ok = True
+        for i in range(min(Q, 64)):
+            m = int(probed[i].sum())
+            ok = ok and torch.equal(w_i[i][probed[i]], f_i[i, :m]) and torch.equal(w_s[i][probed[i]], f_s[i, :m])
+        out["filt_equals_flat_on_probed"] = bool(ok)
+        hit = ((w_i[:, :, None] == f_i[:, None, :]).any(dim=2) & (w_i != 0)).float().sum(dim=1) / (w_i != 0).sum(dim=1).clamp(min=1)
+        out[f"filt_recall_at_{k}"] = round(float(hit.mean()), 4)
+        print(json.dumps(out), flush=True)
+
+
 def child_diversify(N: int, k: int, reps: int) -> None:
     import torch
     from recommendations_amd import kernels as K
@@ -684,6 +794,11 @@ def main() -> int:
                     help="a mode of its own: the catalogue as S shards (1..64) on this device against the unsharded call")
     ap.add_argument("--ivf", type=int, default=0,
                     help="a mode of its own: the catalogue clustered into L lists, nprobe in {1, 8, 32, 64}, against the flat call")
+    ap.add_argument("--ivf-filt", type=int, default=0,
+                    help="a mode of its own: --ivf's catalogue with tags and a bias, the with_filters() view against "
+                         "the plain clustered call and the flat call, nprobe in {1, 8, 32}")
+    ap.add_argument("--baseline-lib", default="",
+                    help="with --ivf-filt: another build of liblthm_hip.so whose lthm_retrieve_ivf_topk is timed in the same loop")
     ap.add_argument("--diversify", action="store_true",
                     help="a mode of its own: K.retrieve_diversify on pools of 512 and 1,024 against a torch greedy loop")
     ap.add_argument("--q8", type=int, default=0,
@@ -707,6 +822,13 @@ def main() -> int:
         raise SystemExit("--diversify is a mode of its own and takes --k in 1..128")
     if not 0 <= a.q8 <= 1024 or (a.q8 and (a.ivf or a.shards or a.diversify or not 1 <= a.k <= min(a.q8, 128))):
         raise SystemExit("--q8 takes 0 (off) or a pool of 1..1024, is a mode of its own and takes --k in 1..min(pool, 128)")
+    if a.ivf_filt < 0 or (a.ivf_filt and (a.ivf or a.shards or a.diversify or a.q8 or not 1 <= a.k <= 128)):
+        raise SystemExit("--ivf-filt takes 0 (off) or a number of lists, is a mode of its own and takes --k in 1..128")
+    if a.baseline_lib and not (a.ivf_filt and os.path.exists(a.baseline_lib)):
+        raise SystemExit("--baseline-lib takes the path of a built liblthm_hip.so and goes with --ivf-filt")
+    if a.child and a.ivf_filt:
+        child_ivf_filt(a.child, a.n_items, a.k, a.reps, a.ivf_filt, a.baseline_lib)
+        return 0
     if a.child and a.q8:
         child_q8(a.child, a.n_items, a.k, a.reps, a.q8)
         return 0
@@ -729,7 +851,8 @@ def main() -> int:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps),
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
-                                 "--ivf", str(a.ivf), "--q8", str(a.q8)]
+                                 "--ivf", str(a.ivf), "--q8", str(a.q8), "--ivf-filt", str(a.ivf_filt),
+                                 "--baseline-lib", a.baseline_lib]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
                                 + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
