@@ -1101,6 +1101,30 @@ int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row
                                 const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
                                 const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
                                 void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_ivf_topk_deep: lthm_retrieve_ivf_topk_filt, argument for argument, with 1 <= k <= 1024:
+ * the lists a ranking stage or lthm_retrieve_diversify's pool take, from the probed lists alone.  The
+ * contract is lthm_retrieve_ivf_topk_filt's with that k: the k first, under (score descending, id
+ * ascending), of the rows that lie in a probed list, are not excluded, pass the filter and lie strictly
+ * behind the cursor, then (-inf, 0); every score has the bits lthm_retrieve_topk_deep returns for the
+ * same (query, item, weight), and with every list probed the result is that entry's.  A list named
+ * twice in a probe row gives both copies.  With k <= 128 the call IS lthm_retrieve_ivf_topk_filt: the
+ * same kernels, the same workspace and the same bits.  Above, the scan keeps every (query, probe)
+ * pair's candidates in 2,048 key slots of the workspace (16 KiB per pair) instead of LDS and sorts
+ * them there; the plan, the grid and the merge are unchanged, nothing synchronises with the host and
+ * the outputs stay a pure function of the inputs.  Every pointer, alignment, range and workspace check
+ * is made before any launch.  Every other clustered entry keeps refusing k > 128.
+ *   workspace lthm_retrieve_ivf_deep_ws_bytes(Q, N, L, P, k, X, has_cursor) bytes, 16-byte aligned:
+ *             lthm_retrieve_ivf_filt_ws_bytes(...) for k <= 128; above, that layout at k plus Q P 16 KiB
+ *             (a caller with many queries splits them: a query's result does not depend on the
+ *             others); -1 for k outside 1..1024 and wherever the _filt size is -1 for another reason */
+int64_t lthm_retrieve_ivf_deep_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X,
+                                        int32_t has_cursor);
+int lthm_retrieve_ivf_topk_deep(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
+                                int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
+                                const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
+                                const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
+                                const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
+                                void* workspace, int64_t ws_bytes, void* stream);
 /* Diversified lists: greedy maximal-marginal-relevance (MMR) selection of k out of a pool of M
  * candidates per query, with an optional cap on the selected items of one group.  The pool is a list
  * any of the calls above returned (lthm_retrieve_topk_deep gives up to 1,024 rows in one scan).

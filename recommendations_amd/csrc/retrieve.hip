@@ -2105,9 +2105,280 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   }
 }
 
+// ---------------------------------------------------------------- clustered deep lists: 128 < k <= 1024
+// retr_ivf_deep_topk_k is retr_ivf_topk_k<true, true, TAGS, BIAS>'s work unit (the block, its list, its
+// up to 64 pairs, the tile loop and the masks are its text) with retr_deep_topk_k's selection: pair p
+// owns the RD_CAP key slots keys[p RD_CAP ..] of the workspace, and only the block that serves the pair
+// ever touches them.  Count, tau and the flags stay in LDS.  An append takes its slot from the LDS
+// counter and writes the key with an ordinary vector store guarded by slot < RD_CAP; the wait and the
+// barrier at the top of the next tile order it ahead of the prune, as retr_deep_topk_k documents.  One
+// wave per flagged pair sorts the pair's keys in its own LDS buffer and writes the first k back.  The
+// stride is RD_CAP whatever list_off holds: a pair whose count is at most RD_LIM at the top of a tile
+// gains at most RT_IT keys in it, so no append passes the guard unwritten and none is lost.  A list
+// of at most RD_CAP rows never sets the flag before its last tile has run (slot >= RD_LIM needs more
+// than RD_LIM appends) and where it does the flag is not read again: its one sort is the final one,
+// which also writes the pair's k-list as (score, id), straight from the sorted LDS buffer, into the
+// layout retr_shard_merge_k reads.  A null list, a null cursor and a null bias are "none", as in
+// retr_deep_topk_k.
+struct RetrIvfDeepShared {
+  unsigned char img[2][RT_IT * 256];
+  u64 sort[4][RD_CAP];  // one buffer per wave
+  float tau[RT_QT];
+  int cnt[RT_QT];
+  int pair[RT_QT];
+  int flag[3];
+  alignas(16) int tag[2][RT_IT];
+  alignas(16) float bias[2][RT_IT];
+};
+static_assert(sizeof(RetrIvfDeepShared) <= 100 * 1024, "LDS budget: the images, four sort buffers and change");
+static_assert(sizeof(RetrIvfDeepShared) <= 160 * 1024, "LDS budget: one block per CU at the least");
+
+struct RetrIvfDeepArgs : RetrIvfFiltArgs {
+  u64* keys;  // [Q P, RD_CAP]: the candidates of every pair
+};
+
+template <bool TAGS>
+__global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
+  const int blk = blockIdx.x;
+  if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
+  __shared__ __attribute__((aligned(16))) RetrIvfDeepShared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int4 tt = a.tab[blk];
+  const int c = tt.x, pbase = tt.y, np = tt.z;
+  // the caller's offsets, kept inside the catalogue whatever they hold
+  int64_t row_lo = a.list_off[c], row_hi = a.list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > a.N ? a.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const bool live = ql < np;
+  const int pr = live ? a.pair_idx[pbase + ql] : 0;  // < Q P
+  const int64_t q = pr / a.P;
+  const bool hasb = a.bias != nullptr;  // uniform
+
+  if (tid < RT_QT) {
+    // a column without a pair never passes the filter
+    sh.tau[tid] = tid < np ? -INFINITY : INFINITY;
+    sh.cnt[tid] = 0;
+    sh.pair[tid] = tid < np ? a.pair_idx[pbase + tid] : 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  {
+    const bf16_t* rp = a.qn + q * RT_D;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (live) v = *reinterpret_cast<const u32x4*>(rp + 16 * s + 8 * hh);
+      qf[s] = __builtin_bit_cast(bf16x8v, v);
+    }
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // no list, a column without a pair: excludes nothing and reads nothing
+  if (live && a.xs != nullptr) {
+    const int* xl = a.xs + q * a.xstride;
+    int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (xl[mid] < row_lo) lo = mid + 1;
+      else hi = mid;
+    }
+    xp = xl + lo;
+    nx = *xp;
+  }
+  int fm = 0, fw = 0, fy = 0;
+  int yz = 1;
+  if constexpr (TAGS) {
+    if (live) {
+      const int* fp = a.filt + q * 3;
+      const int fall = fp[0], fnone = fp[2];
+      fy = fp[1];
+      yz = fy == 0;
+      fm = (fall & fnone) ? 0 : (fall | fnone);
+      fw = (fall & fnone) ? 1 : fall;
+    }
+  }
+  float cs = INFINITY;  // no cursor, a column without a pair
+  int cr = -1;
+  if (live && a.ascore != nullptr) {
+    cs = a.ascore[q];
+    cr = a.crow[pr];
+  }
+  float wq = 0.f;
+  if (live && hasb) wq = a.bw ? a.bw[q] : 1.f;
+  // the pair's key slots; a column without a pair never appends (its tau is +inf)
+  u64* const kbuf = a.keys + (int64_t)pr * RD_CAP;
+  int roff[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
+
+  const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 4 * j;
+      const void* src = row < row_hi ? (const void*)(ibase + row * 256 + ((sch ^ j) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 15));
+      glds16(src, img + (16 * w + 4 * j) * 256);
+    }
+    if constexpr (TAGS) {
+      if (w == 0) {  // never a read at or past row_hi <= N
+        const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+      }
+    }
+    if (hasb && w == 1) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
+      glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
+    }
+  };
+  retire_loads();
+  if (ntile > 0) stage(0);
+  for (int i = 0; i < ntile; ++i) {
+    // the key stores of tile i - 1 count in vmcnt like the DMA: this wait retires both
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;
+    if (sh.flag[(i + 2) % 3]) {  // tile i - 1 pushed a pair past the limit
+      for (int pq = w; pq < np; pq += 4) {
+        int n = sh.cnt[pq];
+        if (n > RD_LIM) {
+          n = n < RD_CAP ? n : RD_CAP;
+          u64* g = a.keys + (int64_t)sh.pair[pq] * RD_CAP;
+          const int m = retr_deep_prune(g, sh.sort[w], n, a.k, false, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.sort[w][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    int4 t4[4];
+    if constexpr (TAGS) {
+      const int4* tp = reinterpret_cast<const int4*>(sh.tag[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
+    }
+    float4 b4[4] = {};
+    if (hasb) {
+      const float4* bp = reinterpret_cast<const float4*>(sh.bias[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b4[j] = bp[2 * j];
+    }
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const bf16x8v af = frag_at(img + roff[s]);
+      acc = mfma32(af, qf[s], acc);
+    }
+    // first catalogue row of this lane's elements: element v is row rb + 8 (v >> 2) + (v & 3)
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {  // partial tile: the rows past the list never pass
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if (hasb) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bw4[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[4 * j + e] = __builtin_fmaf(wq, bw4[e], acc[4 * j + e]);
+      }
+    }
+    {
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    if constexpr (TAGS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int tw[4] = {t4[j].x, t4[j].y, t4[j].z, t4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool bad = ((tw[e] & fm) != fw) | (((tw[e] & fy) | yz) == 0);
+          acc[4 * j + e] = bad ? -INFINITY : acc[4 * j + e];
+        }
+      }
+    }
+    {
+      float m = acc[0];
+#pragma unroll
+      for (int v = 1; v < 16; ++v) m = fmaxf(m, acc[v]);
+      if (!(m < cs)) {
+        const int64_t cd = (int64_t)cr - rb;
+        const int cq = cd < -1 ? -1 : cd > 32 ? 32 : (int)cd;  // element offsets are 0..27
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+          const float s = acc[v];
+          const bool ok = (s < cs) | ((s == cs) & (8 * (v >> 2) + (v & 3) > cq));
+          acc[v] = ok ? s : -INFINITY;
+        }
+      }
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (live && slot < RD_CAP) kbuf[slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RD_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  wait_vm<0>();
+  __syncthreads();  // the last tile's appends have left their waves
+  // every pair's k best of the list, sorted, as (score, id); empty slots are (-inf, 0)
+  for (int pq = w; pq < np; pq += 4) {
+    int n = sh.cnt[pq];
+    n = n < RD_CAP ? n : RD_CAP;
+    const int pp = sh.pair[pq];
+    u64* buf = sh.sort[w];
+    int PS = 512;
+    while (PS < n) PS <<= 1;  // n <= RD_CAP
+    const u64* g = a.keys + (int64_t)pp * RD_CAP;
+    for (int idx = lane; idx < PS; idx += 64) buf[idx] = idx < n ? g[idx] : 0ull;
+    __builtin_amdgcn_wave_barrier();
+    if (n > 1) retr_deep_sort(buf, PS, lane);
+    const int m = n < a.k ? n : a.k;
+    const int64_t pq_q = pp / a.P, pq_s = pp - pq_q * a.P;
+    const int64_t o = (pq_s * a.Q + pq_q) * a.k;
+    for (int idx = lane; idx < a.k; idx += 64) {
+      const bool has = idx < m;
+      const u64 key = has ? buf[idx] : 0ull;  // idx < m <= PS
+      a.scores[o + idx] = has ? retr_key_score(key) : -INFINITY;
+      a.ids[o + idx] = has ? a.row_ids[retr_key_row(key)] : 0;
+    }
+    __builtin_amdgcn_wave_barrier();  // the buffer is read before the wave's next pair refills it
+  }
+}
+
 // the workspace of one call, in bytes from its start
 struct RetrIvfWs {
-  int64_t qn, cnt, off, pidx, tab, xs, scores, ids, crow, total, grid;
+  int64_t qn, cnt, off, pidx, tab, xs, scores, ids, crow, keys, total, grid;
 };
 
 // the scan's grid: sum_c ceil(n_c / 64) <= floor(sum_c n_c / 64) + #{c : n_c > 0} with sum_c n_c <= Q P
@@ -2118,9 +2389,11 @@ inline int64_t retr_ivf_grid(int64_t Q, int64_t P, int64_t L) {
 
 // cursor: the pairs' cursor rows behind everything else, so that the call without one has the
 // layout and the size it always had
-bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o, bool cursor = false) {
+// deep: k up to RD_KMAX and the pairs' key slots behind everything else, for retr_ivf_deep_topk_k
+bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o, bool cursor = false,
+                 bool deep = false) {
   if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || L < 1 || L >= (1ll << 31)) return false;
-  if (P < 1 || P > RS_SMAX || k < 1 || k > RT_KMAX || X < 0 || X > RT_XMAX) return false;
+  if (P < 1 || P > RS_SMAX || k < 1 || k > (deep ? RD_KMAX : RT_KMAX) || X < 0 || X > RT_XMAX) return false;
   if (Q * P >= (1ll << 31)) return false;
   o->grid = retr_ivf_grid(Q, P, L);
   if (o->grid >= (1ll << 31)) return false;
@@ -2134,6 +2407,7 @@ bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t 
   o->scores = at, at += up256(P * Q * k * 4);
   o->ids = at, at += up256(P * Q * k * 8);
   o->crow = at, at += cursor ? up256(Q * P * 4) : 0;
+  o->keys = at, at += deep ? up256(Q * P * RD_CAP * 8) : 0;
   o->total = at;
   return true;
 }
@@ -2166,16 +2440,18 @@ extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_
                                      nullptr, nullptr, out_scores, out_ids, workspace, ws_bytes, stream);
 }
 
+namespace lthm {
+namespace {
+
 // The one call path of the clustered scan: without t, b and c it launches retr_ivf_topk_k<false> /
 // <true>, as lthm_retrieve_ivf_topk always did; with any of them <true, true, TAGS, BIAS>, which takes
-// a null list and a null cursor as "none".
-extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row_ids,
-                                           const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
-                                           int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t k,
-                                           const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
-                                           const lthm_retrieve_bias* b, const lthm_retrieve_ivf_cursor* c,
-                                           float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
-                                           void* stream) {
+// a null list and a null cursor as "none".  deep (lthm_retrieve_ivf_topk_deep with k > 128): the same
+// steps with retr_ivf_deep_topk_k<TAGS> as the scan and the pairs' key slots in the workspace.
+int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off, int64_t L,
+                  const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P,
+                  int32_t k, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
+                  const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids, void* workspace,
+                  int64_t ws_bytes, void* stream, bool deep) {
   LTHM_REQUIRE(items && row_ids && list_off && q && probes && out_scores && out_ids && workspace);
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   LTHM_REQUIRE(!b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0));
@@ -2187,7 +2463,7 @@ extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const i
   LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   RetrIvfWs wo;
-  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo, c != nullptr) && ws_bytes >= wo.total);
+  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo, c != nullptr, deep) && ws_bytes >= wo.total);
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   bf16_t* qn = (bf16_t*)(ws + wo.qn);
@@ -2226,7 +2502,8 @@ extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const i
   LTHM_CHECK_LAUNCH();
   // 3: the scan (with a cursor, the pairs' cursor rows first: one more kernel of the plan's shape)
   const bool filt = t || b || c;
-  RetrIvfFiltArgs a;  // the plain instantiations take its base
+  RetrIvfDeepArgs a;  // the other instantiations take its bases
+  a.keys = deep ? (u64*)(ws + wo.keys) : nullptr;
   a.tags = t ? t->tags : nullptr;
   a.filt = t ? t->filter : nullptr;
   a.bias = b ? b->bias : nullptr;
@@ -2268,22 +2545,61 @@ extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const i
     a.xstride = X + 1;
   }
   const dim3 grid((unsigned)wo.grid);
-  if (!filt) {
+  if (deep) {
+    if (t) hipLaunchKernelGGL(retr_ivf_deep_topk_k<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(retr_ivf_deep_topk_k<false>, grid, dim3(256), 0, s, a);
+  } else if (!filt) {
     const RetrIvfArgs& pa = a;
     if (x) hipLaunchKernelGGL(retr_ivf_topk_k<true>, grid, dim3(256), 0, s, pa);
     else hipLaunchKernelGGL(retr_ivf_topk_k<false>, grid, dim3(256), 0, s, pa);
   } else if (t && b) {
-    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, true>), grid, dim3(256), 0, s, a);
+    const RetrIvfFiltArgs& fa = a;
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, true>), grid, dim3(256), 0, s, fa);
   } else if (t) {
-    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, false>), grid, dim3(256), 0, s, a);
+    const RetrIvfFiltArgs& fa = a;
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, false>), grid, dim3(256), 0, s, fa);
   } else if (b) {
-    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, true>), grid, dim3(256), 0, s, a);
+    const RetrIvfFiltArgs& fa = a;
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, true>), grid, dim3(256), 0, s, fa);
   } else {
-    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, false>), grid, dim3(256), 0, s, a);
+    const RetrIvfFiltArgs& fa = a;
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, false>), grid, dim3(256), 0, s, fa);
   }
   LTHM_CHECK_LAUNCH();
   // 4: the merge of every query's P lists
   return lthm_retrieve_merge_shards(lscores, lids, nullptr, P, Q, k, out_scores, out_ids, nullptr, stream);
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row_ids,
+                                           const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                                           int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t k,
+                                           const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                                           const lthm_retrieve_bias* b, const lthm_retrieve_ivf_cursor* c,
+                                           float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
+                                           void* stream) {
+  return retr_ivf_call(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, Q, probes, P, k, x, t, b, c, out_scores,
+                       out_ids, workspace, ws_bytes, stream, false);
+}
+
+// k <= 128 is lthm_retrieve_ivf_topk_filt: the same kernels, the same workspace and the same bits
+extern "C" int64_t lthm_retrieve_ivf_deep_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X,
+                                                   int32_t has_cursor) {
+  RetrIvfWs w;
+  return retr_ivf_ws(Q, N, L, P, k, X, &w, has_cursor != 0, k > RT_KMAX) ? w.total : -1;
+}
+
+extern "C" int lthm_retrieve_ivf_topk_deep(const void* items, int64_t N, const int64_t* row_ids,
+                                           const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                                           int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t k,
+                                           const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                                           const lthm_retrieve_bias* b, const lthm_retrieve_ivf_cursor* c,
+                                           float* out_scores, int64_t* out_ids, void* workspace, int64_t ws_bytes,
+                                           void* stream) {
+  return retr_ivf_call(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, Q, probes, P, k, x, t, b, c, out_scores,
+                       out_ids, workspace, ws_bytes, stream, k > RT_KMAX);
 }
 
 // ---------------------------------------------------------------- diversified lists (MMR, per-group caps)

@@ -2047,8 +2047,12 @@ def _retrieve_ivf_cursor(who: str, after_scores, after_ids, Q: int, device):
     return c
 
 
+RETRIEVE_IVF_DEEP_WS_BYTES = 1 << 30  # the most workspace one deep clustered call takes: above it the queries are split
+
+
 def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_q: bool = True, exclude_rows=None,
-                      tags=None, tag_filter=None, bias=None, bias_weight=None, after_scores=None, after_ids=None):
+                      tags=None, tag_filter=None, bias=None, bias_weight=None, after_scores=None, after_ids=None,
+                      deep: bool = False):
     """The k best items per query among the lists the query probes (lthm_retrieve_ivf_topk,
     csrc/retrieve.hip retr_ivf_topk_k): the scan of a clustered catalogue.
 
@@ -2067,7 +2071,14 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     row order, the cursor an id, since the cursor row differs per list.  The result is the k first
     of the probed, non-excluded rows that pass the filter and lie strictly behind (after_score,
     after_id), every score fma(w[q], bias[row], dot) as retrieve_topk returns it; with every list
-    probed it is retrieve_topk's list.  With none of them the call is the one it always was."""
+    probed it is retrieve_topk's list.  With none of them the call is the one it always was.
+
+    deep=True lifts k to RETRIEVE_MAX_DEEP = 1024 (lthm_retrieve_ivf_topk_deep, retr_ivf_deep_topk_k):
+    the same contract, every score with the bits retrieve_topk(deep=True) returns; k <= 128 then runs
+    the kernels it always ran.  Above 128 every (query, probe) pair holds 16 KiB of candidates in the
+    workspace, so where one call would take more than RETRIEVE_IVF_DEEP_WS_BYTES (1 GiB) the queries
+    go through in consecutive chunks, each one call: a query's list does not depend on the other
+    queries, so the split changes no bit.  Without deep, k > 128 is refused as it always was."""
     import ctypes
     from ._lib import STRUCTS
     who = "retrieve_ivf_topk"
@@ -2076,7 +2087,11 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
            f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
     _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
     Q, N, k = q.shape[0], items.shape[0], int(k)
-    _check(1 <= k <= RETRIEVE_MAX_K, f"{who} takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    if deep:
+        _check(1 <= k <= RETRIEVE_MAX_DEEP, f"{who} with deep=True takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    else:
+        _check(1 <= k <= RETRIEVE_MAX_K, f"{who} takes k in 1..{RETRIEVE_MAX_K} (got {k})")
+    deep = bool(deep) and k > RETRIEVE_MAX_K
     _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
     _check(row_ids.dtype == torch.int64 and tuple(row_ids.shape) == (N,),
            f"row_ids must be int64 [N], one id per catalogue row (got {row_ids.dtype} {tuple(row_ids.shape)}, N={N})")
@@ -2108,6 +2123,9 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     b, bw = _retrieve_bias(who, bias, bias_weight, items, Q, "Q", dev)
     c = _retrieve_ivf_cursor(who, after_scores, after_ids, Q, dev)
     filt = t is not None or b is not None or c is not None
+    if deep:
+        return _retrieve_ivf_deep(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, tags, tag_filter,
+                                  bias, bw, after_scores, after_ids)
     if filt:
         need = load().lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, P, k, X, int(c is not None))
     else:
@@ -2129,6 +2147,55 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     call("lthm_retrieve_ivf_topk_filt", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
          int(bool(normalize_q)), Q, ptr(probes), P, k, *parts, ptr(scores), ptr(ids), ptr(ws), need, stream(),
          _key="retr_ivf_topk_filt_k", _work=work, _unit="byte")
+    return scores, ids
+
+
+def _retrieve_ivf_deep(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, tags, tag_filter, bias, bw,
+                       after_scores, after_ids):
+    """retrieve_ivf_topk's deep call on checked arguments (bw: the weights as f32 [Q] or None): one
+    lthm_retrieve_ivf_topk_deep per chunk of consecutive queries, the largest chunk whose workspace
+    stays within RETRIEVE_IVF_DEEP_WS_BYTES (one query at the least)."""
+    import ctypes
+    from ._lib import STRUCTS
+    Q, N, L, P = q.shape[0], items.shape[0], list_off.shape[0] - 1, probes.shape[1]
+    X = 0 if exclude_rows is None else exclude_rows.shape[1]
+    has_c = int(after_scores is not None)
+    size = lambda n: load().lthm_retrieve_ivf_deep_ws_bytes(n, N, L, P, k, X, has_c)
+    _check(size(Q) >= 0, f"retrieve_ivf_topk: no workspace size for Q={Q} N={N} L={L} P={P} k={k} X={X} "
+                         "(Q P must stay below 2^31)")
+    step = Q
+    if size(Q) > RETRIEVE_IVF_DEEP_WS_BYTES:
+        lo, hi = 1, Q  # the size ascends with the queries: the most queries that fit, by bisection
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if size(mid) <= RETRIEVE_IVF_DEEP_WS_BYTES else (lo, mid - 1)
+        step = lo
+    dev = q.device
+    q = q.contiguous()
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    ws = torch.empty(size(step), dtype=torch.uint8, device=dev)
+    for q0 in range(0, Q, step):
+        n = min(step, Q - q0)
+        cut = lambda v: None if v is None else v[q0:q0 + n]  # a contiguous tensor's leading rows are contiguous
+        x = t = b = c = None
+        if exclude_rows is not None:
+            x = STRUCTS["lthm_retrieve_excl"]()
+            x.rows, x.X = ptr(cut(exclude_rows)), X
+        if tags is not None:
+            t = STRUCTS["lthm_retrieve_tags"]()
+            t.tags, t.filter = ptr(tags), ptr(cut(tag_filter))
+        if bias is not None:
+            b = STRUCTS["lthm_retrieve_bias"]()
+            b.bias, b.weight = ptr(bias), (ptr(cut(bw)) if bw is not None else None)
+        if after_scores is not None:
+            c = STRUCTS["lthm_retrieve_ivf_cursor"]()
+            c.after_score, c.after_id = ptr(cut(after_scores)), ptr(cut(after_ids))
+        parts = [ctypes.addressof(o) if o is not None else None for o in (x, t, b, c)]
+        work = float(n * RETRIEVE_WIDTH * q.element_size() + 24.0 * P * n * k + 12.0 * n * k + 4.0 * n * (P + X))
+        call("lthm_retrieve_ivf_topk_deep", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(cut(q)), dcode(q),
+             int(bool(normalize_q)), n, ptr(cut(probes)), P, k, *parts, ptr(cut(scores)), ptr(cut(ids)), ptr(ws),
+             ws.numel(), stream(), _key="retr_ivf_deep_topk_k", _work=work, _unit="byte")
     return scores, ids
 
 

@@ -567,7 +567,8 @@ class ClusteredItemCatalogue:
     bias are carried for ``to_flat()`` and for the view ``with_filters()`` returns, whose scan applies
     them and takes cursors; this catalogue's own scan scores the plain dot and filters nothing but
     ``exclude_ids``.  Groups are not carried: a clustered list is diversified against
-    the flat catalogue it was built from (``ItemCatalogue.diversify`` takes its ids)."""
+    the flat catalogue it was built from (``ItemCatalogue.diversify`` takes its ids), or by the view
+    ``with_deep(groups)`` returns, which takes them and whose lists reach k = 1,024."""
 
     def __init__(self, row_ids: torch.Tensor, emb: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
                  tags: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -613,6 +614,7 @@ class ClusteredItemCatalogue:
         self._ids = ids.contiguous()      # ascending
         self._order = order.contiguous()  # the clustered row of every id of _ids
         self._plain = None                # the flat catalogue without tags and bias, for recall
+        self.groups = None                # the with_deep() view: int32 [N] in the rows' order
 
     @classmethod
     def from_assignment(cls, catalogue: ItemCatalogue, centroids: torch.Tensor, assign: torch.Tensor) -> "ClusteredItemCatalogue":
@@ -640,6 +642,8 @@ class ClusteredItemCatalogue:
         return cls(catalogue.ids[order], catalogue.emb[order], list_off, centroids.to(dev),
                    None if catalogue.tags is None else catalogue.tags[order],
                    None if catalogue.bias is None else catalogue.bias[order])
+
+    _MAX_K = K.RETRIEVE_MAX_K  # the longest list of topk (the with_deep() view: K.RETRIEVE_MAX_DEEP)
 
     def __len__(self) -> int:
         return self.row_ids.shape[0]
@@ -680,6 +684,10 @@ class ClusteredItemCatalogue:
         out = ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
                                      self.centroids.to(device), None if self.tags is None else self.tags.to(device),
                                      None if self.bias is None else self.bias.to(device))
+        if self.scans_deep:
+            view = out.with_deep()
+            view.groups = None if self.groups is None else self.groups.to(device)
+            return view
         return out.with_filters() if self.scans_filters else out
 
     @property
@@ -687,6 +695,34 @@ class ClusteredItemCatalogue:
         """Whether ``topk`` follows the flat catalogue's conventions (tags, bias, cursors): False here,
         True on the view ``with_filters()`` returns."""
         return False
+
+    @property
+    def scans_deep(self) -> bool:
+        """Whether ``topk`` takes k up to ``K.RETRIEVE_MAX_DEEP`` = 1024 and the catalogue diversifies its
+        own lists: False here, True on the view ``with_deep()`` returns."""
+        return False
+
+    def with_deep(self, groups: Optional[torch.Tensor] = None) -> "DeepClusteredItemCatalogue":
+        """A view over the same tensors (nothing is copied) that is a ``with_filters()`` view whose
+        ``topk`` takes k up to 1024 and that has ``diversify``: see ``DeepClusteredItemCatalogue``.
+        ``groups`` int32 [N], one key per item in ``to_flat()``'s (id-ascending) order, 0 = no group:
+        the ``groups`` of the flat catalogue this was built from, for ``diversify``'s ``group_cap``.
+        They are permuted once into the clustered row order.  This catalogue is unchanged; neither
+        the flag nor the groups are stored by ``save``."""
+        N = len(self)
+        if groups is not None:
+            if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int32 or tuple(groups.shape) != (N,):
+                raise ValueError(f"with_deep takes groups int32 [N], one key per item in to_flat()'s order "
+                                 f"(got {getattr(groups, 'dtype', type(groups).__name__)} "
+                                 f"{tuple(getattr(groups, 'shape', ()))}, N={N})")
+            perm = torch.empty(N, dtype=torch.int32, device=self.emb.device)
+            perm[self._order] = groups.to(self.emb.device)  # _order: the clustered row of the i-th id
+            groups = perm
+        view = object.__new__(DeepClusteredItemCatalogue)
+        view.__dict__.update(self.__dict__)
+        view._flat = None
+        view.groups = groups
+        return view
 
     def with_filters(self) -> "FilteredClusteredItemCatalogue":
         """A view over the same tensors (nothing is copied) whose scan applies the catalogue's tags and
@@ -707,8 +743,8 @@ class ClusteredItemCatalogue:
         if nprobe < 1:
             raise ValueError(f"nprobe takes at least one list (got {nprobe})")
         k = int(k)
-        if not 1 <= k <= K.RETRIEVE_MAX_K:
-            raise ValueError(f"a clustered catalogue takes k in 1..{K.RETRIEVE_MAX_K} (got {k})")
+        if not 1 <= k <= self._MAX_K:
+            raise ValueError(f"a clustered catalogue takes k in 1..{self._MAX_K} (got {k})")
         return k, nprobe
 
     def probe(self, q: torch.Tensor, nprobe: int, *, normalize_q: bool = True) -> torch.Tensor:
@@ -863,7 +899,8 @@ class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
                                    tag_filter=None if tag_filter is None else tag_filter.contiguous(),
                                    bias=self.bias, bias_weight=bias_weight,
                                    after_scores=None if after_scores is None else after_scores.contiguous(),
-                                   after_ids=None if after_ids is None else after_ids.contiguous())
+                                   after_ids=None if after_ids is None else after_ids.contiguous(),
+                                   deep=self.scans_deep)
 
     def recall(self, q: torch.Tensor, k: int, nprobe: int, **filters) -> float:
         """The mean over the queries of the fraction of ``to_flat().topk(q, k, **filters)``'s ids that
@@ -875,11 +912,71 @@ class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
         want = self._flat.topk(q, k, **filters)[0]
         got = self.topk(q, k, nprobe=nprobe, **filters)[1]
         real = want != 0
-        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
+        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
+        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
+                         for i in range(0, want.shape[0], rows)]).double()
         n = real.sum(dim=1)
         if not bool((n > 0).any()):
             return 1.0
         return float((hit[n > 0] / n[n > 0].double()).mean())
+
+
+class DeepClusteredItemCatalogue(FilteredClusteredItemCatalogue):
+    """``ClusteredItemCatalogue.with_deep(groups)``: the ``with_filters()`` view of the same tensors
+    whose lists reach k = ``K.RETRIEVE_MAX_DEEP`` = 1024 (``K.retrieve_ivf_topk(deep=True)``;
+    csrc/retrieve.hip ``retr_ivf_deep_topk_k``), the length a ranking stage or ``diversify`` takes.
+    ``topk`` and ``recall`` are the filtered view's, argument for argument, with k in 1..1024: k <= 128
+    runs the kernels it runs there, and above every score keeps the bits ``ItemCatalogue.topk``
+    returns.  ``groups`` int32 [N] in the clustered row order, or None."""
+
+    _MAX_K = K.RETRIEVE_MAX_DEEP
+    _DIVERSIFY_QUERIES = 1024  # the queries of one diversify call: their pools' rows are gathered (256 MiB at M = 1024)
+
+    @property
+    def scans_deep(self) -> bool:
+        return True
+
+    @property
+    def has_groups(self) -> bool:
+        return self.groups is not None
+
+    def with_deep(self, groups: Optional[torch.Tensor] = None) -> "DeepClusteredItemCatalogue":
+        return self if groups is None else ClusteredItemCatalogue.with_deep(self, groups)
+
+    def diversify(self, item_ids: torch.Tensor, scores: torch.Tensor, k: int, *,
+                  lam: Union[float, torch.Tensor] = 1.0, group_cap: Optional[int] = None):
+        """``ItemCatalogue.diversify`` on this catalogue's own rows, under its contract and checks:
+        (item_ids int64 [Q, k], scores f32 [Q, k], objective f32 [Q, k]) in selection order, for a pool
+        ``item_ids`` int64 [Q, M] / ``scores`` f32 [Q, M], M <= 1024, k <= 128, ``lam`` a number or a
+        float tensor [Q] in [0, 1], ``group_cap`` with the ``groups`` given to ``with_deep``.  The
+        result is, in all three outputs, what ``to_flat()`` with those groups returns for the pool.
+
+        ``K.retrieve_diversify`` breaks ties by the lower row, and "the lower row" means "the lower
+        id" only where rows ascend with ids, which the clustered order does not across lists.  So
+        the pool's distinct items are gathered from the clustered ``emb`` (through ``rows_of``) into
+        an id-ascending block, at most ``_DIVERSIFY_QUERIES`` queries' pools at a time, and the kernel
+        runs on that block: the catalogue itself is neither copied nor re-ordered."""
+        if item_ids.dtype != torch.int64 or item_ids.dim() != 2:
+            raise ValueError(f"diversify takes int64 item_ids [Q, M] (got {item_ids.dtype} {tuple(item_ids.shape)})")
+        if scores.dtype != torch.float32 or scores.shape != item_ids.shape:
+            raise ValueError(f"diversify takes f32 scores of the ids' shape (got {scores.dtype} {tuple(scores.shape)})")
+        if group_cap is not None and self.groups is None:
+            raise ValueError("group_cap given, but this catalogue carries no groups")
+        Q = item_ids.shape[0]
+        dev = self.emb.device
+        step = self._DIVERSIFY_QUERIES
+        outs = []
+        for q0 in range(0, max(Q, 1), step):
+            pool = item_ids[q0:q0 + step].to(dev)
+            held = torch.unique(pool)  # ascending
+            rows = self.rows_of(held).long()
+            held, rows = held[rows >= 0], rows[rows >= 0]
+            if held.numel() == 0:  # no candidate at all: a catalogue is never empty, so one row stands in
+                held, rows = self.row_ids[:1], torch.zeros(1, dtype=torch.int64, device=dev)
+            block = ItemCatalogue(held, self.emb[rows], groups=None if self.groups is None else self.groups[rows])
+            outs.append(block.diversify(pool, scores[q0:q0 + step], k, group_cap=group_cap,
+                                        lam=lam[q0:q0 + step] if isinstance(lam, torch.Tensor) and lam.dim() == 1 else lam))
+        return tuple(torch.cat([o[i] for o in outs]) for i in range(3))
 
 
 class ShardedItemCatalogue:

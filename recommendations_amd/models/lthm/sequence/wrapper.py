@@ -377,7 +377,10 @@ class LTHMModelWrapper(BaseModelWrapper):
         scores; ``exclude_history`` composes, every other argument above is refused by name.  Its
         ``with_filters()`` view also takes ``tag_all`` / ``tag_any`` / ``tag_none``, ``after`` and
         ``bias_weight``, with the meaning they have on a flat catalogue, on the probed lists (pass the
-        same ``nprobe`` with ``after``); it still refuses ``heads`` and k > 128.
+        same ``nprobe`` with ``after``); it still refuses ``heads`` and k > 128.  Its ``with_deep(groups)``
+        view takes k up to 1024 and ``diversity`` / ``pool`` / ``group_cap`` as a flat catalogue does, below:
+        the pool is the deep list of the probed lists and the view's own ``diversify`` selects from it;
+        ``heads`` it still refuses.
         ``diversity`` = lambda in [0, 1] and / or ``group_cap`` = m (alone it means lambda = 1; the
         catalogue must carry groups) ask a flat ``ItemCatalogue`` for a diversified list: the call
         retrieves ``pool`` items (default min(8 k, 1024); k <= ``pool`` <= 1024, k <= 128; above 128
@@ -385,7 +388,7 @@ class LTHMModelWrapper(BaseModelWrapper):
         ``bias_weight`` in force, and returns the k that ``ItemCatalogue.diversify`` selects from
         them, in selection order: ``scores`` are the pool's own and ``objective`` f32 [B, k] is the
         value each item was selected at.  ``after`` is refused with them: a cursor has no meaning in
-        a re-ordered list.  Sharded and clustered catalogues refuse them.
+        a re-ordered list.  Sharded and clustered catalogues refuse them, but for a ``with_deep()`` view.
         A ``QuantizedItemCatalogue`` (``ItemCatalogue.quantize``) takes ``shortlist`` (None for
         min(max(4 k, 128), 1024); k..1024): the e4m3 scan's ``shortlist`` best rows are re-scored with the
         exact rows and the k best returned (k <= 1024), the flat list wherever the shortlist holds it;
@@ -412,7 +415,9 @@ class LTHMModelWrapper(BaseModelWrapper):
         if clustered:
             given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
                      "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
-            if catalogue.scans_filters:  # a with_filters() view scans tags, prior and cursor itself
+            if catalogue.scans_deep:  # a with_deep() view also diversifies its own lists
+                given = {"heads": heads}
+            elif catalogue.scans_filters:  # a with_filters() view scans tags, prior and cursor itself
                 given = {name: given[name] for name in ("heads", "diversity", "pool", "group_cap")}
             bad = [name for name, v in given.items() if v is not None]
             if bad:
@@ -425,7 +430,7 @@ class LTHMModelWrapper(BaseModelWrapper):
             raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
         diversify = diversity is not None or group_cap is not None
         if diversify:
-            if not isinstance(catalogue, ItemCatalogue):
+            if not isinstance(catalogue, ItemCatalogue) and not (clustered and catalogue.scans_deep):
                 raise ValueError("diversity / group_cap take a flat ItemCatalogue: a sharded or clustered list is "
                                  "diversified with ItemCatalogue.diversify on a flat catalogue over the same items")
             if after is not None:
@@ -486,8 +491,13 @@ class LTHMModelWrapper(BaseModelWrapper):
         if isinstance(bias_weight, torch.Tensor):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
         if clustered and catalogue.scans_filters:
-            scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen, tag_filter=filt,
-                                              after_scores=after_scores, after_ids=after_ids, bias_weight=bias_weight)
+            scores, item_ids = catalogue.topk(q, pool if diversify else k, nprobe=nprobe, normalize_q=True,
+                                              exclude_ids=seen, tag_filter=filt, after_scores=after_scores,
+                                              after_ids=after_ids, bias_weight=bias_weight)
+            if diversify:  # a with_deep() view only: every other clustered catalogue has refused above
+                item_ids, scores, obj = catalogue.diversify(item_ids, scores, k, group_cap=group_cap,
+                                                            lam=1.0 if diversity is None else float(diversity))
+                return {"item_ids": item_ids, "scores": scores, "objective": obj}
             return {"item_ids": item_ids, "scores": scores}
         if clustered:
             scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)

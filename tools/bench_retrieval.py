@@ -81,6 +81,15 @@ medians (min / max):
 With --baseline-lib PATH (another build of liblthm_hip.so, say the parent commit's) a fifth and sixth arm time the
 one C call lthm_retrieve_ivf_topk of that library and of this one on the same probes (base_scan_call_ms,
 scan_call_ms, scan_call_over_base): the unfiltered path's timing against its parent in the same loop.
+--ivf-deep L is a mode of its own too: the catalogue of --ivf with random group keys, its with_deep() view.  One JSON
+line per (shape, nprobe in {8, 32}, k in {256, 1024}), all arms alternating in one loop, medians (min / max):
+  ivf_deep_ms / flat_deep_ms  the view's topk (probe scan + the deep clustered call) and the flat deep call with the same
+                              k; deep_over_flat on the medians (_hi: the worst pairing, ivf max / flat min; faster only if
+                              < 1); deep_equals_flat_on_probed (the flat list's entries that lie in a probed list are, bit
+                              for bit and in order, the head of the clustered list; the first 64 queries) and recall_at_k
+With --baseline-lib PATH two more arms time lthm_retrieve_ivf_topk at k = 100 through that library and through this one
+(scan_call_within_base: each median inside the other's min-max range).  The serving shape adds one line per nprobe for
+the chain deep pool of 1,024 -> diversify k = 100 (lam 0.7, group_cap 2), the view against the flat catalogue.
 --diversify is a mode of its own too: Q = 256 queries, N unit rows drawn as --ivf draws them, the pool the deep
 scan's own first M rows for M in {512, 1024}, k = 100 by default, lam = 0.7.  One JSON line per M:
   kernel_ms / torch_ms        K.retrieve_diversify and a torch greedy loop on the device over the gathered
@@ -645,6 +654,115 @@ def child_ivf_filt(name: str, N: int, k: int, reps: int, L: int, baseline_lib: s
         print(json.dumps(out), flush=True)
 
 
+def child_ivf_deep(name: str, N: int, reps: int, L: int, baseline_lib: str) -> None:
+    import ctypes
+    import torch
+    from recommendations_amd import _lib
+    from recommendations_amd._lib import dcode, ptr, stream
+    from recommendations_amd.models.lthm.sequence.retrieval import ItemCatalogue
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5  # child_ivf's catalogue and queries, drawn the same way
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    groups = torch.randint(0, 64, (N,), generator=g, device=dev).to(torch.int32)
+    flat = ItemCatalogue(torch.arange(1, N + 1, dtype=torch.int64, device=dev) * 3, items, groups=groups)
+    cl = flat.cluster(L, iters=5, seed=0, sample=min(N, 1 << 18))
+    view = cl.with_deep(groups)
+    torch.cuda.synchronize()
+    base = ctypes.CDLL(baseline_lib) if baseline_lib else None  # RTLD_LOCAL: its own kernels behind its own entry
+    if base is not None:
+        base.lthm_retrieve_ivf_topk.restype = ctypes.c_int
+        base.lthm_retrieve_ivf_topk.argtypes = _lib.load().lthm_retrieve_ivf_topk.argtypes
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def run(arms, out):
+        for _ in range(2):
+            for _, fn, _ in arms:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for _, fn, times in arms:  # all arms alternate in one loop
+                times.append(timed(fn))
+        for key, _, times in arms:
+            out.update({f"{key}_ms": round(statistics.median(times), 4), f"{key}_min_ms": round(min(times), 4),
+                        f"{key}_max_ms": round(max(times), 4)})
+
+    for P in (8, 32):
+        if P > L:
+            continue
+        probes = cl.probe(q_bf, P, normalize_q=False)
+        k0 = 100
+        need = _lib.load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k0, 0)
+        sc = torch.empty((Q, k0), dtype=torch.float32, device=dev)
+        ids = torch.empty((Q, k0), dtype=torch.int64, device=dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+        def scan_call(lib):
+            rc = lib.lthm_retrieve_ivf_topk(ptr(cl.emb), N, ptr(cl.row_ids), ptr(cl.list_off), L, ptr(q_bf), dcode(q_bf), 0, Q,
+                                            ptr(probes), P, k0, None, ptr(sc), ptr(ids), ptr(ws), need, stream())
+            if rc != 0:
+                raise RuntimeError(f"lthm_retrieve_ivf_topk failed with hip error {rc}")
+
+        for k in (256, 1024):
+            out = {"shape": name, "mode": "ivf_deep", "Q": Q, "N": N, "k": k, "L": L, "nprobe": P, "reps": reps}
+            arms = [("ivf_deep", lambda: view.topk(q_bf, k, nprobe=P, normalize_q=False), []),
+                    ("flat_deep", lambda: flat.topk(q_bf, k, normalize_q=False), [])]
+            if base is not None:
+                arms += [("base_scan_call", lambda: scan_call(base), []), ("scan_call", lambda: scan_call(_lib.load()), [])]
+            run(arms, out)
+            out["deep_over_flat"] = round(out["ivf_deep_ms"] / out["flat_deep_ms"], 4)
+            out["deep_over_flat_hi"] = round(out["ivf_deep_max_ms"] / out["flat_deep_min_ms"], 4)  # the worst pairing
+            if base is not None:  # the existing k = 100 path did not move: each median inside the other's range
+                out["scan_call_within_base"] = bool(out["base_scan_call_min_ms"] <= out["scan_call_ms"] <= out["base_scan_call_max_ms"]
+                                                    and out["scan_call_min_ms"] <= out["base_scan_call_ms"] <= out["scan_call_max_ms"])
+            # the flat list's entries that lie in a probed list are, in order, the head of the clustered list
+            f_s, f_i = view.topk(q_bf, k, nprobe=P, normalize_q=False)
+            w_i, w_s, _, _ = flat.topk(q_bf, k, normalize_q=False)
+            lists = torch.bucketize(cl.rows_of(w_i).long().clamp(min=0), cl.list_off[1:], right=True)
+            ok, hits = True, 0.0
+            for i in range(0, Q, 64):
+                probed = (lists[i:i + 64, :, None] == probes.long()[i:i + 64, None, :]).any(dim=2) & (w_i[i:i + 64] != 0)
+                hits += float(probed.float().sum(dim=1).div((w_i[i:i + 64] != 0).sum(dim=1).clamp(min=1)).sum())
+                for j in range(probed.shape[0] if i == 0 else 0):
+                    m = int(probed[j].sum())
+                    ok = ok and torch.equal(w_i[j][probed[j]], f_i[j, :m]) \
+                        and torch.equal(w_s[j][probed[j]].view(torch.int32), f_s[j, :m].view(torch.int32))
+            out["deep_equals_flat_on_probed"] = bool(ok)
+            out[f"recall_at_{k}"] = round(hits / Q, 4)  # a flat entry in a probed list is in the clustered list: checked above
+            print(json.dumps(out), flush=True)
+        if name == "serving":  # the wrapper-level chain: deep pool 1,024 -> diversify k = 100, clustered against flat
+            out = {"shape": name, "mode": "ivf_deep_diversify", "Q": Q, "N": N, "pool": 1024, "k": 100, "L": L, "nprobe": P,
+                   "reps": reps}
+
+            def chain_ivf():
+                s, i = view.topk(q_bf, 1024, nprobe=P, normalize_q=False)
+                return view.diversify(i, s, 100, lam=0.7, group_cap=2)
+
+            def chain_flat():
+                i, s, _, _ = flat.topk(q_bf, 1024, normalize_q=False)
+                return flat.diversify(i, s, 100, lam=0.7, group_cap=2)
+
+            run([("ivf_chain", chain_ivf, []), ("flat_chain", chain_flat, [])], out)
+            out["chain_over_flat"] = round(out["ivf_chain_ms"] / out["flat_chain_ms"], 4)
+            out["chain_over_flat_hi"] = round(out["ivf_chain_max_ms"] / out["flat_chain_min_ms"], 4)
+            print(json.dumps(out), flush=True)
+
+
 def child_diversify(N: int, k: int, reps: int) -> None:
     import torch
     from recommendations_amd import kernels as K
@@ -797,8 +915,12 @@ def main() -> int:
     ap.add_argument("--ivf-filt", type=int, default=0,
                     help="a mode of its own: --ivf's catalogue with tags and a bias, the with_filters() view against "
                          "the plain clustered call and the flat call, nprobe in {1, 8, 32}")
+    ap.add_argument("--ivf-deep", type=int, default=0,
+                    help="a mode of its own: --ivf's catalogue, the with_deep() view's k = 256 / 1,024 lists against the "
+                         "flat deep call, and the chain deep pool -> diversify")
     ap.add_argument("--baseline-lib", default="",
-                    help="with --ivf-filt: another build of liblthm_hip.so whose lthm_retrieve_ivf_topk is timed in the same loop")
+                    help="with --ivf-filt / --ivf-deep: another build of liblthm_hip.so whose lthm_retrieve_ivf_topk is timed "
+                         "in the same loop")
     ap.add_argument("--diversify", action="store_true",
                     help="a mode of its own: K.retrieve_diversify on pools of 512 and 1,024 against a torch greedy loop")
     ap.add_argument("--q8", type=int, default=0,
@@ -824,8 +946,13 @@ def main() -> int:
         raise SystemExit("--q8 takes 0 (off) or a pool of 1..1024, is a mode of its own and takes --k in 1..min(pool, 128)")
     if a.ivf_filt < 0 or (a.ivf_filt and (a.ivf or a.shards or a.diversify or a.q8 or not 1 <= a.k <= 128)):
         raise SystemExit("--ivf-filt takes 0 (off) or a number of lists, is a mode of its own and takes --k in 1..128")
-    if a.baseline_lib and not (a.ivf_filt and os.path.exists(a.baseline_lib)):
-        raise SystemExit("--baseline-lib takes the path of a built liblthm_hip.so and goes with --ivf-filt")
+    if a.ivf_deep < 0 or (a.ivf_deep and (a.ivf or a.ivf_filt or a.shards or a.diversify or a.q8)):
+        raise SystemExit("--ivf-deep takes 0 (off) or a number of lists, and is a mode of its own")
+    if a.baseline_lib and not ((a.ivf_filt or a.ivf_deep) and os.path.exists(a.baseline_lib)):
+        raise SystemExit("--baseline-lib takes the path of a built liblthm_hip.so and goes with --ivf-filt or --ivf-deep")
+    if a.child and a.ivf_deep:
+        child_ivf_deep(a.child, a.n_items, a.reps, a.ivf_deep, a.baseline_lib)
+        return 0
     if a.child and a.ivf_filt:
         child_ivf_filt(a.child, a.n_items, a.k, a.reps, a.ivf_filt, a.baseline_lib)
         return 0
@@ -852,7 +979,7 @@ def main() -> int:
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
                                  "--ivf", str(a.ivf), "--q8", str(a.q8), "--ivf-filt", str(a.ivf_filt),
-                                 "--baseline-lib", a.baseline_lib]
+                                 "--ivf-deep", str(a.ivf_deep), "--baseline-lib", a.baseline_lib]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
                                 + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
