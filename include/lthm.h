@@ -376,7 +376,8 @@ typedef struct lthm_attn_desc {
  * mask != NULL: S[b, h, q, k] += mask[b * mask_batch_stride + h * mask_head_stride
  * + q * mask_row_stride + k] (the reference's general additive attn_mask, SDPA :57-58,
  * TransformerBlock.inner_forward :404-408, on top of the causal flag); served by the
- * whole-head VALU kernels, so T <= 256 and K, V, Q, dO of one head fit in LDS. */
+ * whole-head VALU kernels, so T <= 256 and K, V, Q, dO of one head fit in LDS
+ * (lthm_attn_mask_ok: T <= 149 at E = 128). */
 int lthm_attn_fwd(const lthm_attn_desc* desc, void* stream);
 /* dq/dk/dv bf16 (same strides as q/k/v); dtable_part f32 [parts, 2T+1, H] with
  * parts = lthm_attn_bwd_parts(B, T) (reduce over the first dim; = B for T <= 256);
@@ -387,6 +388,10 @@ int64_t lthm_attn_bwd_parts(int32_t B, int32_t T);
  * mask: the long-T' 32x32x16 kernels serve it (T > 256, E = 64, both LDS images fit, not
  * switched off by the A/B environment switches); 0: the caller unpacks to full sequences. */
 int lthm_attn_packed_ok(int32_t T, int32_t E);
+/* 1 when lthm_attn_fwd AND lthm_attn_bwd take a general additive mask at this T and E: the
+ * whole-head VALU kernels keep K, V, Q and dO of one head in LDS, T (8 E + 72) + 16 bytes of the
+ * 160 KiB in the backward, so T <= 256 for E = 16 / 32 / 64 and T <= 149 for E = 128. */
+int lthm_attn_mask_ok(int32_t T, int32_t E);
 
 /* ------------------------------------------------------------------------- */
 /* LTHM towers (models/lthm/sequence/ encoder, product and query towers)     */

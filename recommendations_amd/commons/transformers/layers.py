@@ -135,7 +135,7 @@ class TransformerBlockFn(torch.autograd.Function):
         if pa > 0.0:
             K.dropout_rows_(qkv, 3, pa, seed)  # the attention sees (and the backward saves) the scaled q / k / v
         tab = None if table is None else table.detach().contiguous()
-        mop = K.attn_mask_operand(mask, B, H, T)
+        mop = K.attn_mask_operand(mask, B, H, T, E)
         if pack is not None and K.attn_packed_ok(T, E, mop):
             qkv_f, o_f = qkv, None  # the kernels read the packed rows through the pad-prefix maps
             o, lse = K.attn_fwd_qkv(qkv, B, T, H, E, tab, causal, mop, pack=pack)
@@ -413,7 +413,7 @@ class _SelfAttnFn(torch.autograd.Function):
         xb = K.cast(x.contiguous().view(M, C), torch.bfloat16)
         w_in_b, w_out_b = _bf(w_in), _bf(w_out)
         tab = None if table is None else table.detach().contiguous()
-        mop = ctx.mop = K.attn_mask_operand(mask, B, H, T)
+        mop = ctx.mop = K.attn_mask_operand(mask, B, H, T, E)
         if shared_kv:
             w_kv_b = _bf(w_kv)
             q = K.linear_fwd(xb, w_in_b, _f(b_in))

@@ -2286,6 +2286,14 @@ extern "C" int lthm_attn_packed_ok(int32_t T, int32_t E) {
   return fwd32_ok(a) && bwd32l_ok(a) ? 1 : 0;
 }
 
+// the masked dispatch's own test (attn_dispatch, a.mask set: attn_launch's LDS limit for the
+// backward, the larger of the two), exported so that the caller refuses a shape before the
+// forward runs instead of failing in the backward
+extern "C" int lthm_attn_mask_ok(int32_t T, int32_t E) {
+  if (T <= 0 || T > 256 || (E != 16 && E != 32 && E != 64 && E != 128)) return 0;
+  return fwd_lds(T, E) <= 160 * 1024 && bwd_lds(T, E) <= 160 * 1024 ? 1 : 0;
+}
+
 extern "C" int lthm_attn_fwd(const lthm_attn_desc* d, void* stream) {
   LTHM_REQUIRE(check_desc(d) == 0 && d->lse != nullptr && d->out != nullptr);
   if (d->B == 0) return 0;

@@ -841,10 +841,37 @@ def layernorm_bwd(dy2d, x2d, w, mean, rstd, res1=None, res2=None, want_bf16=True
 
 
 # ----------------------------------------------------------------- attention
-def attn_mask_operand(mask, B, H, T):
+_MASK_OK: dict = {}
+
+
+def attn_mask_ok(T, E):
+    """A general additive mask is served at this (T, E), forward and backward: the C
+    dispatcher's own test (lthm_attn_mask_ok)."""
+    key = (int(T), int(E))
+    ok = _MASK_OK.get(key)
+    if ok is None:
+        from ._lib import load
+        ok = _MASK_OK[key] = bool(load().lthm_attn_mask_ok(key[0], key[1]))
+    return ok
+
+
+def _check_mask_limit(T, E):
+    _check(attn_mask_ok(T, E),
+           f"a general additive attn_mask is supported for T <= 256 with E = 16 / 32 / 64 and T <= 149 with E = 128 "
+           f"(the masked backward keeps Q, K, V and dO of one head in LDS: T (8 E + 72) + 16 bytes <= 160 KiB); "
+           f"got T={T} E={E}")
+
+
+def attn_mask_operand(mask, B, H, T, E=None):
     """The reference's additive attn_mask (broadcast onto the [B, H, T, T] scores,
     commons/transformers/layers.py:57-58) as an f32 operand with its broadcast
-    strides: [T, T], [B or 1, T, T] or [B or 1, H or 1, T, T]."""
+    strides: [T, T], [B or 1, T, T] or [B or 1, H or 1, T, T].
+
+    Limit: the masked kernels hold one head whole in LDS, and the backward (Q, K, V, dO and the
+    row buffers: T (8 E + 72) + 16 bytes of 160 KiB) is the larger of the two, so a mask is taken
+    for T <= 256 at E = 16 / 32 / 64 and for T <= 149 at E = 128 (lthm_attn_mask_ok).  With E
+    given, a shape past the limit is refused here; without it only T <= 256 is checked here and
+    the (T, E) limit when the forward's descriptor is built (_attn_desc), still before any launch."""
     if mask is None:
         return None
     require_gpu(mask)
@@ -853,7 +880,9 @@ def attn_mask_operand(mask, B, H, T):
         m = m.unsqueeze(0 if m.dim() != 3 else 1)
     _check(m.dim() == 4 and tuple(m.shape[-2:]) == (T, T) and m.shape[0] in (1, B) and m.shape[1] in (1, H),
            f"attn_mask of shape {tuple(mask.shape)} does not broadcast onto [B={B}, H={H}, T={T}, T]")
-    _check(T <= 256, "a general additive attn_mask is supported for T <= 256")
+    _check(T <= 256, "a general additive attn_mask is supported for T <= 256 (T <= 149 with E = 128)")
+    if E is not None:
+        _check_mask_limit(T, E)
     m = m.contiguous()
     return m, (0 if m.shape[0] == 1 else m.stride(0)), (0 if m.shape[1] == 1 else m.stride(1)), m.stride(2)
 
@@ -862,6 +891,8 @@ def _attn_desc(q, k, v, B, T, H, E, out, lse, table, causal, q_ts, kv_ts, kv_hs,
     from ._lib import STRUCTS
     _check(min(B, T, H, E) >= 1 and T <= 4096 and (T <= 256 or E in (32, 64, 128)),
            f"attention takes 1 <= T <= 4096 (E in 32/64/128 beyond T = 256; got B={B} T={T} H={H} E={E})")
+    if mask is not None:  # forward and backward alike: never a forward whose backward cannot run
+        _check_mask_limit(T, E)
     rows = pack.M if pack is not None else B * T  # packed rows: the maps index M rows
     _need(q, (rows - 1) * q_ts + (H - 1) * E + E, "q")
     _need(k, (rows - 1) * kv_ts + (H - 1) * kv_hs + E, "k")
