@@ -211,6 +211,57 @@ typedef struct lthm_gemm_desc {
  * v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales. */
 int lthm_gemm(const lthm_gemm_desc* desc, void* stream);
 
+/* The launch plan of lthm_gemm: which kernel a descriptor runs on a device of `cus` compute
+ * units, decided on the host from the descriptor's numbers and its pointers' low bits alone
+ * (no GPU call, no device memory touched).  lthm_gemm launches from lthm_gemm_plan(desc,
+ * the device's CU count); the return value is the one lthm_gemm gives the same descriptor
+ * (1 for a refused one, the plan is then undefined). */
+#define LTHM_GEMM_KERNEL_NONE (-1)  /* M == 0 or N == 0: nothing is launched */
+#define LTHM_GEMM_KERNEL_K128 0     /* gemm_k<KA, KB>: 128 x 128 tiles, any shape / stride, batch, split-K */
+#define LTHM_GEMM_KERNEL_PS 1       /* gemm_ps_k<KB, BRES, EPI>: persistent ring kernel, tall bf16 GEMMs */
+#define LTHM_GEMM_KERNEL_WG 2       /* gemm_wg_k: 256 x 256 split-K tiles, both operands K-strided */
+#define LTHM_GEMM_KERNEL_PP 3       /* gemm_pp_k<false, SPREAD>: 256 x 256 tiles, K-contiguous, K >= 512 */
+#define LTHM_GEMM_KERNEL_PS_F8 4    /* gemm_ps_k<true, BRES, EPI, true>: fp8 operands */
+#define LTHM_GEMM_KERNEL_PP_F8 5    /* gemm_pp_k<true, false>: fp8 operands, K >= 1,024 */
+#define LTHM_GEMM_COMBINE_NONE 0
+#define LTHM_GEMM_COMBINE_REDUCE 1   /* splitk_reduce_k  */
+#define LTHM_GEMM_COMBINE_REDUCE4 2  /* splitk_reduce4_k */
+#define LTHM_GEMM_AMAX_NONE 0
+#define LTHM_GEMM_AMAX_KERNEL 1  /* the GEMM kernel's epilogue takes max |C| */
+#define LTHM_GEMM_AMAX_AFTER 2   /* lthm_amax over C after the GEMM */
+#define LTHM_GEMM_EPI_GENERIC (-1)  /* the runtime epilogue (every kernel but gemm_ps_k) */
+#define LTHM_GEMM_EPI_PLAIN 0       /* (+ bias) */
+#define LTHM_GEMM_EPI_ACT 1         /* (+ bias), GELU / QGELU / GELU_D, optional aux_out */
+#define LTHM_GEMM_EPI_GRAD 2        /* * act'(aux) or * aux, no bias */
+#define LTHM_GEMM_EPI_RES1 3        /* (+ bias) + res1 (f32) */
+#define LTHM_GEMM_EPI_RES2 4        /* (+ bias) + res1 + res2 (f32) */
+typedef struct lthm_gemm_plan_out {
+  int32_t kernel;  /* LTHM_GEMM_KERNEL_* */
+  int32_t ka;      /* template flags of the kernel (0 where it has no such flag) */
+  int32_t kb;
+  int32_t bres;
+  int32_t epi;     /* LTHM_GEMM_EPI_*: the compiled form for PS / PS_F8, the form the epilogue fits elsewhere */
+  int32_t spread;
+  int32_t splits;   /* effective split count (1: no split-K) */
+  int32_t combine;  /* LTHM_GEMM_COMBINE_* */
+  int32_t amax;     /* LTHM_GEMM_AMAX_* */
+  int32_t fast_ok;  /* 16-B aligned operands, leading dims and batch strides % 8 == 0 */
+  int32_t grid_x;   /* the GEMM kernel's grid and block */
+  int32_t grid_y;
+  int32_t grid_z;
+  int32_t block;
+  int32_t tiles_m;  /* in the kernel's own tile (128 or 256 rows / columns) */
+  int32_t tiles_n;
+  int32_t walkers;  /* PS / PS_F8: row-panel walkers per column tile and XCD */
+  int32_t ps_mode;  /* the read-once process settings the plan used: LTHM_GEMM_PS, */
+  int32_t pp_mode;  /* LTHM_GEMM_PP, */
+  int32_t pp_f8_mode;  /* LTHM_GEMM_PP_F8, */
+  int32_t wg_ragged;   /* LTHM_WG_RAGGED */
+  int32_t pad0;
+  int64_t k_per_split;  /* k range of one split (K when splits == 1) */
+} lthm_gemm_plan_out;
+int lthm_gemm_plan(const lthm_gemm_desc* desc, int32_t cus, lthm_gemm_plan_out* plan);
+
 /* Per-tensor fp8 quantisation: scale = amax(|x|) / 448 (1 if x == 0),
  * q = e4m3(clamp(x / scale, -448, 448)) round-to-nearest-even.  x: n f32 / bf16
  * (n % 8 == 0, 16-B aligned); q: n bytes; scale: device f32; work: 4-byte scratch. */

@@ -1438,8 +1438,34 @@ extern "C" int lthm_linear_layernorm_fwd(const void* x, const void* w, const flo
   return 0;
 }
 
-extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
-  LTHM_REQUIRE(d != nullptr);
+static_assert(EPI_PLAIN == LTHM_GEMM_EPI_PLAIN && EPI_ACT == LTHM_GEMM_EPI_ACT && EPI_GRAD == LTHM_GEMM_EPI_GRAD &&
+              EPI_RES1 == LTHM_GEMM_EPI_RES1 && EPI_RES2 == LTHM_GEMM_EPI_RES2, "lthm.h names the epilogue forms");
+
+// the one-tile kernel's split-K: the caller's split count rounded to whole K-tiles per split
+static int gemm_k_splits(int64_t K, int32_t want, int64_t* k_per_split) {
+  int splits = want < 1 ? 1 : want;
+  int64_t kps = (K + splits - 1) / splits;
+  kps = (kps + BK - 1) / BK * BK;
+  if (kps < BK) kps = BK;
+  splits = (int)((K + kps - 1) / kps);
+  if (splits < 1) splits = 1;
+  *k_per_split = (splits == 1) ? (K > 0 ? K : 1) : kps;
+  return splits;
+}
+
+// The dispatch of lthm_gemm as a pure host function (no GPU call): lthm_gemm launches what this
+// returns for cu_count(); tests/test_gemm_host.py holds it to a restatement of the rules below.
+extern "C" int lthm_gemm_plan(const lthm_gemm_desc* d, int32_t cus, lthm_gemm_plan_out* p) {
+  LTHM_REQUIRE(d != nullptr && p != nullptr && cus >= 1);
+  static const bool wg_ragged = !(getenv("LTHM_WG_RAGGED") && getenv("LTHM_WG_RAGGED")[0] == '0');  // A/B
+  *p = lthm_gemm_plan_out{};
+  p->kernel = LTHM_GEMM_KERNEL_NONE;
+  p->epi = LTHM_GEMM_EPI_GENERIC;
+  p->splits = 1;
+  p->ps_mode = lthm_gemm_ps_mode();
+  p->pp_mode = lthm_gemm_pp_mode();
+  p->pp_f8_mode = lthm_gemm_pp_f8();
+  p->wg_ragged = wg_ragged;
   LTHM_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0 && d->batch >= 1);
   LTHM_REQUIRE(d->out_dtype == LTHM_F32 || d->out_dtype == LTHM_BF16);
   if (d->M == 0 || d->N == 0) return 0;
@@ -1450,78 +1476,52 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
   LTHM_REQUIRE(d->act >= 0 && d->act <= LTHM_ACT_MUL_AUX);
   LTHM_REQUIRE(!(d->act == LTHM_ACT_GELU_GRAD || d->act == LTHM_ACT_QGELU_GRAD || d->act == LTHM_ACT_MUL_AUX) ||
                d->aux != nullptr);
-  int splits = d->splits < 1 ? 1 : d->splits;
-  LTHM_REQUIRE(splits == 1 || d->workspace != nullptr);
-  GemmArgs g;
-  g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)d->B; g.C = d->C;
-  g.M = d->M; g.N = d->N; g.K = d->K;
-  g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
-  g.sA = d->sA; g.sB = d->sB; g.sC = d->sC;
-  int64_t kps = (d->K + splits - 1) / splits;
-  kps = (kps + BK - 1) / BK * BK;
-  if (kps < BK) kps = BK;
-  splits = (int)((d->K + kps - 1) / kps);
-  if (splits < 1) splits = 1;
-  g.k_per_split = (splits == 1) ? (d->K > 0 ? d->K : 1) : kps;
-  g.alpha = d->alpha;
-  g.bias = d->bias; g.act = d->act; g.aux = (const bf16_t*)d->aux; g.aux_out = (bf16_t*)d->aux_out;
-  g.ldaux = d->ldaux > 0 ? d->ldaux : d->N;
-  g.res1 = d->res1; g.res2 = d->res2; g.ldr1 = d->ldr1 > 0 ? d->ldr1 : d->N; g.ldr2 = d->ldr2 > 0 ? d->ldr2 : d->N;
-  g.res1_dt = d->res1_dtype; g.res2_dt = d->res2_dtype; g.out_dt = d->out_dtype;
-  g.ws = (splits > 1) ? d->workspace : nullptr;
-  g.sa = nullptr;
-  g.sb = nullptr;
-  g.amax = reinterpret_cast<unsigned*>(d->amax_out);
+  LTHM_REQUIRE(d->splits <= 1 || d->workspace != nullptr);
+  int64_t kps;
+  const int splits = gemm_k_splits(d->K, d->splits, &kps);
+  const int64_t ldaux = d->ldaux > 0 ? d->ldaux : d->N;
+  const int64_t ldr1 = d->ldr1 > 0 ? d->ldr1 : d->N, ldr2 = d->ldr2 > 0 ? d->ldr2 : d->N;
   // the kernels other than gemm_ps_k leave amax_out to a pass over C afterwards
   LTHM_REQUIRE(!d->amax_out || (d->batch == 1 && d->ldc == d->N && (d->M * d->N) % 8 == 0 &&
                                 ((uintptr_t)d->C % 16) == 0));
-  auto amax_after = [&]() -> int {
-    return d->amax_out ? lthm_amax(d->C, d->out_dtype, d->M * d->N, d->amax_out, stream) : 0;
-  };
-  g.fast_ok = ((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 &&
-              d->sA % 8 == 0 && d->sB % 8 == 0;
+  const int amax_after = d->amax_out ? LTHM_GEMM_AMAX_AFTER : LTHM_GEMM_AMAX_NONE;
+  const bool fast_ok = ((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && d->lda % 8 == 0 &&
+                       d->ldb % 8 == 0 && d->sA % 8 == 0 && d->sB % 8 == 0;
+  p->fast_ok = fast_ok;
   if (splits > 1) {
     LTHM_REQUIRE(d->workspace_bytes >= (size_t)splits * d->batch * d->M * d->N * 4);
   }
   const int tiles_m = (int)((d->M + BM - 1) / BM), tiles_n = (int)((d->N + BN - 1) / BN);
-  hipStream_t s = (hipStream_t)stream;
   // weight gradients: 256 x 256 split-K tiles (splits bounded by the caller's workspace)
   // (any K: the packed rows of a shared pad prefix have no alignment; k rows past K read zeros)
-  static const bool wg_ragged = !(getenv("LTHM_WG_RAGGED") && getenv("LTHM_WG_RAGGED")[0] == '0');  // A/B
-  if (lthm_gemm_ps_mode() && !ka && !kb && d->batch == 1 && d->workspace && g.fast_ok && d->M % 8 == 0 &&
+  if (p->ps_mode && !ka && !kb && d->batch == 1 && d->workspace && fast_ok && d->M % 8 == 0 &&
       d->N % 8 == 0 && d->act == LTHM_ACT_NONE && !d->bias && d->M * d->N > 0 && (wg_ragged || d->K % WG_BK == 0)) {
     const int tm = (int)((d->M + 255) / 256), tn = (int)((d->N + 255) / 256);
     const int64_t cap = (int64_t)(d->workspace_bytes / ((size_t)d->M * d->N * 4));
-    int64_t sp = std::min<int64_t>(std::max(1, cu_count() / (tm * tn)), cap);
+    int64_t sp = std::min<int64_t>(std::max(1, cus / (tm * tn)), cap);
     sp = std::min<int64_t>(sp, d->K / (WG_BK * 8));  // >= 8 stages per split
-    if (sp >= 2 && tm * tn <= cu_count()) {
+    if (sp >= 2 && tm * tn <= cus) {
       int64_t kpw = (d->K + sp - 1) / sp;
       kpw = (kpw + WG_BK - 1) / WG_BK * WG_BK;
       const int spl = (int)((d->K + kpw - 1) / kpw);
-      GemmArgs gw = g;
-      gw.ws = d->workspace;
-      gw.res1 = nullptr; gw.res2 = nullptr;
-      hipLaunchKernelGGL(gemm_wg_k, dim3(tm * tn * spl), dim3(512), 0, s, gw, tm, tn, spl, kpw);
-      LTHM_CHECK_LAUNCH();
-      GemmArgs gr = g;
-      gr.ws = d->workspace;
-      gr.alpha = 1.f;  // alpha already applied to the partials
-      const int64_t total = d->M * d->N;
-      if (d->N % 4 == 0 && ((uintptr_t)d->workspace % 16) == 0)
-        hipLaunchKernelGGL(splitk_reduce4_k, dim3(grid_for(total / 4, 256, 256 * 8)), dim3(256), 0, s, gr, spl);
-      else
-        hipLaunchKernelGGL(splitk_reduce_k, dim3(grid_for(total, 256, 256 * 8)), dim3(256), 0, s, gr, spl, 1);
-      LTHM_CHECK_LAUNCH();
-      return amax_after();
+      p->kernel = LTHM_GEMM_KERNEL_WG;
+      p->splits = spl;
+      p->k_per_split = kpw;
+      p->tiles_m = tm; p->tiles_n = tn;
+      p->grid_x = tm * tn * spl; p->grid_y = 1; p->grid_z = 1; p->block = 512;
+      p->combine = (d->N % 4 == 0 && ((uintptr_t)d->workspace % 16) == 0) ? LTHM_GEMM_COMBINE_REDUCE4
+                                                                          : LTHM_GEMM_COMBINE_REDUCE;
+      p->amax = amax_after;
+      return 0;
     }
   }
-  const int per_xcd = cu_count() / 8;
+  const int per_xcd = cus / 8;
   int epi = -1;
   {
     const bool a16 = ((uintptr_t)d->C % 16) == 0 && d->ldc % 8 == 0 && ((uintptr_t)d->bias % 16) == 0;
-    const bool r1 = d->res1 && d->res1_dtype == LTHM_F32 && ((uintptr_t)d->res1 % 16) == 0 && g.ldr1 % 8 == 0;
-    const bool r2 = d->res2 && d->res2_dtype == LTHM_F32 && ((uintptr_t)d->res2 % 16) == 0 && g.ldr2 % 8 == 0;
-    const bool ax = ((uintptr_t)d->aux % 16) == 0 && ((uintptr_t)d->aux_out % 16) == 0 && g.ldaux % 8 == 0;
+    const bool r1 = d->res1 && d->res1_dtype == LTHM_F32 && ((uintptr_t)d->res1 % 16) == 0 && ldr1 % 8 == 0;
+    const bool r2 = d->res2 && d->res2_dtype == LTHM_F32 && ((uintptr_t)d->res2 % 16) == 0 && ldr2 % 8 == 0;
+    const bool ax = ((uintptr_t)d->aux % 16) == 0 && ((uintptr_t)d->aux_out % 16) == 0 && ldaux % 8 == 0;
     const int act = d->act;
     if (!a16 || !ax) epi = -1;
     else if (act == LTHM_ACT_NONE && !d->res1 && !d->res2) epi = EPI_PLAIN;
@@ -1533,31 +1533,136 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
     else if (act == LTHM_ACT_NONE && r1 && !d->res2) epi = EPI_RES1;
     else if (act == LTHM_ACT_NONE && r1 && r2) epi = EPI_RES2;
   }
+  p->epi = epi;
   if (d->ab_dtype == LTHM_FP8_E4M3) {
     // fp8 encoder GEMMs: persistent kernel only, geometry in 2-byte units
     LTHM_REQUIRE(epi >= 0 && ka && kb && splits == 1 && d->batch == 1 && d->K % 128 == 0 && d->K > 0);
     LTHM_REQUIRE(d->a_scale && d->b_scale && d->lda % 16 == 0 && d->ldb % 16 == 0 && d->N % 8 == 0);
     LTHM_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && tiles_n <= per_xcd);
-    GemmArgs g8 = g;
-    g8.K = d->K / 2; g8.lda = d->lda / 2; g8.ldb = d->ldb / 2;
-    g8.sa = d->a_scale; g8.sb = d->b_scale;
-    if (lthm_gemm_pp_mode() && lthm_gemm_pp_f8() && d->K >= 1024 && d->K % (2 * PP_BK) == 0 && d->M >= 256 &&
+    p->ka = 1; p->kb = 1;
+    p->k_per_split = d->K;
+    if (p->pp_mode && p->pp_f8_mode && d->K >= 1024 && d->K % (2 * PP_BK) == 0 && d->M >= 256 &&
         d->N >= 256 && !d->amax_out) {
       // 256 x 256 tiles (the bf16 kernel's geometry in 2-byte units).  From K = 1,024 on (8 K-tiles):
       // C5 fc2 (K = 2,048) 0.767 -> 0.660 ms, 4096^3 0.091 -> 0.065 ms (2.1 PF); the K = 512 forms
       // ran 17-24 % slower here than on the persistent kernel (profiles/r04ab/)
       const int tm = (int)((d->M + 255) / 256), tn = (int)((d->N + 255) / 256);
-      g8.ws = nullptr;
-      g8.amax = nullptr;
-      hipLaunchKernelGGL((gemm_pp_k<true, false>), dim3(tm * tn), dim3(512), 0, s, g8, tm, tn);
-      LTHM_CHECK_LAUNCH();
+      p->kernel = LTHM_GEMM_KERNEL_PP_F8;
+      p->tiles_m = tm; p->tiles_n = tn;
+      p->grid_x = tm * tn; p->grid_y = 1; p->grid_z = 1; p->block = 512;
       return 0;
     }
     const int R = per_xcd / tiles_n;
-    dim3 grid(8 * R * tiles_n);
-    const bool bres = g8.K <= 4 * BK;
+    p->kernel = LTHM_GEMM_KERNEL_PS_F8;
+    p->bres = d->K / 2 <= 4 * BK;
+    p->tiles_m = tiles_m; p->tiles_n = tiles_n; p->walkers = R;
+    p->grid_x = 8 * R * tiles_n; p->grid_y = 1; p->grid_z = 1; p->block = PS_THREADS;
+    p->amax = d->amax_out ? LTHM_GEMM_AMAX_KERNEL : LTHM_GEMM_AMAX_NONE;
+    return 0;
+  }
+  if (p->pp_mode && ka && kb && splits == 1 && d->batch == 1 && fast_ok && d->K >= 512 && d->K % PP_BK == 0 &&
+      d->M >= 256 && d->N >= 256) {
+    // (K = 256 forms stay on the persistent kernel: the C2 qkv / proj / fc forwards ran 5-26 %
+    // slower here, profiles/r04z_gemm_*; from K = 512 on this kernel wins: C4 fc1 forward 0.456 ->
+    // 0.349 ms, its dgrad 0.701 -> 0.376, C5 fc2 forward 1.456 -> 1.133, 4096^3 767 -> 1,179 TF)
+    const int tm = (int)((d->M + 255) / 256), tn = (int)((d->N + 255) / 256);
+    p->kernel = LTHM_GEMM_KERNEL_PP;
+    p->ka = 1; p->kb = 1;
+    // per-phase DMA issue where there are several column tiles (C4: 4-6 % faster); a single
+    // 256-column tile (C2's N = 256 dgrads) runs ~2 % faster with the DMA behind the barrier
+    // (profiles/r04am_ab.log)
+    p->spread = d->N > 256;
+    p->k_per_split = kps;
+    p->tiles_m = tm; p->tiles_n = tn;
+    p->grid_x = tm * tn; p->grid_y = 1; p->grid_z = 1; p->block = 512;
+    p->amax = amax_after;
+    return 0;
+  }
+  if (p->ps_mode && epi >= 0 && ka && splits == 1 && d->batch == 1 && fast_ok && d->K % BK == 0 && d->K > 0 &&
+      d->N % 8 == 0 && tiles_n <= per_xcd && (int64_t)tiles_m * tiles_n >= 4 * 8 * per_xcd) {
+    const int R = per_xcd / tiles_n;  // row-panel walkers per column tile and XCD
+    p->kernel = LTHM_GEMM_KERNEL_PS;
+    p->ka = 1; p->kb = kb;
+    p->bres = d->K <= 4 * BK;
+    p->k_per_split = kps;
+    p->tiles_m = tiles_m; p->tiles_n = tiles_n; p->walkers = R;
+    p->grid_x = 8 * R * tiles_n; p->grid_y = 1; p->grid_z = 1; p->block = PS_THREADS;
+    p->amax = d->amax_out ? LTHM_GEMM_AMAX_KERNEL : LTHM_GEMM_AMAX_NONE;
+    return 0;
+  }
+  p->kernel = LTHM_GEMM_KERNEL_K128;
+  p->ka = ka; p->kb = kb;
+  p->splits = splits;
+  p->k_per_split = kps;
+  p->tiles_m = tiles_m; p->tiles_n = tiles_n;
+  p->grid_x = tiles_m * tiles_n; p->grid_y = d->batch; p->grid_z = splits; p->block = 256;
+  if (splits > 1)
+    p->combine = (d->batch == 1 && d->N % 4 == 0 && ((uintptr_t)d->workspace % 16) == 0) ? LTHM_GEMM_COMBINE_REDUCE4
+                                                                                         : LTHM_GEMM_COMBINE_REDUCE;
+  p->amax = amax_after;
+  return 0;
+}
+
+extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
+  lthm_gemm_plan_out p;
+  LTHM_REQUIRE(d != nullptr);
+  if (const int rc = lthm_gemm_plan(d, cu_count(), &p)) return rc;
+  if (p.kernel == LTHM_GEMM_KERNEL_NONE) return 0;
+  GemmArgs g;
+  g.A = (const bf16_t*)d->A; g.B = (const bf16_t*)d->B; g.C = d->C;
+  g.M = d->M; g.N = d->N; g.K = d->K;
+  g.lda = d->lda; g.ldb = d->ldb; g.ldc = d->ldc;
+  g.sA = d->sA; g.sB = d->sB; g.sC = d->sC;
+  const int splits = gemm_k_splits(d->K, d->splits, &g.k_per_split);  // (gemm_wg_k splits by the plan's own count)
+  g.alpha = d->alpha;
+  g.bias = d->bias; g.act = d->act; g.aux = (const bf16_t*)d->aux; g.aux_out = (bf16_t*)d->aux_out;
+  g.ldaux = d->ldaux > 0 ? d->ldaux : d->N;
+  g.res1 = d->res1; g.res2 = d->res2; g.ldr1 = d->ldr1 > 0 ? d->ldr1 : d->N; g.ldr2 = d->ldr2 > 0 ? d->ldr2 : d->N;
+  g.res1_dt = d->res1_dtype; g.res2_dt = d->res2_dtype; g.out_dt = d->out_dtype;
+  g.ws = (splits > 1) ? d->workspace : nullptr;
+  g.sa = nullptr;
+  g.sb = nullptr;
+  g.amax = reinterpret_cast<unsigned*>(d->amax_out);
+  g.fast_ok = p.fast_ok != 0;
+  auto amax_after = [&]() -> int {
+    return p.amax == LTHM_GEMM_AMAX_AFTER ? lthm_amax(d->C, d->out_dtype, d->M * d->N, d->amax_out, stream) : 0;
+  };
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(p.grid_x, p.grid_y, p.grid_z), block(p.block);
+  const int epi = p.epi;
+  switch (p.kernel) {
+    case LTHM_GEMM_KERNEL_WG: {
+      GemmArgs gw = g;
+      gw.ws = d->workspace;
+      gw.res1 = nullptr; gw.res2 = nullptr;
+      hipLaunchKernelGGL(gemm_wg_k, grid, block, 0, s, gw, p.tiles_m, p.tiles_n, p.splits, p.k_per_split);
+      LTHM_CHECK_LAUNCH();
+      GemmArgs gr = g;
+      gr.ws = d->workspace;
+      gr.alpha = 1.f;  // alpha already applied to the partials
+      const int64_t total = d->M * d->N;
+      if (p.combine == LTHM_GEMM_COMBINE_REDUCE4)
+        hipLaunchKernelGGL(splitk_reduce4_k, dim3(grid_for(total / 4, 256, 256 * 8)), dim3(256), 0, s, gr, p.splits);
+      else
+        hipLaunchKernelGGL(splitk_reduce_k, dim3(grid_for(total, 256, 256 * 8)), dim3(256), 0, s, gr, p.splits, 1);
+      LTHM_CHECK_LAUNCH();
+      return amax_after();
+    }
+    case LTHM_GEMM_KERNEL_PP_F8:
+    case LTHM_GEMM_KERNEL_PS_F8: {
+      // fp8 encoder GEMMs: geometry in 2-byte units
+      GemmArgs g8 = g;
+      g8.K = d->K / 2; g8.lda = d->lda / 2; g8.ldb = d->ldb / 2;
+      g8.sa = d->a_scale; g8.sb = d->b_scale;
+      if (p.kernel == LTHM_GEMM_KERNEL_PP_F8) {
+        g8.ws = nullptr;
+        g8.amax = nullptr;
+        hipLaunchKernelGGL((gemm_pp_k<true, false>), grid, block, 0, s, g8, p.tiles_m, p.tiles_n);
+        LTHM_CHECK_LAUNCH();
+        return 0;
+      }
 #define LTHM_PS8(BRES_, EPI_) \
-  hipLaunchKernelGGL((gemm_ps_k<true, BRES_, EPI_, true>), grid, dim3(PS_THREADS), 0, s, g8, tiles_m, tiles_n, R)
+  hipLaunchKernelGGL((gemm_ps_k<true, BRES_, EPI_, true>), grid, block, 0, s, g8, p.tiles_m, p.tiles_n, p.walkers)
 #define LTHM_PS8_EPI(BRES_)                              \
   switch (epi) {                                         \
     case EPI_PLAIN: LTHM_PS8(BRES_, EPI_PLAIN); break;   \
@@ -1566,37 +1671,24 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
     case EPI_RES1: LTHM_PS8(BRES_, EPI_RES1); break;     \
     default: LTHM_PS8(BRES_, EPI_RES2); break;           \
   }
-    if (bres) { LTHM_PS8_EPI(true) }
-    else { LTHM_PS8_EPI(false) }
+      if (p.bres) { LTHM_PS8_EPI(true) }
+      else { LTHM_PS8_EPI(false) }
 #undef LTHM_PS8_EPI
 #undef LTHM_PS8
-    LTHM_CHECK_LAUNCH();
-    return 0;
-  }
-  if (lthm_gemm_pp_mode() && d->ab_dtype != LTHM_FP8_E4M3 && ka && kb && splits == 1 && d->batch == 1 &&
-      g.fast_ok && d->K >= 512 && d->K % PP_BK == 0 && d->M >= 256 && d->N >= 256) {
-    // (K = 256 forms stay on the persistent kernel: the C2 qkv / proj / fc forwards ran 5-26 %
-    // slower here, profiles/r04z_gemm_*; from K = 512 on this kernel wins: C4 fc1 forward 0.456 ->
-    // 0.349 ms, its dgrad 0.701 -> 0.376, C5 fc2 forward 1.456 -> 1.133, 4096^3 767 -> 1,179 TF)
-    const int tm = (int)((d->M + 255) / 256), tn = (int)((d->N + 255) / 256);
-    GemmArgs gp = g;
-    gp.ws = nullptr;
-    // per-phase DMA issue where there are several column tiles (C4: 4-6 % faster); a single
-    // 256-column tile (C2's N = 256 dgrads) runs ~2 % faster with the DMA behind the barrier
-    // (profiles/r04am_ab.log)
-    if (d->N <= 256)
-      hipLaunchKernelGGL((gemm_pp_k<false, false>), dim3(tm * tn), dim3(512), 0, s, gp, tm, tn);
-    else hipLaunchKernelGGL((gemm_pp_k<false, true>), dim3(tm * tn), dim3(512), 0, s, gp, tm, tn);
-    LTHM_CHECK_LAUNCH();
-    return amax_after();
-  }
-  if (lthm_gemm_ps_mode() && epi >= 0 && ka && splits == 1 && d->batch == 1 && g.fast_ok && d->K % BK == 0 &&
-      d->K > 0 && d->N % 8 == 0 && tiles_n <= per_xcd && (int64_t)tiles_m * tiles_n >= 4 * 8 * per_xcd) {
-    const int R = per_xcd / tiles_n;  // row-panel walkers per column tile and XCD
-    dim3 grid(8 * R * tiles_n);
-    const bool bres = d->K <= 4 * BK;
+      LTHM_CHECK_LAUNCH();
+      return 0;
+    }
+    case LTHM_GEMM_KERNEL_PP: {
+      GemmArgs gp = g;
+      gp.ws = nullptr;
+      if (!p.spread) hipLaunchKernelGGL((gemm_pp_k<false, false>), grid, block, 0, s, gp, p.tiles_m, p.tiles_n);
+      else hipLaunchKernelGGL((gemm_pp_k<false, true>), grid, block, 0, s, gp, p.tiles_m, p.tiles_n);
+      LTHM_CHECK_LAUNCH();
+      return amax_after();
+    }
+    case LTHM_GEMM_KERNEL_PS: {
 #define LTHM_PS(KB_, BRES_, EPI_) \
-  hipLaunchKernelGGL((gemm_ps_k<KB_, BRES_, EPI_>), grid, dim3(PS_THREADS), 0, s, g, tiles_m, tiles_n, R)
+  hipLaunchKernelGGL((gemm_ps_k<KB_, BRES_, EPI_>), grid, block, 0, s, g, p.tiles_m, p.tiles_n, p.walkers)
 #define LTHM_PS_EPI(KB_, BRES_)                        \
   switch (epi) {                                       \
     case EPI_PLAIN: LTHM_PS(KB_, BRES_, EPI_PLAIN); break; \
@@ -1605,28 +1697,30 @@ extern "C" int lthm_gemm(const lthm_gemm_desc* d, void* stream) {
     case EPI_RES1: LTHM_PS(KB_, BRES_, EPI_RES1); break;   \
     default: LTHM_PS(KB_, BRES_, EPI_RES2); break;         \
   }
-    if (bres && kb) { LTHM_PS_EPI(true, true) }
-    else if (bres) { LTHM_PS_EPI(false, true) }
-    else if (kb) { LTHM_PS_EPI(true, false) }
-    else { LTHM_PS_EPI(false, false) }
+      if (p.bres && p.kb) { LTHM_PS_EPI(true, true) }
+      else if (p.bres) { LTHM_PS_EPI(false, true) }
+      else if (p.kb) { LTHM_PS_EPI(true, false) }
+      else { LTHM_PS_EPI(false, false) }
 #undef LTHM_PS_EPI
 #undef LTHM_PS
-    LTHM_CHECK_LAUNCH();
-    return 0;
+      LTHM_CHECK_LAUNCH();
+      return 0;
+    }
+    default:
+      break;
   }
-  dim3 grid(tiles_m * tiles_n, d->batch, splits);
   const size_t shmem = 4 * TILE_BYTES;
-  if (ka && kb) hipLaunchKernelGGL((gemm_k<true, true>), grid, dim3(256), shmem, s, g, tiles_n);
-  else if (ka && !kb) hipLaunchKernelGGL((gemm_k<true, false>), grid, dim3(256), shmem, s, g, tiles_n);
-  else if (!ka && kb) hipLaunchKernelGGL((gemm_k<false, true>), grid, dim3(256), shmem, s, g, tiles_n);
-  else hipLaunchKernelGGL((gemm_k<false, false>), grid, dim3(256), shmem, s, g, tiles_n);
+  if (p.ka && p.kb) hipLaunchKernelGGL((gemm_k<true, true>), grid, block, shmem, s, g, p.tiles_n);
+  else if (p.ka && !p.kb) hipLaunchKernelGGL((gemm_k<true, false>), grid, block, shmem, s, g, p.tiles_n);
+  else if (!p.ka && p.kb) hipLaunchKernelGGL((gemm_k<false, true>), grid, block, shmem, s, g, p.tiles_n);
+  else hipLaunchKernelGGL((gemm_k<false, false>), grid, block, shmem, s, g, p.tiles_n);
   LTHM_CHECK_LAUNCH();
-  if (splits > 1) {
+  if (p.combine != LTHM_GEMM_COMBINE_NONE) {
     const int64_t total = d->M * d->N * d->batch;
-    if (d->batch == 1 && d->N % 4 == 0 && ((uintptr_t)d->workspace % 16) == 0)
-      hipLaunchKernelGGL(splitk_reduce4_k, dim3(grid_for(total / 4, 256, 256 * 8)), dim3(256), 0, s, g, splits);
+    if (p.combine == LTHM_GEMM_COMBINE_REDUCE4)
+      hipLaunchKernelGGL(splitk_reduce4_k, dim3(grid_for(total / 4, 256, 256 * 8)), dim3(256), 0, s, g, p.splits);
     else
-      hipLaunchKernelGGL(splitk_reduce_k, dim3(grid_for(total, 256, 256 * 8)), dim3(256), 0, s, g, splits, d->batch);
+      hipLaunchKernelGGL(splitk_reduce_k, dim3(grid_for(total, 256, 256 * 8)), dim3(256), 0, s, g, p.splits, d->batch);
     LTHM_CHECK_LAUNCH();
   }
   return amax_after();

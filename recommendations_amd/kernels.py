@@ -326,12 +326,19 @@ def _workspace(dev, nbytes: int) -> torch.Tensor:
     return t
 
 
-def gemm(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, out=None,
-         out_dtype=torch.bfloat16, ldc=None, alpha=1.0, bias=None, act=ACT_NONE, aux=None, aux_out=None,
-         res1=None, res2=None, batch=1, sA=0, sB=0, sC=0, splits=1, a_scale=None, b_scale=None, amax_out=None):
-    """C = epi(alpha * A.B) on the MFMA GEMM kernel (include/lthm.h lthm_gemm).  uint8
-    A / B are fp8 e4m3 bytes with per-tensor device scales a_scale / b_scale; amax_out
-    (int32 [1] device word) receives the running max of |C| as f32 bits."""
+GemmPlan = collections.namedtuple(
+    "GemmPlan", "kernel ka kb bres epi spread splits combine amax fast_ok grid block tiles_m tiles_n walkers "
+                "k_per_split ps_mode pp_mode pp_f8_mode wg_ragged")
+GEMM_KERNELS = {-1: "NONE", 0: "K128", 1: "PS", 2: "WG", 3: "PP", 4: "PS_F8", 5: "PP_F8"}
+GEMM_COMBINES = {0: "none", 1: "reduce", 2: "reduce4"}
+GEMM_AMAX = {0: "none", 1: "kernel", 2: "after"}
+
+
+def _gemm_desc(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, out=None,
+               out_dtype=torch.bfloat16, ldc=None, alpha=1.0, bias=None, act=ACT_NONE, aux=None, aux_out=None,
+               res1=None, res2=None, batch=1, sA=0, sB=0, sC=0, splits=1, a_scale=None, b_scale=None, amax_out=None,
+               ldaux=None, ldr1=None, ldr2=None, workspace=None):
+    """The checked lthm_gemm_desc of a gemm() call: (descriptor, out, the tensors it points to)."""
     from ._lib import STRUCTS
     require_gpu(A, B)
     dev = A.device
@@ -341,34 +348,40 @@ def gemm(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, o
     lda_ = lda if lda is not None else (K if a_kcontig else M)
     ldb_ = ldb if ldb is not None else (K if b_kcontig else N)
     ldc_ = ldc if ldc is not None else N
+    ldaux_ = ldaux if ldaux is not None else N
+    ldr1_ = ldr1 if ldr1 is not None else N
+    ldr2_ = ldr2 if ldr2 is not None else N
     sC_ = sC if sC else M * ldc_
     _check(min(M, N, K, batch) >= 1, f"bad GEMM dims M={M} N={N} K={K} batch={batch}")
     _check(lda_ >= (K if a_kcontig else M) and ldb_ >= (K if b_kcontig else N) and ldc_ >= N, "bad leading dims")
+    _check(min(ldaux_, ldr1_, ldr2_) >= N, "bad epilogue leading dims")
     _need(A, (batch - 1) * sA + ((M - 1) * lda_ + K if a_kcontig else (K - 1) * lda_ + M), "A")
     _need(B, (batch - 1) * sB + ((N - 1) * ldb_ + K if b_kcontig else (K - 1) * ldb_ + N), "B")
     _need(out, (batch - 1) * sC_ + (M - 1) * ldc_ + N, "C")
-    for t, nm in ((aux, "aux"), (aux_out, "aux_out"), (res1, "res1"), (res2, "res2")):
-        _need(t, M * N * batch, nm)
+    # the epilogue tensors of batch b start at b * M * ld (csrc/gemm.hip epilogue8)
+    for t, ld, nm in ((aux, ldaux_, "aux"), (aux_out, ldaux_, "aux_out"), (res1, ldr1_, "res1"), (res2, ldr2_, "res2")):
+        _need(t, (batch * M - 1) * ld + N, nm)
     _need(bias, N, "bias")
     d = STRUCTS["lthm_gemm_desc"]()
     d.A, d.B, d.C = ptr(A), ptr(B), ptr(out)
     d.M, d.N, d.K = M, N, K
-    d.lda = lda if lda is not None else (K if a_kcontig else M)
-    d.ldb = ldb if ldb is not None else (K if b_kcontig else N)
-    d.ldc = ldc if ldc is not None else N
-    d.sA, d.sB, d.sC = sA, sB, (sC if sC else M * (ldc if ldc is not None else N))
+    d.lda, d.ldb, d.ldc = lda_, ldb_, ldc_
+    d.sA, d.sB, d.sC = sA, sB, sC_
     d.batch, d.a_kcontig, d.b_kcontig = batch, int(a_kcontig), int(b_kcontig)
     d.out_dtype = dcode(out)
     d.alpha, d.act = alpha, act
     d.bias = ptr(bias)
     d.aux, d.aux_out = ptr(aux), ptr(aux_out)
-    d.ldaux = N
+    d.ldaux = ldaux_
     d.res1, d.res2 = ptr(res1), ptr(res2)
-    d.ldr1 = d.ldr2 = N
+    d.ldr1, d.ldr2 = ldr1_, ldr2_
     d.res1_dtype = dcode(res1) if res1 is not None else F32
     d.res2_dtype = dcode(res2) if res2 is not None else F32
-    if splits > 1:
+    ws = workspace
+    if ws is None and splits > 1:
         ws = _workspace(dev, splits * batch * M * N * 4)
+    if ws is not None:
+        _check(ws.dtype == torch.float32 and ws.is_cuda, "the split-K workspace is f32 device memory")
         d.workspace, d.workspace_bytes = ptr(ws), ws.numel() * 4
     d.splits = splits
     if amax_out is not None:
@@ -379,7 +392,25 @@ def gemm(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, o
         _check(B.dtype == torch.uint8 and a_scale is not None and b_scale is not None,
                "fp8 GEMM takes uint8 (e4m3) A and B with device scales")
         d.ab_dtype, d.a_scale, d.b_scale = FP8_E4M3, ptr(a_scale), ptr(b_scale)
+    return d, out, ws
+
+
+def gemm(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, out=None,
+         out_dtype=torch.bfloat16, ldc=None, alpha=1.0, bias=None, act=ACT_NONE, aux=None, aux_out=None,
+         res1=None, res2=None, batch=1, sA=0, sB=0, sC=0, splits=1, a_scale=None, b_scale=None, amax_out=None,
+         ldaux=None, ldr1=None, ldr2=None, workspace=None):
+    """C = epi(alpha * A.B) on the MFMA GEMM kernel (include/lthm.h lthm_gemm).  uint8
+    A / B are fp8 e4m3 bytes with per-tensor device scales a_scale / b_scale; amax_out
+    (int32 [1] device word) receives the running max of |C| as f32 bits.  ldaux (aux and
+    aux_out), ldr1 and ldr2 are the row strides of the epilogue tensors (default N);
+    workspace: the caller's f32 split-K slabs (default: a cached one when splits > 1)."""
     import ctypes
+    d, out, _ws = _gemm_desc(A, B, M, N, K, a_kcontig=a_kcontig, b_kcontig=b_kcontig, lda=lda, ldb=ldb, out=out,
+                             out_dtype=out_dtype, ldc=ldc, alpha=alpha, bias=bias, act=act, aux=aux, aux_out=aux_out,
+                             res1=res1, res2=res2, batch=batch, sA=sA, sB=sB, sC=sC, splits=splits, a_scale=a_scale,
+                             b_scale=b_scale, amax_out=amax_out, ldaux=ldaux, ldr1=ldr1, ldr2=ldr2,
+                             workspace=workspace)
+    fp8 = A.dtype == torch.uint8
     key = "gemm_fp8" if fp8 else f"gemm_k<{int(a_kcontig)},{int(b_kcontig)}>"
     # compulsory HBM bytes (each operand read once, C written once, epilogue tensors):
     # with the flops this places the call on the roofline (bench.py encoder_gemm)
@@ -390,6 +421,24 @@ def gemm(A, B, M, N, K, *, a_kcontig=True, b_kcontig=True, lda=None, ldb=None, o
     call("lthm_gemm", ctypes.addressof(d), stream(), _key=(_GEMM_TAG[-1] + ":" + key) if _GEMM_TAG else key,
          _work=2.0 * M * N * K * batch, _unit="flop", _bytes=float(nbytes))
     return out
+
+
+def gemm_plan(A, B, M, N, K, *, cus=None, **kw):
+    """The launch plan lthm_gemm takes for gemm(A, B, M, N, K, **kw) on a device of ``cus``
+    compute units (default: A's device), as a GemmPlan (include/lthm.h lthm_gemm_plan_out;
+    kernel, combine and amax by name).  Nothing is launched."""
+    import ctypes
+    from ._lib import STRUCTS
+    d, _out, _ws = _gemm_desc(A, B, M, N, K, **kw)
+    if cus is None:
+        cus = torch.cuda.get_device_properties(A.device).multi_processor_count
+    p = STRUCTS["lthm_gemm_plan_out"]()
+    rc = load().lthm_gemm_plan(ctypes.addressof(d), int(cus), ctypes.addressof(p))
+    if rc != 0:
+        raise OperandError(f"lthm_gemm refuses this descriptor (error {rc})")
+    return GemmPlan(GEMM_KERNELS[p.kernel], p.ka, p.kb, p.bres, p.epi, p.spread, p.splits, GEMM_COMBINES[p.combine],
+                    GEMM_AMAX[p.amax], p.fast_ok, (p.grid_x, p.grid_y, p.grid_z), p.block, p.tiles_m, p.tiles_n,
+                    p.walkers, p.k_per_split, p.ps_mode, p.pp_mode, p.pp_f8_mode, p.wg_ragged)
 
 
 # Kernel-timer key prefix for the GEMMs launched inside a ``gemm_tag`` scope (bench.py

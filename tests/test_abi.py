@@ -18,7 +18,7 @@ from recommendations_amd import _lib
 def test_every_header_symbol_is_exported():
     lib = _lib.load()
     protos = _lib.parse_header()
-    assert len(protos) >= 30 and "lthm_kshift_fwd" in protos and "lthm_gemm" in protos
+    assert len(protos) >= 30 and {"lthm_kshift_fwd", "lthm_gemm", "lthm_gemm_plan"} <= set(protos)
     missing = [n for n in protos if not hasattr(lib, n)]
     assert not missing, missing
 
@@ -39,7 +39,7 @@ def test_device_count_never_fails():
 
 def test_struct_layouts_match_c(tmp_path):
     structs = _lib.STRUCTS
-    assert {"lthm_gemm_desc", "lthm_attn_desc", "lthm_ptower_desc", "lthm_tokens_desc",
+    assert {"lthm_gemm_desc", "lthm_gemm_plan_out", "lthm_attn_desc", "lthm_ptower_desc", "lthm_tokens_desc",
             "lthm_contrastive_desc"} <= set(structs)
     lines = ['#include "%s"' % _lib.HEADER, "#include <stdio.h>", "#include <stddef.h>", "int main(void) {"]
     for name, cls in structs.items():

@@ -31,6 +31,7 @@ def bf(x):
 @pytest.mark.parametrize("M,N,Kd", [(1000, 768, 256), (129, 256, 256), (4096, 1024, 256), (333, 64, 1024), (8, 8, 8)])
 @pytest.mark.parametrize("act", [0, 1, 2, 5])
 def test_gemm_nt_epilogues(dev, M, N, Kd, act):
+    """(Per-element, at a fraction of the size: test_gpu_gemm.py test_gemm_k_epilogues, test_gemm_ps_forms.)"""
     from recommendations_amd import kernels as K
     g = torch.Generator().manual_seed(M + N + Kd + act)
     A = bf(torch.randn(M, Kd, generator=g))
@@ -81,7 +82,8 @@ def test_gemm_dgrad_wgrad(dev, M, N, Kd):
 @pytest.mark.parametrize("M,N,Kd", [(263001, 512, 1536), (70003, 768, 256), (4100, 2048, 512)])
 def test_gemm_wgrad_ragged_rows(dev, M, N, Kd):
     """dW = dY^T X with a row count of no alignment (the packed rows of a shared pad prefix):
-    the split-K weight-gradient kernel zero-fills the k rows past the end."""
+    the split-K weight-gradient kernel zero-fills the k rows past the end.
+    (Per-element, at a fraction of the size: test_gpu_gemm.py test_gemm_wg.)"""
     from recommendations_amd import kernels as K
     g = torch.Generator().manual_seed(M + N)
     dy = bf(torch.randn(M, N, generator=g))
@@ -128,7 +130,8 @@ def test_gemm_large_nt(dev, M, N, Kd, act):
                                               (65536, 1024, 2176, 0, False), (300, 2176, 1024, 5, False)])
 def test_gemm_256_tiles(dev, M, N, Kd, act, res2):
     """The 256 x 256 kernel (K-contiguous operands, K >= 512): ragged row and column tiles,
-    bias, the activations with their saved aux, one or two residuals, f32 and bf16 outputs."""
+    bias, the activations with their saved aux, one or two residuals, f32 and bf16 outputs.
+    (Per-element, at a fraction of the size: test_gpu_gemm.py test_gemm_pp.)"""
     from recommendations_amd import kernels as K
     g = torch.Generator().manual_seed(M + 3 * N + Kd)
     A = bf(torch.randn(M, Kd, generator=g))
@@ -176,6 +179,7 @@ def test_gemm_large_batched(dev):
 
 
 def test_gemm_batched(dev):
+    """(Per-element, with padded batch strides and split-K: test_gpu_gemm.py test_gemm_k_shapes, test_gemm_k_split_k.)"""
     from recommendations_amd import kernels as K
     g = torch.Generator().manual_seed(5)
     Bt, M, N, Kd = 5, 300, 200, 128

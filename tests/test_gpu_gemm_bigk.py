@@ -3,7 +3,8 @@ operands K-contiguous, K > 256, M >= 4096, N >= 512 -- the ranker MLPs and the C
 oracle on the SAME bf16 operands: every epilogue form the layer code uses (bias + QuickGELU /
 GELU with the pre-activation store, the activation-gradient multiply, the residual add) and
 ragged M / N / K edges.  Bound: 1e-5 relative Frobenius for f32 outputs (fp32 accumulation in
-another order), 1e-3 for bf16 outputs (one bf16 rounding)."""
+another order), 1e-3 for bf16 outputs (one bf16 rounding).
+(Per-element fp64 tests of the same kernels at a fraction of the size: test_gpu_gemm.py test_gemm_pp.)"""
 import math
 
 import pytest
