@@ -1157,6 +1157,48 @@ int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const int64_t* row
                                 const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
                                 const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
                                 void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_ivf_topk_group: lthm_retrieve_ivf_topk_filt, argument for argument, with users in place
+ * of queries: user u has G queries (1 <= G <= 8, g->G; lthm_retrieve_group above) and an item is scored
+ * by its best match over them, on the lists the user's one probe row names.
+ *   q       f32 / bf16 [U, G, 128], contiguous, every row prepared as the entries above prepare it
+ *   probes  int32 [U, P], 1 <= P <= 64: one probe row per user
+ *   x->rows [U, X], t->filter [U, 3], b->weight [U] (or NULL), c->after_score / after_id [U] and
+ *   out_scores f32 [U, k], out_ids int64 [U, k], 1 <= k <= 128: one per user
+ *   s_g[u, j]  the f32 score, bit for bit, lthm_retrieve_topk gives query (u, g) against item row j
+ *   s[u, j]    max_g s_g[u, j]; then, in the order lthm_retrieve_topk_group composed with _bias, _tags
+ *              and _after applies them on the flat path: the prior, s = fmaf(weight[u], bias[j], s)
+ *              (added behind the maximum, once); exclusion (a row of x is -inf); the tag filter (a row
+ *              that fails it is -inf); the cursor (a row at or before (after_score, after_id) is -inf)
+ * The result is, per user, the k first under (score descending, id ascending) of the rows that lie in a
+ * probed list, are not excluded, pass the filter and lie strictly behind the cursor, then (-inf, 0).  The
+ * maximum is taken inside the scan, ahead of candidate selection, so an item takes ONE slot per user
+ * however many of the user's queries it matches, and the outputs do not depend on the order of a
+ * user's queries.  With every list probed the result is, bit for bit, what lthm_retrieve_topk_group
+ * composed with the same x, t, b and c returns (rows given as ids).  g == NULL or g->G == 1 IS
+ * lthm_retrieve_ivf_topk_filt: the same kernels, the same workspace size and the same bits.  Deep lists
+ * (k > 128) with groups are refused.  Every pointer, alignment, range and workspace check is made before
+ * any launch; the call runs on `stream` without a host synchronisation and the outputs are a pure
+ * function of the inputs.
+ *   workspace lthm_retrieve_ivf_group_ws_bytes(U, G, N, L, P, k, X, has_cursor) bytes, 16-byte aligned: at
+ *             G = 1 lthm_retrieve_ivf_filt_ws_bytes(U, N, L, P, k, X, has_cursor); above, the U G prepared
+ *             queries and the larger tile table in place of theirs; -1 for what the call refuses (G outside
+ *             1..8, U G >= 2^31, and whatever the _filt size refuses)
+ * The scan: a (user, probe) pair takes G adjacent MFMA columns of one row of 16 columns, so a block serves
+ * up to T(G) = 4 floor(16 / G) pairs of one list (64, 32, 20, 16, 12, 8, 8, 8 for G = 1..8); the columns
+ * left over hold no query and never reach selection.  Its grid is
+ * lthm_retrieve_ivf_group_grid(U, G, P, L) = U P / T(G) + min(L, U P), an upper bound on the tiles there
+ * can be (sum_c ceil(n_c / T) over the lists' pair counts n_c, sum_c n_c <= U P), as
+ * lthm_retrieve_ivf_grid is for G = 1, whose value it has there; the blocks past the true count exit at
+ * once.  -1 for U, P or L < 1, U or L >= 2^31, G outside 1..8. */
+int64_t lthm_retrieve_ivf_group_grid(int64_t U, int32_t G, int32_t P, int64_t L);
+int64_t lthm_retrieve_ivf_group_ws_bytes(int64_t U, int32_t G, int64_t N, int64_t L, int32_t P, int32_t k, int64_t X,
+                                         int32_t has_cursor);
+int lthm_retrieve_ivf_topk_group(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
+                                 int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t U,
+                                 const lthm_retrieve_group* g, const int32_t* probes, int32_t P, int32_t k,
+                                 const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                                 const lthm_retrieve_bias* b, const lthm_retrieve_ivf_cursor* c, float* out_scores,
+                                 int64_t* out_ids, void* workspace, int64_t ws_bytes, void* stream);
 /* lthm_retrieve_ivf_topk_deep: lthm_retrieve_ivf_topk_filt, argument for argument, with 1 <= k <= 1024:
  * the lists a ranking stage or lthm_retrieve_diversify's pool take, from the probed lists alone.  The
  * contract is lthm_retrieve_ivf_topk_filt's with that k: the k first, under (score descending, id

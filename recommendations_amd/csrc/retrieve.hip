@@ -1691,6 +1691,11 @@ extern "C" int lthm_retrieve_merge_shards(const float* scores, const int64_t* id
 // A column's state (B fragments, threshold, candidates, list cursor) is its own and a prune
 // writes each key at its rank, so every pair's list, and with it the merged result, is a pure
 // function of the inputs.  A list named twice in one probe row is two pairs with two outputs.
+//
+// Groups (lthm_retrieve_ivf_topk_group, G >= 2 queries per user): a pair is (user, probe slot), the
+// plan cuts a list's pairs into tiles of retr_ivf_tile_pairs(G) instead of 64, and the scan takes the
+// maximum over a pair's G columns in registers before anything selects (retr_ivf_topk_k<.., true>), so
+// the pairs' lists and the merge see one score per (user, row) and a row takes one slot per user.
 namespace lthm {
 namespace {
 
@@ -1739,8 +1744,54 @@ struct RetrIvfFiltArgs : RetrIvfArgs {
   const float* ascore;  // [Q] or null: no cursor
   const int* crow;      // with ascore: [Q P] the cursor row of every pair (retr_ivf_cursor_k)
 };
-template <bool FILT>
-using RetrIvfScanArgs = std::conditional_t<FILT, RetrIvfFiltArgs, RetrIvfArgs>;
+// retr_ivf_topk_k<true, true, TAGS, BIAS, true> takes the filters' arguments and the group size behind
+// them: Q counts the users, qn is [Q G, 128] and everything else is per user
+struct RetrIvfGroupArgs : RetrIvfFiltArgs {
+  int G;  // queries per user, 2..RT_GMAX
+};
+template <bool FILT, bool GRP = false>
+using RetrIvfScanArgs = std::conditional_t<GRP, RetrIvfGroupArgs, std::conditional_t<FILT, RetrIvfFiltArgs, RetrIvfArgs>>;
+
+// Groups: a pair is (user, probe slot) and takes G adjacent MFMA columns, one per query of the user,
+// that never cross a row of 16 lanes, so that the maximum over them is a few DPP row shifts in
+// registers.  A row of 16 columns holds 16 / G pairs, a tile 4 (16 / G); the columns behind a row's
+// last pair hold no query (whole columns of padding where G does not divide 16).
+__host__ __device__ constexpr int retr_ivf_row_pairs(int G) { return 16 / G; }
+__host__ __device__ constexpr int retr_ivf_tile_pairs(int G) { return (RT_QT / 16) * retr_ivf_row_pairs(G); }
+
+// x of lane i + N of the same row of 16 lanes, the lane's own x where i + N is past the row
+template <int N>
+__device__ __forceinline__ float retr_row_shl(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x100 + N, 0xF, 0xF, false));
+}
+// acc[v] of lane i becomes the maximum over lanes i .. i + G - 1 wherever those lie in the lane's row of
+// 16, which is every pair's first lane: windows of 2, 4 and 8 by doubling, then two windows of the
+// largest power of two p <= G that overlap, at distance G - p.  G is uniform and all 64 lanes are active.
+__device__ __forceinline__ void retr_ivf_group_max(f32x16& acc, int G) {
+  if (G >= 2) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<1>(acc[v]));
+  }
+  if (G >= 4) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<2>(acc[v]));
+  }
+  if (G >= 8) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<4>(acc[v]));
+  }
+  const int rest = G - (G >= 8 ? 8 : G >= 4 ? 4 : G >= 2 ? 2 : 1);
+  if (rest == 1) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<1>(acc[v]));
+  } else if (rest == 2) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<2>(acc[v]));
+  } else if (rest == 3) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = fmaxf(acc[v], retr_row_shl<3>(acc[v]));
+  }
+}
 
 __global__ __launch_bounds__(256) void retr_ivf_count_k(const int* __restrict__ probes, int64_t NP, int L, int P,
                                                         int64_t Q, int k, int* __restrict__ cnt,
@@ -1760,10 +1811,13 @@ __global__ __launch_bounds__(256) void retr_ivf_count_k(const int* __restrict__ 
   }
 }
 
-// One block: thread t owns lists [t per, (t + 1) per)
+// One block: thread t owns lists [t per, (t + 1) per).  GRP: a tile holds tp pairs (retr_ivf_tile_pairs)
+// instead of RT_QT; <false> ignores tp
+template <bool GRP>
 __global__ __launch_bounds__(256) void retr_ivf_offsets_k(const int* __restrict__ cnt, int L, int* __restrict__ pair_off,
-                                                          int* __restrict__ tile_off) {
+                                                          int* __restrict__ tile_off, int tp) {
   __shared__ int sp[256], st[256];
+  const int tq = GRP ? tp : RT_QT;
   const int tid = threadIdx.x;
   const int per = (L + 255) / 256;
   const int64_t lo64 = (int64_t)tid * per;
@@ -1772,7 +1826,7 @@ __global__ __launch_bounds__(256) void retr_ivf_offsets_k(const int* __restrict_
   for (int c = lo; c < hi; ++c) {
     const int n = cnt[c];
     np += n;
-    nt += (n + RT_QT - 1) / RT_QT;
+    nt += (n + tq - 1) / tq;
   }
   sp[tid] = np;
   st[tid] = nt;
@@ -1790,7 +1844,7 @@ __global__ __launch_bounds__(256) void retr_ivf_offsets_k(const int* __restrict_
     pair_off[c] = pa;
     tile_off[c] = ta;
     pa += n;
-    ta += (n + RT_QT - 1) / RT_QT;
+    ta += (n + tq - 1) / tq;
   }
   if (tid == 255) {
     pair_off[L] = sp[255];
@@ -1800,10 +1854,11 @@ __global__ __launch_bounds__(256) void retr_ivf_offsets_k(const int* __restrict_
 
 // pos < cnt[c] (the same pairs were counted), so every index is below Q P and every tile below
 // tile_off[L]
+template <bool GRP>
 __global__ __launch_bounds__(256) void retr_ivf_fill_k(const int* __restrict__ probes, int64_t NP, int L,
                                                        const int* __restrict__ cnt, const int* __restrict__ pair_off,
                                                        const int* __restrict__ tile_off, int* __restrict__ fill,
-                                                       int* __restrict__ pair_idx, int4* __restrict__ tab) {
+                                                       int* __restrict__ pair_idx, int4* __restrict__ tab, int tp) {
   const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (p >= NP) return;
   const int c = probes[p];
@@ -1811,9 +1866,10 @@ __global__ __launch_bounds__(256) void retr_ivf_fill_k(const int* __restrict__ p
   const int pos = atomicAdd(&fill[c], 1);
   const int base = pair_off[c];
   pair_idx[base + pos] = (int)p;
-  if ((pos & (RT_QT - 1)) == 0) {
+  const int tq = GRP ? tp : RT_QT;  // the pairs of a tile
+  if (pos % tq == 0) {
     const int n = cnt[c] - pos;
-    tab[tile_off[c] + pos / RT_QT] = make_int4(c, base + pos, n < RT_QT ? n : RT_QT, 0);
+    tab[tile_off[c] + pos / tq] = make_int4(c, base + pos, n < tq ? n : tq, 0);
   }
 }
 
@@ -1863,9 +1919,19 @@ __global__ __launch_bounds__(256) void retr_ivf_cursor_k(const int* __restrict__
 // element), the score from there on.  The cursor: the pair's score cs and its cursor row cr
 // (retr_ivf_cursor_k), then retr_topk_k's AFTER code unchanged.  The filter, the weight and the
 // cursor are per lane, like every other per-pair value.  <false> and <true> hold none of this.
-template <bool EXCL, bool FILT = false, bool TAGS = false, bool BIAS = false>
-__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) {
+//
+// GRP (with FILT; lthm_retrieve_ivf_topk_group, G >= 2): a pair is (user, probe slot) and owns G
+// adjacent columns of one row of 16 (retr_ivf_row_pairs), column g holding the user's query g; the
+// columns behind a row's last pair, and those of a pair the tile does not have, hold zeros.  Behind the
+// partial-tile mask every pair's first lane (the leader) takes the maximum of its G columns
+// (retr_ivf_group_max), as retr_topk_k<EXCL, GP> does ahead of the prior and the masks; the leader
+// alone has a list cursor, a filter, a weight, a cursor, a threshold and a candidate buffer (its own
+// column's), so everything from the prior on sees one score per (user, row) and a row takes one slot
+// however many of the user's queries it matches.  Every other lane keeps tau = +inf and never appends.
+template <bool EXCL, bool FILT = false, bool TAGS = false, bool BIAS = false, bool GRP = false>
+__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP> a) {
   static_assert(FILT ? EXCL : !(TAGS || BIAS), "tags, prior and cursor ride on the excluding instantiation");
+  static_assert(!GRP || FILT, "groups ride on the filtering instantiations");
   const int blk = blockIdx.x;
   if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
   using RetrIvfSharedFilt = std::conditional_t<TAGS, RetrIvfSharedTags, RetrIvfShared>;
@@ -1880,20 +1946,39 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
   const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
   const int ql = 32 * (w & 1) + r32;
-  const bool live = ql < np;
-  const int64_t q = live ? a.pair_idx[pbase + ql] / a.P : 0;
+  // column ql serves the tile's pair pl (live), as its query gq; lead: the pair's first column
+  int pl = ql, gq = 0, G = 1, upr = 16;
+  bool live = ql < np;
+  if constexpr (GRP) {
+    G = a.G;
+    upr = retr_ivf_row_pairs(G);
+    const int j = (ql & 15) / G;
+    gq = (ql & 15) - j * G;
+    pl = (ql >> 4) * upr + j;
+    live = j < upr && pl < np;
+  }
+  const bool lead = GRP ? (live && gq == 0) : live;
+  const int64_t q = live ? a.pair_idx[pbase + pl] / a.P : 0;
 
   if (tid < RT_QT) {
-    // a column without a pair never passes the filter
-    sh.tau[tid] = tid < np ? -INFINITY : INFINITY;
-    sh.cnt[tid] = 0;
-    sh.pair[tid] = tid < np ? a.pair_idx[pbase + tid] : 0;
+    // a column without a pair never passes the filter, nor does one that is not its pair's first
+    if constexpr (GRP) {
+      const int j = (tid & 15) / G, pt = (tid >> 4) * upr + j;
+      const bool first = j < upr && pt < np && (tid & 15) == j * G;
+      sh.tau[tid] = first ? -INFINITY : INFINITY;
+      sh.cnt[tid] = 0;
+      sh.pair[tid] = first ? a.pair_idx[pbase + pt] : 0;
+    } else {
+      sh.tau[tid] = tid < np ? -INFINITY : INFINITY;
+      sh.cnt[tid] = 0;
+      sh.pair[tid] = tid < np ? a.pair_idx[pbase + tid] : 0;
+    }
   }
   if (tid < 3) sh.flag[tid] = 0;
 
   bf16x8v qf[8];
   {
-    const bf16_t* rp = a.qn + q * RT_D;
+    const bf16_t* rp = a.qn + (GRP ? q * G + gq : q) * RT_D;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       u32x4 v = {0u, 0u, 0u, 0u};
@@ -1904,7 +1989,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   const int* xp = nullptr;
   int nx = INT_MAX;  // a column without a pair excludes nothing and reads nothing
   if constexpr (EXCL) {
-    if (live && (!FILT || a.xs != nullptr)) {
+    if (lead && (!FILT || a.xs != nullptr)) {
       const int* xl = a.xs + q * a.xstride;
       int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
       while (lo < hi) {
@@ -1919,7 +2004,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   int fm = 0, fw = 0, fy = 0;
   int yz = 1;
   if constexpr (TAGS) {
-    if (live) {
+    if (lead) {
       const int* fp = a.filt + q * 3;
       const int fall = fp[0], fnone = fp[2];
       fy = fp[1];
@@ -1932,12 +2017,12 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   int cr = -1;
   float wq = 0.f;  // a column without a pair: no prior
   if constexpr (FILT) {
-    if (live && a.ascore != nullptr) {
+    if (lead && a.ascore != nullptr) {
       cs = a.ascore[q];
-      cr = a.crow[a.pair_idx[pbase + ql]];
+      cr = a.crow[a.pair_idx[pbase + pl]];
     }
     if constexpr (BIAS) {
-      if (live) wq = a.bw ? a.bw[q] : 1.f;
+      if (lead) wq = a.bw ? a.bw[q] : 1.f;
     }
   }
   int roff[8];
@@ -2021,6 +2106,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
       for (int v = 0; v < 16; ++v)
         if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
     }
+    if constexpr (GRP) retr_ivf_group_max(acc, G);  // the leader's elements: the user's best over its queries
     if constexpr (BIAS) {
       // the score from here on; a row past the list is fmaf(wq, 0, -inf) = -inf
 #pragma unroll
@@ -2077,7 +2163,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
 #pragma unroll
     for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
     const float tau = sh.tau[ql];
-    if (mx >= tau) {
+    if ((!GRP || lead) && mx >= tau) {
 #pragma unroll
       for (int v = 0; v < 16; ++v) {
         const float s = acc[v];
@@ -2091,7 +2177,8 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT> a) 
   }
   __syncthreads();
   // every pair's k best of the list, sorted, as (score, id); empty slots are (-inf, 0)
-  for (int pq = w; pq < np; pq += 4) {
+  for (int pi = w; pi < np; pi += 4) {
+    const int pq = GRP ? 16 * (pi / upr) + G * (pi % upr) : pi;  // the pair's (first) column
     const int m = retr_prune<RT_CAP / 64>(sh.cand[pq], sh.cnt[pq], a.k, lane);
     const int pr = sh.pair[pq];
     const int64_t pq_q = pr / a.P, pq_s = pr - pq_q * a.P;
@@ -2381,24 +2468,28 @@ struct RetrIvfWs {
   int64_t qn, cnt, off, pidx, tab, xs, scores, ids, crow, keys, total, grid;
 };
 
-// the scan's grid: sum_c ceil(n_c / 64) <= floor(sum_c n_c / 64) + #{c : n_c > 0} with sum_c n_c <= Q P
-inline int64_t retr_ivf_grid(int64_t Q, int64_t P, int64_t L) {
+// the scan's grid: sum_c ceil(n_c / 64) <= floor(sum_c n_c / 64) + #{c : n_c > 0} with sum_c n_c <= Q P;
+// with groups a tile holds tq = retr_ivf_tile_pairs(G) pairs instead of 64 (the same bound with tq)
+inline int64_t retr_ivf_grid(int64_t Q, int64_t P, int64_t L, int64_t tq = RT_QT) {
   const int64_t np = Q * P;
-  return np / RT_QT + (L < np ? L : np);
+  return np / tq + (L < np ? L : np);
 }
 
 // cursor: the pairs' cursor rows behind everything else, so that the call without one has the
 // layout and the size it always had
 // deep: k up to RD_KMAX and the pairs' key slots behind everything else, for retr_ivf_deep_topk_k
+// G > 1 (lthm_retrieve_ivf_topk_group, never deep): Q users of G queries; the queries and the tile
+// table grow, everything else is per user.  G = 1 is the layout it always was
 bool retr_ivf_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t k, int64_t X, RetrIvfWs* o, bool cursor = false,
-                 bool deep = false) {
+                 bool deep = false, int64_t G = 1) {
   if (Q < 1 || Q >= (1ll << 31) || N < 1 || N >= (1ll << 31) || L < 1 || L >= (1ll << 31)) return false;
   if (P < 1 || P > RS_SMAX || k < 1 || k > (deep ? RD_KMAX : RT_KMAX) || X < 0 || X > RT_XMAX) return false;
-  if (Q * P >= (1ll << 31)) return false;
-  o->grid = retr_ivf_grid(Q, P, L);
+  if (G < 1 || G > RT_GMAX || (deep && G > 1)) return false;
+  if (Q * P >= (1ll << 31) || Q * G >= (1ll << 31)) return false;
+  o->grid = retr_ivf_grid(Q, P, L, retr_ivf_tile_pairs((int)G));
   if (o->grid >= (1ll << 31)) return false;
   int64_t at = 0;
-  o->qn = at, at += up256(Q * RT_D * 2);
+  o->qn = at, at += up256(Q * G * RT_D * 2);
   o->cnt = at, at += up256(2 * L * 4);        // cnt, fill
   o->off = at, at += up256(2 * (L + 1) * 4);  // pair_off, tile_off
   o->pidx = at, at += up256(Q * P * 4);
@@ -2431,6 +2522,17 @@ extern "C" int64_t lthm_retrieve_ivf_filt_ws_bytes(int64_t Q, int64_t N, int64_t
   return retr_ivf_ws(Q, N, L, P, k, X, &w, has_cursor != 0) ? w.total : -1;
 }
 
+extern "C" int64_t lthm_retrieve_ivf_group_grid(int64_t U, int32_t G, int32_t P, int64_t L) {
+  if (U < 1 || P < 1 || L < 1 || U >= (1ll << 31) || L >= (1ll << 31) || G < 1 || G > RT_GMAX) return -1;
+  return retr_ivf_grid(U, P, L, retr_ivf_tile_pairs(G));
+}
+
+extern "C" int64_t lthm_retrieve_ivf_group_ws_bytes(int64_t U, int32_t G, int64_t N, int64_t L, int32_t P, int32_t k,
+                                                    int64_t X, int32_t has_cursor) {
+  RetrIvfWs w;
+  return retr_ivf_ws(U, N, L, P, k, X, &w, has_cursor != 0, false, G) ? w.total : -1;
+}
+
 extern "C" int lthm_retrieve_ivf_topk(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off,
                                       int64_t L, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
                                       const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
@@ -2446,13 +2548,16 @@ namespace {
 // The one call path of the clustered scan: without t, b and c it launches retr_ivf_topk_k<false> /
 // <true>, as lthm_retrieve_ivf_topk always did; with any of them <true, true, TAGS, BIAS>, which takes
 // a null list and a null cursor as "none".  deep (lthm_retrieve_ivf_topk_deep with k > 128): the same
-// steps with retr_ivf_deep_topk_k<TAGS> as the scan and the pairs' key slots in the workspace.
+// steps with retr_ivf_deep_topk_k<TAGS> as the scan and the pairs' key slots in the workspace.  G > 1
+// (lthm_retrieve_ivf_topk_group): Q users of G queries, the plan with retr_ivf_tile_pairs(G) pairs per
+// tile and retr_ivf_topk_k<true, true, TAGS, BIAS, true> as the scan; G = 1 is the call it always was.
 int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const int64_t* list_off, int64_t L,
                   const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P,
                   int32_t k, const lthm_retrieve_excl* x, const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
                   const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids, void* workspace,
-                  int64_t ws_bytes, void* stream, bool deep) {
+                  int64_t ws_bytes, void* stream, bool deep, int G = 1) {
   LTHM_REQUIRE(items && row_ids && list_off && q && probes && out_scores && out_ids && workspace);
+  LTHM_REQUIRE(G >= 1 && G <= RT_GMAX && !(deep && G > 1));
   LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
   LTHM_REQUIRE(!b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0));
   LTHM_REQUIRE(!c || (c->after_score && c->after_id && ((uintptr_t)c->after_score & 3) == 0 &&
@@ -2463,7 +2568,7 @@ int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const in
   LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0);
   LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
   RetrIvfWs wo;
-  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo, c != nullptr, deep) && ws_bytes >= wo.total);
+  LTHM_REQUIRE(retr_ivf_ws(Q, N, L, P, k, x ? x->X : 0, &wo, c != nullptr, deep, G) && ws_bytes >= wo.total);
   hipStream_t s = (hipStream_t)stream;
   unsigned char* ws = (unsigned char*)workspace;
   bf16_t* qn = (bf16_t*)(ws + wo.qn);
@@ -2477,13 +2582,14 @@ int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const in
   int64_t* lids = (int64_t*)(ws + wo.ids);
   const bf16_t* it = (const bf16_t*)items;
   const int64_t NP = Q * P;
-  // 1: the queries, by the arithmetic of every other entry
-  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  // 1: the queries, by the arithmetic of every other entry (with groups q [Q, G, 128] is Q G rows)
+  const int64_t QG = Q * G;
+  const unsigned pgrid = (unsigned)((QG + 15) / 16);
   if (q_dtype == LTHM_BF16)
-    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn, it, N,
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, QG, normalize_q, qn, it, N,
                        (const int*)nullptr, (float*)nullptr, -INFINITY);
   else
-    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn, it, N,
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, QG, normalize_q, qn, it, N,
                        (const int*)nullptr, (float*)nullptr, -INFINITY);
   LTHM_CHECK_LAUNCH();
   // 2: the plan
@@ -2495,10 +2601,16 @@ int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const in
   hipLaunchKernelGGL(retr_ivf_count_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, (int)P, Q, (int)k, cnt, lscores,
                      lids);
   LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_ivf_offsets_k, dim3(1), dim3(256), 0, s, cnt, (int)L, pair_off, tile_off);
+  const int tp = retr_ivf_tile_pairs(G);
+  if (G > 1) hipLaunchKernelGGL(retr_ivf_offsets_k<true>, dim3(1), dim3(256), 0, s, cnt, (int)L, pair_off, tile_off, tp);
+  else hipLaunchKernelGGL(retr_ivf_offsets_k<false>, dim3(1), dim3(256), 0, s, cnt, (int)L, pair_off, tile_off, tp);
   LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_ivf_fill_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off, fill,
-                     pair_idx, tab);
+  if (G > 1)
+    hipLaunchKernelGGL(retr_ivf_fill_k<true>, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off,
+                       fill, pair_idx, tab, tp);
+  else
+    hipLaunchKernelGGL(retr_ivf_fill_k<false>, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off,
+                       fill, pair_idx, tab, tp);
   LTHM_CHECK_LAUNCH();
   // 3: the scan (with a cursor, the pairs' cursor rows first: one more kernel of the plan's shape)
   const bool filt = t || b || c;
@@ -2545,7 +2657,15 @@ int retr_ivf_call(const void* items, int64_t N, const int64_t* row_ids, const in
     a.xstride = X + 1;
   }
   const dim3 grid((unsigned)wo.grid);
-  if (deep) {
+  if (G > 1) {
+    RetrIvfGroupArgs ga;
+    static_cast<RetrIvfFiltArgs&>(ga) = a;
+    ga.G = G;
+    if (t && b) hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, true, true>), grid, dim3(256), 0, s, ga);
+    else if (t) hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, false, true>), grid, dim3(256), 0, s, ga);
+    else if (b) hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, true, true>), grid, dim3(256), 0, s, ga);
+    else hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, false, true>), grid, dim3(256), 0, s, ga);
+  } else if (deep) {
     if (t) hipLaunchKernelGGL(retr_ivf_deep_topk_k<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(retr_ivf_deep_topk_k<false>, grid, dim3(256), 0, s, a);
   } else if (!filt) {
@@ -2582,6 +2702,18 @@ extern "C" int lthm_retrieve_ivf_topk_filt(const void* items, int64_t N, const i
                                            void* stream) {
   return retr_ivf_call(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, Q, probes, P, k, x, t, b, c, out_scores,
                        out_ids, workspace, ws_bytes, stream, false);
+}
+
+// g == NULL or g->G == 1 is lthm_retrieve_ivf_topk_filt: the same kernels, the same workspace and the same bits
+extern "C" int lthm_retrieve_ivf_topk_group(const void* items, int64_t N, const int64_t* row_ids,
+                                            const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                                            int32_t normalize_q, int64_t U, const lthm_retrieve_group* g,
+                                            const int32_t* probes, int32_t P, int32_t k, const lthm_retrieve_excl* x,
+                                            const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
+                                            const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
+                                            void* workspace, int64_t ws_bytes, void* stream) {
+  return retr_ivf_call(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, U, probes, P, k, x, t, b, c, out_scores,
+                       out_ids, workspace, ws_bytes, stream, false, g ? g->G : 1);
 }
 
 // k <= 128 is lthm_retrieve_ivf_topk_filt: the same kernels, the same workspace and the same bits

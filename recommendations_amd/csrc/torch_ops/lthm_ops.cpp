@@ -27,6 +27,7 @@
 //   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
 //   lthm::retrieve_ivf_topk_filt the same with a tag filter, a score prior and an (score, id) cursor per query
 //   lthm::retrieve_ivf_topk_deep the same with k up to 1,024 (lthm_retrieve_ivf_topk_deep)
+//   lthm::retrieve_ivf_topk_group retrieve_ivf_topk_filt for users of G <= 8 queries each: the best score over them
 //   lthm::retrieve_diversify     greedy MMR selection of k out of a pool per query, with a cap per group
 //   lthm::quantize_catalogue_q8, lthm::retrieve_q8_topk, lthm::retrieve_rescore
 //                                an e4m3 catalogue, its shortlist scan and the exact re-scoring of a list
@@ -679,13 +680,15 @@ std::tuple<Tensor, Tensor> retrieve_ivf_topk_cuda(const Tensor& q, const Tensor&
 // f32 [N] in the clustered row numbering, tag_filter int32 [Q, 3], bias_weight f32 [Q] or None (1),
 // after_scores f32 [Q] with after_ids int64 [Q]; tags with tag_filter, after_scores with after_ids,
 // bias_weight only with bias.  With none of them it is retrieve_ivf_topk's call.  deep: k up to 1,024
-// through lthm_retrieve_ivf_topk_deep (retrieve_ivf_topk_deep below), one call for the whole batch
+// through lthm_retrieve_ivf_topk_deep (retrieve_ivf_topk_deep below), one call for the whole batch.
+// grouped: q is [U, G, 128], G in 1..8, everything "per query" above is per user, and the call is
+// lthm_retrieve_ivf_topk_group (retrieve_ivf_topk_group below), k in 1..128
 static std::tuple<Tensor, Tensor> retrieve_ivf_topk_impl(
     const Tensor& q_, const Tensor& items_, const Tensor& row_ids_, const Tensor& list_off_, const Tensor& probes_,
     int64_t k, bool normalize_q, const c10::optional<Tensor>& exclude_rows, const c10::optional<Tensor>& tags_,
     const c10::optional<Tensor>& tag_filter_, const c10::optional<Tensor>& bias_,
     const c10::optional<Tensor>& bias_weight_, const c10::optional<Tensor>& after_scores_,
-    const c10::optional<Tensor>& after_ids_, bool deep) {
+    const c10::optional<Tensor>& after_ids_, bool deep, bool grouped = false) {
   on_gpu(q_, "q");
   on_gpu(items_, "items");
   on_gpu(row_ids_, "row_ids");
@@ -693,7 +696,13 @@ static std::tuple<Tensor, Tensor> retrieve_ivf_topk_impl(
   on_gpu(probes_, "probes");
   TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16,
               "items must be a bf16 [N, 128] catalogue");
-  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128, "q must be [Q, 128]");
+  if (grouped) {
+    TORCH_CHECK(q_.dim() == 3 && q_.size(2) == 128, "q must be [U, G, 128]");
+    TORCH_CHECK(q_.size(1) >= 1 && q_.size(1) <= 8, "retrieve_ivf_topk_group takes 1..8 queries per user, got G=",
+                q_.size(1));
+  } else {
+    TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128, "q must be [Q, 128]");
+  }
   if (deep) {
     TORCH_CHECK(k >= 1 && k <= 1024, "retrieve_ivf_topk_deep takes k in 1..1024, got ", k);
   } else {
@@ -701,7 +710,7 @@ static std::tuple<Tensor, Tensor> retrieve_ivf_topk_impl(
   }
   TORCH_CHECK(items_.size(0) >= 1 && q_.size(0) >= 1, "retrieve_ivf_topk takes a non-empty catalogue and query set");
   auto q = q_.contiguous(), items = items_.contiguous();
-  const int64_t Q = q.size(0), N = items.size(0);
+  const int64_t Q = q.size(0), N = items.size(0), G = grouped ? q.size(1) : 1;
   TORCH_CHECK(row_ids_.scalar_type() == at::kLong && row_ids_.dim() == 1 && row_ids_.size(0) == N,
               "row_ids must be int64 [N], one id per catalogue row");
   TORCH_CHECK(list_off_.scalar_type() == at::kLong && list_off_.dim() == 1 && list_off_.size(0) >= 2,
@@ -772,8 +781,10 @@ static std::tuple<Tensor, Tensor> retrieve_ivf_topk_impl(
     after_ids = after_ids_->contiguous();
   }
   const int64_t need =
-      deep ? lthm_retrieve_ivf_deep_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0, has_cs ? 1 : 0)
-           : lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0, has_cs ? 1 : 0);
+      grouped ? lthm_retrieve_ivf_group_ws_bytes(Q, (int32_t)G, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0,
+                                                 has_cs ? 1 : 0)
+      : deep  ? lthm_retrieve_ivf_deep_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0, has_cs ? 1 : 0)
+              : lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, (int32_t)P, (int32_t)k, excl ? xr.size(1) : 0, has_cs ? 1 : 0);
   TORCH_CHECK(need >= 0, "retrieve_ivf_topk: unsupported sizes Q=", Q, " N=", N, " L=", L, " P=", P);
   auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
   auto ids = at::empty({Q, k}, q.options().dtype(at::kLong));
@@ -797,6 +808,17 @@ static std::tuple<Tensor, Tensor> retrieve_ivf_topk_impl(
   if (has_cs) {
     c.after_score = after_scores.data_ptr<float>();
     c.after_id = after_ids.data_ptr<int64_t>();
+  }
+  if (grouped) {
+    lthm_retrieve_group g = {};
+    g.G = (int32_t)G;
+    hip_ok(lthm_retrieve_ivf_topk_group(items.data_ptr(), N, row_ids.data_ptr<int64_t>(), list_off.data_ptr<int64_t>(), L,
+                                        q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q, &g, probes.data_ptr<int32_t>(),
+                                        (int32_t)P, (int32_t)k, excl ? &x : nullptr, has_tags ? &t : nullptr,
+                                        has_b ? &b : nullptr, has_cs ? &c : nullptr, scores.data_ptr<float>(),
+                                        ids.data_ptr<int64_t>(), ws.data_ptr(), need, cur_stream()),
+           "lthm_retrieve_ivf_topk_group");
+    return std::make_tuple(scores, ids);
   }
   const auto entry = deep ? &lthm_retrieve_ivf_topk_deep : &lthm_retrieve_ivf_topk_filt;
   hip_ok(entry(items.data_ptr(), N, row_ids.data_ptr<int64_t>(), list_off.data_ptr<int64_t>(), L, q.data_ptr(), dcode(q),
@@ -824,6 +846,17 @@ std::tuple<Tensor, Tensor> retrieve_ivf_topk_deep_cuda(
     const c10::optional<Tensor>& after_scores, const c10::optional<Tensor>& after_ids) {
   return retrieve_ivf_topk_impl(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, tags, tag_filter, bias,
                                 bias_weight, after_scores, after_ids, true);
+}
+
+// retrieve_ivf_topk_filt for users of G queries each: q [U, G, 128], probes [U, P], every other argument
+// per user; an item is scored by its best match over the user's queries and takes one slot
+std::tuple<Tensor, Tensor> retrieve_ivf_topk_group_cuda(
+    const Tensor& q, const Tensor& items, const Tensor& row_ids, const Tensor& list_off, const Tensor& probes, int64_t k,
+    bool normalize_q, const c10::optional<Tensor>& exclude_rows, const c10::optional<Tensor>& tags,
+    const c10::optional<Tensor>& tag_filter, const c10::optional<Tensor>& bias, const c10::optional<Tensor>& bias_weight,
+    const c10::optional<Tensor>& after_scores, const c10::optional<Tensor>& after_ids) {
+  return retrieve_ivf_topk_impl(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, tags, tag_filter, bias,
+                                bias_weight, after_scores, after_ids, false, true);
 }
 
 // items bf16 [N, 128], rows int32 [Q, M], scores f32 [Q, M] (M <= 1024), lam f32 [Q] or None (1
@@ -1015,6 +1048,10 @@ TORCH_LIBRARY(lthm, m) {
       "bool normalize_q, Tensor? exclude_rows=None, Tensor? tags=None, Tensor? tag_filter=None, Tensor? bias=None, "
       "Tensor? bias_weight=None, Tensor? after_scores=None, Tensor? after_ids=None) -> (Tensor scores, Tensor ids)");
   m.def(
+      "retrieve_ivf_topk_group(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
+      "bool normalize_q, Tensor? exclude_rows=None, Tensor? tags=None, Tensor? tag_filter=None, Tensor? bias=None, "
+      "Tensor? bias_weight=None, Tensor? after_scores=None, Tensor? after_ids=None) -> (Tensor scores, Tensor ids)");
+  m.def(
       "retrieve_diversify(Tensor items, Tensor rows, Tensor scores, int k, Tensor? lam=None, Tensor? groups=None, "
       "int cap=1) -> (Tensor rows, Tensor scores, Tensor objective)");
   m.def("quantize_catalogue_q8(Tensor items) -> (Tensor codes, Tensor scale)");
@@ -1042,6 +1079,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
   m.impl("retrieve_ivf_topk_filt", &retrieve_ivf_topk_filt_cuda);
   m.impl("retrieve_ivf_topk_deep", &retrieve_ivf_topk_deep_cuda);
+  m.impl("retrieve_ivf_topk_group", &retrieve_ivf_topk_group_cuda);
   m.impl("retrieve_diversify", &retrieve_diversify_cuda);
   m.impl("quantize_catalogue_q8", &quantize_catalogue_q8_cuda);
   m.impl("retrieve_q8_topk", &retrieve_q8_topk_cuda);

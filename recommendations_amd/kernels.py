@@ -2159,13 +2159,59 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     workspace, so where one call would take more than RETRIEVE_IVF_DEEP_WS_BYTES (1 GiB) the queries
     go through in consecutive chunks, each one call: a query's list does not depend on the other
     queries, so the split changes no bit.  Without deep, k > 128 is refused as it always was."""
+    return _retrieve_ivf_scan("retrieve_ivf_topk", q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows,
+                              tags, tag_filter, bias, bias_weight, after_scores, after_ids, deep)
+
+
+def retrieve_ivf_group_grid(U: int, G: int, P: int, L: int) -> int:
+    """The grid of the clustered scan with G queries per user (lthm_retrieve_ivf_group_grid): U P // T +
+    min(L, U P) with T = 4 (16 // G) pairs per tile, an upper bound on sum_c ceil(n_c / T) over the lists'
+    pair counts n_c, whatever they are (sum_c n_c <= U P).  At G = 1 it is retrieve_ivf_grid."""
+    n = int(load().lthm_retrieve_ivf_group_grid(int(U), int(G), int(P), int(L)))
+    _check(n >= 0, f"retrieve_ivf_group_grid takes U, P, L >= 1 and G in 1..{RETRIEVE_MAX_GROUP} "
+                   f"(got U={U} G={G} P={P} L={L})")
+    return n
+
+
+def retrieve_ivf_topk_group(q, items, row_ids, list_off, probes, k: int, *, normalize_q: bool = True, exclude_rows=None,
+                            tags=None, tag_filter=None, bias=None, bias_weight=None, after_scores=None, after_ids=None):
+    """retrieve_ivf_topk for users with several queries each (lthm_retrieve_ivf_topk_group, csrc/retrieve.hip
+    retr_ivf_topk_k<true, true, TAGS, BIAS, true>): an item's score is its best over the user's queries,
+    s[u, j] = max_g s_g[u, j] with s_g the score retrieve_topk gives query (u, g), taken inside the scan
+    ahead of candidate selection, so an item takes one slot per user.
+
+    q f32 / bf16 [U, G, 128], 1 <= G <= 8; probes int32 [U, P], one probe row per user; exclude_rows int32
+    [U, X], tag_filter int32 [U, 3], bias_weight (None, a number or f32 [U]) and after_scores f32 [U] /
+    after_ids int64 [U] are per user and mean what they mean in retrieve_ivf_topk, applied to s[u, j] in
+    retrieve_topk_group's order (the prior behind the maximum, then exclusion, tags and the cursor).
+    Returns (scores f32 [U, k], ids int64 [U, k]), 1 <= k <= 128 (no deep lists with groups): the first k
+    under (score descending, id ascending) of the probed, eligible rows, then (-inf, 0).  The outputs do
+    not depend on the order of a user's queries; with every list probed they are retrieve_topk_group's for
+    the same arguments, bit for bit, and G = 1 is retrieve_ivf_topk on q[:, 0]: the same kernels."""
+    return _retrieve_ivf_scan("retrieve_ivf_topk_group", q, items, row_ids, list_off, probes, k, normalize_q,
+                              exclude_rows, tags, tag_filter, bias, bias_weight, after_scores, after_ids, False)
+
+
+def _retrieve_ivf_scan(who: str, q, items, row_ids, list_off, probes, k: int, normalize_q, exclude_rows, tags,
+                       tag_filter, bias, bias_weight, after_scores, after_ids, deep):
+    """The one call path of retrieve_ivf_topk (q [Q, 128]) and retrieve_ivf_topk_group (q [U, G, 128]),
+    which document the arguments (csrc/retrieve.hip, retr_ivf_call).  Below, Q counts the users of a
+    grouped call."""
     import ctypes
     from ._lib import STRUCTS
-    who = "retrieve_ivf_topk"
+    grouped = who == "retrieve_ivf_topk_group"
     require_gpu(q, items, row_ids, list_off, probes, exclude_rows, tags, tag_filter, bias, after_scores, after_ids)
     _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
            f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
-    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    G = 1
+    if grouped:
+        _check(q.dim() == 3 and q.shape[2] == RETRIEVE_WIDTH,
+               f"{who} takes [U, G, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+        G = q.shape[1]
+        _check(1 <= G <= RETRIEVE_MAX_GROUP, f"{who} takes 1..{RETRIEVE_MAX_GROUP} queries per user (got {G})")
+    else:
+        _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH,
+               f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
     Q, N, k = q.shape[0], items.shape[0], int(k)
     if deep:
         _check(1 <= k <= RETRIEVE_MAX_DEEP, f"{who} with deep=True takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
@@ -2206,7 +2252,9 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     if deep:
         return _retrieve_ivf_deep(q, items, row_ids, list_off, probes, k, normalize_q, exclude_rows, tags, tag_filter,
                                   bias, bw, after_scores, after_ids)
-    if filt:
+    if grouped:
+        need = load().lthm_retrieve_ivf_group_ws_bytes(Q, G, N, L, P, k, X, int(c is not None))
+    elif filt:
         need = load().lthm_retrieve_ivf_filt_ws_bytes(Q, N, L, P, k, X, int(c is not None))
     else:
         need = load().lthm_retrieve_ivf_ws_bytes(Q, N, L, P, k, X)
@@ -2216,7 +2264,7 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     work = float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k + 4.0 * Q * (P + X))
-    if not filt:
+    if not filt and not grouped:
         call("lthm_retrieve_ivf_topk", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
              int(bool(normalize_q)), Q, ptr(probes), P, k, ctypes.addressof(x) if x is not None else None, ptr(scores),
              ptr(ids), ptr(ws), need, stream(), _key="retr_ivf_topk_k", _work=work, _unit="byte")
@@ -2224,6 +2272,13 @@ def retrieve_ivf_topk(q, items, row_ids, list_off, probes, k: int, *, normalize_
     parts = [ctypes.addressof(o) if o is not None else None for o in (x, t, b, c)]
     work += (12.0 * Q if t is not None else 0.0) + (4.0 * Q if bw is not None else 0.0) \
         + (12.0 * Q + 4.0 * Q * P if c is not None else 0.0)
+    if grouped:
+        g = STRUCTS["lthm_retrieve_group"]()
+        g.G = G
+        call("lthm_retrieve_ivf_topk_group", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
+             int(bool(normalize_q)), Q, ctypes.addressof(g), ptr(probes), P, k, *parts, ptr(scores), ptr(ids), ptr(ws),
+             need, stream(), _key="retr_ivf_topk_group_k", _work=work, _unit="byte")
+        return scores, ids
     call("lthm_retrieve_ivf_topk_filt", ptr(items), N, ptr(row_ids), ptr(list_off), L, ptr(q), dcode(q),
          int(bool(normalize_q)), Q, ptr(probes), P, k, *parts, ptr(scores), ptr(ids), ptr(ws), need, stream(),
          _key="retr_ivf_topk_filt_k", _work=work, _unit="byte")

@@ -38,7 +38,9 @@ rows grouped into lists around centroids, and its ``topk`` scans only the ``npro
 to each query (``K.retrieve_ivf_topk``): the exact top-k of the probed lists, with the flat scan's
 score bits, and with ``nprobe`` = L the flat scan's result.  Its ``with_filters()`` view scans the same
 lists with the catalogue's tags and bias and behind a (score, id) cursor, under ``ItemCatalogue.topk``'s
-conventions.
+conventions.  Its ``with_heads()`` view is that view for users with several queries each (``q``
+[U, G, 128], ``K.retrieve_ivf_topk_group``): one probe row per user, an item scored by its best match
+over the user's queries inside the scan, one slot per item.
 """
 from __future__ import annotations
 
@@ -568,7 +570,9 @@ class ClusteredItemCatalogue:
     them and takes cursors; this catalogue's own scan scores the plain dot and filters nothing but
     ``exclude_ids``.  Groups are not carried: a clustered list is diversified against
     the flat catalogue it was built from (``ItemCatalogue.diversify`` takes its ids), or by the view
-    ``with_deep(groups)`` returns, which takes them and whose lists reach k = 1,024."""
+    ``with_deep(groups)`` returns, which takes them and whose lists reach k = 1,024.  Several queries per
+    user (``q`` [U, G, 128], the wrapper's ``heads``) take the view ``with_heads()`` returns; this
+    catalogue and the other two views take one query per row."""
 
     def __init__(self, row_ids: torch.Tensor, emb: torch.Tensor, list_off: torch.Tensor, centroids: torch.Tensor,
                  tags: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
@@ -684,8 +688,8 @@ class ClusteredItemCatalogue:
         out = ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
                                      self.centroids.to(device), None if self.tags is None else self.tags.to(device),
                                      None if self.bias is None else self.bias.to(device))
-        if self.scans_deep:
-            view = out.with_deep()
+        if self.scans_deep or self.scans_heads:
+            view = out.with_deep() if self.scans_deep else out.with_heads()
             view.groups = None if self.groups is None else self.groups.to(device)
             return view
         return out.with_filters() if self.scans_filters else out
@@ -702,6 +706,42 @@ class ClusteredItemCatalogue:
         own lists: False here, True on the view ``with_deep()`` returns."""
         return False
 
+    @property
+    def scans_heads(self) -> bool:
+        """Whether ``topk`` takes several queries per user, ``q`` [U, G, 128], and scores an item by its
+        best match over them: False here and on the other views, True on the view ``with_heads()``
+        returns."""
+        return False
+
+    def _rows_of_groups(self, groups: Optional[torch.Tensor], who: str) -> Optional[torch.Tensor]:
+        """``groups`` int32 [N] in ``to_flat()``'s (id-ascending) order, permuted into the clustered row
+        order (None stays None)."""
+        N = len(self)
+        if groups is None:
+            return None
+        if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int32 or tuple(groups.shape) != (N,):
+            raise ValueError(f"{who} takes groups int32 [N], one key per item in to_flat()'s order "
+                             f"(got {getattr(groups, 'dtype', type(groups).__name__)} "
+                             f"{tuple(getattr(groups, 'shape', ()))}, N={N})")
+        perm = torch.empty(N, dtype=torch.int32, device=self.emb.device)
+        perm[self._order] = groups.to(self.emb.device)  # _order: the clustered row of the i-th id
+        return perm
+
+    def with_heads(self, groups: Optional[torch.Tensor] = None) -> "GroupedClusteredItemCatalogue":
+        """A view over the same tensors (nothing is copied) that is a ``with_filters()`` view whose
+        ``topk`` takes ``q`` [U, G, 128], G <= 8 queries per user (say one per lookahead head), and
+        scores an item by its best match over them, one slot per item: see
+        ``GroupedClusteredItemCatalogue``.  ``groups`` int32 [N] in ``to_flat()``'s order are carried in
+        the clustered row order, as ``with_deep`` carries them, for a caller who diversifies the lists
+        elsewhere; this view's own scan does not read them and it refuses ``group_cap``.  This
+        catalogue is unchanged; neither the flag nor the groups are stored by ``save``."""
+        groups = self._rows_of_groups(groups, "with_heads")
+        view = object.__new__(GroupedClusteredItemCatalogue)
+        view.__dict__.update(self.__dict__)
+        view._flat = None
+        view.groups = groups
+        return view
+
     def with_deep(self, groups: Optional[torch.Tensor] = None) -> "DeepClusteredItemCatalogue":
         """A view over the same tensors (nothing is copied) that is a ``with_filters()`` view whose
         ``topk`` takes k up to 1024 and that has ``diversify``: see ``DeepClusteredItemCatalogue``.
@@ -709,15 +749,7 @@ class ClusteredItemCatalogue:
         the ``groups`` of the flat catalogue this was built from, for ``diversify``'s ``group_cap``.
         They are permuted once into the clustered row order.  This catalogue is unchanged; neither
         the flag nor the groups are stored by ``save``."""
-        N = len(self)
-        if groups is not None:
-            if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int32 or tuple(groups.shape) != (N,):
-                raise ValueError(f"with_deep takes groups int32 [N], one key per item in to_flat()'s order "
-                                 f"(got {getattr(groups, 'dtype', type(groups).__name__)} "
-                                 f"{tuple(getattr(groups, 'shape', ()))}, N={N})")
-            perm = torch.empty(N, dtype=torch.int32, device=self.emb.device)
-            perm[self._order] = groups.to(self.emb.device)  # _order: the clustered row of the i-th id
-            groups = perm
+        groups = self._rows_of_groups(groups, "with_deep")
         view = object.__new__(DeepClusteredItemCatalogue)
         view.__dict__.update(self.__dict__)
         view._flat = None
@@ -977,6 +1009,72 @@ class DeepClusteredItemCatalogue(FilteredClusteredItemCatalogue):
             outs.append(block.diversify(pool, scores[q0:q0 + step], k, group_cap=group_cap,
                                         lam=lam[q0:q0 + step] if isinstance(lam, torch.Tensor) and lam.dim() == 1 else lam))
         return tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+
+class GroupedClusteredItemCatalogue(FilteredClusteredItemCatalogue):
+    """``ClusteredItemCatalogue.with_heads()``: the ``with_filters()`` view of the same tensors whose
+    queries come in groups, ``q`` [U, G, 128] with G <= ``K.RETRIEVE_MAX_GROUP`` = 8 per user
+    (``K.retrieve_ivf_topk_group``; csrc/retrieve.hip ``retr_ivf_topk_k<true, true, TAGS, BIAS, true>``).
+    An item's score is its best over the user's queries, taken inside the scan ahead of candidate
+    selection, so an item takes one slot per user and the order of a user's queries does not matter.
+    A user probes one set of lists: the ``nprobe`` centroids that score best for any of its queries.
+    ``exclude_ids``, ``tag_filter``, ``after_scores`` / ``after_ids`` and ``bias_weight`` are the
+    filtered view's, one per user; k stays in 1..128.  A 2-D ``q`` [Q, 128] is G = 1, the filtered
+    view's own call."""
+
+    @property
+    def scans_heads(self) -> bool:
+        return True
+
+    def with_heads(self, groups: Optional[torch.Tensor] = None) -> "GroupedClusteredItemCatalogue":
+        return self if groups is None else ClusteredItemCatalogue.with_heads(self, groups)
+
+    @staticmethod
+    def _grouped(q: torch.Tensor) -> torch.Tensor:
+        if q.dim() == 2:
+            return q[:, None, :]
+        if q.dim() != 3 or not 1 <= q.shape[1] <= K.RETRIEVE_MAX_GROUP:
+            raise ValueError(f"a with_heads() view takes [U, G, {WIDTH}] queries, G in 1..{K.RETRIEVE_MAX_GROUP} "
+                             f"per user (got {tuple(q.shape)})")
+        return q
+
+    def probe(self, q: torch.Tensor, nprobe: int, *, normalize_q: bool = True) -> torch.Tensor:
+        """int32 [U, nprobe]: per user the lists of the nprobe first centroids under (the centroid's best
+        score over the user's queries descending, list ascending): ``K.retrieve_topk_group`` with the
+        centroids as the catalogue.  At G = 1 (and for a 2-D ``q``) it is the plain catalogue's ``probe``."""
+        _, nprobe = self._check_call(1, nprobe)
+        q = self._grouped(q)
+        if q.shape[1] == 1:
+            return K.retrieve_topk(q[:, 0].contiguous(), self.centroids, nprobe, normalize_q=normalize_q)[1]
+        return K.retrieve_topk_group(q.contiguous(), self.centroids, nprobe, normalize_q=normalize_q)[1]
+
+    def topk(self, q: torch.Tensor, k: int, *, nprobe: int, normalize_q: bool = True,
+             exclude_ids: Optional[torch.Tensor] = None, tag_filter: Optional[torch.Tensor] = None,
+             after_scores: Optional[torch.Tensor] = None, after_ids: Optional[torch.Tensor] = None,
+             bias_weight: Union[None, float, torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores f32 [U, k], ids int64 [U, k]): the filtered view's ``topk``, argument for argument,
+        for ``q`` [U, G, 128]: per user the k first, under (score descending, id ascending), of the items
+        that lie in the user's ``nprobe`` lists (``probe``), are not among its ``exclude_ids`` [U, X],
+        pass its ``tag_filter`` [U, 3] and lie strictly behind its cursor, then (-inf, 0), on the score
+        max_g q[u, g] . e_j (with a bias, fma(w[u], bias[j], that maximum)).  No item appears twice in a
+        user's list.  Every score has the bits ``ItemCatalogue.topk`` returns for the same 3-D ``q`` and
+        arguments, and with ``nprobe`` = L the whole result is ``to_flat().topk``'s."""
+        k, nprobe = self._check_call(k, nprobe)
+        q = self._grouped(q)
+        self._check_filters(q[:, 0], tag_filter, after_scores, after_ids, bias_weight)
+        xr = None
+        if exclude_ids is not None:
+            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
+                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+            xr = self.rows_of(exclude_ids).contiguous()
+        probes = self.probe(q, nprobe, normalize_q=normalize_q)
+        kw = dict(normalize_q=normalize_q, exclude_rows=xr, tags=self.tags if tag_filter is not None else None,
+                  tag_filter=None if tag_filter is None else tag_filter.contiguous(), bias=self.bias,
+                  bias_weight=bias_weight, after_scores=None if after_scores is None else after_scores.contiguous(),
+                  after_ids=None if after_ids is None else after_ids.contiguous())
+        if q.shape[1] == 1:
+            return K.retrieve_ivf_topk(q[:, 0].contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
+        return K.retrieve_ivf_topk_group(q.contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
 
 
 class ShardedItemCatalogue:

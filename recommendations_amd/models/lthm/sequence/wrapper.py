@@ -380,7 +380,13 @@ class LTHMModelWrapper(BaseModelWrapper):
         same ``nprobe`` with ``after``); it still refuses ``heads`` and k > 128.  Its ``with_deep(groups)``
         view takes k up to 1024 and ``diversity`` / ``pool`` / ``group_cap`` as a flat catalogue does, below:
         the pool is the deep list of the probed lists and the view's own ``diversify`` selects from it;
-        ``heads`` it still refuses.
+        ``heads`` it still refuses.  Its ``with_heads()`` view takes everything the ``with_filters()`` view
+        takes and ``heads``: the queries are ``next_token_emb[:, -1, heads]``, sequence b probes the
+        ``nprobe`` lists whose centroids score best for any of them and gets the k best items (k <= 128)
+        of those lists by the best match over the heads, every item once; ``exclude_history``,
+        ``tag_*``, ``bias_weight`` and ``after`` compose as on a flat catalogue, and with ``nprobe`` = L
+        the result is the flat catalogue's for the same arguments.  It refuses ``diversity`` / ``pool`` /
+        ``group_cap`` and k > 128: deep lists with heads take ``to_flat()``.
         ``diversity`` = lambda in [0, 1] and / or ``group_cap`` = m (alone it means lambda = 1; the
         catalogue must carry groups) ask a flat ``ItemCatalogue`` for a diversified list: the call
         retrieves ``pool`` items (default min(8 k, 1024); k <= ``pool`` <= 1024, k <= 128; above 128
@@ -417,6 +423,8 @@ class LTHMModelWrapper(BaseModelWrapper):
                      "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
             if catalogue.scans_deep:  # a with_deep() view also diversifies its own lists
                 given = {"heads": heads}
+            elif catalogue.scans_heads:  # a with_heads() view is a with_filters() view that also takes heads
+                given = {name: given[name] for name in ("diversity", "pool", "group_cap")}
             elif catalogue.scans_filters:  # a with_filters() view scans tags, prior and cursor itself
                 given = {name: given[name] for name in ("heads", "diversity", "pool", "group_cap")}
             bad = [name for name, v in given.items() if v is not None]

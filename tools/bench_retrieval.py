@@ -5,6 +5,7 @@
                                     [--group G] [--tags P] [--after] [--deep K] [--bias]
     python tools/bench_retrieval.py --shards S [--shapes ...] [--reps 20] [--n-items 2000000] [--k 100]
     python tools/bench_retrieval.py --ivf L [--shapes ...] [--reps 20] [--n-items 2000000] [--k 100]
+    python tools/bench_retrieval.py --ivf-heads L [--group 3] [--shapes ...] [--reps 20] [--n-items 2000000] [--k 100]
 
 Each shape runs in a child process of its own (checked exit status, time limit); a failed
 shape stops the run.  One JSON line per shape:
@@ -90,6 +91,16 @@ line per (shape, nprobe in {8, 32}, k in {256, 1024}), all arms alternating in o
 With --baseline-lib PATH two more arms time lthm_retrieve_ivf_topk at k = 100 through that library and through this one
 (scan_call_within_base: each median inside the other's min-max range).  The serving shape adds one line per nprobe for
 the chain deep pool of 1,024 -> diversify k = 100 (lam 0.7, group_cap 2), the view against the flat catalogue.
+--ivf-heads L is a mode of its own too: the catalogue of --ivf, U users of G = --group (default 3) queries each, every
+query drawn around a centre of its own, nprobe = 8.  One JSON line per shape, three arms alternating in one loop,
+medians (min / max):
+  ivf_heads_ms                the with_heads() view's topk: the grouped probe scan + lthm_retrieve_ivf_topk_group
+  flat_group_ms               K.retrieve_topk_group over the whole catalogue; heads_over_flat (_hi: the worst pairing,
+                              heads max / flat min; faster only if < 1)
+  separate_ms                 G ClusteredItemCatalogue.topk calls, one per head with its own 8 probes, and a torch merge
+                              that removes an id's duplicates (merge_heads); heads_over_separate
+  recall_at_k, separate_recall_at_k   the mean fraction of the flat grouped call's top-k each returns; rows_per_user and
+                              separate_rows_per_user the rows either scans per user; no_item_twice
 --diversify is a mode of its own too: Q = 256 queries, N unit rows drawn as --ivf draws them, the pool the deep
 scan's own first M rows for M in {512, 1024}, k = 100 by default, lam = 0.7.  One JSON line per M:
   kernel_ms / torch_ms        K.retrieve_diversify and a torch greedy loop on the device over the gathered
@@ -556,6 +567,75 @@ def child_ivf(name: str, N: int, k: int, reps: int, L: int) -> None:
         print(json.dumps(out), flush=True)
 
 
+def child_ivf_heads(name: str, N: int, k: int, reps: int, L: int, G: int) -> None:
+    """--ivf-heads: child_ivf's catalogue, U users of G queries each, every query drawn around a centre of
+    its own (the heads of a user point at different lists: the hard case for one shared probe row)."""
+    import torch
+    from recommendations_amd import kernels as K
+    from recommendations_amd.models.lthm.sequence.retrieval import ItemCatalogue
+    U = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5  # child_ivf's catalogue, drawn the same way
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (U * G,), generator=g, device=dev)] + sigma * torch.randn((U * G, 128), generator=g, device=dev)
+    q = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16).view(U, G, 128).contiguous()
+    heads = [q[:, i].contiguous() for i in range(G)]
+    flat = ItemCatalogue(torch.arange(1, N + 1, dtype=torch.int64, device=dev) * 3, items)
+    cl = flat.cluster(L, iters=5, seed=0, sample=min(N, 1 << 18))
+    view = cl.with_heads()
+    lens = cl.list_lengths()
+    P = 8
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def separate():
+        return merge_heads([cl.topk(h, k, nprobe=P, normalize_q=False) for h in heads], k)
+
+    arms = [("ivf_heads", lambda: view.topk(q, k, nprobe=P, normalize_q=False), []),
+            ("flat_group", lambda: K.retrieve_topk_group(q, items, k, normalize_q=False), []),
+            ("separate", separate, [])]
+    for _ in range(2):
+        for _, fn, _ in arms:
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for _, fn, times in arms:
+            times.append(timed(fn))
+    out = {"shape": name, "mode": "ivf_heads", "U": U, "G": G, "N": N, "k": k, "L": L, "nprobe": P, "reps": reps,
+           "heads": "every query around a centre of its own"}
+    for key, _, times in arms:
+        out.update({f"{key}_ms": round(statistics.median(times), 4), f"{key}_min_ms": round(min(times), 4),
+                    f"{key}_max_ms": round(max(times), 4)})
+    out["heads_over_flat"] = round(out["ivf_heads_ms"] / out["flat_group_ms"], 4)
+    out["heads_over_flat_hi"] = round(out["ivf_heads_max_ms"] / out["flat_group_min_ms"], 4)  # the worst pairing
+    out["heads_over_separate"] = round(out["ivf_heads_ms"] / out["separate_ms"], 4)
+    want = flat.topk(q, k, normalize_q=False)[0]
+
+    def recall(got):
+        return round(float(((want[:, :, None] == got[:, None, :]).any(dim=2).float().sum(dim=1) / k).mean()), 4)
+
+    got = view.topk(q, k, nprobe=P, normalize_q=False)[1]
+    out[f"recall_at_{k}"] = recall(got)
+    out[f"separate_recall_at_{k}"] = recall(separate()[1])
+    out["no_item_twice"] = bool((got.sort(dim=1)[0][:, 1:] != got.sort(dim=1)[0][:, :-1]).logical_or(got.sort(dim=1)[0][:, 1:] == 0).all())
+    out["rows_per_user"] = round(float(lens[view.probe(q, P, normalize_q=False).long()].sum(dim=1).float().mean()), 1)
+    out["separate_rows_per_user"] = round(float(sum(lens[cl.probe(h, P, normalize_q=False).long()].sum(dim=1).float().mean()
+                                                    for h in heads)), 1)
+    print(json.dumps(out), flush=True)
+
+
 def child_ivf_filt(name: str, N: int, k: int, reps: int, L: int, baseline_lib: str) -> None:
     import ctypes
     import torch
@@ -918,6 +998,9 @@ def main() -> int:
     ap.add_argument("--ivf-deep", type=int, default=0,
                     help="a mode of its own: --ivf's catalogue, the with_deep() view's k = 256 / 1,024 lists against the "
                          "flat deep call, and the chain deep pool -> diversify")
+    ap.add_argument("--ivf-heads", type=int, default=0,
+                    help="a mode of its own: --ivf's catalogue, --group (default 3) queries per user, nprobe 8: the "
+                         "with_heads() view against the flat grouped call and against one clustered call per head")
     ap.add_argument("--baseline-lib", default="",
                     help="with --ivf-filt / --ivf-deep: another build of liblthm_hip.so whose lthm_retrieve_ivf_topk is timed "
                          "in the same loop")
@@ -950,6 +1033,12 @@ def main() -> int:
         raise SystemExit("--ivf-deep takes 0 (off) or a number of lists, and is a mode of its own")
     if a.baseline_lib and not ((a.ivf_filt or a.ivf_deep) and os.path.exists(a.baseline_lib)):
         raise SystemExit("--baseline-lib takes the path of a built liblthm_hip.so and goes with --ivf-filt or --ivf-deep")
+    if a.ivf_heads < 0 or (a.ivf_heads and (a.ivf or a.ivf_filt or a.ivf_deep or a.shards or a.diversify or a.q8
+                                            or not 1 <= a.k <= 128)):
+        raise SystemExit("--ivf-heads takes 0 (off) or a number of lists, is a mode of its own and takes --k in 1..128")
+    if a.child and a.ivf_heads:
+        child_ivf_heads(a.child, a.n_items, a.k, a.reps, a.ivf_heads, a.group or 3)
+        return 0
     if a.child and a.ivf_deep:
         child_ivf_deep(a.child, a.n_items, a.reps, a.ivf_deep, a.baseline_lib)
         return 0
@@ -979,7 +1068,7 @@ def main() -> int:
                                  "--n-items", str(a.n_items), "--k", str(a.k), "--exclude", str(a.exclude),
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
                                  "--ivf", str(a.ivf), "--q8", str(a.q8), "--ivf-filt", str(a.ivf_filt),
-                                 "--ivf-deep", str(a.ivf_deep), "--baseline-lib", a.baseline_lib]
+                                 "--ivf-deep", str(a.ivf_deep), "--ivf-heads", str(a.ivf_heads), "--baseline-lib", a.baseline_lib]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
                                 + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
