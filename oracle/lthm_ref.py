@@ -182,12 +182,13 @@ def contrastive_loss(next_emb, cur_emb, mask, offsets: np.ndarray, mbs: int, tau
             la = lu.mean()
             loss = loss + la
             rank = (logits > logits.gather(1, labels[:, None])).sum(1)
+            fdt = logits.dtype  # the means of the counts in the dtype of the inputs (f32 as wrapper.py, or f64)
             hits = []
             for k_ in ks:
                 k = min(k_, int(num_negatives.min()))
-                hits.append(float((logits.topk(k=k)[1] == labels.unsqueeze(-1)).sum(dim=1).float().mean()))
-            st.append(dict(loss=float(la), used=int(lu.numel()), neg=float(num_negatives.float().mean()),
-                           mean_rank=float(rank.float().mean()), median_rank=float(rank.float().quantile(0.5)),
+                hits.append(float((logits.topk(k=k)[1] == labels.unsqueeze(-1)).sum(dim=1).to(fdt).mean()))
+            st.append(dict(loss=float(la.detach()), used=int(lu.numel()), neg=float(num_negatives.to(fdt).mean()),
+                           mean_rank=float(rank.to(fdt).mean()), median_rank=float(rank.to(fdt).quantile(0.5)),
                            hits=hits))
         total = total + loss / n_mb
         stats.append(st)

@@ -1,13 +1,14 @@
 // Fused in-batch contrastive loss of the LTHM wrapper
 // (models/lthm/sequence/wrapper.py:114-245), forward + backward, for gfx950.
 //
-// Per mini-batch of <= 32 sequences and per lookahead head i with offset o
+// Per mini-batch of mb_size sequences (any number in the separate passes; the fused and compact
+// training passes take up to CL_UMAXB = 4096) and per lookahead head i with offset o
 // (drawn per mini-batch, wrapper.py:147-153):
 //   rows r = (b, t), t < L = T - o:   out_r = normalize(next_token_emb[b, t, i])
 //   cols c = (b', t'):                in_c  = normalize(current_token_emb[b', t' + o])
 //   logits = out . in^T / tau, -inf where same sequence & r != c, or col/row pad;
 //   rows kept iff not pad and >= 1 finite negative; CE(logits, r) averaged.
-// The [n, n] logits (n <= 32 T) are never written: transposed 64 x 32 tiles
+// The [n, n] logits (n <= mb_size T) are never written: transposed 64 x 32 tiles
 // S^T = img . regrows^T are produced by bf16 MFMA (K = 128) from LDS-staged
 // column tiles and reduced on the fly to per-row (sum-exp, finite count, rank
 // of the positive).  The backward recomputes each tile from the saved LSE; dS
@@ -323,7 +324,7 @@ __device__ __forceinline__ void reg_frags(bf16x8v (&f)[4], int lane, int cnt, in
   }
 }
 
-// diag[r] = out_r . in_r / tau (fp32 dot of the bf16 operands), per (mb, row);
+// diag[r] = out_r . in_r * (1 / tau) (fp32 dot of the bf16 operands), per (mb, row);
 // -inf for pad rows and for the rows n <= r < n_max (the forward reads the
 // diag of its columns as their pad flag)
 __global__ __launch_bounds__(256) void cl_diag_k(ClArgs a0) {
@@ -348,7 +349,10 @@ __global__ __launch_bounds__(256) void cl_diag_k(ClArgs a0) {
     }
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) acc += __shfl_xor(acc, o, 64);
-    if (live) s = acc / a.tau;
+    // acc * (1 / tau), the product every pass forms for its logits (v = acc * it): a negative whose
+    // dot equals the positive's then gives the same float and is not ranked above it.  acc / tau
+    // rounds differently wherever 1 / tau is inexact in f32 and counted such ties as hits above
+    if (live) s = acc * (1.f / a.tau);
     if (sub == 0 && r < a.n_max) {
       a.diag[(int64_t)mb * a.n_max + r] = s;
       if (a.colb) a.colb[(int64_t)mb * a.n_max + r] = s == -INFINITY ? -INFINITY : -(1.f / a.tau) * 1.4426950408889634f;
@@ -1956,7 +1960,7 @@ __global__ __launch_bounds__(256) void cl_vgather_k(ClArgs a0) {
       if (i < m) {
         *reinterpret_cast<u32x4*>(a.vR + (base + i) * DE + sub * 8) = ov[u];
         *reinterpret_cast<u32x4*>(a.vC + (base + i) * DE + sub * 8) = iv[u];
-        if (sub == 0) a.diag[base + rr[u]] = acc / a.tau;
+        if (sub == 0) a.diag[base + rr[u]] = acc * (1.f / a.tau);
       }
     }
   }
