@@ -1290,6 +1290,48 @@ int64_t lthm_retrieve_rescore_ws_bytes(int64_t Q, int32_t M, int32_t k);
 int lthm_retrieve_rescore(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q, int64_t Q,
                           const int32_t* rows, int32_t M, int32_t k, float* out_scores, int32_t* out_rows,
                           void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_rescore with a prior and an id order: a listed row's score is fmaf(weight[q],
+ * bias[row], dot), dot the bits lthm_retrieve_rescore returns, one explicit f32 fma as
+ * lthm_retrieve_topk_bias does on its score (weight NULL: 1 for every query).  order_ids int64 [N] or
+ * NULL: with it the list comes out under (score descending, order_ids[row] ascending), the order of
+ * the clustered calls, whose rows do not ascend with their ids across lists; without it under (score
+ * descending, row ascending).  With bias == NULL and order_ids == NULL the call IS
+ * lthm_retrieve_rescore: the same kernel body, the same bits.  weight without bias is refused.  The
+ * workspace is lthm_retrieve_rescore_ws_bytes(Q, M, k). */
+int lthm_retrieve_rescore_bias(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q,
+                               int64_t Q, const int32_t* rows, int32_t M, int32_t k, const float* bias,
+                               const float* weight, const int64_t* order_ids, float* out_scores, int32_t* out_rows,
+                               void* workspace, int64_t ws_bytes, void* stream);
+/* Clustered e4m3 catalogues: lthm_retrieve_q8_topk's shortlist from the probed lists alone, with
+ * lthm_retrieve_ivf_topk_deep's eligibility.  codes uint8 [N, 128] / scale f32 [N] are
+ * lthm_catalogue_quantize_q8 of the list-major rows; row_ids, list_off, probes, x, t and b are
+ * lthm_retrieve_ivf_topk_deep's (rows, tags and bias in the clustered numbering).
+ *   s^[q, j] = acc (scale_q scale_j), lthm_retrieve_q8_topk's score bit for bit (the same query
+ *              preparation and quantiser, the same eight bf16 MFMA steps from zero, two explicit f32
+ *              multiplies); with b the ranked score is fmaf(weight[q], bias[j], s^), one explicit fma
+ *              under lthm_retrieve_topk_bias' rules (a non-finite weight gives that query an
+ *              unspecified list and harms nothing else)
+ *   a row is a candidate of query q iff it lies in a list of probes[q, 0..P) (entries outside [0, L)
+ *              are ignored, an empty list contributes nothing, a list named twice gives both copies),
+ *              is not excluded (x) and passes the query's (all, any, none) filter (t)
+ *   out_scores f32 [Q, M] / out_rows int32 [Q, M] (clustered rows), 1 <= M <= 1024: the M first
+ *              candidates under (score descending, id ascending), lthm_retrieve_ivf_topk_deep's
+ *              total order, then -inf / -1
+ * A pure function of the inputs: no output depends on Q, on the order of a probe row, on how lists
+ * map to blocks or on slot order (the plan's two integer atomics decide only which block column
+ * serves a pair).  Every pointer, alignment, range and workspace check is made before any launch.
+ *   workspace  lthm_retrieve_ivf_q8_ws_bytes(Q, N, L, P, M, X) bytes, 16-byte aligned:
+ *              lthm_retrieve_ivf_deep_ws_bytes' layout at k = M with the key slots (Q P 16 KiB)
+ *              whatever M is, plus the queries' codes and scales (Q 132 B, rounded) and the merged
+ *              ids (Q M 8 B); -1 for M outside 1..1024, X outside 0..1024, P outside 1..64, and Q,
+ *              N, L or Q P outside 1..2^31-1 */
+int64_t lthm_retrieve_ivf_q8_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t M, int64_t X);
+int lthm_retrieve_ivf_q8_topk(const uint8_t* codes, const float* scale, int64_t N, const int64_t* row_ids,
+                              const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                              int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t M,
+                              const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                              const lthm_retrieve_bias* b, float* out_scores, int32_t* out_rows, void* workspace,
+                              int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -3234,12 +3234,29 @@ __global__ __launch_bounds__(256) void retr_q8_topk_k(RetrQ8Args a) {
 // 32 t + (lane & 31) is A row lane & 31 (an entry outside [0, N) reads row 0 and becomes key 0), the
 // query is every B column, so every column of the accumulator holds the 32 scores; lane (r < 16, h)
 // owns element r of its registers: entry 32 t + 8 (r >> 2) + 4 h + (r & 3).
+//
+// BIAS (lthm_retrieve_rescore_bias; the prior rides behind the plain arguments, so that <false> keeps
+// the argument block and the text it always had): a listed row's score becomes fmaf(wq, bias[row],
+// dot), one explicit fma on the MFMA's score.  With p.oids the low word of a key is not the row but
+// the entry's rank among the list's entries under (p.oids[row] ascending, list position ascending)
+// (one pass of P broadcast LDS reads per entry; entries that are no candidates rank behind every row),
+// so that equal scores come out in id order, and the sorted keys are mapped back through the inverse.
+struct RetrRescorePrior {
+  const float* bias;    // [N] or null
+  const float* bw;      // [Q] or null: 1 for everyone
+  const int64_t* oids;  // [N] or null: ties by row
+};
+template <bool BIAS, class... Prior>
 __global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__ items, int64_t N,
                                                       const bf16_t* __restrict__ qn, const int* __restrict__ rows,
                                                       int M, int k, float* __restrict__ scores,
-                                                      int* __restrict__ out_rows) {
+                                                      int* __restrict__ out_rows, Prior... prior) {
   __shared__ u64 keys[RD_KMAX];
   __shared__ int srow[RD_KMAX];
+  __shared__ int64_t sid[BIAS ? RD_KMAX : 1];
+  __shared__ int spos[BIAS ? RD_KMAX : 1], sinv[BIAS ? RD_KMAX : 1];
+  RetrRescorePrior pr = {nullptr, nullptr, nullptr};
+  if constexpr (BIAS) pr = (prior, ...);
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5;
   const int64_t q = blockIdx.x;
@@ -3258,6 +3275,25 @@ __global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__
   for (int s = 0; s < 8; ++s)
     qf[s] = __builtin_bit_cast(bf16x8v, *reinterpret_cast<const u32x4*>(qn + q * RT_D + 16 * s + 8 * hh));
   __syncthreads();
+  float wq = 1.f;
+  if constexpr (BIAS) {
+    if (pr.bw) wq = pr.bw[q];
+    if (pr.oids) {  // uniform
+      for (int i = tid; i < P; i += 256) sid[i] = srow[i] >= 0 ? pr.oids[srow[i]] : INT64_MAX;
+      __syncthreads();
+      for (int i = tid; i < P; i += 256) {
+        const int64_t mine = sid[i];
+        int rk = 0;
+        for (int j = 0; j < P; ++j) {
+          const int64_t o = sid[j];
+          rk += (o < mine || (o == mine && j < i)) ? 1 : 0;
+        }
+        spos[i] = rk;  // a permutation of 0..P-1
+        sinv[rk] = i;
+      }
+      __syncthreads();
+    }
+  }
   const int ntile = (M + 31) / 32;
   for (int t = w; t < ntile; t += 4) {
     const int ar = srow[32 * t + r32];
@@ -3275,7 +3311,14 @@ __global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__
     if (r32 < 16) {
       const int e = 32 * t + 8 * (r32 >> 2) + 4 * hh + (r32 & 3);
       const int er = srow[e];
-      if (er >= 0) keys[e] = retr_key(mine, er);
+      if constexpr (BIAS) {
+        if (er >= 0) {
+          const float sc = pr.bias ? __builtin_fmaf(wq, pr.bias[er], mine) : mine;
+          keys[e] = retr_key(sc, pr.oids ? spos[e] : er);
+        }
+      } else {
+        if (er >= 0) keys[e] = retr_key(mine, er);
+      }
     }
   }
   __syncthreads();
@@ -3284,7 +3327,13 @@ __global__ __launch_bounds__(256) void retr_rescore_k(const bf16_t* __restrict__
   for (int i = tid; i < k; i += 256) {
     const u64 key = keys[i];
     scores[q * k + i] = key ? retr_key_score(key) : -INFINITY;
-    out_rows[q * k + i] = key ? retr_key_row(key) : -1;
+    if constexpr (BIAS) {
+      int r = key ? retr_key_row(key) : -1;
+      if (key && pr.oids) r = srow[sinv[r]];  // the key's low word is a rank below P
+      out_rows[q * k + i] = r;
+    } else {
+      out_rows[q * k + i] = key ? retr_key_row(key) : -1;
+    }
   }
 }
 
@@ -3392,11 +3441,16 @@ extern "C" int64_t lthm_retrieve_rescore_ws_bytes(int64_t Q, int32_t M, int32_t 
   return up256(Q * RT_D * 2);
 }
 
-extern "C" int lthm_retrieve_rescore(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q,
-                                     int64_t Q, const int32_t* rows, int32_t M, int32_t k, float* out_scores,
-                                     int32_t* out_rows, void* workspace, int64_t ws_bytes, void* stream) {
+// bias == NULL and order_ids == NULL is lthm_retrieve_rescore: retr_rescore_k<false>, as it always ran
+extern "C" int lthm_retrieve_rescore_bias(const void* items, int64_t N, const void* q, int32_t q_dtype,
+                                          int32_t normalize_q, int64_t Q, const int32_t* rows, int32_t M, int32_t k,
+                                          const float* bias, const float* weight, const int64_t* order_ids,
+                                          float* out_scores, int32_t* out_rows, void* workspace, int64_t ws_bytes,
+                                          void* stream) {
   LTHM_REQUIRE(items && q && rows && out_scores && out_rows && workspace);
   LTHM_REQUIRE(N >= 1 && N < (1ll << 31));
+  LTHM_REQUIRE(bias || !weight);
+  LTHM_REQUIRE(((uintptr_t)bias & 3) == 0 && ((uintptr_t)weight & 3) == 0 && ((uintptr_t)order_ids & 7) == 0);
   LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
   LTHM_REQUIRE(((uintptr_t)items & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
   LTHM_REQUIRE(((uintptr_t)rows & 3) == 0 && ((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_rows & 3) == 0);
@@ -3412,8 +3466,484 @@ extern "C" int lthm_retrieve_rescore(const void* items, int64_t N, const void* q
     hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn,
                        (const bf16_t*)items, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
   LTHM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(retr_rescore_k, dim3((unsigned)Q), dim3(256), 0, s, (const bf16_t*)items, N, (const bf16_t*)qn, rows,
-                     (int)M, (int)k, out_scores, out_rows);
+  if (bias || order_ids) {
+    const RetrRescorePrior pr = {bias, weight, order_ids};
+    hipLaunchKernelGGL((retr_rescore_k<true, RetrRescorePrior>), dim3((unsigned)Q), dim3(256), 0, s, (const bf16_t*)items,
+                       N, (const bf16_t*)qn, rows, (int)M, (int)k, out_scores, out_rows, pr);
+  } else {
+    hipLaunchKernelGGL(retr_rescore_k<false>, dim3((unsigned)Q), dim3(256), 0, s, (const bf16_t*)items, N,
+                       (const bf16_t*)qn, rows, (int)M, (int)k, out_scores, out_rows);
+  }
   LTHM_CHECK_LAUNCH();
   return 0;
 }
+
+extern "C" int lthm_retrieve_rescore(const void* items, int64_t N, const void* q, int32_t q_dtype, int32_t normalize_q,
+                                     int64_t Q, const int32_t* rows, int32_t M, int32_t k, float* out_scores,
+                                     int32_t* out_rows, void* workspace, int64_t ws_bytes, void* stream) {
+  return lthm_retrieve_rescore_bias(items, N, q, q_dtype, normalize_q, Q, rows, M, k, nullptr, nullptr, nullptr,
+                                    out_scores, out_rows, workspace, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- clustered e4m3 catalogues
+// lthm_retrieve_ivf_q8_topk: retr_ivf_deep_topk_k's work unit and selection (the block, its list, its
+// up to 64 pairs, the pairs' RD_CAP key slots in the workspace, the flagged bitonic prune, the final
+// sort into the layout retr_shard_merge_k reads) over retr_q8_topk_k's tile body (64 x 128 B images of
+// codes under its swizzle, the 64 row scales of tile i + 1 staged by wave 1, the codes of a fragment
+// to bf16 in registers, its eight MFMA steps in its k order, acc (scale_q scale_j)).  The tag words of
+// tile i + 1 ride with wave 0 as in retr_ivf_topk_k; the bias words with wave 2, since wave 1 carries
+// the scales.  Order per tile: the score, the partial-tile mask, the prior, exclusion, tags, then the
+// threshold and the appends: retr_ivf_deep_topk_k's order without a cursor.  A row at or past row_hi
+// reads the zero row, the zero scale, the zero tag and the zero bias: acc 0 * 0, then -inf by the
+// mask and fmaf(wq, 0, -inf) = -inf.  A tile starts at row_lo + 64 i, so a list that starts at any row
+// has whole 128-byte rows as DMA sources (16-byte aligned whatever row_lo is) and only its last tile
+// is partial.  The plan (retr_ivf_count_k / offsets / fill), the grid bound and the merge are the
+// bf16 clustered call's; retr_ivf_q8_rows_k then names every merged id's clustered row by a binary
+// search of the query's probed lists (ids ascend inside a list), for the re-scoring call.
+namespace lthm {
+namespace {
+
+struct RetrIvfQ8Shared {
+  unsigned char img[2][RT_IT * RQ_ROWB];
+  u64 sort[4][RD_CAP];  // one buffer per wave
+  float tau[RT_QT];
+  int cnt[RT_QT];
+  int pair[RT_QT];
+  int flag[3];
+  alignas(16) float scl[2][RT_IT];
+  alignas(16) int tag[2][RT_IT];
+  alignas(16) float bias[2][RT_IT];
+};
+static_assert(sizeof(RetrIvfQ8Shared) <= 96 * 1024, "LDS budget: the images, four sort buffers and change");
+
+struct RetrIvfQ8Args {
+  const unsigned char* codes;  // [N, 128] e4m3fn, list-major
+  const float* scale;          // [N]
+  const unsigned char* cq;     // [Q, 128] the queries' codes
+  const float* sq;             // [Q]
+  const int64_t* row_ids;      // [N]
+  const int64_t* list_off;     // [L + 1]
+  const int* tile_off;         // [L + 1]; tile_off[L]: the tiles there are
+  const int4* tab;             // per tile: list, first slot in pair_idx, pairs (1..64)
+  const int* pair_idx;         // [Q P] pairs grouped by list
+  const int* xs;               // [Q, xstride] ascending rows or null: no exclusion
+  const int* tags;             // TAGS: [N]
+  const int* filt;             // TAGS: [Q, 3]
+  const float* bias;           // [N] or null: no prior
+  const float* bw;             // [Q] or null: 1 for everyone
+  float* scores;               // [P, Q, k]
+  int64_t* ids;                // [P, Q, k]
+  u64* keys;                   // [Q P, RD_CAP]
+  int64_t Q, N;
+  int L, P, k, xstride;
+};
+
+template <bool TAGS>
+__global__ __launch_bounds__(256) void retr_ivf_q8_topk_k(RetrIvfQ8Args a) {
+  const int blk = blockIdx.x;
+  if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
+  __shared__ __attribute__((aligned(16))) RetrIvfQ8Shared sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
+  const int4 tt = a.tab[blk];
+  const int c = tt.x, pbase = tt.y, np = tt.z;
+  // the caller's offsets, kept inside the catalogue whatever they hold
+  int64_t row_lo = a.list_off[c], row_hi = a.list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > a.N ? a.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
+  const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
+  const int ql = 32 * (w & 1) + r32;
+  const bool live = ql < np;
+  const int pr = live ? a.pair_idx[pbase + ql] : 0;  // < Q P
+  const int64_t q = pr / a.P;
+  const bool hasb = a.bias != nullptr;  // uniform
+
+  if (tid < RT_QT) {
+    // a column without a pair never passes the filter
+    sh.tau[tid] = tid < np ? -INFINITY : INFINITY;
+    sh.cnt[tid] = 0;
+    sh.pair[tid] = tid < np ? a.pair_idx[pbase + tid] : 0;
+  }
+  if (tid < 3) sh.flag[tid] = 0;
+
+  bf16x8v qf[8];
+  float sq = 0.f;
+  {
+    const unsigned char* rp = a.cq + q * RQ_ROWB;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u32x4 lo = {0u, 0u, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+      if (live) {
+        lo = *reinterpret_cast<const u32x4*>(rp + 64 * s + 32 * hh);
+        hi = *reinterpret_cast<const u32x4*>(rp + 64 * s + 32 * hh + 16);
+      }
+      retr_q8_frags(lo, qf[4 * s], qf[4 * s + 1]);
+      retr_q8_frags(hi, qf[4 * s + 2], qf[4 * s + 3]);
+    }
+    if (live) sq = a.sq[q];
+  }
+  const int* xp = nullptr;
+  int nx = INT_MAX;  // no list, a column without a pair: excludes nothing and reads nothing
+  if (live && a.xs != nullptr) {
+    const int* xl = a.xs + q * a.xstride;
+    int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (xl[mid] < row_lo) lo = mid + 1;
+      else hi = mid;
+    }
+    xp = xl + lo;
+    nx = *xp;
+  }
+  int fm = 0, fw = 0, fy = 0;
+  int yz = 1;
+  if constexpr (TAGS) {
+    if (live) {
+      const int* fp = a.filt + q * 3;
+      const int fall = fp[0], fnone = fp[2];
+      fy = fp[1];
+      yz = fy == 0;
+      fm = (fall & fnone) ? 0 : (fall | fnone);
+      fw = (fall & fnone) ? 1 : fall;
+    }
+  }
+  float wq = 0.f;
+  if (live && hasb) wq = a.bw ? a.bw[q] : 1.f;
+  // the pair's key slots; a column without a pair never appends (its tau is +inf)
+  u64* const kbuf = a.keys + (int64_t)pr * RD_CAP;
+  int roff[4];
+#pragma unroll
+  for (int ch4 = 0; ch4 < 4; ++ch4) {
+    const int R = 32 * ih + r32, ch = 4 * (ch4 >> 1) + 2 * hh + (ch4 & 1);
+    roff[ch4] = R * RQ_ROWB + ((ch ^ ((R >> 1) & 7)) << 4);
+  }
+
+  // retr_q8_topk_k's staging: wave w stages rows 16 w .. 16 w + 15 of an image with two DMAs of 8
+  // rows x 128 B; rows at or past row_hi come from the zero row
+  const int srow = 16 * w + (lane >> 3), sch = (lane & 7) ^ (lane >> 4);
+  auto stage = [&](int t) {
+    unsigned char* img = sh.img[t & 1];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t row = row_lo + (int64_t)RT_IT * t + srow + 8 * j;
+      const void* src = row < row_hi ? (const void*)(a.codes + row * RQ_ROWB + ((sch ^ (4 * j)) << 4))
+                                     : (const void*)(retr_zero_row + 16 * (lane & 7));
+      glds16(src, img + (16 * w + 8 * j) * RQ_ROWB);
+    }
+    // lane l of one wave: the word of the image's row l; never a read at or past row_hi <= N
+    const int64_t wrow = row_lo + (int64_t)RT_IT * t + lane;
+    if (w == 1) glds4(wrow < row_hi ? a.scale + wrow : &retr_zero_bias, sh.scl[t & 1]);
+    if constexpr (TAGS) {
+      if (w == 0) glds4(wrow < row_hi ? a.tags + wrow : &retr_zero_tag, sh.tag[t & 1]);
+    }
+    if (hasb && w == 2) glds4(wrow < row_hi ? a.bias + wrow : &retr_zero_bias, sh.bias[t & 1]);
+  };
+  retire_loads();
+  if (ntile > 0) stage(0);
+  for (int i = 0; i < ntile; ++i) {
+    // the key stores of tile i - 1 count in vmcnt like the DMA: this wait retires both
+    wait_vm<0>();
+    __syncthreads();  // image i landed; every wave is past tile i - 1 (its image and its appends)
+    if (i + 1 < ntile) stage(i + 1);
+    if (tid == 0) sh.flag[(i + 1) % 3] = 0;
+    if (sh.flag[(i + 2) % 3]) {  // tile i - 1 pushed a pair past the limit
+      for (int pq = w; pq < np; pq += 4) {
+        int n = sh.cnt[pq];
+        if (n > RD_LIM) {
+          n = n < RD_CAP ? n : RD_CAP;
+          u64* g = a.keys + (int64_t)sh.pair[pq] * RD_CAP;
+          const int m = retr_deep_prune(g, sh.sort[w], n, a.k, false, lane);
+          if (lane == 0) {
+            sh.cnt[pq] = m;
+            if (m == a.k) sh.tau[pq] = retr_key_score(sh.sort[w][a.k - 1]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+    const unsigned char* img = sh.img[i & 1];
+    // the lane's rows are four runs of four consecutive words (broadcast reads): element 4 j + e is
+    // image row 32 ih + 4 hh + 8 j + e
+    float4 s4[4];
+    {
+      const float4* sp = reinterpret_cast<const float4*>(sh.scl[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s4[j] = sp[2 * j];
+    }
+    int4 t4[4];
+    if constexpr (TAGS) {
+      const int4* tp = reinterpret_cast<const int4*>(sh.tag[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t4[j] = tp[2 * j];
+    }
+    float4 b4[4] = {};
+    if (hasb) {
+      const float4* bp = reinterpret_cast<const float4*>(sh.bias[i & 1] + 32 * ih + 4 * hh);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b4[j] = bp[2 * j];
+    }
+    f32x16 acc = {};
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(img + roff[2 * s]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(img + roff[2 * s + 1]);
+      bf16x8v af[4];
+      retr_q8_frags(lo, af[0], af[1]);
+      retr_q8_frags(hi, af[2], af[3]);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc = mfma32(af[t], qf[4 * s + t], acc);
+    }
+    // the approximate score: acc (scale_q scale_j), two multiplies by powers of two
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float sj[4] = {s4[j].x, s4[j].y, s4[j].z, s4[j].w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[4 * j + e] = acc[4 * j + e] * (sq * sj[e]);
+    }
+    // first catalogue row of this lane's elements: element v is row rb + 8 (v >> 2) + (v & 3)
+    const int64_t rb = row_lo + (int64_t)RT_IT * i + 32 * ih + 4 * hh;
+    if (row_lo + (int64_t)RT_IT * (i + 1) > row_hi) {  // partial tile: the rows past the list never pass
+#pragma unroll
+      for (int v = 0; v < 16; ++v)
+        if (rb + 8 * (v >> 2) + (v & 3) >= row_hi) acc[v] = -INFINITY;
+    }
+    if (hasb) {
+      // the ranked score from here on; a row past the list is fmaf(wq, 0, -inf) = -inf
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float bw4[4] = {b4[j].x, b4[j].y, b4[j].z, b4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[4 * j + e] = __builtin_fmaf(wq, bw4[e], acc[4 * j + e]);
+      }
+    }
+    {
+      const int64_t tile_end = row_lo + (int64_t)RT_IT * (i + 1) < row_hi ? row_lo + (int64_t)RT_IT * (i + 1) : row_hi;
+      unsigned xm = 0u;
+      while (nx < tile_end) {
+        const int64_t xrel = (int64_t)nx - rb;
+        if (xrel >= 0 && xrel < 32 && !(xrel & 4)) xm |= 1u << (int)(((xrel >> 3) << 2) | (xrel & 3));
+        nx = *++xp;
+      }
+      if (xm) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          if ((xm >> v) & 1u) acc[v] = -INFINITY;
+      }
+    }
+    if constexpr (TAGS) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int tw[4] = {t4[j].x, t4[j].y, t4[j].z, t4[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool bad = ((tw[e] & fm) != fw) | (((tw[e] & fy) | yz) == 0);
+          acc[4 * j + e] = bad ? -INFINITY : acc[4 * j + e];
+        }
+      }
+    }
+    float mx = acc[0];
+#pragma unroll
+    for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
+    const float tau = sh.tau[ql];
+    if (mx >= tau) {
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const float s = acc[v];
+        if (s >= tau && s > -INFINITY) {
+          const int slot = atomicAdd(&sh.cnt[ql], 1);
+          if (live && slot < RD_CAP) kbuf[slot] = retr_key(s, (int)(rb + 8 * (v >> 2) + (v & 3)));
+          if (slot >= RD_LIM) sh.flag[i % 3] = 1;
+        }
+      }
+    }
+  }
+  wait_vm<0>();
+  __syncthreads();  // the last tile's appends have left their waves
+  // every pair's k best of the list, sorted, as (score, id); empty slots are (-inf, 0)
+  for (int pq = w; pq < np; pq += 4) {
+    int n = sh.cnt[pq];
+    n = n < RD_CAP ? n : RD_CAP;
+    const int pp = sh.pair[pq];
+    u64* buf = sh.sort[w];
+    int PS = 512;
+    while (PS < n) PS <<= 1;  // n <= RD_CAP
+    const u64* g = a.keys + (int64_t)pp * RD_CAP;
+    for (int idx = lane; idx < PS; idx += 64) buf[idx] = idx < n ? g[idx] : 0ull;
+    __builtin_amdgcn_wave_barrier();
+    if (n > 1) retr_deep_sort(buf, PS, lane);
+    const int m = n < a.k ? n : a.k;
+    const int64_t pq_q = pp / a.P, pq_s = pp - pq_q * a.P;
+    const int64_t o = (pq_s * a.Q + pq_q) * a.k;
+    for (int idx = lane; idx < a.k; idx += 64) {
+      const bool has = idx < m;
+      const u64 key = has ? buf[idx] : 0ull;  // idx < m <= PS
+      a.scores[o + idx] = has ? retr_key_score(key) : -INFINITY;
+      a.ids[o + idx] = has ? a.row_ids[retr_key_row(key)] : 0;
+    }
+    __builtin_amdgcn_wave_barrier();  // the buffer is read before the wave's next pair refills it
+  }
+}
+
+// One thread per merged entry (q, j): the clustered row of ids[q, j], found in one of the query's
+// probed lists (ids ascend inside a list: a lower bound over row_ids[row_lo, row_hi) on the scan's own
+// clamped offsets), -1 for an empty slot.  A merged entry came from a probed list, so it is found.
+__global__ __launch_bounds__(256) void retr_ivf_q8_rows_k(const float* __restrict__ scores, const int64_t* __restrict__ ids,
+                                                          const int* __restrict__ probes, int64_t Q, int P, int k, int L,
+                                                          int64_t N, const int64_t* __restrict__ list_off,
+                                                          const int64_t* __restrict__ row_ids, int* __restrict__ out_rows) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= Q * k) return;
+  const int64_t q = e / k;
+  int row = -1;
+  if (retr_image(scores[e]) > RS_EMPTY) {
+    const int64_t id = ids[e];
+    for (int s = 0; s < P && row < 0; ++s) {
+      const int c = probes[q * P + s];
+      if (c < 0 || c >= L) continue;
+      int64_t row_lo = list_off[c], row_hi = list_off[c + 1];
+      row_lo = row_lo < 0 ? 0 : row_lo > N ? N : row_lo;
+      row_hi = row_hi < row_lo ? row_lo : row_hi > N ? N : row_hi;
+      int64_t lo = row_lo, hi = row_hi;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (row_ids[mid] < id) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < row_hi && row_ids[lo] == id) row = (int)lo;
+    }
+  }
+  out_rows[e] = row;
+}
+
+// the deep clustered layout at k = M with the key slots whatever M is, then the queries' codes and
+// scales and the merged ids
+struct RetrIvfQ8Ws {
+  RetrIvfWs ivf;
+  int64_t cq, sq, mids, total;
+};
+bool retr_ivf_q8_ws(int64_t Q, int64_t N, int64_t L, int64_t P, int64_t M, int64_t X, RetrIvfQ8Ws* o) {
+  if (!retr_ivf_ws(Q, N, L, P, M, X, &o->ivf, false, true)) return false;
+  int64_t at = o->ivf.total;
+  o->cq = at, at += up256(Q * RQ_ROWB);
+  o->sq = at, at += up256(Q * 4);
+  o->mids = at, at += up256(Q * M * 8);
+  o->total = at;
+  return true;
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int64_t lthm_retrieve_ivf_q8_ws_bytes(int64_t Q, int64_t N, int64_t L, int32_t P, int32_t M, int64_t X) {
+  RetrIvfQ8Ws w;
+  return retr_ivf_q8_ws(Q, N, L, P, M, X, &w) ? w.total : -1;
+}
+
+extern "C" int lthm_retrieve_ivf_q8_topk(const uint8_t* codes, const float* scale, int64_t N, const int64_t* row_ids,
+                                         const int64_t* list_off, int64_t L, const void* q, int32_t q_dtype,
+                                         int32_t normalize_q, int64_t Q, const int32_t* probes, int32_t P, int32_t M,
+                                         const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
+                                         const lthm_retrieve_bias* b, float* out_scores, int32_t* out_rows,
+                                         void* workspace, int64_t ws_bytes, void* stream) {
+  LTHM_REQUIRE(codes && scale && row_ids && list_off && q && probes && out_scores && out_rows && workspace);
+  LTHM_REQUIRE(!t || (t->tags && t->filter && ((uintptr_t)t->tags & 3) == 0 && ((uintptr_t)t->filter & 3) == 0));
+  LTHM_REQUIRE(!b || (b->bias && ((uintptr_t)b->bias & 3) == 0 && ((uintptr_t)b->weight & 3) == 0));
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)codes & 15) == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+  LTHM_REQUIRE(((uintptr_t)scale & 3) == 0 && ((uintptr_t)row_ids & 7) == 0 && ((uintptr_t)list_off & 7) == 0 &&
+               ((uintptr_t)probes & 3) == 0);
+  LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_rows & 3) == 0);
+  LTHM_REQUIRE(!x || (x->rows && x->X >= 1 && x->X <= RT_XMAX && ((uintptr_t)x->rows & 3) == 0));
+  RetrIvfQ8Ws wq;
+  LTHM_REQUIRE(retr_ivf_q8_ws(Q, N, L, P, M, x ? x->X : 0, &wq) && ws_bytes >= wq.total);
+  const RetrIvfWs& wo = wq.ivf;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  bf16_t* qn = (bf16_t*)(ws + wo.qn);
+  int* cnt = (int*)(ws + wo.cnt);
+  int* fill = cnt + L;
+  int* pair_off = (int*)(ws + wo.off);
+  int* tile_off = pair_off + (L + 1);
+  int* pair_idx = (int*)(ws + wo.pidx);
+  int4* tab = (int4*)(ws + wo.tab);
+  float* lscores = (float*)(ws + wo.scores);
+  int64_t* lids = (int64_t*)(ws + wo.ids);
+  unsigned char* cq = ws + wq.cq;
+  float* sq = (float*)(ws + wq.sq);
+  int64_t* mids = (int64_t*)(ws + wq.mids);
+  const int64_t NP = Q * P;
+  // 1: the flat e4m3 call's queries: its prep, then the catalogue's quantiser on the bf16 rows
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  if (q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, s, (const bf16_t*)q, Q, normalize_q, qn,
+                       (const bf16_t*)nullptr, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, s, (const float*)q, Q, normalize_q, qn,
+                       (const bf16_t*)nullptr, N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_q8_quant_k, dim3(pgrid), dim3(256), 0, s, (const bf16_t*)qn, Q, cq, sq);
+  LTHM_CHECK_LAUNCH();
+  // 2: the clustered plan
+  {
+    const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(2 * L) * 4, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  const unsigned ngrid = (unsigned)((NP + 255) / 256);
+  hipLaunchKernelGGL(retr_ivf_count_k, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, (int)P, Q, (int)M, cnt, lscores,
+                     lids);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_offsets_k<false>, dim3(1), dim3(256), 0, s, cnt, (int)L, pair_off, tile_off, RT_QT);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_fill_k<false>, dim3(ngrid), dim3(256), 0, s, probes, NP, (int)L, cnt, pair_off, tile_off,
+                     fill, pair_idx, tab, RT_QT);
+  LTHM_CHECK_LAUNCH();
+  // 3: the scan
+  RetrIvfQ8Args a;
+  a.codes = codes;
+  a.scale = scale;
+  a.cq = cq;
+  a.sq = sq;
+  a.row_ids = row_ids;
+  a.list_off = list_off;
+  a.tile_off = tile_off;
+  a.tab = tab;
+  a.pair_idx = pair_idx;
+  a.xs = nullptr;
+  a.xstride = 0;
+  a.tags = t ? t->tags : nullptr;
+  a.filt = t ? t->filter : nullptr;
+  a.bias = b ? b->bias : nullptr;
+  a.bw = b ? b->weight : nullptr;
+  a.scores = lscores;
+  a.ids = lids;
+  a.keys = (u64*)(ws + wo.keys);
+  a.Q = Q;
+  a.N = N;
+  a.L = (int)L;
+  a.P = P;
+  a.k = M;
+  if (x) {
+    int* xs = (int*)(ws + wo.xs);
+    const int X = (int)x->X;
+    int XP = 1;
+    while (XP < X) XP <<= 1;
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)Q), dim3(256), 0, s, x->rows, X, XP, N, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = X + 1;
+  }
+  const dim3 grid((unsigned)wo.grid);
+  if (t) hipLaunchKernelGGL(retr_ivf_q8_topk_k<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(retr_ivf_q8_topk_k<false>, grid, dim3(256), 0, s, a);
+  LTHM_CHECK_LAUNCH();
+  // 4: the merge of every query's P lists, then the merged ids' rows
+  {
+    const int e = lthm_retrieve_merge_shards(lscores, lids, nullptr, P, Q, M, out_scores, mids, nullptr, stream);
+    if (e) return e;
+  }
+  hipLaunchKernelGGL(retr_ivf_q8_rows_k, dim3((unsigned)((Q * M + 255) / 256)), dim3(256), 0, s, (const float*)out_scores,
+                     (const int64_t*)mids, probes, Q, (int)P, (int)M, (int)L, N, list_off, row_ids, out_rows);
+  LTHM_CHECK_LAUNCH();
+  return 0;
+}
+

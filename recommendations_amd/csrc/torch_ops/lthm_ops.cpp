@@ -997,6 +997,173 @@ std::tuple<Tensor, Tensor> retrieve_rescore_cuda(const Tensor& q_, const Tensor&
   return {scores, out_rows};
 }
 
+// retrieve_rescore with a prior (bias f32 [N], bias_weight f32 [Q] or None: 1) and an id order
+// (order_ids int64 [N] or None): fma(w, bias[row], dot) under (score descending, order_ids[row] ascending)
+std::tuple<Tensor, Tensor> retrieve_rescore_bias_cuda(const Tensor& q_, const Tensor& items_, const Tensor& rows_, int64_t k,
+                                                      bool normalize_q, const c10::optional<Tensor>& bias_,
+                                                      const c10::optional<Tensor>& bias_weight_,
+                                                      const c10::optional<Tensor>& order_ids_) {
+  on_gpu(q_, "q");
+  on_gpu(items_, "items");
+  on_gpu(rows_, "rows");
+  TORCH_CHECK(items_.dim() == 2 && items_.size(1) == 128 && items_.scalar_type() == at::kBFloat16 && items_.size(0) >= 1,
+              "items must be a bf16 [N, 128] catalogue, N >= 1");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128 && q_.size(0) >= 1, "q must be [Q, 128], Q >= 1");
+  const int64_t Q = q_.size(0), N = items_.size(0);
+  TORCH_CHECK(rows_.dim() == 2 && rows_.scalar_type() == at::kInt && rows_.size(0) == Q, "rows must be int32 [Q, M]");
+  const int64_t M = rows_.size(1);
+  TORCH_CHECK(M >= 1 && M <= 1024, "retrieve_rescore_bias takes lists of 1..1024 rows (got M=", M, ")");
+  TORCH_CHECK(k >= 1 && k <= M, "retrieve_rescore_bias takes k in 1..M (got k=", k, ", M=", M, ")");
+  TORCH_CHECK(rows_.device() == q_.device() && items_.device() == q_.device(),
+              "rows and the catalogue must be on the queries' device");
+  const bool has_b = bias_.has_value() && bias_->defined(), has_w = bias_weight_.has_value() && bias_weight_->defined();
+  const bool has_o = order_ids_.has_value() && order_ids_->defined();
+  TORCH_CHECK(has_b || !has_w, "retrieve_rescore_bias takes a bias_weight only with a bias");
+  Tensor bias, bias_weight, order_ids;
+  if (has_b) {
+    on_gpu(*bias_, "bias");
+    TORCH_CHECK(bias_->scalar_type() == at::kFloat && bias_->dim() == 1 && bias_->size(0) == N &&
+                    bias_->device() == items_.device(),
+                "bias must be f32 [N] on the catalogue's device");
+    bias = bias_->contiguous();
+  }
+  if (has_w) {
+    on_gpu(*bias_weight_, "bias_weight");
+    TORCH_CHECK(bias_weight_->scalar_type() == at::kFloat && bias_weight_->dim() == 1 && bias_weight_->size(0) == Q &&
+                    bias_weight_->device() == q_.device(),
+                "bias_weight must be f32 [Q] on the queries' device");
+    bias_weight = bias_weight_->contiguous();
+  }
+  if (has_o) {
+    on_gpu(*order_ids_, "order_ids");
+    TORCH_CHECK(order_ids_->scalar_type() == at::kLong && order_ids_->dim() == 1 && order_ids_->size(0) == N &&
+                    order_ids_->device() == items_.device(),
+                "order_ids must be int64 [N] on the catalogue's device");
+    order_ids = order_ids_->contiguous();
+  }
+  const Tensor q = q_.contiguous(), items = items_.contiguous(), rows = rows_.contiguous();
+  const int64_t need = lthm_retrieve_rescore_ws_bytes(Q, (int32_t)M, (int32_t)k);
+  TORCH_CHECK(need >= 0, "retrieve_rescore_bias: unsupported sizes Q=", Q, " M=", M, " k=", k);
+  auto scores = at::empty({Q, k}, q.options().dtype(at::kFloat));
+  auto out_rows = at::empty({Q, k}, rows.options());
+  auto ws = at::empty({need}, rows.options().dtype(at::kByte));
+  hip_ok(lthm_retrieve_rescore_bias(items.data_ptr(), N, q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q,
+                                    rows.data_ptr<int32_t>(), (int32_t)M, (int32_t)k,
+                                    has_b ? bias.data_ptr<float>() : nullptr, has_w ? bias_weight.data_ptr<float>() : nullptr,
+                                    has_o ? order_ids.data_ptr<int64_t>() : nullptr, scores.data_ptr<float>(),
+                                    out_rows.data_ptr<int32_t>(), ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_rescore_bias");
+  return {scores, out_rows};
+}
+
+// The shortlist of a clustered e4m3 catalogue (lthm_retrieve_ivf_q8_topk): q f32 / bf16 [Q, 128], codes
+// uint8 [N, 128] and scale f32 [N] list-major, row_ids int64 [N], list_off int64 [L + 1], probes int32
+// [Q, P], pool in 1..1024, exclude_rows / tags / tag_filter / bias / bias_weight as retrieve_ivf_topk_deep
+// takes them -> (scores f32 [Q, pool], rows int32 [Q, pool]) under (score descending, id ascending),
+// padded with -inf / -1
+std::tuple<Tensor, Tensor> retrieve_ivf_q8_topk_cuda(
+    const Tensor& q_, const Tensor& codes_, const Tensor& scale_, const Tensor& row_ids_, const Tensor& list_off_,
+    const Tensor& probes_, int64_t pool, bool normalize_q, const c10::optional<Tensor>& exclude_rows,
+    const c10::optional<Tensor>& tags_, const c10::optional<Tensor>& tag_filter_, const c10::optional<Tensor>& bias_,
+    const c10::optional<Tensor>& bias_weight_) {
+  on_gpu(q_, "q");
+  on_gpu(codes_, "codes");
+  on_gpu(scale_, "scale");
+  on_gpu(row_ids_, "row_ids");
+  on_gpu(list_off_, "list_off");
+  on_gpu(probes_, "probes");
+  TORCH_CHECK(codes_.dim() == 2 && codes_.size(1) == 128 && codes_.scalar_type() == at::kByte && codes_.size(0) >= 1,
+              "codes must be uint8 [N, 128], N >= 1");
+  const int64_t N = codes_.size(0);
+  TORCH_CHECK(scale_.scalar_type() == at::kFloat && scale_.dim() == 1 && scale_.size(0) == N, "scale must be f32 [N]");
+  TORCH_CHECK(q_.dim() == 2 && q_.size(1) == 128 && q_.size(0) >= 1, "q must be [Q, 128], Q >= 1");
+  TORCH_CHECK(pool >= 1 && pool <= 1024, "retrieve_ivf_q8_topk takes a pool of 1..1024 rows (got ", pool, ")");
+  const int64_t Q = q_.size(0);
+  TORCH_CHECK(row_ids_.scalar_type() == at::kLong && row_ids_.dim() == 1 && row_ids_.size(0) == N,
+              "row_ids must be int64 [N], one id per catalogue row");
+  TORCH_CHECK(list_off_.scalar_type() == at::kLong && list_off_.dim() == 1 && list_off_.size(0) >= 2,
+              "list_off must be int64 [L + 1], L >= 1");
+  TORCH_CHECK(probes_.scalar_type() == at::kInt && probes_.dim() == 2 && probes_.size(0) == Q, "probes must be int32 [Q, P]");
+  TORCH_CHECK(probes_.size(1) >= 1 && probes_.size(1) <= 64, "retrieve_ivf_q8_topk takes 1..64 probes per query, got P=",
+              probes_.size(1));
+  TORCH_CHECK(scale_.device() == codes_.device() && row_ids_.device() == codes_.device() &&
+                  list_off_.device() == codes_.device() && probes_.device() == codes_.device() &&
+                  q_.device() == codes_.device(),
+              "q, scale, row_ids, list_off and probes must be on the catalogue's device");
+  const Tensor q = q_.contiguous(), codes = codes_.contiguous(), scale = scale_.contiguous();
+  const Tensor row_ids = row_ids_.contiguous(), list_off = list_off_.contiguous(), probes = probes_.contiguous();
+  const int64_t L = list_off.size(0) - 1, P = probes.size(1);
+  Tensor xr;
+  const bool excl = exclude_rows.has_value() && exclude_rows->defined();
+  if (excl) {
+    on_gpu(*exclude_rows, "exclude_rows");
+    TORCH_CHECK(exclude_rows->scalar_type() == at::kInt && exclude_rows->dim() == 2 && exclude_rows->size(0) == Q,
+                "exclude_rows must be int32 [Q, X]");
+    TORCH_CHECK(exclude_rows->size(1) >= 1 && exclude_rows->size(1) <= 1024,
+                "exclude_rows takes 1..1024 rows per query, got ", exclude_rows->size(1));
+    TORCH_CHECK(exclude_rows->device() == q.device(), "exclude_rows must be on the queries' device");
+    xr = exclude_rows->contiguous();
+  }
+  const bool has_tags = tags_.has_value() && tags_->defined(), has_filter = tag_filter_.has_value() && tag_filter_->defined();
+  TORCH_CHECK(has_tags == has_filter, "retrieve_ivf_q8_topk takes tags and tag_filter together or neither");
+  const bool has_b = bias_.has_value() && bias_->defined(), has_w = bias_weight_.has_value() && bias_weight_->defined();
+  TORCH_CHECK(has_b || !has_w, "retrieve_ivf_q8_topk takes a bias_weight only with a bias");
+  Tensor tags, tag_filter, bias, bias_weight;
+  if (has_tags) {
+    on_gpu(*tags_, "tags");
+    on_gpu(*tag_filter_, "tag_filter");
+    TORCH_CHECK(tags_->scalar_type() == at::kInt && tags_->dim() == 1 && tags_->size(0) == N &&
+                    tags_->device() == codes.device(),
+                "tags must be int32 [N] on the catalogue's device");
+    TORCH_CHECK(tag_filter_->scalar_type() == at::kInt && tag_filter_->dim() == 2 && tag_filter_->size(0) == Q &&
+                    tag_filter_->size(1) == 3 && tag_filter_->device() == q.device(),
+                "tag_filter must be int32 [Q, 3] on the queries' device");
+    tags = tags_->contiguous();
+    tag_filter = tag_filter_->contiguous();
+  }
+  if (has_b) {
+    on_gpu(*bias_, "bias");
+    TORCH_CHECK(bias_->scalar_type() == at::kFloat && bias_->dim() == 1 && bias_->size(0) == N &&
+                    bias_->device() == codes.device(),
+                "bias must be f32 [N] on the catalogue's device");
+    bias = bias_->contiguous();
+    if (has_w) {
+      on_gpu(*bias_weight_, "bias_weight");
+      TORCH_CHECK(bias_weight_->scalar_type() == at::kFloat && bias_weight_->dim() == 1 && bias_weight_->size(0) == Q &&
+                      bias_weight_->device() == q.device(),
+                  "bias_weight must be f32 [Q] on the queries' device");
+      bias_weight = bias_weight_->contiguous();
+    }
+  }
+  const int64_t need = lthm_retrieve_ivf_q8_ws_bytes(Q, N, L, (int32_t)P, (int32_t)pool, excl ? xr.size(1) : 0);
+  TORCH_CHECK(need >= 0, "retrieve_ivf_q8_topk: unsupported sizes Q=", Q, " N=", N, " L=", L, " P=", P);
+  auto scores = at::empty({Q, pool}, q.options().dtype(at::kFloat));
+  auto rows = at::empty({Q, pool}, q.options().dtype(at::kInt));
+  auto ws = at::empty({need}, q.options().dtype(at::kByte));
+  lthm_retrieve_excl x = {};
+  if (excl) {
+    x.rows = xr.data_ptr<int32_t>();
+    x.X = xr.size(1);
+  }
+  lthm_retrieve_tags t = {};
+  if (has_tags) {
+    t.tags = tags.data_ptr<int32_t>();
+    t.filter = tag_filter.data_ptr<int32_t>();
+  }
+  lthm_retrieve_bias b = {};
+  if (has_b) {
+    b.bias = bias.data_ptr<float>();
+    b.weight = has_w ? bias_weight.data_ptr<float>() : nullptr;
+  }
+  hip_ok(lthm_retrieve_ivf_q8_topk(codes.data_ptr<uint8_t>(), scale.data_ptr<float>(), N, row_ids.data_ptr<int64_t>(),
+                                   list_off.data_ptr<int64_t>(), L, q.data_ptr(), dcode(q), normalize_q ? 1 : 0, Q,
+                                   probes.data_ptr<int32_t>(), (int32_t)P, (int32_t)pool, excl ? &x : nullptr,
+                                   has_tags ? &t : nullptr, has_b ? &b : nullptr, scores.data_ptr<float>(),
+                                   rows.data_ptr<int32_t>(), ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_ivf_q8_topk");
+  return {scores, rows};
+}
+
 int64_t abi_version() { return lthm_abi_version(); }
 // the include/lthm.h this op library was compiled against (descriptor layouts)
 int64_t built_abi_version() { return LTHM_ABI_VERSION; }
@@ -1059,6 +1226,13 @@ TORCH_LIBRARY(lthm, m) {
       "retrieve_q8_topk(Tensor q, Tensor codes, Tensor scale, int pool, bool normalize_q, Tensor? exclude_rows=None) -> "
       "(Tensor scores, Tensor rows)");
   m.def("retrieve_rescore(Tensor q, Tensor items, Tensor rows, int k, bool normalize_q) -> (Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_rescore_bias(Tensor q, Tensor items, Tensor rows, int k, bool normalize_q, Tensor? bias=None, "
+      "Tensor? bias_weight=None, Tensor? order_ids=None) -> (Tensor scores, Tensor rows)");
+  m.def(
+      "retrieve_ivf_q8_topk(Tensor q, Tensor codes, Tensor scale, Tensor row_ids, Tensor list_off, Tensor probes, "
+      "int pool, bool normalize_q, Tensor? exclude_rows=None, Tensor? tags=None, Tensor? tag_filter=None, "
+      "Tensor? bias=None, Tensor? bias_weight=None) -> (Tensor scores, Tensor rows)");
 }
 
 TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
@@ -1084,6 +1258,8 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("quantize_catalogue_q8", &quantize_catalogue_q8_cuda);
   m.impl("retrieve_q8_topk", &retrieve_q8_topk_cuda);
   m.impl("retrieve_rescore", &retrieve_rescore_cuda);
+  m.impl("retrieve_rescore_bias", &retrieve_rescore_bias_cuda);
+  m.impl("retrieve_ivf_q8_topk", &retrieve_ivf_q8_topk_cuda);
 }
 
 TORCH_LIBRARY_IMPL(lthm, Autograd, m) {

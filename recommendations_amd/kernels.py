@@ -2491,3 +2491,131 @@ def retrieve_rescore(q, items, rows, k: int, *, normalize_q: bool = True):
          ptr(scores), ptr(out_rows), ptr(ws), need, stream(), _key="retr_rescore_k",
          _work=2.0 * Q * M * RETRIEVE_WIDTH, _unit="flop")
     return scores, out_rows
+
+
+def retrieve_rescore_bias(q, items, rows, k: int, *, normalize_q: bool = True, bias=None, bias_weight=None, order_ids=None):
+    """retrieve_rescore with a prior and an id order (lthm_retrieve_rescore_bias, csrc/retrieve.hip
+    retr_rescore_k<true>): a listed row's score is fma(w[q], bias[row], dot), dot the bits retrieve_rescore
+    returns, one explicit f32 fma as retrieve_topk does with a bias.
+
+    bias f32 [N] or None; bias_weight None (1 for everyone), a number or f32 [Q], only with a bias;
+    order_ids int64 [N] or None: with it the list comes out under (score descending, order_ids[row]
+    ascending), the order of the clustered calls, whose rows do not ascend with their ids across lists.
+    With neither a bias nor order_ids the call is retrieve_rescore, bit for bit.  Returns (scores f32
+    [Q, k], rows int32 [Q, k]), padded with -inf / -1."""
+    who = "retrieve_rescore_bias"
+    require_gpu(q, items, rows, bias, order_ids)
+    _check(items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and items.dtype == torch.bfloat16,
+           f"{who} takes a bf16 [N, {RETRIEVE_WIDTH}] catalogue (got {items.dtype} {tuple(items.shape)})")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries")
+    Q, N, k = q.shape[0], items.shape[0], int(k)
+    _check(rows.dim() == 2 and rows.dtype == torch.int32 and rows.shape[0] == Q,
+           f"{who} takes int32 rows [Q, M] (got {rows.dtype} {tuple(rows.shape)}, Q={Q})")
+    M = rows.shape[1]
+    _check(1 <= M <= RETRIEVE_Q8_MAX_POOL, f"{who} takes lists of 1..{RETRIEVE_Q8_MAX_POOL} rows (got M={M})")
+    _check(1 <= k <= M, f"{who} takes k in 1..M (got k={k}, M={M})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    _check(rows.is_contiguous(), "rows must be contiguous")
+    dev = q.device
+    _check(rows.device == dev and items.device == dev, "rows and the catalogue must be on the queries' device")
+    b, bw = _retrieve_bias(who, bias, bias_weight, items, Q, "Q", dev)
+    if order_ids is not None:
+        _check(order_ids.dtype == torch.int64 and tuple(order_ids.shape) == (N,) and order_ids.is_contiguous(),
+               f"order_ids must be contiguous int64 [N] (got {order_ids.dtype} {tuple(order_ids.shape)}, N={N})")
+        _check(order_ids.device == items.device, "order_ids must be on the catalogue's device")
+    need = load().lthm_retrieve_rescore_ws_bytes(Q, M, k)
+    _check(need >= 0, f"{who}: no workspace size for Q={Q} M={M} k={k}")
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    call("lthm_retrieve_rescore_bias", ptr(items), N, ptr(q), dcode(q), int(bool(normalize_q)), Q, ptr(rows), M, k,
+         ptr(bias), ptr(bw), ptr(order_ids), ptr(scores), ptr(out_rows), ptr(ws), need, stream(),
+         _key="retr_rescore_bias_k", _work=2.0 * Q * M * RETRIEVE_WIDTH, _unit="flop")
+    return scores, out_rows
+
+
+def retrieve_ivf_q8_topk(q, codes, scale, row_ids, list_off, probes, pool: int, *, normalize_q: bool = True,
+                         exclude_rows=None, tags=None, tag_filter=None, bias=None, bias_weight=None):
+    """The shortlist of a clustered e4m3 catalogue: per query the `pool` first rows of the lists it probes
+    under (approximate score descending, id ascending) (lthm_retrieve_ivf_q8_topk, csrc/retrieve.hip
+    retr_ivf_q8_topk_k).
+
+    q f32 / bf16 [Q, 128]; codes uint8 [N, 128] and scale f32 [N], quantize_catalogue_q8 of the
+    list-major rows; row_ids int64 [N], list_off int64 [L + 1] and probes int32 [Q, P] as retrieve_ivf_topk
+    takes them; pool in 1..1024.  The score of (query, row) is retrieve_q8_topk's, bit for bit; with a
+    bias f32 [N] the ranked score is fma(w[q], bias[row], score) (bias_weight None, a number or f32 [Q]).
+    exclude_rows int32 [Q, X] (clustered rows) and tags int32 [N] / tag_filter int32 [Q, 3] follow
+    retrieve_ivf_topk: an ineligible row takes no slot.  Returns (scores f32 [Q, pool], rows int32
+    [Q, pool]), the clustered rows, padded with -inf / -1; a pure function of the inputs.  Every (query,
+    probe) pair holds 16 KiB of candidates in the workspace, so where one call would take more than
+    RETRIEVE_IVF_DEEP_WS_BYTES the queries go through in consecutive chunks, each one call: a query's
+    list does not depend on the other queries."""
+    import ctypes
+    from ._lib import STRUCTS
+    who = "retrieve_ivf_q8_topk"
+    require_gpu(q, codes, scale, row_ids, list_off, probes, exclude_rows, tags, tag_filter, bias)
+    _check(codes.dim() == 2 and codes.shape[1] == RETRIEVE_WIDTH and codes.dtype == torch.uint8,
+           f"{who} takes uint8 [N, {RETRIEVE_WIDTH}] codes (got {codes.dtype} {tuple(codes.shape)})")
+    N = codes.shape[0]
+    _check(scale.dtype == torch.float32 and tuple(scale.shape) == (N,),
+           f"{who} takes f32 [N] scales (got {scale.dtype} {tuple(scale.shape)}, N={N})")
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH, f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    Q, M = q.shape[0], int(pool)
+    _check(1 <= M <= RETRIEVE_Q8_MAX_POOL, f"{who} takes a pool of 1..{RETRIEVE_Q8_MAX_POOL} rows (got {M})")
+    _check(N >= 1 and Q >= 1, f"{who} takes a non-empty catalogue and at least one query (N={N}, Q={Q})")
+    _check(row_ids.dtype == torch.int64 and tuple(row_ids.shape) == (N,),
+           f"row_ids must be int64 [N], one id per catalogue row (got {row_ids.dtype} {tuple(row_ids.shape)}, N={N})")
+    _check(list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.shape[0] >= 2,
+           f"list_off must be int64 [L + 1], L >= 1 (got {list_off.dtype} {tuple(list_off.shape)})")
+    L = list_off.shape[0] - 1
+    _check(probes.dtype == torch.int32 and probes.dim() == 2 and probes.shape[0] == Q,
+           f"probes must be int32 [Q, P] (got {probes.dtype} {tuple(probes.shape)}, Q={Q})")
+    P = probes.shape[1]
+    _check(1 <= P <= RETRIEVE_MAX_PROBE, f"{who} takes 1..{RETRIEVE_MAX_PROBE} probes per query (got P={P})")
+    _check(codes.is_contiguous() and scale.is_contiguous() and row_ids.is_contiguous() and list_off.is_contiguous()
+           and probes.is_contiguous(), "codes, scale, row_ids, list_off and probes must be contiguous")
+    dev = q.device
+    _check(all(t.device == dev for t in (codes, scale, row_ids, list_off, probes)),
+           "codes, scale, row_ids, list_off and probes must be on the queries' device")
+    X = 0
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 2 and exclude_rows.shape[0] == Q,
+               f"exclude_rows must be int32 [Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, Q={Q})")
+        X = exclude_rows.shape[1]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
+        _check(exclude_rows.is_contiguous(), "exclude_rows must be contiguous")
+        _check(exclude_rows.device == dev, "exclude_rows must be on the queries' device")
+    _retrieve_tags(who, tags, tag_filter, codes, Q, "Q")
+    _, bw = _retrieve_bias(who, bias, bias_weight, codes, Q, "Q", dev)
+    size = lambda n: load().lthm_retrieve_ivf_q8_ws_bytes(n, N, L, P, M, X)
+    _check(size(Q) >= 0, f"{who}: no workspace size for Q={Q} N={N} L={L} P={P} pool={M} X={X} (Q P must stay below 2^31)")
+    step = Q
+    if size(Q) > RETRIEVE_IVF_DEEP_WS_BYTES:
+        lo, hi = 1, Q  # the size ascends with the queries: the most queries that fit, by bisection
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if size(mid) <= RETRIEVE_IVF_DEEP_WS_BYTES else (lo, mid - 1)
+        step = lo
+    q = q.contiguous()
+    scores = torch.empty((Q, M), dtype=torch.float32, device=dev)
+    rows = torch.empty((Q, M), dtype=torch.int32, device=dev)
+    ws = torch.empty(size(step), dtype=torch.uint8, device=dev)
+    for q0 in range(0, Q, step):
+        n = min(step, Q - q0)
+        cut = lambda v: None if v is None else v[q0:q0 + n]  # a contiguous tensor's leading rows are contiguous
+        x = t = b = None
+        if exclude_rows is not None:
+            x = STRUCTS["lthm_retrieve_excl"]()
+            x.rows, x.X = ptr(cut(exclude_rows)), X
+        if tags is not None:
+            t = STRUCTS["lthm_retrieve_tags"]()
+            t.tags, t.filter = ptr(tags), ptr(cut(tag_filter))
+        if bias is not None:
+            b = STRUCTS["lthm_retrieve_bias"]()
+            b.bias, b.weight = ptr(bias), (ptr(cut(bw)) if bw is not None else None)
+        parts = [ctypes.addressof(o) if o is not None else None for o in (x, t, b)]
+        work = float(n * RETRIEVE_WIDTH * q.element_size() + 24.0 * P * n * M + 12.0 * n * M + 4.0 * n * (P + X))
+        call("lthm_retrieve_ivf_q8_topk", ptr(codes), ptr(scale), N, ptr(row_ids), ptr(list_off), L, ptr(cut(q)), dcode(q),
+             int(bool(normalize_q)), n, ptr(cut(probes)), P, M, *parts, ptr(cut(scores)), ptr(cut(rows)), ptr(ws),
+             ws.numel(), stream(), _key="retr_ivf_q8_topk_k", _work=work, _unit="byte")
+    return scores, rows

@@ -41,6 +41,11 @@ lists with the catalogue's tags and bias and behind a (score, id) cursor, under 
 conventions.  Its ``with_heads()`` view is that view for users with several queries each (``q``
 [U, G, 128], ``K.retrieve_ivf_topk_group``): one probe row per user, an item scored by its best match
 over the user's queries inside the scan, one slot per item.
+
+Clustered e4m3: ``ClusteredItemCatalogue.quantize`` gives a ``QuantizedClusteredItemCatalogue``, the same lists
+as e4m3 codes with the catalogue's tags and bias: its ``topk`` scans the probed lists' codes for a shortlist of
+the eligible rows (``K.retrieve_ivf_q8_topk``) and re-scores it with the exact rows and the prior
+(``K.retrieve_rescore_bias``), which is the ``with_filters()`` / ``with_deep()`` list restricted to the shortlist.
 """
 from __future__ import annotations
 
@@ -817,6 +822,15 @@ class ClusteredItemCatalogue:
         hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
         return float((hit / real.sum(dim=1).clamp(min=1).double()).mean())
 
+    def quantize(self, keep_exact: bool = True) -> "QuantizedClusteredItemCatalogue":
+        """This catalogue as e4m3 codes with one power-of-two scale per row, in the same lists
+        (``K.quantize_catalogue_q8`` of the clustered rows, on the catalogue's device), with its tags and
+        bias, and with ``keep_exact`` the bf16 rows beside the codes for re-scoring: see
+        ``QuantizedClusteredItemCatalogue``.  Groups are not carried."""
+        codes, scale = K.quantize_catalogue_q8(self.emb)
+        return QuantizedClusteredItemCatalogue(self.row_ids, codes, scale, self.list_off, self.centroids, self.tags,
+                                               self.bias, self.emb if keep_exact else None)
+
     def save(self, path: str) -> None:
         """The flat catalogue's file (``ItemCatalogue.load`` reads it as the id-sorted catalogue) with
         ``row_ids``, ``list_off`` and ``centroids`` beside its tensors."""
@@ -1075,6 +1089,247 @@ class GroupedClusteredItemCatalogue(FilteredClusteredItemCatalogue):
         if q.shape[1] == 1:
             return K.retrieve_ivf_topk(q[:, 0].contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
         return K.retrieve_ivf_topk_group(q.contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
+
+
+IVF_Q8_INDEX = "lthm-ivf-q8-v1"
+
+
+class QuantizedClusteredItemCatalogue:
+    """``ClusteredItemCatalogue.quantize()``: the clustered catalogue stored as OCP e4m3fn codes, small and
+    cheap to query at once, and still able to filter.
+
+    ``row_ids`` int64 [N] in the clustered (list, id) order, ``list_off`` int64 [L + 1] and ``centroids``
+    bf16 [L, 128] as the source has them; ``codes`` uint8 [N, 128] and ``scale`` f32 [N],
+    ``K.quantize_catalogue_q8`` of the clustered rows; ``tags`` int32 [N] / ``bias`` f32 [N] in the rows'
+    order or None; ``emb`` bf16 [N, 128], the exact rows, or None.  The centroids stay bf16 and ``probe`` is
+    the bf16 catalogue's, so a query scans exactly the lists it scans there.  ``topk`` scans the probed
+    lists' codes for a shortlist of the eligible rows (``K.retrieve_ivf_q8_topk``) and, where the exact
+    rows are kept, re-scores the shortlist in bf16 with the prior (``K.retrieve_rescore_bias``): the
+    result is the ``with_filters()`` / ``with_deep()`` list with the same arguments restricted to the
+    shortlist, so it equals that list whenever the shortlist holds its first k.  One query per row;
+    cursors, heads, diversification and target ranks are not offered here."""
+
+    def __init__(self, row_ids: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, list_off: torch.Tensor,
+                 centroids: torch.Tensor, tags: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                 emb: Optional[torch.Tensor] = None):
+        if row_ids.dtype != torch.int64 or row_ids.dim() != 1 or row_ids.shape[0] < 1:
+            raise ValueError(f"clustered row_ids must be int64 [N], N >= 1 (got {row_ids.dtype} {tuple(row_ids.shape)})")
+        N = row_ids.shape[0]
+        if codes.dtype != torch.uint8 or tuple(codes.shape) != (N, WIDTH):
+            raise ValueError(f"catalogue codes must be uint8 [N, {WIDTH}] (got {codes.dtype} {tuple(codes.shape)}, N={N})")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != (N,):
+            raise ValueError(f"catalogue scales must be f32 [N] (got {scale.dtype} {tuple(scale.shape)}, N={N})")
+        if emb is not None and (emb.dtype != torch.bfloat16 or tuple(emb.shape) != (N, WIDTH)):
+            raise ValueError(f"clustered embeddings must be bf16 [N, {WIDTH}] (got {emb.dtype} {tuple(emb.shape)}, N={N})")
+        if centroids.dim() != 2 or centroids.shape[1] != WIDTH or centroids.shape[0] < 1:
+            raise ValueError(f"centroids must be [L, {WIDTH}], L >= 1 (got {tuple(centroids.shape)})")
+        if centroids.dtype != torch.bfloat16:
+            raise ValueError(f"centroids must be bf16, as the catalogue's rows are (got {centroids.dtype})")
+        L = centroids.shape[0]
+        if list_off.dtype != torch.int64 or tuple(list_off.shape) != (L + 1,):
+            raise ValueError(f"list_off must be int64 [L + 1] (got {list_off.dtype} {tuple(list_off.shape)}, L={L})")
+        dev = codes.device
+        if any(t.device != dev for t in (row_ids, scale, list_off, centroids)) or (emb is not None and emb.device != dev):
+            raise ValueError("a clustered catalogue's tensors must live on one device")
+        if int(list_off[0]) != 0 or int(list_off[-1]) != N or bool((list_off[1:] < list_off[:-1]).any()):
+            raise ValueError("list_off must ascend from 0 to N")
+        ids, order = torch.sort(row_ids)
+        if bool((ids == 0).any()):
+            raise ValueError("catalogue ids must not hold 0, the pad id")
+        if N > 1 and bool((ids[1:] == ids[:-1]).any()):
+            raise ValueError("catalogue ids must be distinct")
+        if N > 1:
+            inside = torch.ones(N - 1, dtype=torch.bool, device=dev)  # row i and row i + 1 share a list
+            cut = list_off[1:-1]
+            cut = cut[(cut > 0) & (cut < N)]
+            inside[cut - 1] = False
+            if bool((inside & (row_ids[1:] <= row_ids[:-1])).any()):
+                raise ValueError("the ids of a list must ascend")
+        for t, name, dt in ((tags, "tags", torch.int32), (bias, "bias", torch.float32)):
+            if t is not None and (t.dtype != dt or tuple(t.shape) != (N,) or t.device != dev):
+                raise ValueError(f"clustered {name} must be {dt} [N] on the catalogue's device "
+                                 f"(got {t.dtype} {tuple(t.shape)})")
+        self.row_ids = row_ids.contiguous()
+        self.codes = codes.contiguous()
+        self.scale = scale.contiguous()
+        self.list_off = list_off.contiguous()
+        self.centroids = centroids.contiguous()
+        self.tags = None if tags is None else tags.contiguous()
+        self.bias = None if bias is None else bias.contiguous()
+        self.emb = None if emb is None else emb.contiguous()
+        self._ids = ids.contiguous()      # ascending
+        self._order = order.contiguous()  # the clustered row of every id of _ids
+        self._exact = None                # the bf16 with_deep() view, for recall
+
+    def __len__(self) -> int:
+        return self.row_ids.shape[0]
+
+    @property
+    def nlist(self) -> int:
+        return self.centroids.shape[0]
+
+    @property
+    def has_tags(self) -> bool:
+        return self.tags is not None
+
+    @property
+    def has_bias(self) -> bool:
+        return self.bias is not None
+
+    @property
+    def keep_exact(self) -> bool:
+        return self.emb is not None
+
+    def list_lengths(self) -> torch.Tensor:
+        """int64 [L]: the rows of every list."""
+        return self.list_off[1:] - self.list_off[:-1]
+
+    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
+        """The clustered row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
+        flat = ids.reshape(-1).to(self._ids.device)
+        at = torch.searchsorted(self._ids, flat).clamp_(max=len(self) - 1)
+        rows = torch.where(self._ids[at] == flat, self._order[at], torch.full_like(at, -1))
+        return rows.to(torch.int32).view(ids.shape)
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of ``ids``: the catalogue holds this id."""
+        return self.rows_of(ids) >= 0
+
+    def to(self, device) -> "QuantizedClusteredItemCatalogue":
+        on = lambda t: None if t is None else t.to(device)
+        return QuantizedClusteredItemCatalogue(self.row_ids.to(device), self.codes.to(device), self.scale.to(device),
+                                               self.list_off.to(device), self.centroids.to(device), on(self.tags),
+                                               on(self.bias), on(self.emb))
+
+    def to_clustered(self) -> ClusteredItemCatalogue:
+        """The bf16 clustered catalogue over the same lists, tags and bias; needs ``keep_exact``."""
+        if self.emb is None:
+            raise ValueError("to_flat needs the exact rows: this catalogue was built with keep_exact=False")
+        return ClusteredItemCatalogue(self.row_ids, self.emb, self.list_off, self.centroids, self.tags, self.bias)
+
+    def to_flat(self) -> ItemCatalogue:
+        """The exact id-sorted ``ItemCatalogue`` of the same items, with tags and bias; needs ``keep_exact``."""
+        return self.to_clustered().to_flat()
+
+    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
+        """``ItemCatalogue.filter_like``: per target t the row (tags[t] & mask, 0, ~tags[t] & mask) of an
+        int32 [Q, 3] filter, (0, 0, 0) for a target the catalogue does not hold."""
+        if self.tags is None:
+            raise ValueError("filter_like needs a catalogue with tags")
+        if target_ids.dim() != 1:
+            raise ValueError("filter_like takes target ids [Q]")
+        rows = self.rows_of(target_ids).long()
+        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
+        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
+        m = torch.where(rows >= 0, m, torch.zeros_like(m))
+        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+
+    @staticmethod
+    def default_shortlist(k: int) -> int:
+        return QuantizedItemCatalogue.default_shortlist(k)
+
+    _MAX_K = K.RETRIEVE_Q8_MAX_POOL
+    _check_call = ClusteredItemCatalogue._check_call
+    probe = ClusteredItemCatalogue.probe
+
+    def _check_filters(self, q, exclude_ids, tag_filter, bias_weight) -> None:
+        if tag_filter is not None and self.tags is None:
+            raise ValueError("tag_filter given, but this catalogue carries no tags")
+        if bias_weight is not None and self.bias is None:
+            raise ValueError("bias_weight given, but this catalogue carries no bias")
+        if q.dim() != 2:
+            raise ValueError(f"a quantised catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        Q = q.shape[0]
+        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
+            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+        if tag_filter is not None and (tag_filter.dtype != torch.int32 or tuple(tag_filter.shape) != (Q, 3)):
+            raise ValueError(f"tag_filter must be int32 [Q, 3] = (all, any, none) "
+                             f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, Q={Q})")
+        if isinstance(bias_weight, torch.Tensor):
+            if bias_weight.dtype != torch.float32 or tuple(bias_weight.shape) != (Q,):
+                raise ValueError(f"bias_weight must be None, a number or f32 [Q] "
+                                 f"(got {bias_weight.dtype} {tuple(bias_weight.shape)}, Q={Q})")
+        elif bias_weight is not None and (isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float))):
+            raise ValueError(f"bias_weight must be None, a number or f32 [Q] (got {type(bias_weight).__name__})")
+
+    def topk(self, q: torch.Tensor, k: int, *, nprobe: int, shortlist: Optional[int] = None, rescore: bool = True,
+             normalize_q: bool = True, exclude_ids: Optional[torch.Tensor] = None,
+             tag_filter: Optional[torch.Tensor] = None,
+             bias_weight: Union[None, float, torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(item_ids int64 [Q, k], scores f32 [Q, k]), empty slots (0, -inf), as ``QuantizedItemCatalogue.topk``
+        returns them.  Stage one: of the rows that lie in the query's ``nprobe`` nearest lists, are not among
+        its ``exclude_ids`` (int64 [Q, X], X <= 1024) and pass its ``tag_filter`` (int32 [Q, 3]), the
+        ``shortlist`` first (default min(max(4 k, 128), 1024); in k..1024) under the approximate e4m3 score,
+        which a catalogue that carries a ``bias`` ranks as fma(w, bias[j], s^) (``bias_weight`` = w: None for
+        1, a number or f32 [Q]; a catalogue without a bias refuses a weight).  Stage two (``rescore=True``,
+        needs ``keep_exact``): those rows get the exact score fma(w, bias[j], q . e_j), with the bits
+        ``ClusteredItemCatalogue.with_filters()`` / ``with_deep()`` return, and the k first under (score
+        descending, id ascending) are returned.  ``rescore=False`` returns the first k of the shortlist
+        with the approximate scores.  ``k`` in 1..1024, ``q`` [Q, 128]."""
+        k, nprobe = self._check_call(k, nprobe)
+        M = self.default_shortlist(k) if shortlist is None else int(shortlist)
+        if not k <= M <= K.RETRIEVE_Q8_MAX_POOL:
+            raise ValueError(f"shortlist must lie in k..{K.RETRIEVE_Q8_MAX_POOL} (got shortlist={M}, k={k})")
+        if rescore and self.emb is None:
+            raise ValueError("rescore=True needs the exact rows: this catalogue was built with keep_exact=False "
+                             "(pass rescore=False)")
+        self._check_filters(q, exclude_ids, tag_filter, bias_weight)
+        xr = None if exclude_ids is None else self.rows_of(exclude_ids).contiguous()
+        probes = self.probe(q, nprobe, normalize_q=normalize_q)
+        scores, rows = K.retrieve_ivf_q8_topk(q, self.codes, self.scale, self.row_ids, self.list_off, probes, M,
+                                              normalize_q=normalize_q, exclude_rows=xr,
+                                              tags=self.tags if tag_filter is not None else None,
+                                              tag_filter=None if tag_filter is None else tag_filter.contiguous(),
+                                              bias=self.bias, bias_weight=bias_weight)
+        if rescore:
+            scores, rows = K.retrieve_rescore_bias(q, self.emb, rows, k, normalize_q=normalize_q, bias=self.bias,
+                                                   bias_weight=bias_weight, order_ids=self.row_ids)
+        else:
+            scores, rows = scores[:, :k].contiguous(), rows[:, :k].contiguous()
+        item_ids = torch.where(rows >= 0, self.row_ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+        return item_ids, scores
+
+    def recall(self, q: torch.Tensor, k: int, nprobe: int, shortlist: Optional[int] = None, **filters) -> float:
+        """The mean over the queries of the fraction of the bf16 clustered list's ids (``with_deep()`` with
+        the same ``nprobe`` and ``filters``: ``exclude_ids``, ``tag_filter``, ``bias_weight``) that
+        ``topk(q, k, nprobe=nprobe, shortlist=shortlist, **filters)`` returns, over the queries whose bf16
+        list is not empty (1.0 where every one is); needs ``keep_exact``."""
+        if self._exact is None:
+            self._exact = self.to_clustered().with_deep()
+        want = self._exact.topk(q, k, nprobe=nprobe, **filters)[1]
+        got = self.topk(q, k, nprobe=nprobe, shortlist=shortlist, **filters)[0]
+        real = want != 0
+        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
+        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
+                         for i in range(0, want.shape[0], rows)]).double()
+        n = real.sum(dim=1)
+        if not bool((n > 0).any()):
+            return 1.0
+        return float((hit[n > 0] / n[n > 0].double()).mean())
+
+    def save(self, path: str) -> None:
+        """safetensors with the catalogue's tensors under their names (``emb`` where the exact rows are kept),
+        all in the clustered order, and the format tag of this kind of catalogue."""
+        from safetensors.torch import save_file
+        tensors = {"row_ids": self.row_ids, "codes": self.codes, "scale": self.scale, "list_off": self.list_off,
+                   "centroids": self.centroids}
+        for name in ("tags", "bias", "emb"):
+            if getattr(self, name) is not None:
+                tensors[name] = getattr(self, name)
+        save_file({n: t.detach().cpu().contiguous() for n, t in tensors.items()}, path,
+                  metadata={"format": FORMAT, "index": IVF_Q8_INDEX})
+
+    @classmethod
+    def load(cls, path: str, *, device=None) -> "QuantizedClusteredItemCatalogue":
+        from safetensors import safe_open
+        with safe_open(path, framework="pt") as f:
+            meta = f.metadata() or {}
+            if meta.get("format") != FORMAT or meta.get("index") != IVF_Q8_INDEX:
+                raise ValueError(f"{path}: not a quantised clustered item catalogue (metadata {json.dumps(meta)})")
+            opt = lambda n: f.get_tensor(n) if n in f.keys() else None
+            cat = cls(f.get_tensor("row_ids"), f.get_tensor("codes"), f.get_tensor("scale"), f.get_tensor("list_off"),
+                      f.get_tensor("centroids"), opt("tags"), opt("bias"), opt("emb"))
+        return cat.to(device) if device is not None else cat
 
 
 class ShardedItemCatalogue:

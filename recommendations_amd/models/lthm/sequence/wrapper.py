@@ -351,7 +351,7 @@ class LTHMModelWrapper(BaseModelWrapper):
                  tag_all=None, tag_any=None, tag_none=None, after=None,
                  bias_weight=None, nprobe: Optional[int] = None, diversity: Optional[float] = None,
                  pool: Optional[int] = None, group_cap: Optional[int] = None,
-                 shortlist: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                 shortlist: Optional[int] = None, exclude_seen: bool = False) -> Dict[str, torch.Tensor]:
         """The k best catalogue items for each sequence's next event (build-defined; see
         retrieval.py): the query is ``next_token_emb[:, -1, head]``, the prediction after the
         most recent token.  Returns ``item_ids`` int64 [B, k] (0 in empty slots) and ``scores``
@@ -400,10 +400,56 @@ class LTHMModelWrapper(BaseModelWrapper):
         min(max(4 k, 128), 1024); k..1024): the e4m3 scan's ``shortlist`` best rows are re-scored with the
         exact rows and the k best returned (k <= 1024), the flat list wherever the shortlist holds it;
         ``exclude_history`` composes, every other argument above is refused by name.  Any other
-        catalogue refuses ``shortlist``."""
-        from .retrieval import ClusteredItemCatalogue, ItemCatalogue, QuantizedItemCatalogue
+        catalogue refuses ``shortlist``.
+        A ``QuantizedClusteredItemCatalogue`` (``ClusteredItemCatalogue.quantize``) takes ``nprobe`` together
+        with ``shortlist``, and ``tag_all`` / ``tag_any`` / ``tag_none``, ``bias_weight`` and ``exclude_history``
+        with the meaning they have on a ``with_filters()`` view: the e4m3 scan of the probed lists gives the
+        ``shortlist`` best eligible rows, which are re-scored with the exact rows and the prior (k <= 1024), the
+        ``with_deep()`` list wherever the shortlist holds it.  ``heads``, ``after`` and ``diversity`` / ``pool`` /
+        ``group_cap`` are refused by name.  ``exclude_seen`` is ``catalogue_metrics``' name for
+        ``exclude_history`` and means the same here, for every catalogue."""
+        from .retrieval import (ClusteredItemCatalogue, ItemCatalogue, QuantizedClusteredItemCatalogue,
+                                QuantizedItemCatalogue)
+        exclude_history = bool(exclude_history) or bool(exclude_seen)
         clustered = isinstance(catalogue, ClusteredItemCatalogue)
         quantized = isinstance(catalogue, QuantizedItemCatalogue)
+        if isinstance(catalogue, QuantizedClusteredItemCatalogue):
+            given = {"heads": heads, "after": after, "diversity": diversity, "pool": pool, "group_cap": group_cap}
+            bad = [name for name, v in given.items() if v is not None]
+            if bad:
+                raise ValueError(f"retrieve with a quantised clustered catalogue does not take {', '.join(bad)}: "
+                                 "use catalogue.to_clustered() for it")
+            if nprobe is None:
+                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
+            catalogue._check_call(k, nprobe)
+            if shortlist is not None and (isinstance(shortlist, bool) or not isinstance(shortlist, int)
+                                          or not int(k) <= shortlist <= K.RETRIEVE_Q8_MAX_POOL):
+                raise ValueError(f"shortlist takes k..{K.RETRIEVE_Q8_MAX_POOL} rows (got shortlist={shortlist!r}, k={k})")
+            if bias_weight is not None and not catalogue.has_bias:
+                raise ValueError("bias_weight given, but this catalogue carries no bias")
+            filt = None
+            if tag_all is not None or tag_any is not None or tag_none is not None:
+                if not catalogue.has_tags:
+                    raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
+            out = self.forward(batch)
+            q = out["next_token_emb"][:, -1, head].contiguous()
+            if q.dtype not in (torch.float32, torch.bfloat16):
+                q = q.float()
+            seen = None
+            if exclude_history:
+                seen = out["current_token_ids"]
+                if seen.shape[1] > K.RETRIEVE_MAX_EXCLUDE:
+                    raise ValueError(f"exclude_history takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens "
+                                     f"(T = {seen.shape[1]})")
+            if tag_all is not None or tag_any is not None or tag_none is not None:
+                from .retrieval import make_tag_filter
+                filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
+                                       0 if tag_none is None else tag_none, device=q.device)
+            if isinstance(bias_weight, torch.Tensor):
+                bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
+            item_ids, scores = catalogue.topk(q, k, nprobe=nprobe, shortlist=shortlist, rescore=catalogue.keep_exact,
+                                              normalize_q=True, exclude_ids=seen, tag_filter=filt, bias_weight=bias_weight)
+            return {"item_ids": item_ids, "scores": scores}
         if quantized:
             given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
                      "bias_weight": bias_weight, "nprobe": nprobe, "diversity": diversity, "pool": pool,
@@ -548,9 +594,12 @@ class LTHMModelWrapper(BaseModelWrapper):
         included, is fma(bias_weight, bias[j], q . e_j): the hit position under the prior.  The
         keys then take the suffix ``_biased``, after ``_unseen`` / ``_tagged``.  Without it the
         metrics are those of the plain dot, whether or not the catalogue carries a bias."""
-        from .retrieval import ClusteredItemCatalogue
+        from .retrieval import ClusteredItemCatalogue, QuantizedClusteredItemCatalogue
         if isinstance(catalogue, ClusteredItemCatalogue):
             raise ValueError("catalogue_metrics counts exact ranks, which take the flat scan: pass catalogue.to_flat()")
+        if isinstance(catalogue, QuantizedClusteredItemCatalogue):
+            raise ValueError("catalogue_metrics does not take a quantised clustered catalogue: it counts exact ranks, "
+                             "which take the flat scan (pass catalogue.to_flat())")
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])
