@@ -1223,6 +1223,50 @@ int lthm_retrieve_ivf_topk_deep(const void* items, int64_t N, const int64_t* row
                                 const lthm_retrieve_tags* t, const lthm_retrieve_bias* b,
                                 const lthm_retrieve_ivf_cursor* c, float* out_scores, int64_t* out_ids,
                                 void* workspace, int64_t ws_bytes, void* stream);
+/* lthm_retrieve_ivf_topk_shards: S clustered catalogues on one device (1 <= S <= 64), each with tensors,
+ * centroids and a number of lists of its own and with ids no other shard holds, answer one batch of
+ * queries in one call.  Shard s probes its P_s = min(nprobe, L_s) nearest lists per query (the probe row
+ * lthm_retrieve_topk gives over its centroids: ties go to the lower list); sum_s P_s <= 64.  The result
+ * is the k first, under (score descending, id ascending), of the rows of all probed lists that are
+ * eligible under lthm_retrieve_ivf_topk_deep's rules, then (-inf, 0): bit for bit what S calls of
+ * lthm_retrieve_ivf_topk_deep (one per shard, with that shard's probe row) followed by
+ * lthm_retrieve_merge_shards return, from one plan, one scan launch and one merge.  1 <= k <= 1024.
+ *   shards        host array [S]; items bf16 [N, 128] list-major, row_ids int64 [N], list_off int64
+ *                 [L + 1], centroids bf16 [L, 128], tags int32 [N] / bias f32 [N] in the rows' order or
+ *                 NULL, all device pointers
+ *   exclude_rows  int32 [S, Q, X] (X in 1..1024) or NULL with X = 0: the excluded rows of every query in
+ *                 every shard's own numbering, entries outside [0, N_s) ignored
+ *   tag_filter    int32 [Q, 3] or NULL; with it every shard must carry tags
+ *   use_bias      != 0: every shard must carry a bias, and the score is fmaf(w[q], bias[row], dot) with
+ *                 bias_weight f32 [Q] or NULL (1 for every query); 0: the plain dot, bias_weight NULL
+ *   c             the (score, id) cursor of every query, or NULL
+ *   target_rows   int32 [S, Q], target_score f32 [Q] and out_rank int64 [Q], all three or none: the row
+ *                 of every query's target in every shard (-1: not there) and the target's score (from
+ *                 lthm_retrieve_target_score on the shard that holds it; NaN: no shard does).  out_rank
+ *                 is the number of eligible rows of the probed lists, other than the target's, that score
+ *                 strictly above target_score (0 for a NaN score: the caller knows no shard holds it)
+ *   workspace     lthm_retrieve_ivf_shards_ws_bytes(shards, S, Q, nprobe, k, X, has_cursor) bytes, 256-byte
+ *                 aligned; -1 for sizes the call refuses (sum_s P_s > 64 among them)
+ * Every pointer, alignment, range and workspace check is made before any launch; nothing synchronises
+ * with the host and the outputs are a pure function of the inputs. */
+typedef struct lthm_retrieve_ivf_shard {
+  const void* items;
+  const int64_t* row_ids;
+  const int64_t* list_off;
+  const void* centroids;
+  const int32_t* tags;
+  const float* bias;
+  int64_t N;
+  int64_t L;
+} lthm_retrieve_ivf_shard;
+int64_t lthm_retrieve_ivf_shards_ws_bytes(const lthm_retrieve_ivf_shard* shards, int32_t S, int64_t Q, int32_t nprobe,
+                                          int32_t k, int64_t X, int32_t has_cursor);
+int lthm_retrieve_ivf_topk_shards(const lthm_retrieve_ivf_shard* shards, int32_t S, const void* q, int32_t q_dtype,
+                                  int32_t normalize_q, int64_t Q, int32_t nprobe, int32_t k,
+                                  const int32_t* exclude_rows, int64_t X, const int32_t* tag_filter, int32_t use_bias,
+                                  const float* bias_weight, const lthm_retrieve_ivf_cursor* c,
+                                  const int32_t* target_rows, const float* target_score, float* out_scores,
+                                  int64_t* out_ids, int64_t* out_rank, void* workspace, int64_t ws_bytes, void* stream);
 /* Diversified lists: greedy maximal-marginal-relevance (MMR) selection of k out of a pool of M
  * candidates per query, with an optional cap on the selected items of one group.  The pool is a list
  * any of the calls above returned (lthm_retrieve_topk_deep gives up to 1,024 rows in one scan).

@@ -1903,6 +1903,116 @@ __global__ __launch_bounds__(256) void retr_ivf_cursor_k(const int* __restrict__
   crow[p] = (int)(lo - 1);  // row_lo - 1 >= -1 and row_hi - 1 < N < 2^31
 }
 
+// Shards (lthm_retrieve_ivf_topk_shards): S clustered catalogues with tensors of their own are scanned
+// as one catalogue whose lists are the shards' lists side by side: shard s owns the lists lbase[s] ..
+// lbase[s] + L_s of the plan and the probe slots pbase[s] .. pbase[s] + P_s of every query.  The plan
+// kernels see only list numbers, so they run unchanged; a scan block looks its tile's shard up from
+// the list number (at most six steps over the descriptors) and reads that shard's tensors.
+struct RetrIvfShardDev {
+  const bf16_t* items;      // [N, 128], list-major
+  const int64_t* row_ids;   // [N]
+  const int64_t* list_off;  // [L + 1]
+  const int* tags;          // [N] or null
+  const float* bias;        // [N] or null
+  int64_t N;
+  int lbase;                // the shard's first list in the plan's numbering
+};
+// retr_ivf_topk_k<true, true, TAGS, BIAS, false, true> and retr_ivf_deep_topk_k<TAGS, true>: L counts all
+// lists and P all probe slots, xs is [S, Q, xstride] (the excluded rows in every shard's own numbering),
+// items, row_ids, list_off, N, tags and bias are unused: the descriptors hold them.
+// Targets (rank != null): tsc [Q] is every query's target score (NaN: no shard holds the target), trow
+// [S, Q] the target's row in every shard (-1: not there), and rank [P, Q], zeroed by the caller, receives
+// per pair the rows of its list that pass every mask, are not the target's and score strictly above tsc:
+// integer adds of per-lane counts, so the sums are a pure function of the inputs.
+struct RetrIvfShardArgs : RetrIvfFiltArgs {
+  u64* keys;                  // deep: [Q P, RD_CAP]
+  const RetrIvfShardDev* sh;  // [S], lbase ascending from 0
+  const float* tsc;
+  const int* trow;
+  int* rank;
+  int S;
+};
+
+// the last shard whose first list is at or below c (0 <= c < L)
+__device__ __forceinline__ int retr_ivf_shard_of(const RetrIvfShardDev* sh, int S, int c) {
+  int lo = 0, hi = S - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (sh[mid].lbase <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// what a scan block reads of its catalogue: the arguments' own tensors, or with SH those of the shard
+// that owns list c, which becomes the list's number inside the shard
+struct RetrIvfView {
+  const bf16_t* items;
+  const int64_t* row_ids;
+  const int64_t* list_off;
+  const int* tags;
+  const float* bias;
+  const int* xs;
+  int64_t N;
+  int shard;  // SH: the shard of the tile, else 0
+};
+template <bool SH, class A>
+__device__ __forceinline__ RetrIvfView retr_ivf_view(const A& a, int& c) {
+  RetrIvfView cv;
+  if constexpr (SH) {
+    const int s = retr_ivf_shard_of(a.sh, a.S, c);
+    const RetrIvfShardDev d = a.sh[s];
+    c -= d.lbase;
+    cv.shard = s;
+    cv.items = d.items, cv.row_ids = d.row_ids, cv.list_off = d.list_off, cv.tags = d.tags, cv.bias = d.bias, cv.N = d.N;
+    cv.xs = a.xs ? a.xs + (int64_t)s * a.Q * a.xstride : nullptr;
+  } else {
+    cv.items = a.items, cv.row_ids = a.row_ids, cv.list_off = a.list_off, cv.N = a.N, cv.xs = a.xs;
+    cv.tags = nullptr, cv.bias = nullptr, cv.shard = 0;
+    if constexpr (std::is_base_of_v<RetrIvfFiltArgs, A>) cv.tags = a.tags, cv.bias = a.bias;
+  }
+  return cv;
+}
+
+// retr_ivf_cursor_k over shards: pair p = q P + slot probes list c of the plan, which is list c - lbase
+// of the shard that owns it; the bound runs over that shard's row_ids
+__global__ __launch_bounds__(256) void retr_ivf_cursor_shards_k(const int* __restrict__ probes, int64_t NP, int L, int P,
+                                                                const RetrIvfShardDev* __restrict__ sh, int S,
+                                                                const int64_t* __restrict__ after_ids,
+                                                                int* __restrict__ crow) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= NP) return;
+  const int c = probes[p];
+  if (c < 0 || c >= L) {
+    crow[p] = -1;
+    return;
+  }
+  const RetrIvfShardDev d = sh[retr_ivf_shard_of(sh, S, c)];
+  int64_t row_lo = d.list_off[c - d.lbase], row_hi = d.list_off[c - d.lbase + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > d.N ? d.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > d.N ? d.N : row_hi;
+  const int64_t aid = after_ids[p / P];
+  int64_t lo = row_lo, hi = row_hi;  // the first row of [row_lo, row_hi) whose id is above aid
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (d.row_ids[mid] <= aid) lo = mid + 1;
+    else hi = mid;
+  }
+  crow[p] = (int)(lo - 1);
+}
+
+// the probe slots of shard s, for every query: probes[q, pbase + j] = lbase + rows[q, j], the shard's
+// probe row (retr_topk_k over its centroids) in the plan's list numbering; -1 stays -1
+__global__ __launch_bounds__(256) void retr_ivf_probe_pack_k(const int* __restrict__ rows, int64_t Q, int Ps, int lbase,
+                                                             int pbase, int P, int* __restrict__ probes) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= Q * Ps) return;
+  const int64_t q = i / Ps;
+  const int j = (int)(i - q * Ps);
+  const int r = rows[i];
+  probes[q * P + pbase + j] = r >= 0 ? lbase + r : -1;
+}
+
 // Wave w: columns 32 (w & 1) + (lane & 31) of the tile (one pair each, so every per-pair value is a
 // per-lane scalar), image rows 32 (w >> 1) + 8 (v >> 2) + 4 (lane >> 5) + (v & 3), as in retr_topk_k.
 // EXCL: the lane walks its query's sorted list of excluded rows (the clustered numbering) from the
@@ -1928,10 +2038,11 @@ __global__ __launch_bounds__(256) void retr_ivf_cursor_k(const int* __restrict__
 // alone has a list cursor, a filter, a weight, a cursor, a threshold and a candidate buffer (its own
 // column's), so everything from the prior on sees one score per (user, row) and a row takes one slot
 // however many of the user's queries it matches.  Every other lane keeps tau = +inf and never appends.
-template <bool EXCL, bool FILT = false, bool TAGS = false, bool BIAS = false, bool GRP = false>
-__global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP> a) {
+template <bool EXCL, bool FILT = false, bool TAGS = false, bool BIAS = false, bool GRP = false, bool SH = false>
+__global__ __launch_bounds__(256) void retr_ivf_topk_k(std::conditional_t<SH, RetrIvfShardArgs, RetrIvfScanArgs<FILT, GRP>> a) {
   static_assert(FILT ? EXCL : !(TAGS || BIAS), "tags, prior and cursor ride on the excluding instantiation");
   static_assert(!GRP || FILT, "groups ride on the filtering instantiations");
+  static_assert(!SH || (FILT && !GRP), "shards ride on the filtering instantiations, one query per pair");
   const int blk = blockIdx.x;
   if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
   using RetrIvfSharedFilt = std::conditional_t<TAGS, RetrIvfSharedTags, RetrIvfShared>;
@@ -1939,11 +2050,13 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
   const int4 tt = a.tab[blk];
-  const int c = tt.x, pbase = tt.y, np = tt.z;
+  const int pbase = tt.y, np = tt.z;
+  int c = tt.x;
+  const RetrIvfView cv = retr_ivf_view<SH>(a, c);  // SH: the tile's shard, c its list there
   // the caller's offsets, kept inside the catalogue whatever they hold
-  int64_t row_lo = a.list_off[c], row_hi = a.list_off[c + 1];
-  row_lo = row_lo < 0 ? 0 : row_lo > a.N ? a.N : row_lo;
-  row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
+  int64_t row_lo = cv.list_off[c], row_hi = cv.list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > cv.N ? cv.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > cv.N ? cv.N : row_hi;
   const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
   const int ql = 32 * (w & 1) + r32;
   // column ql serves the tile's pair pl (live), as its query gq; lead: the pair's first column
@@ -1959,6 +2072,15 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
   }
   const bool lead = GRP ? (live && gq == 0) : live;
   const int64_t q = live ? a.pair_idx[pbase + pl] / a.P : 0;
+  // SH with targets: the lane counts the rows of its elements that stand above the query's target
+  float tsq = NAN;
+  int trq = -1, nabove = 0;
+  if constexpr (SH) {
+    if (a.rank != nullptr && lead) {
+      tsq = a.tsc[q];
+      trq = a.trow[(int64_t)cv.shard * a.Q + q];
+    }
+  }
 
   if (tid < RT_QT) {
     // a column without a pair never passes the filter, nor does one that is not its pair's first
@@ -1989,8 +2111,8 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
   const int* xp = nullptr;
   int nx = INT_MAX;  // a column without a pair excludes nothing and reads nothing
   if constexpr (EXCL) {
-    if (lead && (!FILT || a.xs != nullptr)) {
-      const int* xl = a.xs + q * a.xstride;
+    if (lead && (!FILT || cv.xs != nullptr)) {
+      const int* xl = cv.xs + q * a.xstride;
       int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo: lower_bound in at most 11 steps
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -2032,7 +2154,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
   // retr_topk_k's staging: wave w brings rows 16 w .. 16 w + 15 of an image with four DMAs of
   // 4 rows x 256 B; rows at or past row_hi come from the zero row
   const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
-  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(cv.items);
   auto stage = [&](int t) {
     unsigned char* img = sh.img[t & 1];
 #pragma unroll
@@ -2046,14 +2168,14 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
       // wave 0, lane l: the tag of the image's row l; never a read at or past row_hi <= N
       if (w == 0) {
         const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
-        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+        glds4(row < row_hi ? cv.tags + row : &retr_zero_tag, sh.tag[t & 1]);
       }
     }
     if constexpr (BIAS) {
       // wave 1, lane l: the bias of the image's row l; never a read at or past row_hi <= N
       if (w == 1) {
         const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
-        glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
+        glds4(row < row_hi ? cv.bias + row : &retr_zero_bias, sh.bias[t & 1]);
       }
     }
   };
@@ -2159,6 +2281,13 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
         }
       }
     }
+    if constexpr (SH) {
+      if (a.rank != nullptr) {  // uniform; a NaN target score counts nothing, a masked row is -inf
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          nabove += (acc[v] > tsq) & (rb + 8 * (v >> 2) + (v & 3) != (int64_t)trq);
+      }
+    }
     float mx = acc[0];
 #pragma unroll
     for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
@@ -2175,6 +2304,12 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
       }
     }
   }
+  if constexpr (SH) {
+    if (a.rank != nullptr && lead && nabove) {
+      const int pr = a.pair_idx[pbase + pl];
+      atomicAdd(&a.rank[(int64_t)(pr - q * a.P) * a.Q + q], nabove);
+    }
+  }
   __syncthreads();
   // every pair's k best of the list, sorted, as (score, id); empty slots are (-inf, 0)
   for (int pi = w; pi < np; pi += 4) {
@@ -2187,7 +2322,7 @@ __global__ __launch_bounds__(256) void retr_ivf_topk_k(RetrIvfScanArgs<FILT, GRP
       const bool has = idx < m;
       const u64 key = has ? sh.cand[pq][idx] : 0ull;
       a.scores[o + idx] = has ? retr_key_score(key) : -INFINITY;
-      a.ids[o + idx] = has ? a.row_ids[retr_key_row(key)] : 0;
+      a.ids[o + idx] = has ? cv.row_ids[retr_key_row(key)] : 0;
     }
   }
 }
@@ -2224,25 +2359,36 @@ struct RetrIvfDeepArgs : RetrIvfFiltArgs {
   u64* keys;  // [Q P, RD_CAP]: the candidates of every pair
 };
 
-template <bool TAGS>
-__global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
+template <bool TAGS, bool SH = false>
+__global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(std::conditional_t<SH, RetrIvfShardArgs, RetrIvfDeepArgs> a) {
   const int blk = blockIdx.x;
   if (blk >= a.tile_off[a.L]) return;  // past the tiles there are: before LDS and the DMA
   __shared__ __attribute__((aligned(16))) RetrIvfDeepShared sh;
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, hh = lane >> 5, ih = w >> 1;
   const int4 tt = a.tab[blk];
-  const int c = tt.x, pbase = tt.y, np = tt.z;
+  const int pbase = tt.y, np = tt.z;
+  int c = tt.x;
+  const RetrIvfView cv = retr_ivf_view<SH>(a, c);  // SH: the tile's shard, c its list there
   // the caller's offsets, kept inside the catalogue whatever they hold
-  int64_t row_lo = a.list_off[c], row_hi = a.list_off[c + 1];
-  row_lo = row_lo < 0 ? 0 : row_lo > a.N ? a.N : row_lo;
-  row_hi = row_hi < row_lo ? row_lo : row_hi > a.N ? a.N : row_hi;
+  int64_t row_lo = cv.list_off[c], row_hi = cv.list_off[c + 1];
+  row_lo = row_lo < 0 ? 0 : row_lo > cv.N ? cv.N : row_lo;
+  row_hi = row_hi < row_lo ? row_lo : row_hi > cv.N ? cv.N : row_hi;
   const int ntile = (int)((row_hi - row_lo + RT_IT - 1) / RT_IT);
   const int ql = 32 * (w & 1) + r32;
   const bool live = ql < np;
   const int pr = live ? a.pair_idx[pbase + ql] : 0;  // < Q P
   const int64_t q = pr / a.P;
-  const bool hasb = a.bias != nullptr;  // uniform
+  const bool hasb = cv.bias != nullptr;  // uniform
+  // SH with targets: the lane counts the rows of its elements that stand above the query's target
+  float tsq = NAN;
+  int trq = -1, nabove = 0;
+  if constexpr (SH) {
+    if (a.rank != nullptr && live) {
+      tsq = a.tsc[q];
+      trq = a.trow[(int64_t)cv.shard * a.Q + q];
+    }
+  }
 
   if (tid < RT_QT) {
     // a column without a pair never passes the filter
@@ -2264,8 +2410,8 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
   }
   const int* xp = nullptr;
   int nx = INT_MAX;  // no list, a column without a pair: excludes nothing and reads nothing
-  if (live && a.xs != nullptr) {
-    const int* xl = a.xs + q * a.xstride;
+  if (live && cv.xs != nullptr) {
+    const int* xl = cv.xs + q * a.xstride;
     int lo = 0, hi = a.xstride - 1;  // xl[hi] = INT_MAX >= row_lo
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
@@ -2302,7 +2448,7 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
   for (int s = 0; s < 8; ++s) roff[s] = ih * 8192 + ko32(r32, 2 * s + hh);
 
   const int srow = 16 * w + (lane >> 4), sch = (lane & 15) ^ (((lane >> 4) & 3) << 2);
-  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(a.items);
+  const unsigned char* ibase = reinterpret_cast<const unsigned char*>(cv.items);
   auto stage = [&](int t) {
     unsigned char* img = sh.img[t & 1];
 #pragma unroll
@@ -2315,12 +2461,12 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
     if constexpr (TAGS) {
       if (w == 0) {  // never a read at or past row_hi <= N
         const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
-        glds4(row < row_hi ? a.tags + row : &retr_zero_tag, sh.tag[t & 1]);
+        glds4(row < row_hi ? cv.tags + row : &retr_zero_tag, sh.tag[t & 1]);
       }
     }
     if (hasb && w == 1) {
       const int64_t row = row_lo + (int64_t)RT_IT * t + lane;
-      glds4(row < row_hi ? a.bias + row : &retr_zero_bias, sh.bias[t & 1]);
+      glds4(row < row_hi ? cv.bias + row : &retr_zero_bias, sh.bias[t & 1]);
     }
   };
   retire_loads();
@@ -2420,6 +2566,13 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
         }
       }
     }
+    if constexpr (SH) {
+      if (a.rank != nullptr) {  // uniform; a NaN target score counts nothing, a masked row is -inf
+#pragma unroll
+        for (int v = 0; v < 16; ++v)
+          nabove += (acc[v] > tsq) & (rb + 8 * (v >> 2) + (v & 3) != (int64_t)trq);
+      }
+    }
     float mx = acc[0];
 #pragma unroll
     for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
@@ -2435,6 +2588,9 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
         }
       }
     }
+  }
+  if constexpr (SH) {
+    if (a.rank != nullptr && live && nabove) atomicAdd(&a.rank[(int64_t)(pr - q * a.P) * a.Q + q], nabove);
   }
   wait_vm<0>();
   __syncthreads();  // the last tile's appends have left their waves
@@ -2457,7 +2613,7 @@ __global__ __launch_bounds__(256) void retr_ivf_deep_topk_k(RetrIvfDeepArgs a) {
       const bool has = idx < m;
       const u64 key = has ? buf[idx] : 0ull;  // idx < m <= PS
       a.scores[o + idx] = has ? retr_key_score(key) : -INFINITY;
-      a.ids[o + idx] = has ? a.row_ids[retr_key_row(key)] : 0;
+      a.ids[o + idx] = has ? cv.row_ids[retr_key_row(key)] : 0;
     }
     __builtin_amdgcn_wave_barrier();  // the buffer is read before the wave's next pair refills it
   }
@@ -2732,6 +2888,257 @@ extern "C" int lthm_retrieve_ivf_topk_deep(const void* items, int64_t N, const i
                                            void* stream) {
   return retr_ivf_call(items, N, row_ids, list_off, L, q, q_dtype, normalize_q, Q, probes, P, k, x, t, b, c, out_scores,
                        out_ids, workspace, ws_bytes, stream, k > RT_KMAX);
+}
+
+// ---------------------------------------------------------------- sharded clustered catalogues
+// lthm_retrieve_ivf_topk_shards: S clustered catalogues of one device, each with centroids and lists of
+// its own, answer one batch of queries in one call.
+//   1  per shard: its probe row, retr_scan over the shard's centroids with k = P_s = min(nprobe, L_s)
+//      (the kernels, and so the bits and the ties, of the single catalogue's probe), packed into the
+//      probe slots [pbase_s, pbase_s + P_s) of probes [Q, P], P = sum_s P_s, as list numbers lbase_s + c;
+//   2  once: retr_ivf_call's plan over the L = sum_s L_s lists (count, offsets, fill: unchanged kernels),
+//      the excluded rows of every shard sorted (one retr_excl_prep_k launch for all), the cursor rows;
+//   3  once: the scan, retr_ivf_topk_k<true, true, TAGS, BIAS, false, true> or retr_ivf_deep_topk_k<TAGS,
+//      true>: the block-to-(shard, list) map is the plan's tile table and the descriptors' lbase, both on
+//      the device; every pair's list lands in [P, Q, k] as (score, id);
+//   4  once: lthm_retrieve_merge_shards over the P lists of every query, which also sums the pairs' counts
+//      of rows above the target into the query's rank where targets are given.
+// The descriptors reach the device as kernel arguments of retr_ivf_desc_k (32 per launch), which stores
+// them into the workspace with ordinary vector stores: the call stays stream-ordered end to end.
+namespace lthm {
+namespace {
+
+constexpr int RI_PACK = 32;  // descriptors per retr_ivf_desc_k launch: 2 KiB of kernel arguments
+struct RetrIvfShardPack {
+  RetrIvfShardDev d[RI_PACK];
+};
+__global__ __launch_bounds__(64) void retr_ivf_desc_k(RetrIvfShardPack pk, int n, RetrIvfShardDev* __restrict__ dst) {
+  const int t = threadIdx.x;
+  if (t < n) dst[t] = pk.d[t];
+}
+
+struct RetrIvfShardsWs {
+  int64_t desc, probes, prow, pscore, pws, pws_bytes, xs, rank, ivf, total;
+  int64_t L, P, Nmax;
+  int Pmax;
+  RetrIvfWs w;
+};
+
+// nprobe <= 0 is refused; P_s = min(nprobe, L_s)
+bool retr_ivf_shards_ws(const lthm_retrieve_ivf_shard* sh, int S, int64_t Q, int nprobe, int k, int64_t X, bool cursor,
+                        RetrIvfShardsWs* o) {
+  if (!sh || S < 1 || S > RS_SMAX || nprobe < 1 || Q < 1 || Q >= (1ll << 31) || X < 0 || X > RT_XMAX) return false;
+  int64_t L = 0, P = 0, Nmax = 0, pws = 0;
+  int Pmax = 0;
+  for (int s = 0; s < S; ++s) {
+    if (sh[s].N < 1 || sh[s].N >= (1ll << 31) || sh[s].L < 1 || sh[s].L >= (1ll << 31)) return false;
+    const int Ps = (int)(sh[s].L < nprobe ? sh[s].L : nprobe);
+    const int64_t b = retr_plan_bytes(Q, 1, sh[s].L, Ps, 0, 0);
+    if (b < 0) return false;
+    pws = b > pws ? b : pws;
+    L += sh[s].L, P += Ps;
+    Nmax = sh[s].N > Nmax ? sh[s].N : Nmax;
+    Pmax = Ps > Pmax ? Ps : Pmax;
+  }
+  if (L >= (1ll << 31) || P > RS_SMAX) return false;
+  if (!retr_ivf_ws(Q, Nmax, L, P, k, 0, &o->w, cursor, k > RT_KMAX)) return false;
+  o->L = L, o->P = P, o->Nmax = Nmax, o->Pmax = Pmax, o->pws_bytes = pws;
+  int64_t at = 0;
+  o->desc = at, at += up256((int64_t)S * (int64_t)sizeof(RetrIvfShardDev));
+  o->probes = at, at += up256(Q * P * 4);
+  o->prow = at, at += up256(Q * Pmax * 4);
+  o->pscore = at, at += up256(Q * Pmax * 4);
+  o->pws = at, at += up256(pws);
+  o->xs = at, at += X ? up256((int64_t)S * Q * (X + 1) * 4) : 0;
+  o->rank = at, at += up256(Q * P * 4);
+  o->ivf = at, at += o->w.total;
+  o->total = at;
+  return true;
+}
+
+}  // namespace
+}  // namespace lthm
+
+extern "C" int64_t lthm_retrieve_ivf_shards_ws_bytes(const lthm_retrieve_ivf_shard* shards, int32_t S, int64_t Q,
+                                                     int32_t nprobe, int32_t k, int64_t X, int32_t has_cursor) {
+  RetrIvfShardsWs o;
+  return retr_ivf_shards_ws(shards, S, Q, nprobe, k, X, has_cursor != 0, &o) ? o.total : -1;
+}
+
+extern "C" int lthm_retrieve_ivf_topk_shards(const lthm_retrieve_ivf_shard* shards, int32_t S, const void* q,
+                                             int32_t q_dtype, int32_t normalize_q, int64_t Q, int32_t nprobe, int32_t k,
+                                             const int32_t* exclude_rows, int64_t X, const int32_t* tag_filter,
+                                             int32_t use_bias, const float* bias_weight,
+                                             const lthm_retrieve_ivf_cursor* c, const int32_t* target_rows,
+                                             const float* target_score, float* out_scores, int64_t* out_ids,
+                                             int64_t* out_rank, void* workspace, int64_t ws_bytes, void* stream) {
+  LTHM_REQUIRE(shards && q && out_scores && out_ids && workspace);
+  LTHM_REQUIRE((target_rows != nullptr) == (target_score != nullptr) && (target_rows != nullptr) == (out_rank != nullptr));
+  LTHM_REQUIRE(((uintptr_t)target_rows & 3) == 0 && ((uintptr_t)target_score & 3) == 0 && ((uintptr_t)out_rank & 7) == 0);
+  LTHM_REQUIRE(q_dtype == LTHM_F32 || q_dtype == LTHM_BF16);
+  LTHM_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)workspace & 255) == 0);
+  LTHM_REQUIRE(((uintptr_t)out_scores & 3) == 0 && ((uintptr_t)out_ids & 7) == 0);
+  LTHM_REQUIRE((exclude_rows != nullptr) == (X > 0) && ((uintptr_t)exclude_rows & 3) == 0);
+  LTHM_REQUIRE(((uintptr_t)tag_filter & 3) == 0 && ((uintptr_t)bias_weight & 3) == 0 && (use_bias || !bias_weight));
+  LTHM_REQUIRE(!c || (c->after_score && c->after_id && ((uintptr_t)c->after_score & 3) == 0 &&
+                      ((uintptr_t)c->after_id & 7) == 0));
+  RetrIvfShardsWs wo;
+  LTHM_REQUIRE(retr_ivf_shards_ws(shards, S, Q, nprobe, k, X, c != nullptr, &wo) && ws_bytes >= wo.total);
+  const bool deep = k > RT_KMAX;
+  RetrIvfShardPack pk[(RS_SMAX + RI_PACK - 1) / RI_PACK] = {};
+  int sP[RS_SMAX], sPbase[RS_SMAX];  // every shard's probe slots and the first of them
+  {
+    int lbase = 0, pbase = 0;
+    for (int s = 0; s < S; ++s) {
+      const lthm_retrieve_ivf_shard& h = shards[s];
+      LTHM_REQUIRE(h.items && h.row_ids && h.list_off && h.centroids);
+      LTHM_REQUIRE(((uintptr_t)h.items & 15) == 0 && ((uintptr_t)h.centroids & 15) == 0);
+      LTHM_REQUIRE(((uintptr_t)h.row_ids & 7) == 0 && ((uintptr_t)h.list_off & 7) == 0);
+      LTHM_REQUIRE(((uintptr_t)h.tags & 3) == 0 && ((uintptr_t)h.bias & 3) == 0);
+      LTHM_REQUIRE(!tag_filter || h.tags);
+      LTHM_REQUIRE(!use_bias || h.bias);
+      RetrIvfShardDev& d = pk[s / RI_PACK].d[s % RI_PACK];
+      d.items = (const bf16_t*)h.items;
+      d.row_ids = h.row_ids;
+      d.list_off = h.list_off;
+      d.tags = tag_filter ? h.tags : nullptr;
+      d.bias = use_bias ? h.bias : nullptr;
+      d.N = h.N;
+      d.lbase = lbase;
+      sP[s] = (int)(h.L < nprobe ? h.L : nprobe), sPbase[s] = pbase;
+      lbase += (int)h.L, pbase += sP[s];
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  unsigned char* ws = (unsigned char*)workspace;
+  RetrIvfShardDev* dsh = (RetrIvfShardDev*)(ws + wo.desc);
+  for (int s0 = 0; s0 < S; s0 += RI_PACK) {
+    const int n = S - s0 < RI_PACK ? S - s0 : RI_PACK;
+    hipLaunchKernelGGL(retr_ivf_desc_k, dim3(1), dim3(64), 0, st, pk[s0 / RI_PACK], n, dsh + s0);
+    LTHM_CHECK_LAUNCH();
+  }
+  const int64_t L = wo.L, P = wo.P, NP = Q * P;
+  int* probes = (int*)(ws + wo.probes);
+  int* prow = (int*)(ws + wo.prow);
+  // 1: every shard's probe row
+  for (int s = 0; s < S; ++s) {
+    const RetrIvfShardDev& d = pk[s / RI_PACK].d[s % RI_PACK];
+    lthm_retrieve_desc pd = {};
+    pd.items = shards[s].centroids;
+    pd.N = shards[s].L;
+    pd.q = q;
+    pd.q_dtype = q_dtype;
+    pd.normalize_q = normalize_q;
+    pd.Q = Q;
+    pd.k = sP[s];
+    pd.slab_rows = 0;
+    pd.scores = (float*)(ws + wo.pscore);
+    pd.rows = prow;
+    pd.workspace = ws + wo.pws;
+    pd.ws_bytes = wo.pws_bytes;
+    const int rc = retr_scan(&pd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(retr_ivf_probe_pack_k, dim3((unsigned)((Q * sP[s] + 255) / 256)), dim3(256), 0, st, prow, Q, sP[s],
+                       d.lbase, sPbase[s], (int)P, probes);
+    LTHM_CHECK_LAUNCH();
+  }
+  // 2: retr_ivf_call's preparation and plan over all lists
+  unsigned char* iw = ws + wo.ivf;
+  const RetrIvfWs& w = wo.w;
+  bf16_t* qn = (bf16_t*)(iw + w.qn);
+  int* cnt = (int*)(iw + w.cnt);
+  int* fill = cnt + L;
+  int* pair_off = (int*)(iw + w.off);
+  int* tile_off = pair_off + (L + 1);
+  int* pair_idx = (int*)(iw + w.pidx);
+  int4* tab = (int4*)(iw + w.tab);
+  float* lscores = (float*)(iw + w.scores);
+  int64_t* lids = (int64_t*)(iw + w.ids);
+  const bf16_t* it0 = (const bf16_t*)shards[0].items;  // retr_prep_k reads no item without a target
+  const unsigned pgrid = (unsigned)((Q + 15) / 16);
+  if (q_dtype == LTHM_BF16)
+    hipLaunchKernelGGL((retr_prep_k<bf16_t>), dim3(pgrid), dim3(256), 0, st, (const bf16_t*)q, Q, normalize_q, qn, it0,
+                       shards[0].N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  else
+    hipLaunchKernelGGL((retr_prep_k<float>), dim3(pgrid), dim3(256), 0, st, (const float*)q, Q, normalize_q, qn, it0,
+                       shards[0].N, (const int*)nullptr, (float*)nullptr, -INFINITY);
+  LTHM_CHECK_LAUNCH();
+  {
+    const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)(2 * L) * 4, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  const unsigned ngrid = (unsigned)((NP + 255) / 256);
+  hipLaunchKernelGGL(retr_ivf_count_k, dim3(ngrid), dim3(256), 0, st, probes, NP, (int)L, (int)P, Q, (int)k, cnt, lscores,
+                     lids);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_offsets_k<false>, dim3(1), dim3(256), 0, st, cnt, (int)L, pair_off, tile_off, RT_QT);
+  LTHM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(retr_ivf_fill_k<false>, dim3(ngrid), dim3(256), 0, st, probes, NP, (int)L, cnt, pair_off, tile_off,
+                     fill, pair_idx, tab, RT_QT);
+  LTHM_CHECK_LAUNCH();
+  RetrIvfShardArgs a = {};
+  a.keys = deep ? (u64*)(iw + w.keys) : nullptr;
+  a.sh = dsh;
+  a.S = S;
+  a.filt = tag_filter;
+  a.bw = bias_weight;
+  if (c) {
+    int* crow = (int*)(iw + w.crow);
+    hipLaunchKernelGGL(retr_ivf_cursor_shards_k, dim3(ngrid), dim3(256), 0, st, probes, NP, (int)L, (int)P, dsh, (int)S,
+                       c->after_id, crow);
+    LTHM_CHECK_LAUNCH();
+    a.ascore = c->after_score;
+    a.crow = crow;
+  }
+  a.qn = qn;
+  a.tile_off = tile_off;
+  a.tab = tab;
+  a.pair_idx = pair_idx;
+  a.scores = lscores;
+  a.ids = lids;
+  a.Q = Q;
+  a.L = (int)L;
+  a.P = (int)P;
+  a.k = k;
+  if (X) {
+    int* xs = (int*)(ws + wo.xs);
+    int XP = 1;
+    while (XP < X) XP <<= 1;
+    // one launch for the S Q lists.  The bound is the longest shard's: a row at or past its own shard's
+    // N_s stays in the list and excludes nothing, since a block's walk ends at its list's end <= N_s
+    LTHM_REQUIRE((int64_t)S * Q < (1ll << 31));
+    hipLaunchKernelGGL(retr_excl_prep_k, dim3((unsigned)(S * Q)), dim3(256), 0, st, exclude_rows, (int)X, XP, wo.Nmax, xs);
+    LTHM_CHECK_LAUNCH();
+    a.xs = xs;
+    a.xstride = (int)X + 1;
+  }
+  int* ranks = nullptr;
+  if (target_rows) {
+    ranks = (int*)(ws + wo.rank);
+    const hipError_t e = hipMemsetAsync(ranks, 0, (size_t)NP * 4, st);
+    if (e != hipSuccess) return (int)e;
+    a.tsc = target_score;
+    a.trow = target_rows;
+    a.rank = ranks;
+  }
+  // 3: the scan
+  const dim3 grid((unsigned)w.grid);
+  const bool t = tag_filter != nullptr, b = use_bias != 0;
+  if (deep) {
+    if (t) hipLaunchKernelGGL((retr_ivf_deep_topk_k<true, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((retr_ivf_deep_topk_k<false, true>), grid, dim3(256), 0, st, a);
+  } else if (t && b) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, true, false, true>), grid, dim3(256), 0, st, a);
+  } else if (t) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, true, false, false, true>), grid, dim3(256), 0, st, a);
+  } else if (b) {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, true, false, true>), grid, dim3(256), 0, st, a);
+  } else {
+    hipLaunchKernelGGL((retr_ivf_topk_k<true, true, false, false, false, true>), grid, dim3(256), 0, st, a);
+  }
+  LTHM_CHECK_LAUNCH();
+  // 4: the merge of every query's P lists
+  return lthm_retrieve_merge_shards(lscores, lids, ranks, (int32_t)P, Q, k, out_scores, out_ids, out_rank, stream);
 }
 
 // ---------------------------------------------------------------- diversified lists (MMR, per-group caps)

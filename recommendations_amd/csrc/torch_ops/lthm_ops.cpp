@@ -24,6 +24,7 @@
 //   lthm::retrieve_topk_bias  any of the above on the score fma(weight[q], bias[row], dot)
 //   lthm::retrieve_topk_deep  any of the above with k up to 1024, from one scan of the catalogue
 //   lthm::retrieve_merge_shards  the k first of the union of S sorted (score, id) lists per query
+//   lthm::retrieve_ivf_topk_shards the scan of S clustered catalogues of one device in one call, merged
 //   lthm::retrieve_ivf_topk      the scan of a clustered catalogue: each query visits the lists it probes
 //   lthm::retrieve_ivf_topk_filt the same with a tag filter, a score prior and an (score, id) cursor per query
 //   lthm::retrieve_ivf_topk_deep the same with k up to 1,024 (lthm_retrieve_ivf_topk_deep)
@@ -659,6 +660,101 @@ std::tuple<Tensor, Tensor, Tensor> retrieve_merge_shards_cuda(const Tensor& scor
   return {out_scores, out_ids, out_rank};
 }
 
+// S clustered catalogues of one device in one call (lthm_retrieve_ivf_topk_shards): items / row_ids /
+// list_off / centroids are lists of S tensors, tags and bias lists of S tensors or empty (none); every shard
+// probes its min(nprobe, L_s) nearest lists.  exclude_rows int32 [S, Q, X]; tag_filter int32 [Q, 3]; use_bias
+// with bias_weight f32 [Q] or None; after_scores f32 [Q] / after_ids int64 [Q]; target_rows int32 [S, Q] with
+// target_scores f32 [Q].  (scores f32 [Q, k], ids int64 [Q, k], rank int64 [Q], empty without targets)
+std::tuple<Tensor, Tensor, Tensor> retrieve_ivf_topk_shards_cuda(
+    const Tensor& q_, at::TensorList items, at::TensorList row_ids, at::TensorList list_off, at::TensorList centroids,
+    at::TensorList tags, at::TensorList bias, int64_t nprobe, int64_t k, bool normalize_q,
+    const c10::optional<Tensor>& exclude_rows, const c10::optional<Tensor>& tag_filter, bool use_bias,
+    const c10::optional<Tensor>& bias_weight, const c10::optional<Tensor>& after_scores,
+    const c10::optional<Tensor>& after_ids, const c10::optional<Tensor>& target_rows,
+    const c10::optional<Tensor>& target_scores) {
+  const int64_t S = (int64_t)items.size();
+  TORCH_CHECK(S >= 1 && S <= 64, "retrieve_ivf_topk_shards takes 1..64 shards (got S=", S, ")");
+  TORCH_CHECK((int64_t)row_ids.size() == S && (int64_t)list_off.size() == S && (int64_t)centroids.size() == S,
+              "retrieve_ivf_topk_shards takes one row_ids, list_off and centroids tensor per shard");
+  TORCH_CHECK(tags.empty() || (int64_t)tags.size() == S, "tags: one tensor per shard, or none");
+  TORCH_CHECK(bias.empty() || (int64_t)bias.size() == S, "bias: one tensor per shard, or none");
+  TORCH_CHECK(q_.is_cuda() && q_.dim() == 2 && q_.size(1) == 128 && q_.size(0) >= 1, "q must be a CUDA tensor [Q, 128]");
+  TORCH_CHECK(q_.scalar_type() == at::kFloat || q_.scalar_type() == at::kBFloat16, "q must be f32 or bf16");
+  TORCH_CHECK(nprobe >= 1 && k >= 1 && k <= 1024, "retrieve_ivf_topk_shards takes nprobe >= 1 and k in 1..1024");
+  const Tensor q = q_.contiguous();
+  const int64_t Q = q.size(0);
+  const auto dev = q.device();
+  std::vector<Tensor> keep;  // the contiguous tensors the descriptors point at
+  std::vector<lthm_retrieve_ivf_shard> sh((size_t)S);
+  auto held = [&](const Tensor& t, at::ScalarType ty, const char* what) {
+    TORCH_CHECK(t.device() == dev && t.scalar_type() == ty, what, ": wrong device or dtype");
+    keep.push_back(t.contiguous());
+    return keep.back().data_ptr();
+  };
+  for (int64_t i = 0; i < S; ++i) {
+    const int64_t N = items[i].size(0), L = centroids[i].size(0);
+    TORCH_CHECK(items[i].dim() == 2 && items[i].size(1) == 128 && N >= 1, "items must be bf16 [N, 128]");
+    TORCH_CHECK(centroids[i].dim() == 2 && centroids[i].size(1) == 128 && L >= 1, "centroids must be bf16 [L, 128]");
+    TORCH_CHECK(row_ids[i].dim() == 1 && row_ids[i].size(0) == N, "row_ids must be int64 [N]");
+    TORCH_CHECK(list_off[i].dim() == 1 && list_off[i].size(0) == L + 1, "list_off must be int64 [L + 1]");
+    sh[i].items = held(items[i], at::kBFloat16, "items");
+    sh[i].row_ids = (const int64_t*)held(row_ids[i], at::kLong, "row_ids");
+    sh[i].list_off = (const int64_t*)held(list_off[i], at::kLong, "list_off");
+    sh[i].centroids = held(centroids[i], at::kBFloat16, "centroids");
+    sh[i].tags = nullptr;
+    sh[i].bias = nullptr;
+    if (!tags.empty()) {
+      TORCH_CHECK(tags[i].dim() == 1 && tags[i].size(0) == N, "tags must be int32 [N]");
+      sh[i].tags = (const int32_t*)held(tags[i], at::kInt, "tags");
+    }
+    if (!bias.empty()) {
+      TORCH_CHECK(bias[i].dim() == 1 && bias[i].size(0) == N, "bias must be f32 [N]");
+      sh[i].bias = (const float*)held(bias[i], at::kFloat, "bias");
+    }
+    sh[i].N = N;
+    sh[i].L = L;
+  }
+  auto opt = [&](const c10::optional<Tensor>& t, at::ScalarType ty, std::vector<int64_t> shape, const char* what) -> void* {
+    if (!t.has_value() || !t->defined()) return nullptr;
+    TORCH_CHECK(t->device() == dev && t->scalar_type() == ty && t->sizes() == at::IntArrayRef(shape), what,
+                ": wrong device, dtype or shape");
+    keep.push_back(t->contiguous());
+    return keep.back().data_ptr();
+  };
+  int64_t X = 0;
+  if (exclude_rows.has_value() && exclude_rows->defined()) {
+    TORCH_CHECK(exclude_rows->dim() == 3, "exclude_rows must be int32 [S, Q, X]");
+    X = exclude_rows->size(2);
+    TORCH_CHECK(X >= 1 && X <= 1024, "exclude_rows takes 1..1024 rows per query");
+  }
+  const int32_t* xr = (const int32_t*)opt(exclude_rows, at::kInt, {S, Q, X}, "exclude_rows");
+  const int32_t* tf = (const int32_t*)opt(tag_filter, at::kInt, {Q, 3}, "tag_filter");
+  TORCH_CHECK(!tf || !tags.empty(), "tag_filter takes shards with tags");
+  TORCH_CHECK(!use_bias || !bias.empty(), "use_bias takes shards with a bias");
+  const float* bw = (const float*)opt(bias_weight, at::kFloat, {Q}, "bias_weight");
+  TORCH_CHECK(use_bias || !bw, "bias_weight takes use_bias");
+  lthm_retrieve_ivf_cursor c = {};
+  c.after_score = (const float*)opt(after_scores, at::kFloat, {Q}, "after_scores");
+  c.after_id = (const int64_t*)opt(after_ids, at::kLong, {Q}, "after_ids");
+  TORCH_CHECK((c.after_score != nullptr) == (c.after_id != nullptr), "after_scores and after_ids come together or neither");
+  const int32_t* tr = (const int32_t*)opt(target_rows, at::kInt, {S, Q}, "target_rows");
+  const float* ts = (const float*)opt(target_scores, at::kFloat, {Q}, "target_scores");
+  TORCH_CHECK((tr != nullptr) == (ts != nullptr), "target_rows and target_scores come together or neither");
+  const int64_t need = lthm_retrieve_ivf_shards_ws_bytes(sh.data(), (int32_t)S, Q, (int32_t)std::min<int64_t>(nprobe, 1 << 30),
+                                                         (int32_t)k, X, c.after_score ? 1 : 0);
+  TORCH_CHECK(need >= 0, "retrieve_ivf_topk_shards: unsupported sizes (the probe slots of all shards together stay within 64)");
+  Tensor ws = at::empty({need}, q.options().dtype(at::kByte));
+  Tensor out_scores = at::empty({Q, k}, q.options().dtype(at::kFloat)), out_ids = at::empty({Q, k}, q.options().dtype(at::kLong));
+  Tensor out_rank = at::empty({tr ? Q : 0}, q.options().dtype(at::kLong));
+  hip_ok(lthm_retrieve_ivf_topk_shards(sh.data(), (int32_t)S, q.data_ptr(), q.scalar_type() == at::kBFloat16 ? LTHM_BF16 : LTHM_F32,
+                                       normalize_q ? 1 : 0, Q, (int32_t)std::min<int64_t>(nprobe, 1 << 30), (int32_t)k, xr, X, tf,
+                                       use_bias ? 1 : 0, bw, c.after_score ? &c : nullptr, tr, ts,
+                                       out_scores.data_ptr<float>(), out_ids.data_ptr<int64_t>(),
+                                       tr ? out_rank.data_ptr<int64_t>() : nullptr, ws.data_ptr(), need, cur_stream()),
+         "lthm_retrieve_ivf_topk_shards");
+  return {out_scores, out_ids, out_rank};
+}
+
 // the scan of a clustered catalogue: items bf16 [N, 128] list-major, row_ids int64 [N], list_off int64
 // [L + 1], probes int32 [Q, P] (P <= 64), exclude_rows int32 [Q, X] in the clustered row numbering or
 // None; (scores f32 [Q, k], ids int64 [Q, k])
@@ -1204,6 +1300,11 @@ TORCH_LIBRARY(lthm, m) {
       "(Tensor scores, Tensor rows)");
   m.def("retrieve_merge_shards(Tensor scores, Tensor ids, Tensor? ranks=None) -> (Tensor scores, Tensor ids, Tensor rank)");
   m.def(
+      "retrieve_ivf_topk_shards(Tensor q, Tensor[] items, Tensor[] row_ids, Tensor[] list_off, Tensor[] centroids, "
+      "Tensor[] tags, Tensor[] bias, int nprobe, int k, bool normalize_q=True, Tensor? exclude_rows=None, "
+      "Tensor? tag_filter=None, bool use_bias=False, Tensor? bias_weight=None, Tensor? after_scores=None, "
+      "Tensor? after_ids=None, Tensor? target_rows=None, Tensor? target_scores=None) -> (Tensor scores, Tensor ids, Tensor rank)");
+  m.def(
       "retrieve_ivf_topk(Tensor q, Tensor items, Tensor row_ids, Tensor list_off, Tensor probes, int k, "
       "bool normalize_q, Tensor? exclude_rows=None) -> (Tensor scores, Tensor ids)");
   m.def(
@@ -1250,6 +1351,7 @@ TORCH_LIBRARY_IMPL(lthm, CUDA, m) {
   m.impl("retrieve_topk_bias", &retrieve_topk_bias_cuda);
   m.impl("retrieve_topk_deep", &retrieve_topk_deep_cuda);
   m.impl("retrieve_merge_shards", &retrieve_merge_shards_cuda);
+  m.impl("retrieve_ivf_topk_shards", &retrieve_ivf_topk_shards_cuda);
   m.impl("retrieve_ivf_topk", &retrieve_ivf_topk_cuda);
   m.impl("retrieve_ivf_topk_filt", &retrieve_ivf_topk_filt_cuda);
   m.impl("retrieve_ivf_topk_deep", &retrieve_ivf_topk_deep_cuda);

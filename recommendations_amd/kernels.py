@@ -2334,6 +2334,122 @@ def _retrieve_ivf_deep(q, items, row_ids, list_off, probes, k, normalize_q, excl
     return scores, ids
 
 
+def retrieve_ivf_shard_descs(shards):
+    """The host array of lthm_retrieve_ivf_shard for ``shards``, a sequence of (items bf16 [N, 128], row_ids
+    int64 [N], list_off int64 [L + 1], centroids bf16 [L, 128], tags int32 [N] | None, bias f32 [N] | None),
+    all contiguous and on one device.  The array holds pointers only: the caller keeps the tensors alive."""
+    from ._lib import STRUCTS
+    S = len(shards)
+    _check(1 <= S <= RETRIEVE_MAX_SHARDS, f"retrieve_ivf_topk_shards takes 1..{RETRIEVE_MAX_SHARDS} shards (got S={S})")
+    arr = (STRUCTS["lthm_retrieve_ivf_shard"] * S)()
+    dev = shards[0][0].device
+    for i, (items, row_ids, list_off, centroids, tags, bias) in enumerate(shards):
+        require_gpu(items, row_ids, list_off, centroids, tags, bias)
+        N, L = items.shape[0], centroids.shape[0]
+        _check(items.dtype == torch.bfloat16 and items.dim() == 2 and items.shape[1] == RETRIEVE_WIDTH and N >= 1,
+               f"shard {i}: items must be bf16 [N, {RETRIEVE_WIDTH}] (got {items.dtype} {tuple(items.shape)})")
+        _check(centroids.dtype == torch.bfloat16 and centroids.dim() == 2 and centroids.shape[1] == RETRIEVE_WIDTH and L >= 1,
+               f"shard {i}: centroids must be bf16 [L, {RETRIEVE_WIDTH}] (got {centroids.dtype} {tuple(centroids.shape)})")
+        _check(row_ids.dtype == torch.int64 and tuple(row_ids.shape) == (N,), f"shard {i}: row_ids must be int64 [N]")
+        _check(list_off.dtype == torch.int64 and tuple(list_off.shape) == (L + 1,), f"shard {i}: list_off must be int64 [L + 1]")
+        _check(tags is None or (tags.dtype == torch.int32 and tuple(tags.shape) == (N,)), f"shard {i}: tags must be int32 [N]")
+        _check(bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (N,)), f"shard {i}: bias must be f32 [N]")
+        _check(all(t is None or t.device == dev for t in (items, row_ids, list_off, centroids, tags, bias)),
+               "the shards of one call must be on one device")
+        d = arr[i]
+        d.items, d.row_ids, d.list_off, d.centroids = ptr(items), ptr(row_ids), ptr(list_off), ptr(centroids)
+        d.tags, d.bias, d.N, d.L = ptr(tags), ptr(bias), N, L
+    return arr
+
+
+def retrieve_ivf_topk_shards(q, shards, nprobe: int, k: int, *, normalize_q: bool = True, exclude_rows=None,
+                             tag_filter=None, use_bias: bool = False, bias_weight=None, after_scores=None,
+                             after_ids=None, target_rows=None, target_scores=None, out=None):
+    """The k best items per query over S clustered catalogues of one device, each probing its own
+    min(nprobe, L_s) nearest lists (lthm_retrieve_ivf_topk_shards, csrc/retrieve.hip): one plan, one scan
+    launch (retr_ivf_topk_k / retr_ivf_deep_topk_k with the shard descriptors) and one merge for all shards.
+
+    ``shards``: the tuples retrieve_ivf_shard_descs takes (the descriptors are rebuilt per call: a few dozen
+    small structs); q f32 / bf16 [Q, 128]; exclude_rows int32 [S, Q, X] or None, the excluded rows in
+    every shard's own numbering; tag_filter int32 [Q, 3] (every shard then carries tags); use_bias scores
+    with every shard's bias and bias_weight (None, a number or f32 [Q]); after_scores f32 [Q] / after_ids
+    int64 [Q], the cursor.  k in 1..1024; the probe slots of all shards together number at most 64.
+    target_rows int32 [S, Q] (the row of every query's target in every shard, -1 where it is not there) with
+    target_scores f32 [Q] (retrieve_target_score on the shard that holds the target; NaN: none does), both
+    or neither: rank then counts the eligible rows of the probed lists, other than the target's, that score
+    strictly above the target score (inside the scan, on its own scores).  ``out``: (scores, ids) f32 / int64
+    [Q, k] contiguous tensors to write into.
+    Returns (scores f32 [Q, k], ids int64 [Q, k], rank int64 [Q] | None): scores and ids bit for bit what one
+    retrieve_ivf_topk(deep=True) per shard, each with the shard's own probe row, followed by
+    retrieve_merge_shards returns."""
+    import ctypes
+    who = "retrieve_ivf_topk_shards"
+    arr = retrieve_ivf_shard_descs(shards)
+    S = len(arr)
+    require_gpu(q, exclude_rows, tag_filter, after_scores, after_ids, target_rows, target_scores)
+    _check(q.dim() == 2 and q.shape[1] == RETRIEVE_WIDTH and q.shape[0] >= 1,
+           f"{who} takes [Q, {RETRIEVE_WIDTH}] queries (got {tuple(q.shape)})")
+    Q, k = q.shape[0], int(k)
+    dev = q.device
+    _check(shards[0][0].device == dev, "q must be on the shards' device")
+    _check(isinstance(nprobe, int) and not isinstance(nprobe, bool) and nprobe >= 1, f"{who} takes nprobe >= 1 (got {nprobe!r})")
+    _check(1 <= k <= RETRIEVE_MAX_DEEP, f"{who} takes k in 1..{RETRIEVE_MAX_DEEP} (got {k})")
+    X = 0
+    if exclude_rows is not None:
+        _check(exclude_rows.dtype == torch.int32 and exclude_rows.dim() == 3 and tuple(exclude_rows.shape[:2]) == (S, Q),
+               f"exclude_rows must be int32 [S, Q, X] (got {exclude_rows.dtype} {tuple(exclude_rows.shape)}, S={S}, Q={Q})")
+        X = exclude_rows.shape[2]
+        _check(1 <= X <= RETRIEVE_MAX_EXCLUDE, f"exclude_rows takes 1..{RETRIEVE_MAX_EXCLUDE} rows per query (got {X})")
+        _check(exclude_rows.device == dev, "exclude_rows must be on the queries' device")
+    if tag_filter is not None:
+        _check(tag_filter.dtype == torch.int32 and tuple(tag_filter.shape) == (Q, 3) and tag_filter.device == dev,
+               f"tag_filter must be int32 [Q, 3] on the queries' device (got {tag_filter.dtype} {tuple(tag_filter.shape)})")
+        _check(all(s[4] is not None for s in shards), f"{who} takes a tag_filter only where every shard carries tags")
+    bw = None
+    if use_bias:
+        _check(all(s[5] is not None for s in shards), f"{who} takes use_bias only where every shard carries a bias")
+        bw = bias_weight
+        if bw is not None and not isinstance(bw, torch.Tensor):
+            _check(isinstance(bw, (int, float)) and not isinstance(bw, bool),
+                   f"bias_weight must be None, a number or an f32 tensor [Q] (got {type(bw).__name__})")
+            bw = torch.full((Q,), float(bw), dtype=torch.float32, device=dev)
+        if bw is not None:
+            require_gpu(bw)
+            _check(bw.dtype == torch.float32 and tuple(bw.shape) == (Q,) and bw.device == dev,
+                   f"bias_weight must be f32 [Q] on the queries' device (got {bw.dtype} {tuple(bw.shape)}, Q={Q})")
+    else:
+        _check(bias_weight is None, f"{who} takes a bias_weight only with use_bias")
+    c = _retrieve_ivf_cursor(who, after_scores, after_ids, Q, dev)
+    need = load().lthm_retrieve_ivf_shards_ws_bytes(ctypes.addressof(arr), S, Q, nprobe, k, X, int(c is not None))
+    _check(need >= 0, f"{who}: no workspace size for S={S} Q={Q} nprobe={nprobe} k={k} X={X} "
+                      f"(the probe slots of all shards together must stay within {RETRIEVE_MAX_PROBE})")
+    _check((target_rows is None) == (target_scores is None), f"{who} takes target_rows and target_scores together or neither")
+    rank = None
+    if target_rows is not None:
+        _check(target_rows.dtype == torch.int32 and tuple(target_rows.shape) == (S, Q) and target_rows.device == dev,
+               f"target_rows must be int32 [S, Q] on the queries' device (got {target_rows.dtype} {tuple(target_rows.shape)})")
+        _check(target_scores.dtype == torch.float32 and tuple(target_scores.shape) == (Q,) and target_scores.device == dev,
+               f"target_scores must be f32 [Q] on the queries' device (got {target_scores.dtype} {tuple(target_scores.shape)})")
+        rank = torch.empty(Q, dtype=torch.int64, device=dev)
+    if out is not None:
+        scores, ids = out
+        require_gpu(scores, ids)
+        _check(scores.dtype == torch.float32 and ids.dtype == torch.int64 and tuple(scores.shape) == (Q, k)
+               and tuple(ids.shape) == (Q, k) and scores.device == dev and ids.device == dev,
+               f"out must be (f32 [Q, k], int64 [Q, k]) on the queries' device")
+    else:
+        scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+        ids = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    P = sum(min(nprobe, s[3].shape[0]) for s in shards)
+    work = float(q.numel() * q.element_size() + 24.0 * P * Q * k + 12.0 * Q * k + 4.0 * Q * (P + S * X))
+    call("lthm_retrieve_ivf_topk_shards", ctypes.addressof(arr), S, ptr(q), dcode(q), int(bool(normalize_q)), Q, nprobe, k,
+         ptr(exclude_rows), X, ptr(tag_filter), int(bool(use_bias)), ptr(bw),
+         ctypes.addressof(c) if c is not None else None, ptr(target_rows), ptr(target_scores), ptr(scores), ptr(ids),
+         ptr(rank), ptr(ws), need, stream(), _key="retr_ivf_topk_shards_k", _work=work, _unit="byte")
+    return scores, ids, rank
+
+
 RETRIEVE_MAX_POOL = RETRIEVE_MAX_DEEP  # RV_MMAX: the largest candidate pool of retrieve_diversify (a deep list)
 
 

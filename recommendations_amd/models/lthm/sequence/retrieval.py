@@ -42,6 +42,11 @@ conventions.  Its ``with_heads()`` view is that view for users with several quer
 [U, G, 128], ``K.retrieve_ivf_topk_group``): one probe row per user, an item scored by its best match
 over the user's queries inside the scan, one slot per item.
 
+Clustered shards: a ``ShardedClusteredItemCatalogue`` holds clustered catalogues (plain, ``with_filters()``
+or ``with_deep()``) with disjoint ids as the shards of one catalogue: every shard probes its own ``nprobe``
+nearest lists, one call scans the probed lists of all shards of a device and merges them
+(``K.retrieve_ivf_topk_shards``), and with every list probed the result is the flat catalogue's bit for bit.
+
 Clustered e4m3: ``ClusteredItemCatalogue.quantize`` gives a ``QuantizedClusteredItemCatalogue``, the same lists
 as e4m3 codes with the catalogue's tags and bias: its ``topk`` scans the probed lists' codes for a shortlist of
 the eligible rows (``K.retrieve_ivf_q8_topk``) and re-scores it with the exact rows and the prior
@@ -1524,6 +1529,266 @@ class ShardedItemCatalogue:
         """``ItemCatalogue.target_ranks`` over the union of the shards (int64)."""
         return self._scan(q, 1, True, target_ids, 0, exclude_ids, tag_filter, None, None, bias_weight,
                           bias_weight is not None)[2]
+
+
+class ShardedClusteredItemCatalogue:
+    """One catalogue held as clustered shards: ``local_shards`` are ``ClusteredItemCatalogue``s of this
+    process, all plain, all ``with_filters()`` views or all ``with_deep()`` views (on one device or on
+    several; disjoint ids, checked here), and with ``group`` the catalogue also covers the shards of the
+    group's other ranks.  Every shard has centroids and a number of lists of its own.  All shards agree on
+    carrying tags and on carrying a bias; at most ``K.RETRIEVE_MAX_SHARDS`` = 64 shards in all.
+
+    ``nprobe`` is per shard: every shard probes its own min(``nprobe``, ``shard.nlist``) nearest lists for
+    every query, so a query scans up to ``nprobe`` lists in each shard.
+
+    Contract of ``topk``: with every list of every shard probed (``nprobe`` >= every ``nlist``) the result is,
+    ids and score bits, what one ``ItemCatalogue`` over all items returns for the same arguments (for plain
+    shards: a catalogue without a bias, as for the plain ``ClusteredItemCatalogue``).  With fewer lists
+    probed it is the exact top-k of the union of the probed rows, in the flat scan's total order (score
+    descending, id ascending) with the flat scan's score bits.
+
+    The local shards of one device go through ``K.retrieve_ivf_topk_shards``: one plan, one scan launch and
+    one merge for all of them (as many calls as keep the shards' probe slots within 64 each).  With a
+    ``group`` the constructor, ``topk``, ``filter_like``, ``holds`` and ``validate`` are collectives, as on
+    ``ShardedItemCatalogue``: every rank merges its own shards, the ranks' lists are gathered and merged
+    again, and every rank gets the full result.  ``target_ids`` give the target's score and its rank among
+    the probed rows (``topk``, ``target_ranks``)."""
+
+    _KINDS = {ClusteredItemCatalogue: 0, FilteredClusteredItemCatalogue: 1, DeepClusteredItemCatalogue: 2}
+
+    def __init__(self, local_shards: Sequence[ClusteredItemCatalogue], group=None):
+        shards = list(local_shards)
+        if not shards or not all(type(s) in self._KINDS for s in shards):
+            raise ValueError("ShardedClusteredItemCatalogue takes one or more ClusteredItemCatalogue shards, or "
+                             "their with_filters() / with_deep() views")
+        if len({type(s) for s in shards}) != 1:
+            raise ValueError("the shards of a clustered catalogue are of one kind: all plain, all with_filters() "
+                             "or all with_deep()")
+        if len({s.has_tags for s in shards}) != 1:
+            raise ValueError("the shards of a catalogue all carry tags, or none does")
+        if len({s.has_bias for s in shards}) != 1:
+            raise ValueError("the shards of a catalogue all carry a bias, or none does")
+        dev = shards[0].emb.device
+        ids = torch.sort(torch.cat([s._ids.to(dev) for s in shards]))[0]
+        if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+            bad = int(ids[1:][ids[1:] == ids[:-1]][0])
+            raise ValueError(f"the shards of a catalogue hold disjoint ids (id {bad} is in two of them)")
+        self.shards = shards
+        self.group = group
+        self.device = dev
+        self._kind = self._KINDS[type(shards[0])]
+        self._total = int(ids.numel())
+        self._max_items = self._total
+        self._flat = None
+        n_all = len(shards)
+        if group is not None:
+            mine = torch.tensor([len(shards), self._total, int(shards[0].has_tags), int(shards[0].has_bias), self._kind],
+                                dtype=torch.int64, device=dev)
+            every = all_gather_stack(mine, group).cpu()
+            if bool((every[:, 2] != every[0, 2]).any()) or bool((every[:, 3] != every[0, 3]).any()):
+                raise ValueError("the shards of a catalogue all carry tags / a bias, or none does (the ranks disagree)")
+            if bool((every[:, 4] != every[0, 4]).any()):
+                raise ValueError("the shards of a clustered catalogue are of one kind (the ranks disagree)")
+            self._total = int(every[:, 1].sum())
+            self._max_items = int(every[:, 1].max())
+            n_all = int(every[:, 0].max()) * every.shape[0]
+        if n_all > K.RETRIEVE_MAX_SHARDS:
+            raise ValueError(f"a sharded catalogue takes at most {K.RETRIEVE_MAX_SHARDS} shards (got {n_all})")
+
+    def __len__(self) -> int:
+        return self._total
+
+    @property
+    def has_tags(self) -> bool:
+        return self.shards[0].has_tags
+
+    @property
+    def has_bias(self) -> bool:
+        return self.shards[0].has_bias
+
+    @property
+    def scans_filters(self) -> bool:
+        return self._kind >= 1
+
+    @property
+    def scans_deep(self) -> bool:
+        return self._kind == 2
+
+    @property
+    def max_k(self) -> int:
+        return K.RETRIEVE_MAX_DEEP if self.scans_deep else K.RETRIEVE_MAX_K
+
+    def validate(self) -> None:
+        """Disjointness of the ids across the ranks of the group, as ``ShardedItemCatalogue.validate``."""
+        dev = self.device
+        ids = torch.cat([s._ids.to(dev) for s in self.shards])
+        if self.group is not None:
+            pad = torch.zeros(self._max_items, dtype=torch.int64, device=dev)
+            pad[:ids.numel()] = ids
+            ids = all_gather_stack(pad, self.group).reshape(-1)
+            ids = ids[ids != 0]
+        ids = torch.sort(ids)[0]
+        if ids.numel() > 1 and bool((ids[1:] == ids[:-1]).any()):
+            bad = int(ids[1:][ids[1:] == ids[:-1]][0])
+            raise ValueError(f"the shards of a catalogue hold disjoint ids (id {bad} is in two of them)")
+
+    _reduce_max = ShardedItemCatalogue._reduce_max
+    holds = ShardedItemCatalogue.holds
+    filter_like = ShardedItemCatalogue.filter_like
+
+    def to_flat(self) -> ItemCatalogue:
+        """The id-sorted ``ItemCatalogue`` over the items of all shards, with their tags and bias; for a
+        catalogue without a group."""
+        if self.group is not None:
+            raise ValueError("to_flat takes a catalogue without a group: the other ranks' items are not here")
+        dev = self.device
+        flats = [s.to_flat() for s in self.shards]
+        cat = lambda name: None if getattr(flats[0], name) is None else torch.cat([getattr(f, name).to(dev) for f in flats])
+        return ItemCatalogue.from_embeddings(cat("ids"), cat("emb"), cat("tags"), cat("bias"))
+
+    def _check_call(self, k: int, nprobe) -> Tuple[int, int]:
+        if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
+            raise ValueError(f"a clustered catalogue takes nprobe, an int (got {nprobe!r})")
+        if nprobe > K.RETRIEVE_MAX_PROBE:
+            raise ValueError(f"nprobe takes at most {K.RETRIEVE_MAX_PROBE} lists per query (got {nprobe})")
+        if nprobe < 1:
+            raise ValueError(f"nprobe takes at least one list (got {nprobe})")
+        k = int(k)
+        if not 1 <= k <= self.max_k:
+            raise ValueError(f"a clustered catalogue takes k in 1..{self.max_k} (got {k})")
+        return k, nprobe
+
+    def _chunks(self, nprobe: int):
+        """The local shards cut into the calls of ``K.retrieve_ivf_topk_shards``: consecutive shards of one
+        device whose probe slots, min(nprobe, nlist) each, number at most ``K.RETRIEVE_MAX_PROBE`` together."""
+        out, cur, slots = [], [], 0
+        for s in self.shards:
+            p = min(nprobe, s.nlist)
+            if cur and (cur[0].emb.device != s.emb.device or slots + p > K.RETRIEVE_MAX_PROBE):
+                out.append(cur)
+                cur, slots = [], 0
+            cur.append(s)
+            slots += p
+        out.append(cur)
+        return out
+
+    def _scan(self, q, k, nprobe, normalize_q, target_ids, exclude_ids, tag_filter, after_scores, after_ids,
+              bias_weight, use_bias):
+        k, nprobe = self._check_call(k, nprobe)
+        if not self.scans_filters:
+            given = {"tag_filter": tag_filter, "after_scores": after_scores, "after_ids": after_ids,
+                     "bias_weight": bias_weight}
+            bad = [name for name, v in given.items() if v is not None]
+            if bad:
+                raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
+                                 "use catalogue.to_flat() for it")
+            if q.dim() != 2:
+                raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        else:
+            self.shards[0]._check_filters(q, tag_filter, after_scores, after_ids, bias_weight)
+        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
+            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+        if target_ids is not None and (target_ids.dtype != torch.int64 or tuple(target_ids.shape) != (q.shape[0],)):
+            raise ValueError(f"target_ids must be int64 [Q] (got {target_ids.dtype} {tuple(target_ids.shape)})")
+        home = q.device
+        use_bias = use_bias and self.scans_filters and self.has_bias
+        if isinstance(bias_weight, (int, float)) and not isinstance(bias_weight, bool):
+            bias_weight = torch.full((q.shape[0],), float(bias_weight), dtype=torch.float32, device=home)
+        on = lambda t, dev: None if t is None else t.to(dev).contiguous()
+        # the target's score, from the one shard that holds the target (ShardedItemCatalogue._scan's steps 1, 2)
+        tscore = tscore_out = None
+        if target_ids is not None:
+            parts = []
+            for s in self.shards:
+                dev = s.emb.device
+                with torch.cuda.device(dev):
+                    parts.append(K.retrieve_target_score(on(q, dev), s.emb, s.rows_of(target_ids).contiguous(),
+                                                         normalize_q=normalize_q, bias=s.bias if use_bias else None,
+                                                         bias_weight=on(bias_weight, dev) if use_bias else None).to(home))
+            ts = torch.stack(parts)
+            ts = self._reduce_max(torch.where(torch.isnan(ts), torch.full_like(ts, float("-inf")), ts).amax(dim=0))
+            tscore = torch.where(ts == float("-inf"), torch.full_like(ts, float("nan")), ts).contiguous()
+            tscore_out = ts
+        ls, li, lr = [], [], []
+        for chunk in self._chunks(nprobe):
+            dev = chunk[0].emb.device
+            tup = [(s.emb, s.row_ids, s.list_off, s.centroids, s.tags, s.bias) for s in chunk]
+            rows = lambda ids: None if ids is None else torch.stack([s.rows_of(ids) for s in chunk]).to(dev).contiguous()
+            with torch.cuda.device(dev):
+                sc, ids, rk = K.retrieve_ivf_topk_shards(on(q, dev), tup, nprobe, k, normalize_q=normalize_q,
+                                                         exclude_rows=rows(exclude_ids), tag_filter=on(tag_filter, dev),
+                                                         use_bias=use_bias,
+                                                         bias_weight=on(bias_weight, dev) if use_bias else None,
+                                                         after_scores=on(after_scores, dev), after_ids=on(after_ids, dev),
+                                                         target_rows=rows(target_ids), target_scores=on(tscore, dev))
+            ls.append(sc.to(home))
+            li.append(ids.to(home))
+            if rk is not None:
+                lr.append(rk.to(home))
+        scores, ids = torch.stack(ls), torch.stack(li)
+        rank = torch.stack(lr).sum(dim=0) if lr else None
+        if self.group is not None:
+            if scores.shape[0] > 1:  # one list per rank goes through the gather
+                with torch.cuda.device(home):
+                    sc, idm, _ = K.retrieve_merge_shards(scores.contiguous(), ids.contiguous())
+                scores, ids = sc[None], idm[None]
+            scores = all_gather_stack(scores[0].contiguous(), self.group)
+            ids = all_gather_stack(ids[0].contiguous(), self.group)
+            if rank is not None:
+                rank = all_gather_stack(rank.contiguous(), self.group).sum(dim=0)
+        if rank is not None:
+            rank = torch.where(torch.isnan(tscore), torch.full_like(rank, -1), rank)
+        if scores.shape[0] == 1:
+            return ids[0], scores[0], rank, tscore_out
+        with torch.cuda.device(home):
+            out_scores, out_ids, _ = K.retrieve_merge_shards(scores.contiguous(), ids.contiguous())
+        return out_ids, out_scores, rank, tscore_out
+
+    def topk(self, q: torch.Tensor, k: int, *, nprobe: int, normalize_q: bool = True,
+             target_ids: Optional[torch.Tensor] = None, exclude_ids: Optional[torch.Tensor] = None,
+             tag_filter: Optional[torch.Tensor] = None, after_scores: Optional[torch.Tensor] = None,
+             after_ids: Optional[torch.Tensor] = None, bias_weight: Union[None, float, torch.Tensor] = None):
+        """(item_ids int64 [Q, k], scores f32 [Q, k], rank, target_score), the order of
+        ``ShardedItemCatalogue.topk``: per query the k first, under (score descending, id ascending), of the
+        items that lie in the min(``nprobe``, nlist) nearest lists of any shard (``nprobe`` is per shard), are
+        not among its ``exclude_ids``, pass its ``tag_filter`` and lie strictly behind (``after_scores``,
+        ``after_ids``), then (0, -inf).  ``tag_filter``, the cursor and ``bias_weight`` need ``with_filters()`` or
+        ``with_deep()`` shards, which also score with the shards' bias where they carry one; k reaches 128, on
+        ``with_deep()`` shards 1,024.  See the class for the contract against the flat catalogue.
+        With ``target_ids`` int64 [Q], ``target_score`` is the target's score from the shard that holds it
+        (-inf where none does), whether or not its list is probed, and ``rank`` (int64) the number of eligible
+        items of the probed lists, other than the target, that score strictly above it, -1 where no shard
+        holds the target: with every list probed the flat catalogue's rank, with fewer a lower bound of it.
+        Else both are None.  The outputs are on ``q``'s device."""
+        return self._scan(q, k, nprobe, normalize_q, target_ids, exclude_ids, tag_filter, after_scores, after_ids,
+                          bias_weight, True)
+
+    def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, nprobe: int,
+                     exclude_ids: Optional[torch.Tensor] = None, tag_filter: Optional[torch.Tensor] = None,
+                     bias_weight: Optional[float] = None) -> torch.Tensor:
+        """``ItemCatalogue.target_ranks`` over the probed lists (int64): ``topk``'s ``rank`` at k = 1, on the
+        plain dots unless ``bias_weight`` is given."""
+        return self._scan(q, 1, nprobe, True, target_ids, exclude_ids, tag_filter, None, None, bias_weight,
+                          bias_weight is not None)[2]
+
+    def recall(self, q: torch.Tensor, k: int, nprobe: int, **filters) -> float:
+        """The mean over the queries of the fraction of the flat union's list, ``to_flat().topk(q, k,
+        **filters)`` (for plain shards on the plain dots), that ``topk(q, k, nprobe=nprobe, **filters)``
+        returns, over the queries whose flat list is not empty (1.0 where every one is).  Never decreases
+        in ``nprobe``; 1.0 once every list of every shard is probed.  For a catalogue without a group."""
+        if self._flat is None:
+            flat = self.to_flat()
+            self._flat = flat if self.scans_filters else ItemCatalogue(flat.ids, flat.emb, flat.tags)
+        want = self._flat.topk(q, k, **filters)[0]
+        got = self.topk(q, k, nprobe=nprobe, **filters)[0]
+        real = want != 0
+        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
+        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
+                         for i in range(0, want.shape[0], rows)]).double()
+        n = real.sum(dim=1)
+        if not bool((n > 0).any()):
+            return 1.0
+        return float((hit[n > 0] / n[n > 0].double()).mean())
 
 
 def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:

@@ -406,11 +406,31 @@ class LTHMModelWrapper(BaseModelWrapper):
         with the meaning they have on a ``with_filters()`` view: the e4m3 scan of the probed lists gives the
         ``shortlist`` best eligible rows, which are re-scored with the exact rows and the prior (k <= 1024), the
         ``with_deep()`` list wherever the shortlist holds it.  ``heads``, ``after`` and ``diversity`` / ``pool`` /
-        ``group_cap`` are refused by name.  ``exclude_seen`` is ``catalogue_metrics``' name for
+        ``group_cap`` are refused by name.
+        A ``ShardedClusteredItemCatalogue`` takes ``nprobe`` per shard (every shard probes its own
+        min(nprobe, nlist) nearest lists) and the arguments a clustered catalogue of its shards' kind takes,
+        but ``heads`` and ``diversity`` / ``pool`` / ``group_cap``, which it refuses.  ``exclude_seen`` is ``catalogue_metrics``' name for
         ``exclude_history`` and means the same here, for every catalogue."""
         from .retrieval import (ClusteredItemCatalogue, ItemCatalogue, QuantizedClusteredItemCatalogue,
-                                QuantizedItemCatalogue)
+                                QuantizedItemCatalogue, ShardedClusteredItemCatalogue)
         exclude_history = bool(exclude_history) or bool(exclude_seen)
+        sharded_ivf = isinstance(catalogue, ShardedClusteredItemCatalogue)
+        if sharded_ivf:
+            # the keyword checks of a clustered catalogue of the shards' kind; nprobe is per shard
+            if heads is not None:
+                raise ValueError("retrieve with a sharded clustered catalogue does not take heads: several queries "
+                                 "per user over clustered shards are not supported (use catalogue.to_flat() for it)")
+            given = {"diversity": diversity, "pool": pool, "group_cap": group_cap}
+            if not catalogue.scans_filters:
+                given.update({"tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
+                              "bias_weight": bias_weight})
+            bad = [name for name, v in given.items() if v is not None]
+            if bad:
+                raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
+                                 "use catalogue.to_flat() for it")
+            if nprobe is None:
+                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
+            catalogue._check_call(k, nprobe)
         clustered = isinstance(catalogue, ClusteredItemCatalogue)
         quantized = isinstance(catalogue, QuantizedItemCatalogue)
         if isinstance(catalogue, QuantizedClusteredItemCatalogue):
@@ -481,7 +501,7 @@ class LTHMModelWrapper(BaseModelWrapper):
             if nprobe is None:
                 raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
             catalogue._check_call(k, nprobe)
-        elif nprobe is not None:
+        elif nprobe is not None and not sharded_ivf:
             raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
         diversify = diversity is not None or group_cap is not None
         if diversify:
@@ -545,6 +565,11 @@ class LTHMModelWrapper(BaseModelWrapper):
             after_ids = after_ids.to(q.device).contiguous()
         if isinstance(bias_weight, torch.Tensor):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
+        if sharded_ivf:
+            item_ids, scores, _, _ = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen,
+                                                    tag_filter=filt, after_scores=after_scores, after_ids=after_ids,
+                                                    bias_weight=bias_weight)
+            return {"item_ids": item_ids, "scores": scores}
         if clustered and catalogue.scans_filters:
             scores, item_ids = catalogue.topk(q, pool if diversify else k, nprobe=nprobe, normalize_q=True,
                                               exclude_ids=seen, tag_filter=filt, after_scores=after_scores,
@@ -573,7 +598,7 @@ class LTHMModelWrapper(BaseModelWrapper):
     @torch.no_grad()
     def catalogue_metrics(self, output, catalogue, ks: Optional[List[int]] = None, head: int = 0,
                           exclude_seen: bool = False, same_tags_mask: Optional[int] = None,
-                          bias_weight: Optional[float] = None) -> Dict[str, float]:
+                          bias_weight: Optional[float] = None, nprobe: Optional[int] = None) -> Dict[str, float]:
         """Hit rate and hit position of one forward against the whole catalogue: the in-batch
         metrics of wrapper.py:228-238 with every catalogue item as a negative.  Queries are the
         positions t whose target ``current_token_ids[:, t + lookahead[head]]`` is a non-pad
@@ -593,8 +618,22 @@ class LTHMModelWrapper(BaseModelWrapper):
         With ``bias_weight`` (a float; the catalogue must carry a bias) every score, the target's
         included, is fma(bias_weight, bias[j], q . e_j): the hit position under the prior.  The
         keys then take the suffix ``_biased``, after ``_unseen`` / ``_tagged``.  Without it the
-        metrics are those of the plain dot, whether or not the catalogue carries a bias."""
-        from .retrieval import ClusteredItemCatalogue, QuantizedClusteredItemCatalogue
+        metrics are those of the plain dot, whether or not the catalogue carries a bias.
+
+        A ``ShardedClusteredItemCatalogue`` takes ``nprobe`` (per shard): the hit position is then the
+        number of items of the probed lists scoring strictly above the target, the flat catalogue's once
+        every list is probed and a lower bound of it before (the target's own list need not be probed)."""
+        from .retrieval import ClusteredItemCatalogue, QuantizedClusteredItemCatalogue, ShardedClusteredItemCatalogue
+        sharded_ivf = isinstance(catalogue, ShardedClusteredItemCatalogue)
+        if sharded_ivf:
+            if nprobe is None:
+                raise ValueError("catalogue_metrics with a sharded clustered catalogue takes nprobe, the lists each "
+                                 "query scans in every shard")
+            catalogue._check_call(1, nprobe)
+            if not catalogue.scans_filters and (same_tags_mask is not None or bias_weight is not None):
+                raise ValueError("same_tags_mask / bias_weight take with_filters() or with_deep() shards")
+        elif nprobe is not None:
+            raise ValueError("nprobe given, but this catalogue is not a sharded clustered one")
         if isinstance(catalogue, ClusteredItemCatalogue):
             raise ValueError("catalogue_metrics counts exact ranks, which take the flat scan: pass catalogue.to_flat()")
         if isinstance(catalogue, QuantizedClusteredItemCatalogue):
@@ -631,8 +670,9 @@ class LTHMModelWrapper(BaseModelWrapper):
             filt = catalogue.filter_like(tid, same_tags_mask)
         # the scans are the catalogue's (target_ranks): one K.retrieve_topk with k = 1 per call for an
         # ItemCatalogue, one per shard and a merge for a ShardedItemCatalogue
+        kw = {"nprobe": nprobe} if sharded_ivf else {}
         if not exclude_seen:
-            rank = catalogue.target_ranks(q, tid, tag_filter=filt, bias_weight=bias_weight)
+            rank = catalogue.target_ranks(q, tid, tag_filter=filt, bias_weight=bias_weight, **kw)
         else:
             T = ids.shape[1]
             if T > K.RETRIEVE_MAX_EXCLUDE:
@@ -645,7 +685,7 @@ class LTHMModelWrapper(BaseModelWrapper):
                 xi = torch.where(col[None, :] <= t[:, None], ids[b], torch.zeros_like(ids[b])).contiguous()
                 ranks.append(catalogue.target_ranks(q[lo:lo + 16384], tid[lo:lo + 16384], exclude_ids=xi,
                                                     tag_filter=None if filt is None else filt[lo:lo + 16384],
-                                                    bias_weight=bias_weight))
+                                                    bias_weight=bias_weight, **kw))
             rank = torch.cat(ranks)
         pos = rank.float()
         res["catalogue_queries" + sfx] = n

@@ -482,6 +482,75 @@ def child_shards(name: str, N: int, k: int, reps: int, S: int) -> None:
     print(json.dumps(out), flush=True)
 
 
+def child_shards_ivf(name: str, N: int, k: int, reps: int, S: int, L: int) -> None:
+    """The shards leg: N rows in S id-range shards on one device, L lists per shard, nprobe 1 / 4 / 8 per
+    shard.  Arms: the fused call (ShardedClusteredItemCatalogue.topk), the flat sharded scan
+    (ShardedItemCatalogue over the same shards) and a Python loop of single-catalogue clustered calls plus
+    K.retrieve_merge_shards; recall@k of the clustered list against the flat list."""
+    import time
+    import torch
+    from recommendations_amd import kernels as K
+    from recommendations_amd.models.lthm.sequence.retrieval import (ItemCatalogue, ShardedClusteredItemCatalogue,
+                                                                    ShardedItemCatalogue)
+    Q = SHAPES[name]
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(1)
+    C, sigma = 4096, 0.7 / 128 ** 0.5
+    centres = torch.nn.functional.normalize(torch.randn((C, 128), generator=g, device=dev), dim=-1)
+    items = torch.empty((N, 128), dtype=torch.bfloat16, device=dev)
+    for lo in range(0, N, 1 << 18):
+        n = min(1 << 18, N - lo)
+        x = centres[torch.randint(0, C, (n,), generator=g, device=dev)] + sigma * torch.randn((n, 128), generator=g, device=dev)
+        items[lo:lo + n] = torch.nn.functional.normalize(x, dim=-1).to(torch.bfloat16)
+    xq = centres[torch.randint(0, C, (Q,), generator=g, device=dev)] + sigma * torch.randn((Q, 128), generator=g, device=dev)
+    q_bf = torch.nn.functional.normalize(xq, dim=-1).to(torch.bfloat16)
+    flat = ItemCatalogue(torch.arange(1, N + 1, dtype=torch.int64, device=dev) * 3, items)
+    parts = flat.split(S)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    cl = [p.cluster(L, iters=5, seed=0, sample=min(len(p), 1 << 17)) for p in parts]
+    torch.cuda.synchronize()
+    build_s = time.time() - t0
+    fused, sharded_flat = ShardedClusteredItemCatalogue(cl), ShardedItemCatalogue(parts)
+    want = flat.topk(q_bf, k, normalize_q=False)[0]
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1), (time.perf_counter() - t) * 1e3
+
+    for P in (1, 4, 8):
+        def loop():
+            lists = [c.topk(q_bf, k, nprobe=min(P, c.nlist), normalize_q=False) for c in cl]
+            return K.retrieve_merge_shards(torch.stack([x[0] for x in lists]), torch.stack([x[1] for x in lists]))
+
+        arms = [("fused", lambda: fused.topk(q_bf, k, nprobe=P, normalize_q=False), []),
+                ("sharded_flat", lambda: sharded_flat.topk(q_bf, k, normalize_q=False), []),
+                ("loop", loop, [])]
+        for _ in range(2):
+            for _, fn, _ in arms:
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for _, fn, times in arms:
+                times.append(timed(fn))
+        out = {"shape": name, "mode": "shards_ivf", "Q": Q, "N": N, "k": k, "S": S, "L": L, "nprobe": P, "reps": reps,
+               "build_s": round(build_s, 2)}
+        for key, _, times in arms:
+            dev_ms, wall_ms = [t[0] for t in times], [t[1] for t in times]
+            out.update({f"{key}_ms": round(statistics.median(dev_ms), 4), f"{key}_min_ms": round(min(dev_ms), 4),
+                        f"{key}_max_ms": round(max(dev_ms), 4), f"{key}_wall_ms": round(statistics.median(wall_ms), 4)})
+        a, b = fused.topk(q_bf, k, nprobe=P, normalize_q=False), loop()
+        out["check_equal"] = bool(torch.equal(a[0], b[1]) and torch.equal(a[1].view(torch.int32), b[0].view(torch.int32)))
+        hit = (want[:, :, None] == a[0][:, None, :]).any(dim=2).float().sum(dim=1) / k
+        out[f"recall_at_{k}"] = round(float(hit.mean()), 4)
+        print(json.dumps(out), flush=True)
+
+
 def child_ivf(name: str, N: int, k: int, reps: int, L: int) -> None:
     import time
     import torch
@@ -1067,6 +1136,9 @@ def main() -> int:
                     help="also time the call with a random f32 bias per row and weight 1 next to the plain call")
     ap.add_argument("--shards", type=int, default=0,
                     help="a mode of its own: the catalogue as S shards (1..64) on this device against the unsharded call")
+    ap.add_argument("--shards-ivf", type=int, default=0,
+                    help="with --shards S: S clustered shards of this many lists each (the sharded clustered call "
+                         "against the flat sharded scan and a Python loop of clustered calls)")
     ap.add_argument("--ivf", type=int, default=0,
                     help="a mode of its own: the catalogue clustered into L lists, nprobe in {1, 8, 32, 64}, against the flat call")
     ap.add_argument("--ivf-filt", type=int, default=0,
@@ -1136,6 +1208,11 @@ def main() -> int:
     if a.child and a.diversify:
         child_diversify(a.n_items, a.k, a.reps)
         return 0
+    if a.shards_ivf < 0 or (a.shards_ivf and (not a.shards or not 1 <= a.k <= 128)):
+        raise SystemExit("--shards-ivf takes 0 (off) or a number of lists per shard, goes with --shards and takes --k in 1..128")
+    if a.child and a.shards and a.shards_ivf:
+        child_shards_ivf(a.child, a.n_items, a.k, a.reps, a.shards, a.shards_ivf)
+        return 0
     if a.child and a.shards:
         child_shards(a.child, a.n_items, a.k, a.reps, a.shards)
         return 0
@@ -1154,7 +1231,7 @@ def main() -> int:
                                  "--group", str(a.group), "--tags", str(a.tags), "--deep", str(a.deep), "--shards", str(a.shards),
                                  "--ivf", str(a.ivf), "--q8", str(a.q8), "--ivf-filt", str(a.ivf_filt),
                                  "--ivf-deep", str(a.ivf_deep), "--ivf-heads", str(a.ivf_heads), "--ivf-q8", str(a.ivf_q8),
-                                 "--baseline-lib", a.baseline_lib]
+                                 "--shards-ivf", str(a.shards_ivf), "--baseline-lib", a.baseline_lib]
                                 + (["--after"] if a.after else []) + (["--bias"] if a.bias else [])
                                 + (["--diversify"] if a.diversify else []),
                                 timeout=a.step_timeout).returncode
