@@ -284,6 +284,36 @@ int lthm_amax(const void* x, int32_t dtype, int64_t n, int32_t* amax, void* stre
 /* Supported shapes: lthm_mlp_supported(D, HID) (D 128 or 256, HID % 32 == 0).  */
 /* ------------------------------------------------------------------------- */
 int lthm_mlp_supported(int32_t D, int32_t HID);
+/* The launch geometry of one fused-MLP entry point on a device of `cus` compute units, decided
+ * on the host from the numbers alone (no GPU call).  The six launchers and
+ * lthm_mlp_wgrad_ws_bytes take their geometry from lthm_mlp_plan(entry, M, D, HID, the device's
+ * CU count); the return value is nonzero (1) for a shape the entry refuses (the plan is then
+ * undefined): D not 128 / 256, HID not a multiple of 32 in 32 .. 8192, M < 0, HID > 4096 for
+ * BWD_HIDDEN and BWD_DX, HID % 128 != 0 for WGRAD, or static + dynamic LDS above the 160 KiB a
+ * gfx950 workgroup can hold.  lthm_mlp_supported(D, HID) is true where the FWD and the BWD plan
+ * both accept. */
+#define LTHM_MLP_FWD 0         /* lthm_mlp_fwd:        mlp_fwd_k<D, 8>  */
+#define LTHM_MLP_FWD_LN 1      /* lthm_mlp_fwd_ln:     mlp_fwd_k<D, 8>, ln_2 in the prologue */
+#define LTHM_MLP_BWD 2         /* lthm_mlp_bwd:        mlp_bwd_k<D, 4, true> */
+#define LTHM_MLP_BWD_HIDDEN 3  /* lthm_mlp_bwd_hidden: mlp_bwdp_k<D, 8> */
+#define LTHM_MLP_BWD_DX 4      /* lthm_mlp_bwd_dx:     mlp_bwdx_k<D, 4> */
+#define LTHM_MLP_WGRAD 5       /* lthm_mlp_wgrad:      mlp_wgrad_k<D, 4, FULL> + mlp_wgrad_fold_k */
+#define LTHM_MLP_LDS_MAX 163840 /* bytes of LDS one gfx950 workgroup can hold */
+typedef struct lthm_mlp_plan_out {
+  int32_t waves;      /* waves per workgroup */
+  int32_t tile_rows;  /* token rows per tile: 32 x waves; WGRAD: 32 (the staged token tile) */
+  int32_t grid;       /* workgroups of the main kernel (0: M == 0, it is not launched) */
+  int32_t max_tiles;  /* the most tiles one workgroup walks (WGRAD: token tiles of the longest slice) */
+  int32_t nslice;     /* WGRAD: token slices (partial slabs), 0 elsewhere */
+  int32_t ngroup;     /* WGRAD: hidden groups of 32 x waves units, 0 elsewhere */
+  int32_t full;       /* WGRAD: 1 when M % 32 == 0 (mlp_wgrad_k<.., true>, no row mask) */
+  int32_t pad0;
+  int64_t ntiles;     /* tiles of tile_rows rows over all M */
+  int64_t ws_bytes;   /* WGRAD: workspace bytes, 0 elsewhere */
+  int64_t lds_static;   /* bytes of the kernel's __shared__ arrays */
+  int64_t lds_dynamic;  /* bytes of dynamic LDS passed at the launch */
+} lthm_mlp_plan_out;
+int lthm_mlp_plan(int32_t entry, int64_t M, int32_t D, int32_t HID, int32_t cus, lthm_mlp_plan_out* plan);
 /* out f32 [M, D] = res1 [+ res2] + c_proj(GELU(c_fc(x))); res1 / res2 f32 [M, D] or NULL
  * (replaces TransformerBlock's x + mlp(ln_2 x), commons/transformers/layers.py:371). */
 int lthm_mlp_fwd(const void* x, int64_t M, int32_t D, int32_t HID, const void* W1, const float* b1,

@@ -360,6 +360,7 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
   };
   int g = 0;
   int64_t tix = 0;
+  bool fed = true;  // the previous step issued the DMAs of a further chunk (workgroup-uniform)
   for (int64_t t0 = rs; t0 < re; t0 += TR, ++tix) {
     const int64_t lim = min(t0 + TR, re), rb = t0 + 32 * wave;
     const bool active = rb < lim;  // wave-uniform: a wave past the tile's rows only streams weights
@@ -372,14 +373,20 @@ __global__ __launch_bounds__(64 * NW, 1) void mlp_fwd_k(MlpArgs a) {
     for (int j = 0; j < NC; ++j, ++g) {
       // retire chunk g; at prefetch distance 2 chunk g + 1 stays in flight (a tile's first step
       // drains: the x / residual / output accesses were issued behind the DMAs)
-      if (j == 0) wait_vm<0>();
+      // vmcnt(DPC) retires chunk g only while the DPC newest operations are chunk g + 1's DMAs,
+      // issued by the previous step.  The stream's last step follows a step that issued none
+      // (chunk g + 1 does not exist): the newest DPC operations are then chunk g's own, which
+      // vmcnt(DPC) would leave in flight before the LDS reads below, so that step drains too
+      // (NC >= 3; at NC <= 2 the last step's chunk was retired by a tile's first step)
+      if (j == 0 || !fed) wait_vm<0>();
       else wait_vm<DPC>();
       __syncthreads();  // chunk g landed everywhere; every wave is done with chunk g + DIST - NS
       asm volatile("" ::: "memory");
       {
         // chunk g + DIST: of this tile, or the next tile's (same weights, chunk index wraps)
         const int64_t cg = (int64_t)j + DIST;
-        if (tix + cg / NC < ntile_wg) {
+        fed = tix + cg / NC < ntile_wg;
+        if (fed) {
           const int jn = (int)(cg % NC);
           unsigned char* dst = img[(g + DIST) % NS][0];
           mlp_dma32<D, NTH>(dst, a.W1 + (int64_t)jn * 32 * D, tid);
@@ -1025,53 +1032,124 @@ __global__ __launch_bounds__(256) void mlp_wgrad_fold_k(const float* __restrict_
 
 using namespace lthm;
 
-extern "C" int lthm_mlp_supported(int32_t D, int32_t HID) {
-  return (D == 128 || D == 256) && HID >= 32 && HID % 32 == 0 && HID <= 8192;
+// waves per workgroup of each kernel (a wave owns 32 token rows; the weight-gradient kernel: 32
+// hidden units, one wave per SIMD: the two [32 x D] sums are 2 D / 2 registers)
+constexpr int MLP_FWD_NW = 8, MLP_BWD_NW = 4, MLP_BWDP_NW = 8, MLP_BWDX_NW = 4, MLP_WG_NW = 4;
+
+// The launch geometry of every entry point, on the host alone (include/lthm.h).  The LDS sums
+// restate the kernels' __shared__ arrays (IMG = 32 x D bf16, a 4-KiB strip per wave: keep them in
+// step with the kernels); tests/test_mlp_host.py holds the plan to a restatement of these rules.
+extern "C" int lthm_mlp_plan(int32_t entry, int64_t M, int32_t D, int32_t HID, int32_t cus, lthm_mlp_plan_out* p) {
+  LTHM_REQUIRE(p != nullptr && cus >= 1 && M >= 0);
+  LTHM_REQUIRE((D == 128 || D == 256) && HID >= 32 && HID % 32 == 0 && HID <= 8192);
+  *p = lthm_mlp_plan_out{};
+  const int64_t img = 32 * (int64_t)D * 2, strip = 32 * 32 * 4;
+  int nw = 0;
+  switch (entry) {
+    case LTHM_MLP_FWD:
+    case LTHM_MLP_FWD_LN:  // 3-slot ring of (W1_j, W2T_j), strips; dynamic: b1, b2, ln w, ln b
+      nw = MLP_FWD_NW;
+      p->lds_static = 3 * 2 * img + nw * strip;
+      p->lds_dynamic = ((int64_t)HID + 3 * D) * 4;
+      break;
+    case LTHM_MLP_BWD:  // 2-slot ring, strips, b1s[8192]
+      nw = MLP_BWD_NW;
+      p->lds_static = 2 * 2 * img + nw * strip + 8192 * 4;
+      break;
+    case LTHM_MLP_BWD_HIDDEN:  // 2-slot ring, bf16 g / dp strips, b1s[4096]
+      LTHM_REQUIRE(HID <= 4096);
+      nw = MLP_BWDP_NW;
+      p->lds_static = 2 * 2 * img + nw * strip + 4096 * 4;
+      break;
+    case LTHM_MLP_BWD_DX:  // 4-slot ring, strips, b1s[4096]
+      LTHM_REQUIRE(HID <= 4096);
+      nw = MLP_BWDX_NW;
+      p->lds_static = 4 * 2 * img + nw * strip + 4096 * 4;
+      break;
+    case LTHM_MLP_WGRAD:  // 3-slot ring of (x, dy) tiles, each wave's W2T_j image
+      LTHM_REQUIRE(HID % (32 * MLP_WG_NW) == 0);
+      nw = MLP_WG_NW;
+      p->lds_static = 3 * 2 * img + nw * img;
+      break;
+    default:
+      return (int)hipErrorInvalidValue;
+  }
+  LTHM_REQUIRE(p->lds_static + p->lds_dynamic <= LTHM_MLP_LDS_MAX);
+  p->waves = nw;
+  if (entry == LTHM_MLP_WGRAD) {
+    p->tile_rows = 32;
+    p->ntiles = (M + 31) / 32;
+    p->ngroup = HID / (32 * nw);
+    // one workgroup per CU: slices x groups ~ the CU count, at least one token tile per slice
+    const int ns = std::max(1, cus / std::max(1, p->ngroup));
+    p->nslice = (int)std::max<int64_t>(1, std::min<int64_t>(ns, p->ntiles));
+    p->full = M % 32 == 0;
+    p->ws_bytes = (int64_t)p->nslice * HID * (2 * (int64_t)D + 1) * 4;
+    p->grid = M > 0 ? p->nslice * p->ngroup : 0;
+    p->max_tiles = (int)((p->ntiles + p->nslice - 1) / p->nslice);
+    return 0;
+  }
+  // persistent over contiguous row ranges: workgroup b owns rows M b / grid .. M (b + 1) / grid
+  p->tile_rows = 32 * nw;
+  p->ntiles = (M + p->tile_rows - 1) / p->tile_rows;
+  p->grid = (int)std::min<int64_t>(p->ntiles, (int64_t)cus);
+  if (p->grid > 0) {
+    const int64_t rows = (M + p->grid - 1) / p->grid;  // the longest range
+    p->max_tiles = (int)((rows + p->tile_rows - 1) / p->tile_rows);
+  }
+  return 0;
 }
 
-static int mlp_fwd_launch(MlpArgs a, int D, void* stream);
+extern "C" int lthm_mlp_supported(int32_t D, int32_t HID) {
+  // what both the forward and the backward take: at D = 256 the forward's dynamic LDS (b1) ends
+  // this at HID = 7,424
+  lthm_mlp_plan_out p;
+  return lthm_mlp_plan(LTHM_MLP_FWD, 0, D, HID, 1, &p) == 0 && lthm_mlp_plan(LTHM_MLP_BWD, 0, D, HID, 1, &p) == 0;
+}
+
+static int mlp_fwd_launch(MlpArgs a, int D, const lthm_mlp_plan_out& pl, void* stream);
 
 extern "C" int lthm_mlp_fwd_ln(const float* x, const float* ln_w, const float* ln_b, int64_t M, int32_t D,
                                int32_t HID, const void* W1, const float* b1, const void* W2T, const float* b2,
                                const float* res1, const float* res2, float* out, void* h_out, float* mean,
                                float* rstd, void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && M >= 0);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_FWD_LN, M, D, HID, cu_count(), &pl)) return rc;
+  if (M == 0) return 0;  // nothing to do: an empty tensor's pointers may be null
   LTHM_REQUIRE(x && ln_w && W1 && W2T && out);
   LTHM_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)W1 % 16) == 0 && ((uintptr_t)W2T % 16) == 0 &&
                ((uintptr_t)b1 % 16) == 0 && ((uintptr_t)h_out % 16) == 0);
-  if (M == 0) return 0;
   MlpArgs a{};
   a.X = nullptr; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1; a.b2 = b2; a.res1 = res1; a.res2 = res2; a.out = out;
   a.M = M; a.HID = HID;
   a.x32 = x; a.ln_w = ln_w; a.ln_b = ln_b; a.h_out = (bf16_t*)h_out; a.mean = mean; a.rstd = rstd;
-  return mlp_fwd_launch(a, D, stream);
+  return mlp_fwd_launch(a, D, pl, stream);
 }
 
 extern "C" int lthm_mlp_fwd(const void* X, int64_t M, int32_t D, int32_t HID, const void* W1, const float* b1,
                             const void* W2T, const float* b2, const float* res1, const float* res2, float* out,
                             void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && M >= 0);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_FWD, M, D, HID, cu_count(), &pl)) return rc;
+  if (M == 0) return 0;  // nothing to do: an empty tensor's pointers may be null
   LTHM_REQUIRE(X && W1 && W2T && out);
   LTHM_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)W1 % 16) == 0 && ((uintptr_t)W2T % 16) == 0 &&
                ((uintptr_t)b1 % 16) == 0);
-  if (M == 0) return 0;
   MlpArgs a{};
   a.X = (const bf16_t*)X; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1; a.b2 = b2; a.res1 = res1; a.res2 = res2; a.out = out;
   a.M = M; a.HID = HID;
-  return mlp_fwd_launch(a, D, stream);
+  return mlp_fwd_launch(a, D, pl, stream);
 }
 
-static int mlp_fwd_launch(MlpArgs a, int D, void* stream) {
-  const int64_t M = a.M;
-  const int HID = a.HID;
+static int mlp_fwd_launch(MlpArgs a, int D, const lthm_mlp_plan_out& pl, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const size_t dyn = (size_t)(HID + 3 * D) * 4;
+  const size_t dyn = (size_t)pl.lds_dynamic;
   // 8 waves: one workgroup per CU, 256-row tiles
-  constexpr int NW = 8;
-  a.ntiles = (int)((M + 32 * NW - 1) / (32 * NW));
-  const int grid = (int)std::min<int64_t>(a.ntiles, (int64_t)cu_count());
+  constexpr int NW = MLP_FWD_NW;
+  a.ntiles = (int)pl.ntiles;
+  const int grid = pl.grid;
   if (D == 256) hipLaunchKernelGGL((mlp_fwd_k<256, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
   else hipLaunchKernelGGL((mlp_fwd_k<128, NW>), dim3(grid), dim3(64 * NW), dyn, s, a);
   LTHM_CHECK_LAUNCH();
@@ -1081,12 +1159,13 @@ static int mlp_fwd_launch(MlpArgs a, int D, void* stream) {
 extern "C" int lthm_mlp_bwd(const void* X, const void* dY, int64_t M, int32_t D, int32_t HID, const void* W1,
                             const float* b1, const void* W2T, void* dX, int32_t dx_dtype, void* G, void* dP,
                             void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && M >= 0);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_BWD, M, D, HID, cu_count(), &pl)) return rc;
+  if (M == 0) return 0;  // nothing to do: an empty tensor's pointers may be null
   LTHM_REQUIRE(X && dY && W1 && W2T && dX && G && dP && (dx_dtype == LTHM_F32 || dx_dtype == LTHM_BF16));
   LTHM_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)W1 % 16) == 0 &&
                ((uintptr_t)W2T % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ((uintptr_t)dX % 16) == 0 &&
                ((uintptr_t)G % 16) == 0 && ((uintptr_t)dP % 16) == 0);
-  if (M == 0) return 0;
   MlpBwdArgs a;
   a.X = (const bf16_t*)X; a.dY = (const bf16_t*)dY; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1; a.G = (bf16_t*)G; a.dP = (bf16_t*)dP;
@@ -1094,45 +1173,31 @@ extern "C" int lthm_mlp_bwd(const void* X, const void* dY, int64_t M, int32_t D,
   a.dXf = (float*)dX; a.dXb = (bf16_t*)dX;
   a.M = M; a.HID = HID;
   hipStream_t s = (hipStream_t)stream;
-  constexpr int NW = 4;
-  const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
+  constexpr int NW = MLP_BWD_NW;
+  const int grid = pl.grid;
   if (D == 256) hipLaunchKernelGGL((mlp_bwd_k<256, NW, true>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwd_k<128, NW, true>), dim3(grid), dim3(64 * NW), 0, s, a);
   LTHM_CHECK_LAUNCH();
   return 0;
 }
 
-// waves per weight-gradient workgroup (one per SIMD: the two [32 x D] sums are 2 D / 2 registers)
-constexpr int MLP_WG_NW = 4;
-
-static void mlp_wgrad_geometry(int64_t M, int D, int HID, int* nslice, int* ngroup) {
-  *ngroup = HID / (32 * MLP_WG_NW);
-  const int64_t ntile = (M + 31) / 32;
-  // one workgroup per CU: slices x groups ~ the CU count, at least one token tile per slice
-  int ns = std::max(1, cu_count() / std::max(1, *ngroup));
-  *nslice = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ntile));
-  (void)D;
-}
-
 extern "C" int64_t lthm_mlp_wgrad_ws_bytes(int64_t M, int32_t D, int32_t HID) {
-  if (!lthm_mlp_supported(D, HID) || HID % (32 * MLP_WG_NW) || M < 0) return -1;
-  int ns, ng;
-  mlp_wgrad_geometry(M, D, HID, &ns, &ng);
-  return (int64_t)ns * HID * (2 * (int64_t)D + 1) * 4;
+  lthm_mlp_plan_out pl;
+  if (lthm_mlp_plan(LTHM_MLP_WGRAD, M, D, HID, cu_count(), &pl)) return -1;
+  return pl.ws_bytes;
 }
 
 extern "C" int lthm_mlp_wgrad(const void* X, const void* dY, int64_t M, int32_t D, int32_t HID, const void* W1,
                               const float* b1, const void* W2T, float* dW1, float* dW2, float* db1, void* workspace,
                               int64_t ws_bytes, void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && HID % (32 * MLP_WG_NW) == 0 && M >= 0);
-  LTHM_REQUIRE(X && dY && W1 && W2T && dW1 && dW2 && workspace);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_WGRAD, M, D, HID, cu_count(), &pl)) return rc;
+  LTHM_REQUIRE((M == 0 || (X && dY)) && W1 && W2T && dW1 && dW2 && workspace);  // M == 0: zeros
   LTHM_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)W1 % 16) == 0 &&
                ((uintptr_t)W2T % 16) == 0 && ((uintptr_t)workspace % 16) == 0);
-  LTHM_REQUIRE(ws_bytes >= lthm_mlp_wgrad_ws_bytes(M, D, HID));
+  LTHM_REQUIRE(ws_bytes >= pl.ws_bytes);
   hipStream_t s = (hipStream_t)stream;
-  int ns, ng;
-  mlp_wgrad_geometry(M, D, HID, &ns, &ng);
+  const int ns = pl.nslice, ng = pl.ngroup;
   MlpWgArgs a{};
   a.X = (const bf16_t*)X; a.dY = (const bf16_t*)dY; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1;
@@ -1142,7 +1207,7 @@ extern "C" int lthm_mlp_wgrad(const void* X, const void* dY, int64_t M, int32_t 
   a.M = M; a.HID = HID; a.nslice = ns; a.ngroup = ng;
   if (M > 0) {
     // every token tile full (M % 32 == 0, C2's 528,384 rows): no per-element row mask
-    const bool full = M % 32 == 0;
+    const bool full = pl.full != 0;
     if (D == 256) {
       if (full) hipLaunchKernelGGL((mlp_wgrad_k<256, MLP_WG_NW, true>), dim3(ns * ng), dim3(64 * MLP_WG_NW), 0, s, a);
       else hipLaunchKernelGGL((mlp_wgrad_k<256, MLP_WG_NW, false>), dim3(ns * ng), dim3(64 * MLP_WG_NW), 0, s, a);
@@ -1152,7 +1217,7 @@ extern "C" int lthm_mlp_wgrad(const void* X, const void* dY, int64_t M, int32_t 
     }
     LTHM_CHECK_LAUNCH();
   } else {
-    LTHM_REQUIRE(hipMemsetAsync(workspace, 0, (size_t)lthm_mlp_wgrad_ws_bytes(M, D, HID), s) == hipSuccess);
+    LTHM_REQUIRE(hipMemsetAsync(workspace, 0, (size_t)pl.ws_bytes, s) == hipSuccess);
   }
   hipLaunchKernelGGL(mlp_wgrad_fold_k, dim3(D / 32, HID / 32), dim3(256), 0, s, (const float*)a.dW1p,
                      (const float*)a.dW2Tp, (const float*)a.db1p, ns, HID, D, dW1, dW2, db1);
@@ -1162,11 +1227,12 @@ extern "C" int lthm_mlp_wgrad(const void* X, const void* dY, int64_t M, int32_t 
 
 extern "C" int lthm_mlp_bwd_dx(const void* X, const void* dY, int64_t M, int32_t D, int32_t HID, const void* W1,
                                const float* b1, const void* W2T, void* dX, int32_t dx_dtype, void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && M >= 0);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_BWD_DX, M, D, HID, cu_count(), &pl)) return rc;
+  if (M == 0) return 0;  // nothing to do: an empty tensor's pointers may be null
   LTHM_REQUIRE(X && dY && W1 && W2T && dX && (dx_dtype == LTHM_F32 || dx_dtype == LTHM_BF16));
   LTHM_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)W1 % 16) == 0 &&
                ((uintptr_t)W2T % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ((uintptr_t)dX % 16) == 0);
-  if (M == 0) return 0;
   MlpBwdArgs a{};
   a.X = (const bf16_t*)X; a.dY = (const bf16_t*)dY; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1;
@@ -1174,10 +1240,8 @@ extern "C" int lthm_mlp_bwd_dx(const void* X, const void* dY, int64_t M, int32_t
   a.dXf = (float*)dX; a.dXb = (bf16_t*)dX;
   a.M = M; a.HID = HID;
   hipStream_t s = (hipStream_t)stream;
-  constexpr int NW = 4;
-  const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
-  LTHM_REQUIRE(HID <= 4096);
+  constexpr int NW = MLP_BWDX_NW;
+  const int grid = pl.grid;
   if (D == 256) hipLaunchKernelGGL((mlp_bwdx_k<256, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwdx_k<128, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   LTHM_CHECK_LAUNCH();
@@ -1186,20 +1250,20 @@ extern "C" int lthm_mlp_bwd_dx(const void* X, const void* dY, int64_t M, int32_t
 
 extern "C" int lthm_mlp_bwd_hidden(const void* X, const void* dY, int64_t M, int32_t D, int32_t HID, const void* W1,
                                    const float* b1, const void* W2T, void* G, void* dP, void* stream) {
-  LTHM_REQUIRE(lthm_mlp_supported(D, HID) && HID <= 4096 && M >= 0);
+  lthm_mlp_plan_out pl;
+  if (const int rc = lthm_mlp_plan(LTHM_MLP_BWD_HIDDEN, M, D, HID, cu_count(), &pl)) return rc;
+  if (M == 0) return 0;  // nothing to do: an empty tensor's pointers may be null
   LTHM_REQUIRE(X && dY && W1 && W2T && G && dP);
   LTHM_REQUIRE(((uintptr_t)X % 16) == 0 && ((uintptr_t)dY % 16) == 0 && ((uintptr_t)W1 % 16) == 0 &&
                ((uintptr_t)W2T % 16) == 0 && ((uintptr_t)b1 % 16) == 0 && ((uintptr_t)G % 16) == 0 &&
                ((uintptr_t)dP % 16) == 0);
-  if (M == 0) return 0;
   MlpBwdArgs a{};
   a.X = (const bf16_t*)X; a.dY = (const bf16_t*)dY; a.W1 = (const bf16_t*)W1; a.W2T = (const bf16_t*)W2T;
   a.b1 = b1; a.G = (bf16_t*)G; a.dP = (bf16_t*)dP;
   a.M = M; a.HID = HID;
   hipStream_t s = (hipStream_t)stream;
-  constexpr int NW = 8;
-  const int64_t ntiles = (M + 32 * NW - 1) / (32 * NW);
-  const int grid = (int)std::min<int64_t>(ntiles, (int64_t)cu_count());
+  constexpr int NW = MLP_BWDP_NW;
+  const int grid = pl.grid;
   if (D == 256) hipLaunchKernelGGL((mlp_bwdp_k<256, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   else hipLaunchKernelGGL((mlp_bwdp_k<128, NW>), dim3(grid), dim3(64 * NW), 0, s, a);
   LTHM_CHECK_LAUNCH();

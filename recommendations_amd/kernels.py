@@ -574,6 +574,27 @@ def mlp_supported(D: int, HID: int) -> bool:
     return bool(load().lthm_mlp_supported(D, HID))
 
 
+MLP_ENTRIES = {"fwd": 0, "fwd_ln": 1, "bwd": 2, "bwd_hidden": 3, "bwd_dx": 4, "wgrad": 5}
+MlpPlan = collections.namedtuple(
+    "MlpPlan", "entry waves tile_rows grid max_tiles nslice ngroup full ntiles ws_bytes lds_static lds_dynamic")
+
+
+def mlp_plan(entry: str, M: int, D: int, HID: int, cus=None):
+    """The launch geometry of a fused-MLP entry point ("fwd", "fwd_ln", "bwd", "bwd_hidden", "bwd_dx",
+    "wgrad") on a device of ``cus`` compute units (default: the current device), as an MlpPlan
+    (include/lthm.h lthm_mlp_plan_out).  Nothing is launched; OperandError for a refused shape."""
+    import ctypes
+    from ._lib import STRUCTS, load
+    if cus is None:
+        cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    p = STRUCTS["lthm_mlp_plan_out"]()
+    rc = load().lthm_mlp_plan(MLP_ENTRIES[entry], int(M), int(D), int(HID), int(cus), ctypes.addressof(p))
+    if rc != 0:
+        raise OperandError(f"the fused MLP's {entry} entry refuses M={M} D={D} HID={HID} (error {rc})")
+    return MlpPlan(entry, p.waves, p.tile_rows, p.grid, p.max_tiles, p.nslice, p.ngroup, p.full, p.ntiles,
+                   p.ws_bytes, p.lds_static, p.lds_dynamic)
+
+
 def mlp_fwd(x2d, w1_b, b1, w2t_b, b2, res1=None, res2=None):
     """res1 [+ res2] + c_proj(GELU(c_fc(x))) in one kernel, hidden on chip (lthm_mlp_fwd).
     x2d [M, D] bf16, w1_b [HID, D] bf16 (c_fc.weight), w2t_b [HID, D] bf16 (c_proj.weight^T)."""

@@ -18,7 +18,7 @@ from recommendations_amd import _lib
 def test_every_header_symbol_is_exported():
     lib = _lib.load()
     protos = _lib.parse_header()
-    assert len(protos) >= 30 and {"lthm_kshift_fwd", "lthm_gemm", "lthm_gemm_plan"} <= set(protos)
+    assert len(protos) >= 30 and {"lthm_kshift_fwd", "lthm_gemm", "lthm_gemm_plan", "lthm_mlp_plan"} <= set(protos)
     missing = [n for n in protos if not hasattr(lib, n)]
     assert not missing, missing
 
