@@ -1406,6 +1406,61 @@ int lthm_retrieve_ivf_q8_topk(const uint8_t* codes, const float* scale, int64_t 
                               const lthm_retrieve_excl* x, const lthm_retrieve_tags* t,
                               const lthm_retrieve_bias* b, float* out_scores, int32_t* out_rows, void* workspace,
                               int64_t ws_bytes, void* stream);
+/* Catalogue updates: the list-major catalogue that remains when some old rows are dropped and delta
+ * rows are merged in, list by list, every list's ids still ascending (csrc/catalogue_update.hip).  A
+ * flat, id-ascending catalogue is the case L = 1.  Nothing is sorted and no output is written through
+ * an atomic: every output row is written once, from the one source row that binary searches find, so
+ * two calls give the same bytes.
+ *   N, M, L       old rows (>= 1), delta rows (>= 0), lists (1..2^30); N + M <= 2^31 - 2
+ *   N_out         the rows of the output tensors: (the old rows with dead == 0) + M, which the caller
+ *                 reads once from the device; the call writes no row at or beyond it
+ *   old_ids       int64 [N]; old_emb bf16 [N, 128], 16-byte aligned; old_tags int32 [N], old_bias f32 [N]
+ *                 and old_groups int32 [N], each or NULL: the columns, list-major
+ *   old_off       int64 [L + 1]: list c is old rows old_off[c] .. old_off[c + 1], its ids ascending
+ *                 (compared as signed int64)
+ *   dead          uint8 [N]: != 0 for an old row that is removed or replaced.  The call sums the flag
+ *                 itself: live_before[p], the rows before p with dead == 0, int32 [N + 1] in the workspace
+ *   delta_*       the M delta rows in (list, id) order, with exactly the optional columns the old rows
+ *                 carry; delta_off int64 [L + 1] their lists.  No delta id equals a surviving id of
+ *                 its list.  With M = 0 the column pointers may be NULL (delta_off still holds L + 1 zeros)
+ *   out_*         the N_out output rows and out_off int64 [L + 1], all written by the call:
+ *                 out_off[c] = live_before[old_off[c]] + delta_off[c]
+ *   workspace     lthm_catalogue_update_ws_bytes(N, M, L) bytes, 16-byte aligned (live_before, the chunk
+ *                 table and the delta rows' destinations); -1 for N, M or L outside the ranges above
+ * The output is cut into chunks of LTHM_CATALOGUE_UPDATE_CHUNK rows of one list, listed in a table
+ * that is built on the device, so the call reads no list length on the host and nothing synchronises.
+ * Pointer, alignment, range and workspace checks are made before any launch; offsets on the device that
+ * break the contract give wrong rows, never an access outside the tensors. */
+#define LTHM_CATALOGUE_UPDATE_CHUNK 256
+typedef struct lthm_catalogue_update_desc {
+  int64_t N;
+  int64_t M;
+  int64_t L;
+  int64_t N_out;
+  const int64_t* old_ids;
+  const void* old_emb;
+  const int32_t* old_tags;
+  const float* old_bias;
+  const int32_t* old_groups;
+  const int64_t* old_off;
+  const uint8_t* dead;
+  const int64_t* delta_ids;
+  const void* delta_emb;
+  const int32_t* delta_tags;
+  const float* delta_bias;
+  const int32_t* delta_groups;
+  const int64_t* delta_off;
+  int64_t* out_ids;
+  void* out_emb;
+  int32_t* out_tags;
+  float* out_bias;
+  int32_t* out_groups;
+  int64_t* out_off;
+  void* workspace;
+  int64_t ws_bytes;
+} lthm_catalogue_update_desc;
+int64_t lthm_catalogue_update_ws_bytes(int64_t N, int64_t M, int64_t L);
+int lthm_catalogue_update(const lthm_catalogue_update_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */

@@ -2756,3 +2756,81 @@ def retrieve_ivf_q8_topk(q, codes, scale, row_ids, list_off, probes, pool: int, 
              int(bool(normalize_q)), n, ptr(cut(probes)), P, M, *parts, ptr(cut(scores)), ptr(cut(rows)), ptr(ws),
              ws.numel(), stream(), _key="retr_ivf_q8_topk_k", _work=work, _unit="byte")
     return scores, rows
+
+
+CATALOGUE_UPDATE_CHUNK = 256  # csrc/catalogue_update.hip CU_CHUNK (include/lthm.h LTHM_CATALOGUE_UPDATE_CHUNK)
+
+
+def catalogue_update(ids, emb, list_off, dead, delta_ids, delta_emb, delta_off, *, tags=None, bias=None, groups=None,
+                     delta_tags=None, delta_bias=None, delta_groups=None, n_out: Optional[int] = None):
+    """A list-major catalogue without its dead rows and with the delta rows merged in, list by list
+    (lthm_catalogue_update, csrc/catalogue_update.hip): the kernel of ``ItemCatalogue.update`` (L = 1) and
+    ``ClusteredItemCatalogue.update``.
+
+    ids int64 [N], emb bf16 [N, 128], list_off int64 [L + 1] and tags int32 [N] / bias f32 [N] / groups int32
+    [N] (each or None): the old rows, the ids of a list ascending.  dead uint8 or bool [N]: the rows to drop.
+    delta_ids int64 [M], delta_emb bf16 [M, 128], delta_off int64 [L + 1] and delta_tags / delta_bias /
+    delta_groups [M], exactly the optional columns the old rows carry: the rows to merge in, in (list, id)
+    order; no delta id equals a surviving id of its list.  M may be 0.  The offsets and the order are the
+    caller's contract and are not read on the host; offsets that break it give wrong rows, no fault.
+
+    Returns (ids, emb, list_off, tags, bias, groups) of the N' = N - dead + M output rows.  One device-to-host
+    read, of N', sizes the outputs; nothing else synchronises, and a caller that has read N' already hands it
+    in as ``n_out`` (it must be the true count) and the call reads nothing.  N' = 0 is refused.  No sort and
+    no atomics: two calls give the same bytes."""
+    import ctypes
+    from ._lib import STRUCTS
+    who = "catalogue_update"
+    cols = (("tags", tags, delta_tags, torch.int32), ("bias", bias, delta_bias, torch.float32),
+            ("groups", groups, delta_groups, torch.int32))
+    require_gpu(ids, emb, list_off, dead, delta_ids, delta_emb, delta_off, *[t for _, a, b, _ in cols for t in (a, b)])
+    _check(ids.dtype == torch.int64 and ids.dim() == 1 and ids.shape[0] >= 1,
+           f"{who} takes int64 [N] ids, N >= 1 (got {ids.dtype} {tuple(ids.shape)})")
+    N = ids.shape[0]
+    _check(emb.dtype == torch.bfloat16 and tuple(emb.shape) == (N, RETRIEVE_WIDTH),
+           f"{who} takes bf16 [N, {RETRIEVE_WIDTH}] rows (got {emb.dtype} {tuple(emb.shape)}, N={N})")
+    _check(list_off.dtype == torch.int64 and list_off.dim() == 1 and list_off.shape[0] >= 2,
+           f"{who} takes int64 [L + 1] list_off, L >= 1 (got {list_off.dtype} {tuple(list_off.shape)})")
+    L = list_off.shape[0] - 1
+    _check(dead.dtype in (torch.uint8, torch.bool) and tuple(dead.shape) == (N,),
+           f"{who} takes a uint8 or bool [N] dead flag (got {dead.dtype} {tuple(dead.shape)}, N={N})")
+    _check(delta_ids.dtype == torch.int64 and delta_ids.dim() == 1,
+           f"{who} takes int64 [M] delta_ids (got {delta_ids.dtype} {tuple(delta_ids.shape)})")
+    M = delta_ids.shape[0]
+    _check(delta_emb.dtype == torch.bfloat16 and tuple(delta_emb.shape) == (M, RETRIEVE_WIDTH),
+           f"{who} takes bf16 [M, {RETRIEVE_WIDTH}] delta rows (got {delta_emb.dtype} {tuple(delta_emb.shape)}, M={M})")
+    _check(delta_off.dtype == torch.int64 and tuple(delta_off.shape) == (L + 1,),
+           f"{who} takes int64 [L + 1] delta_off (got {delta_off.dtype} {tuple(delta_off.shape)}, L={L})")
+    for name, old, new, dt in cols:
+        _check((old is None) == (new is None), f"{who}: the old rows and the delta carry {name} together or not at all")
+        _check(old is None or (old.dtype == dt and tuple(old.shape) == (N,)), f"{who} takes {dt} [N] {name}")
+        _check(new is None or (new.dtype == dt and tuple(new.shape) == (M,)), f"{who} takes {dt} [M] delta_{name}")
+    dev = ids.device
+    _check(all(t is None or t.device == dev for t in (emb, list_off, dead, delta_ids, delta_emb, delta_off,
+                                                      *[t for _, a, b, _ in cols for t in (a, b)])),
+           f"{who} takes tensors of one device")
+    _check(N + M <= 2 ** 31 - 2 and L <= 2 ** 30, f"{who} takes N + M <= 2^31 - 2 rows and L <= 2^30 lists")
+    _check(emb.data_ptr() % 16 == 0 and delta_emb.data_ptr() % 16 == 0, f"{who} takes 16-byte aligned rows")
+    n_out = int((dead == 0).sum()) + M if n_out is None else int(n_out)  # the one device-to-host read
+    _check(M <= n_out <= N + M, f"{who}: n_out must lie in M..N + M (got {n_out}, N={N}, M={M})")
+    _check(n_out >= 1, f"{who}: no row remains, and a catalogue is never empty")
+    out_ids = torch.empty(n_out, dtype=torch.int64, device=dev)
+    out_emb = torch.empty((n_out, RETRIEVE_WIDTH), dtype=torch.bfloat16, device=dev)
+    out_off = torch.empty(L + 1, dtype=torch.int64, device=dev)
+    outs = [None if old is None else torch.empty(n_out, dtype=dt, device=dev) for _, old, _, dt in cols]
+    need = load().lthm_catalogue_update_ws_bytes(N, M, L)
+    _check(need > 0, f"{who} refuses M={M}, L={L}")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    dead8 = dead.view(torch.uint8) if dead.dtype == torch.bool else dead
+    d = STRUCTS["lthm_catalogue_update_desc"]()
+    d.N, d.M, d.L, d.N_out = N, M, L, n_out
+    d.old_ids, d.old_emb, d.old_off, d.dead = ptr(ids), ptr(emb), ptr(list_off), ptr(dead8)
+    d.old_tags, d.old_bias, d.old_groups = ptr(tags), ptr(bias), ptr(groups)
+    d.delta_ids, d.delta_emb, d.delta_off = ptr(delta_ids), ptr(delta_emb), ptr(delta_off)
+    d.delta_tags, d.delta_bias, d.delta_groups = ptr(delta_tags), ptr(delta_bias), ptr(delta_groups)
+    d.out_ids, d.out_emb, d.out_off = ptr(out_ids), ptr(out_emb), ptr(out_off)
+    d.out_tags, d.out_bias, d.out_groups = ptr(outs[0]), ptr(outs[1]), ptr(outs[2])
+    d.workspace, d.ws_bytes = ptr(ws), need
+    row = RETRIEVE_WIDTH * 2 + 8 + 4 * sum(o is not None for o in outs)
+    call("lthm_catalogue_update", ctypes.addressof(d), stream(), _key="cat_upd_merge_k", _bytes=2.0 * n_out * row)
+    return out_ids, out_emb, out_off, outs[0], outs[1], outs[2]

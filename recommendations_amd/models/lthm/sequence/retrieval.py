@@ -51,6 +51,12 @@ Clustered e4m3: ``ClusteredItemCatalogue.quantize`` gives a ``QuantizedClustered
 as e4m3 codes with the catalogue's tags and bias: its ``topk`` scans the probed lists' codes for a shortlist of
 the eligible rows (``K.retrieve_ivf_q8_topk``) and re-scores it with the exact rows and the prior
 (``K.retrieve_rescore_bias``), which is the ``with_filters()`` / ``with_deep()`` list restricted to the shortlist.
+
+Updates: ``ItemCatalogue.update`` and ``ClusteredItemCatalogue.update`` return a new catalogue without some ids
+and with the rows of an ``upsert`` catalogue replacing or joining the old ones, an upserted row in the list of
+its nearest centroid: per list one merge of two ascending id sequences (``K.catalogue_update``,
+csrc/catalogue_update.hip), bit for bit ``from_assignment`` of the rebuilt flat catalogue.  The quantised and
+the sharded catalogues refuse ``update`` and say what to do instead.
 """
 from __future__ import annotations
 
@@ -96,6 +102,81 @@ def make_tag_filter(n: int, tag_all: Union[int, torch.Tensor] = 0, tag_any: Unio
         raise ValueError("make_tag_filter takes n >= 1")
     cols = [_bits32(v, n, name, device) for v, name in ((tag_all, "tag_all"), (tag_any, "tag_any"), (tag_none, "tag_none"))]
     return torch.stack(cols, dim=1).to(torch.int32).contiguous()
+
+
+_UPDATE_COLUMNS = (("tags", torch.int32), ("bias", torch.float32), ("groups", torch.int32))
+
+
+def _update_dead(cat, upsert, remove_ids, missing_ok: bool, who: str) -> Tuple[torch.Tensor, int]:
+    """The argument checks of ``update`` on ``cat`` (flat or clustered) and (dead, N'): the uint8 [N] flag
+    of the old rows that are removed or replaced, found with ``cat.rows_of``, and the row count of the
+    result.  The count and the three verdicts that only the device knows (an absent, a repeated, a doubly
+    named id) come to the host in one read."""
+    N, dev = len(cat), cat.emb.device
+    if upsert is not None:
+        if not isinstance(upsert, ItemCatalogue):
+            raise ValueError(f"{who} takes an ItemCatalogue as upsert (got {type(upsert).__name__})")
+        if upsert.ids.device != dev:
+            raise ValueError(f"{who} takes an upsert on the catalogue's device ({dev}; got {upsert.ids.device})")
+        for name, _ in _UPDATE_COLUMNS:
+            has, gets = getattr(cat, name) is not None, getattr(upsert, name) is not None
+            if has != gets:
+                raise ValueError(f"{who}: upsert must carry {name} exactly when the catalogue does "
+                                 f"(the catalogue {'has' if has else 'has no'} {name}, upsert {'has' if gets else 'has none'})")
+    if remove_ids is not None:
+        if not isinstance(remove_ids, torch.Tensor) or remove_ids.dtype != torch.int64 or remove_ids.dim() != 1:
+            raise ValueError(f"{who} takes remove_ids int64 [R] (got {getattr(remove_ids, 'dtype', type(remove_ids).__name__)} "
+                             f"{tuple(getattr(remove_ids, 'shape', ()))})")
+        if remove_ids.device != dev:
+            raise ValueError(f"{who} takes remove_ids on the catalogue's device ({dev}; got {remove_ids.device})")
+        if remove_ids.numel() == 0:
+            remove_ids = None
+    hit = torch.zeros(N + 1, dtype=torch.uint8, device=dev)  # slot N takes the ids the catalogue does not hold
+    flags = torch.zeros(3, dtype=torch.int64, device=dev)    # absent, repeated, in both arguments
+    if remove_ids is not None:
+        rows = cat.rows_of(remove_ids).long()
+        hit[torch.where(rows >= 0, rows, torch.full_like(rows, N))] = 1
+        srt = torch.sort(remove_ids)[0]
+        flags[0] = (rows < 0).sum()
+        flags[1] = (srt[1:] == srt[:-1]).sum()
+        if upsert is not None:
+            flags[2] = upsert.holds(remove_ids).sum()
+    if upsert is not None:
+        rows = cat.rows_of(upsert.ids).long()
+        hit[torch.where(rows >= 0, rows, torch.full_like(rows, N))] = 1
+    dead = hit[:N]
+    live, absent, repeated, both = torch.cat([(N - dead.sum(dtype=torch.int64)).reshape(1), flags]).tolist()  # the one read
+    if repeated:
+        raise ValueError(f"{who}: remove_ids must be distinct ({repeated} repeated)")
+    if both:
+        raise ValueError(f"{who}: {both} ids are in both upsert and remove_ids; an id is replaced or removed, not both")
+    if absent and not missing_ok:
+        raise ValueError(f"{who}: {absent} of the remove_ids are not in the catalogue (missing_ok=True ignores them)")
+    n_out = live + (0 if upsert is None else len(upsert))
+    if n_out < 1:
+        raise ValueError(f"{who}: no row remains, and a catalogue is never empty")
+    return dead, n_out
+
+
+def _update_delta(cat, upsert: Optional["ItemCatalogue"], order: Optional[torch.Tensor]) -> dict:
+    """The delta arguments of ``K.catalogue_update``: the upsert's rows in ``order`` (None: as they are), or
+    no rows with the columns ``cat`` carries."""
+    dev = cat.emb.device
+    if upsert is None:
+        kw = {"delta_ids": torch.empty(0, dtype=torch.int64, device=dev),
+              "delta_emb": torch.empty((0, WIDTH), dtype=torch.bfloat16, device=dev)}
+        for name, dt in _UPDATE_COLUMNS:
+            kw["delta_" + name] = None if getattr(cat, name) is None else torch.empty(0, dtype=dt, device=dev)
+        return kw
+    pick = (lambda t: t) if order is None else (lambda t: t[order])
+    kw = {"delta_ids": pick(upsert.ids), "delta_emb": pick(upsert.emb)}
+    for name, _ in _UPDATE_COLUMNS:
+        kw["delta_" + name] = None if getattr(upsert, name) is None else pick(getattr(upsert, name))
+    return kw
+
+
+def _no_update(what: str, instead: str):
+    raise ValueError(f"{what} has no update: {instead}")
 
 
 class ItemCatalogue:
@@ -433,6 +514,36 @@ class ItemCatalogue:
         assign = K.retrieve_topk(self.emb, centroids, 1, normalize_q=False)[1][:, 0].long()
         return ClusteredItemCatalogue.from_assignment(self, centroids, assign)
 
+    @classmethod
+    def _trusted(cls, ids, emb, tags, bias, groups) -> "ItemCatalogue":
+        """A catalogue of tensors that ``update`` produced from checked catalogues: what the constructor
+        checks holds by construction, so nothing is read back from the device."""
+        cat = object.__new__(cls)
+        cat.ids, cat.emb, cat.tags, cat.bias, cat.groups = ids, emb, tags, bias, groups
+        return cat
+
+    @torch.no_grad()
+    def update(self, upsert: Optional["ItemCatalogue"] = None, remove_ids: Optional[torch.Tensor] = None, *,
+               missing_ok: bool = False) -> "ItemCatalogue":
+        """A new catalogue: this one without the ``remove_ids`` (int64 [R], distinct, on this device), with
+        the rows of ``upsert`` (an ``ItemCatalogue`` on this device) in place of the rows with their ids, and
+        with its other rows added, ids ascending.  ``upsert`` carries exactly the optional columns (tags, bias,
+        groups) this catalogue carries.  An id to remove that the catalogue does not hold is refused unless
+        ``missing_ok``; so are an id in both arguments and a result without rows.  Neither argument (or an
+        empty ``remove_ids`` alone) gives an equal catalogue.  This catalogue is unchanged.
+
+        One merge of two ascending id sequences on the device (``K.catalogue_update``, the one-list case),
+        with one device-to-host read, of the new row count and the verdicts on the ids."""
+        who = "ItemCatalogue.update"
+        dead, n_out = _update_dead(self, upsert, remove_ids, missing_ok, who)
+        dev = self.ids.device
+        M = 0 if upsert is None else len(upsert)
+        ids, emb, _, tags, bias, groups = K.catalogue_update(
+            self.ids, self.emb, torch.tensor([0, len(self)], dtype=torch.int64, device=dev), dead,
+            delta_off=torch.tensor([0, M], dtype=torch.int64, device=dev), tags=self.tags, bias=self.bias,
+            groups=self.groups, n_out=n_out, **_update_delta(self, upsert, None))
+        return ItemCatalogue._trusted(ids, emb, tags, bias, groups)
+
 
 Q8_INDEX = "lthm-q8-v1"
 
@@ -473,6 +584,10 @@ class QuantizedItemCatalogue:
     @property
     def keep_exact(self) -> bool:
         return self.emb is not None
+
+    def update(self, *args, **kwargs):
+        """Refused: the codes and scales are made per catalogue by ``quantize()``."""
+        _no_update("a QuantizedItemCatalogue", "update the bf16 ItemCatalogue and call quantize() again")
 
     def to(self, device) -> "QuantizedItemCatalogue":
         return QuantizedItemCatalogue(self.ids.to(device), self.codes.to(device), self.scale.to(device),
@@ -656,6 +771,55 @@ class ClusteredItemCatalogue:
         return cls(catalogue.ids[order], catalogue.emb[order], list_off, centroids.to(dev),
                    None if catalogue.tags is None else catalogue.tags[order],
                    None if catalogue.bias is None else catalogue.bias[order])
+
+    @classmethod
+    def _trusted(cls, row_ids, emb, list_off, centroids, tags, bias) -> "ClusteredItemCatalogue":
+        """A catalogue of tensors that ``update`` produced from a checked catalogue: what the constructor
+        checks holds by construction, so nothing is read back from the device.  The id lookup is the
+        constructor's sort."""
+        cat = object.__new__(ClusteredItemCatalogue)
+        cat.row_ids, cat.emb, cat.list_off, cat.centroids, cat.tags, cat.bias = row_ids, emb, list_off, centroids, tags, bias
+        ids, order = torch.sort(row_ids)
+        cat._ids, cat._order = ids.contiguous(), order.contiguous()
+        cat._plain = None
+        cat.groups = None
+        return cat
+
+    @torch.no_grad()
+    def update(self, upsert: Optional[ItemCatalogue] = None, remove_ids: Optional[torch.Tensor] = None, *,
+               missing_ok: bool = False) -> "ClusteredItemCatalogue":
+        """A new clustered catalogue around the same centroids: this one without the ``remove_ids`` (int64
+        [R], distinct, on this device) and with the rows of ``upsert`` (an ``ItemCatalogue`` on this device,
+        carrying tags and bias exactly when this catalogue does, and groups exactly when this view does).
+        An upsert row, whether its id is new or replaces a row, goes to the list of its nearest centroid
+        (``K.retrieve_topk`` with k = 1, ties to the lower list: ``cluster()``'s last assignment); every
+        other row keeps its list.  The result equals, in every tensor, ``from_assignment`` of the updated
+        flat catalogue with that assignment, and a ``with_filters()`` / ``with_deep()`` / ``with_heads()``
+        view gives a view of its kind.  An id to remove that the catalogue does not hold is refused unless
+        ``missing_ok``; so are an id in both arguments and a result without rows.  This catalogue is
+        unchanged, the centroids are not re-fitted.
+
+        Per list one merge of two ascending id sequences on the device (``K.catalogue_update``) instead of
+        the rebuild's assignment, argsort and gathers of all N rows, with one device-to-host read, of the new
+        row count and the verdicts on the ids."""
+        who = "ClusteredItemCatalogue.update"
+        dead, n_out = _update_dead(self, upsert, remove_ids, missing_ok, who)
+        dev, L = self.emb.device, self.nlist
+        if upsert is None:
+            order, delta_off = None, torch.zeros(L + 1, dtype=torch.int64, device=dev)
+        else:
+            assign = K.retrieve_topk(upsert.emb, self.centroids, 1, normalize_q=False)[1][:, 0].long()
+            order = torch.argsort(assign, stable=True)  # (list, id): the upsert's ids ascend
+            delta_off = torch.searchsorted(assign[order], torch.arange(L + 1, dtype=torch.int64, device=dev))
+        row_ids, emb, list_off, tags, bias, groups = K.catalogue_update(
+            self.row_ids, self.emb, self.list_off, dead, delta_off=delta_off, tags=self.tags, bias=self.bias,
+            groups=self.groups, n_out=n_out, **_update_delta(self, upsert, order))
+        out = ClusteredItemCatalogue._trusted(row_ids, emb, list_off, self.centroids, tags, bias)
+        if self.scans_deep or self.scans_heads:
+            view = out.with_deep() if self.scans_deep else out.with_heads()
+            view.groups = groups
+            return view
+        return out.with_filters() if self.scans_filters else out
 
     _MAX_K = K.RETRIEVE_MAX_K  # the longest list of topk (the with_deep() view: K.RETRIEVE_MAX_DEEP)
 
@@ -1200,6 +1364,10 @@ class QuantizedClusteredItemCatalogue:
         """bool, the shape of ``ids``: the catalogue holds this id."""
         return self.rows_of(ids) >= 0
 
+    def update(self, *args, **kwargs):
+        """Refused: the codes and scales are made per catalogue by ``quantize()``."""
+        _no_update("a QuantizedClusteredItemCatalogue", "update the bf16 ClusteredItemCatalogue and call quantize() again")
+
     def to(self, device) -> "QuantizedClusteredItemCatalogue":
         on = lambda t: None if t is None else t.to(device)
         return QuantizedClusteredItemCatalogue(self.row_ids.to(device), self.codes.to(device), self.scale.to(device),
@@ -1392,6 +1560,10 @@ class ShardedItemCatalogue:
     @property
     def has_bias(self) -> bool:
         return self.shards[0].has_bias
+
+    def update(self, *args, **kwargs):
+        """Refused: an id belongs to one shard, and only the caller knows which."""
+        _no_update("a ShardedItemCatalogue", "update the shards (ItemCatalogue.update) and construct the sharded catalogue again")
 
     def validate(self) -> None:
         """Disjointness of the ids across the ranks of the group: one all-gather of every rank's ids
@@ -1617,6 +1789,11 @@ class ShardedClusteredItemCatalogue:
     @property
     def max_k(self) -> int:
         return K.RETRIEVE_MAX_DEEP if self.scans_deep else K.RETRIEVE_MAX_K
+
+    def update(self, *args, **kwargs):
+        """Refused: an id belongs to one shard, and only the caller knows which."""
+        _no_update("a ShardedClusteredItemCatalogue",
+                   "update the shards (ClusteredItemCatalogue.update) and construct the sharded catalogue again")
 
     def validate(self) -> None:
         """Disjointness of the ids across the ranks of the group, as ``ShardedItemCatalogue.validate``."""
