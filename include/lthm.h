@@ -519,6 +519,46 @@ typedef struct lthm_ptower_desc {
 
 int lthm_product_tower_fwd(const lthm_ptower_desc* desc, void* stream);
 
+/* Which kernels lthm_product_tower_fwd runs for a descriptor and with what geometry, decided on
+ * the host from the descriptor's numbers and from which of its pointers are null (no GPU call,
+ * no device memory touched).  lthm_product_tower_fwd launches from this plan.  The return value
+ * is nonzero (1) for a descriptor the forward refuses (the plan is then undefined): Din outside
+ * 1 .. 256, Dout outside 1 .. 512, more than LTHM_MAX_CVE modules, more than 1024 index slots,
+ * Dout no multiple of the per-token kernel's outputs per lane, or the per-token kernel's LDS
+ * above 160 KiB (asked of every descriptor, whichever path it takes).  With n == 0 nothing is
+ * launched: the plan is all zeros and only the first three ranges are asked.
+ *   LTHM_PT_MFMA:  ptower_rows_k<x, DM> (bucket rows, mask, xn) then ptower_emb_mfma_k<x, NF, DMA>
+ *                  (bag sums as a one-hot MFMA GEMM, mapper as bf16 hi / lo splits).  Taken when
+ *                  the descriptor is a tower (not cve_only) with bf16 tables and bf16 emb_out,
+ *                  ids, rows_out and mask_out given, a column slice of 16 / 32 / 64 / 128 / 256,
+ *                  1 <= R <= 4096 table rows, Din <= 64 and a multiple of 4, at most 32 bins per
+ *                  module, at most 256 projections, and the embedding kernel's LDS within 160 KiB.
+ *   LTHM_PT_TOKEN: ptower_fwd_k<x, table, OPL>, a wave per token; everything else. */
+#define LTHM_PT_TOKEN 0
+#define LTHM_PT_MFMA 1
+typedef struct lthm_ptower_plan_out {
+  int32_t path;        /* LTHM_PT_MFMA or LTHM_PT_TOKEN */
+  int32_t total;       /* index slots per token: all projections + 1 for the histogram row */
+  int32_t R;           /* table rows: cve_rows + norm_bins */
+  int32_t R32;         /* R rounded up to the 32-row slab */
+  int32_t nslab;       /* R32 / 32 */
+  int32_t nslice;      /* column slices of Dout (grid.y of the embedding kernel): 2 for Dout 512 */
+  int32_t rows_dm;     /* MFMA: ptower_rows_k's DM, 32 or 64; 0 on the per-token path */
+  int32_t rows_full;   /* MFMA: 1 when Din == DM, the x rows stage through LDS */
+  int32_t nf;          /* MFMA: 16-column fragments of one slice (1, 2, 4, 8, 16); else 0 */
+  int32_t dma;         /* MFMA: 1 = 4-deep LDS-DMA slab ring, 0 = register double buffer */
+  int32_t opl;         /* outputs per lane of ptower_fwd_k for this Dout (1, 2, 4, 8) */
+  int32_t rows_grid;   /* workgroups of ptower_rows_k (256 threads); 0: not launched */
+  int32_t emb_grid_x;  /* workgroups of ptower_emb_mfma_k (512 threads): 128-token blocks ... */
+  int32_t emb_grid_y;  /* ... by column slices; 0: not launched */
+  int32_t tok_grid;    /* workgroups of ptower_fwd_k (256 threads); 0: not launched */
+  int32_t pad0;
+  int64_t rows_lds_static;  /* bytes of ptower_rows_k's __shared__ arrays (0 when not launched) */
+  int64_t emb_lds_dynamic;  /* dynamic LDS of ptower_emb_mfma_k (as computed, also when not taken) */
+  int64_t tok_lds_dynamic;  /* dynamic LDS of ptower_fwd_k (as computed, also when not taken) */
+} lthm_ptower_plan_out;
+int lthm_product_tower_plan(const lthm_ptower_desc* desc, lthm_ptower_plan_out* plan);
+
 /* Row gather (scatter = 0: dst row i = src row idx[i], a zero row where idx[i] < 0) or scatter
  * (scatter = 1: dst row idx[i] = src row i, skipped where idx[i] < 0) of `count` rows of
  * row_bytes (a multiple of 16; 16-B aligned pointers and leading dims).  The product tower's

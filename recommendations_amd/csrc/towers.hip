@@ -1065,18 +1065,21 @@ extern "C" int lthm_flip_tokens(const int64_t* in, int64_t* out, int64_t B, int3
   return 0;
 }
 
-extern "C" int lthm_product_tower_fwd(const lthm_ptower_desc* d, void* stream) {
-  LTHM_REQUIRE(d && d->n >= 0 && d->Din > 0 && d->Din <= 256 && d->n_mod >= 0 && d->n_mod <= LTHM_MAX_CVE);
+extern "C" int lthm_product_tower_plan(const lthm_ptower_desc* d, lthm_ptower_plan_out* p) {
+  LTHM_REQUIRE(d && p);
+  *p = lthm_ptower_plan_out{};
+  LTHM_REQUIRE(d->n >= 0 && d->Din > 0 && d->Din <= 256 && d->n_mod >= 0 && d->n_mod <= LTHM_MAX_CVE);
   LTHM_REQUIRE(d->Dout > 0 && d->Dout <= 512);
-  if (d->n == 0) return 0;
-  int total = 0;
-  for (int j = 0; j < d->n_mod; ++j) total += d->mod_nproj[j];
-  total += d->norm_bins > 0 ? 1 : 0;
+  if (d->n == 0) return 0;  // nothing is launched and nothing more is asked of the descriptor
+  int total = 0, maxnb = 0, nproj = 0;
+  for (int j = 0; j < d->n_mod; ++j) {
+    maxnb = std::max(maxnb, d->mod_nbins[j]);
+    nproj += d->mod_nproj[j];
+  }
+  total = nproj + (d->norm_bins > 0 ? 1 : 0);
   LTHM_REQUIRE(total <= 1024);
   const size_t sh = (size_t)(d->Din * d->Dout + d->proj_total + d->grid_total + 8 * d->Din) * 4 + (size_t)4 * total * 2 + 16;
   LTHM_REQUIRE(sh <= 160 * 1024);
-  const int grid = grid_for(d->n, 4, 256 * 8);
-  hipStream_t s = (hipStream_t)stream;
   const int opl = d->Dout <= 64 ? 1 : d->Dout <= 128 ? 2 : d->Dout <= 256 ? 4 : 8;
   LTHM_REQUIRE(d->Dout % opl == 0);
   // MFMA path: per-token pass (rows, mask) + one-hot GEMM for the bag sums
@@ -1087,18 +1090,46 @@ extern "C" int lthm_product_tower_fwd(const lthm_ptower_desc* d, void* stream) {
   const int Ds = Dm / nsl;
   const size_t sh_mfma = (size_t)2 * 32 * Ds * 2 + (size_t)(d->Din + 4) * Ds * 4 + (size_t)PE_TOK * (d->Din + 4) * 4 +
                          (size_t)512 * 8 + (size_t)PE_TOK * pe_rbw(R32) * 4;
-  int maxnb = 0, nproj = 0;
-  for (int j = 0; j < d->n_mod; ++j) {
-    maxnb = std::max(maxnb, d->mod_nbins[j]);
-    nproj += d->mod_nproj[j];
-  }
   const bool mfma = !d->cve_only && d->tab_dtype == LTHM_BF16 && d->emb_dtype == LTHM_BF16 && d->rows_out &&
                     d->mask_out && d->ids && (Ds == 16 || Ds == 32 || Ds == 64 || Ds == 128 || Ds == 256) && nsl <= 4 && R > 0 &&
                     R <= PE_MAXR && sh_mfma <= 160 * 1024 && d->Din <= PR_DMAX && d->Din % 4 == 0 &&
                     maxnb <= PR_NBMAX && nproj <= 256;
+  p->path = mfma ? LTHM_PT_MFMA : LTHM_PT_TOKEN;
+  p->total = total;
+  p->R = R;
+  p->R32 = R32;
+  p->nslab = R32 / 32;
+  p->nslice = nsl;
+  p->opl = opl;
+  p->emb_lds_dynamic = (int64_t)sh_mfma;
+  p->tok_lds_dynamic = (int64_t)sh;
   if (mfma) {
-    const dim3 g1((unsigned)std::min<int64_t>((d->n + PR_TOK - 1) / PR_TOK, 4096));
-    if (d->Din <= 32) {
+    p->rows_dm = d->Din <= 32 ? 32 : 64;
+    p->rows_full = d->Din == p->rows_dm;
+    p->nf = Ds / 16;
+    // the 4-deep DMA ring needs the mapper staging (wN + xs) to hold two 32-row slabs
+    p->dma = (Ds == 128 || Ds == 256) &&
+             (size_t)(d->Din + 4) * Ds * 4 + (size_t)PE_TOK * (d->Din + 4) * 4 >= (size_t)2 * 32 * Ds * 2;
+    p->rows_grid = (int)std::min<int64_t>((d->n + PR_TOK - 1) / PR_TOK, 4096);
+    p->emb_grid_x = (int)((d->n + PE_TOK - 1) / PE_TOK);
+    p->emb_grid_y = nsl;
+    p->rows_lds_static = (int64_t)PR_TOK * (p->rows_dm + 4) * 4 + PR_TOK;
+  } else {
+    p->tok_grid = grid_for(d->n, 4, 256 * 8);
+  }
+  return 0;
+}
+
+extern "C" int lthm_product_tower_fwd(const lthm_ptower_desc* d, void* stream) {
+  lthm_ptower_plan_out pl;
+  if (const int rc = lthm_product_tower_plan(d, &pl)) return rc;
+  if (d->n == 0) return 0;
+  const int total = pl.total, R = pl.R;
+  const size_t sh = (size_t)pl.tok_lds_dynamic, sh_mfma = (size_t)pl.emb_lds_dynamic;
+  hipStream_t s = (hipStream_t)stream;
+  if (pl.path == LTHM_PT_MFMA) {
+    const dim3 g1((unsigned)pl.rows_grid);
+    if (pl.rows_dm == 32) {
       if (d->x_dtype == LTHM_BF16) hipLaunchKernelGGL((ptower_rows_k<bf16_t, 32>), g1, dim3(256), 0, s, *d, total);
       else hipLaunchKernelGGL((ptower_rows_k<float, 32>), g1, dim3(256), 0, s, *d, total);
     } else {
@@ -1106,16 +1137,14 @@ extern "C" int lthm_product_tower_fwd(const lthm_ptower_desc* d, void* stream) {
       else hipLaunchKernelGGL((ptower_rows_k<float, 64>), g1, dim3(256), 0, s, *d, total);
     }
     LTHM_CHECK_LAUNCH();
-    const dim3 g2((unsigned)((d->n + PE_TOK - 1) / PE_TOK), (unsigned)nsl);
-    // the 4-deep DMA ring needs the mapper staging (wN + xs) to hold two 32-row slabs
-    const bool dma = (Ds == 128 || Ds == 256) &&
-                     (size_t)(d->Din + 4) * Ds * 4 + (size_t)PE_TOK * (d->Din + 4) * 4 >= (size_t)2 * 32 * Ds * 2;
+    const dim3 g2((unsigned)pl.emb_grid_x, (unsigned)pl.emb_grid_y);
+    const bool dma = pl.dma != 0;
 #define LTHM_PT_EMB(TX)                                                                                     \
-  switch (Ds) {                                                                                             \
-    case 16: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 1>), g2, dim3(512), sh_mfma, s, *d, total, R); break;  \
-    case 32: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 2>), g2, dim3(512), sh_mfma, s, *d, total, R); break;  \
-    case 64: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 4>), g2, dim3(512), sh_mfma, s, *d, total, R); break;  \
-    case 128:                                                                                               \
+  switch (pl.nf) {                                                                                          \
+    case 1: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 1>), g2, dim3(512), sh_mfma, s, *d, total, R); break;   \
+    case 2: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 2>), g2, dim3(512), sh_mfma, s, *d, total, R); break;   \
+    case 4: hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 4>), g2, dim3(512), sh_mfma, s, *d, total, R); break;   \
+    case 8:                                                                                                 \
       if (dma) hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 8, true>), g2, dim3(512), sh_mfma, s, *d, total, R);   \
       else hipLaunchKernelGGL((ptower_emb_mfma_k<TX, 8>), g2, dim3(512), sh_mfma, s, *d, total, R);             \
       break;                                                                                                \
@@ -1129,12 +1158,12 @@ extern "C" int lthm_product_tower_fwd(const lthm_ptower_desc* d, void* stream) {
     LTHM_CHECK_LAUNCH();
     return 0;
   }
+  const int grid = pl.tok_grid, opl = pl.opl;
 #define LTHM_PT(TX, TT)                                                                                   \
   if (opl == 1) hipLaunchKernelGGL((ptower_fwd_k<TX, TT, 1>), dim3(grid), dim3(256), sh, s, *d, total);    \
   else if (opl == 2) hipLaunchKernelGGL((ptower_fwd_k<TX, TT, 2>), dim3(grid), dim3(256), sh, s, *d, total); \
   else if (opl == 4) hipLaunchKernelGGL((ptower_fwd_k<TX, TT, 4>), dim3(grid), dim3(256), sh, s, *d, total); \
   else hipLaunchKernelGGL((ptower_fwd_k<TX, TT, 8>), dim3(grid), dim3(256), sh, s, *d, total);
-  LTHM_REQUIRE(opl == 1 || opl == 2 || opl == 4 || opl == 8);
   if (d->x_dtype == LTHM_BF16 && d->tab_dtype == LTHM_BF16) { LTHM_PT(bf16_t, bf16_t) }
   else if (d->x_dtype == LTHM_F32 && d->tab_dtype == LTHM_F32) { LTHM_PT(float, float) }
   else if (d->x_dtype == LTHM_BF16 && d->tab_dtype == LTHM_F32) { LTHM_PT(bf16_t, float) }

@@ -595,6 +595,24 @@ def mlp_plan(entry: str, M: int, D: int, HID: int, cus=None):
                    p.ws_bytes, p.lds_static, p.lds_dynamic)
 
 
+PTowerPlan = collections.namedtuple(
+    "PTowerPlan", "path total R R32 nslab nslice rows_dm rows_full nf dma opl rows_grid emb_grid_x emb_grid_y "
+                  "tok_grid rows_lds_static emb_lds_dynamic tok_lds_dynamic")
+
+
+def product_tower_plan(desc):
+    """Which kernels lthm_product_tower_fwd runs for ``desc`` (a filled STRUCTS["lthm_ptower_desc"]) and
+    their geometry, as a PTowerPlan (include/lthm.h lthm_ptower_plan_out; path "mfma" or "token").
+    Nothing is launched and no pointer is followed; OperandError for a refused descriptor."""
+    import ctypes
+    from ._lib import STRUCTS, load
+    p = STRUCTS["lthm_ptower_plan_out"]()
+    rc = load().lthm_product_tower_plan(ctypes.addressof(desc), ctypes.addressof(p))
+    if rc != 0:
+        raise OperandError(f"lthm_product_tower_fwd refuses this descriptor (error {rc})")
+    return PTowerPlan("mfma" if p.path == 1 else "token", *[getattr(p, f) for f in PTowerPlan._fields[1:]])
+
+
 def mlp_fwd(x2d, w1_b, b1, w2t_b, b2, res1=None, res2=None):
     """res1 [+ res2] + c_proj(GELU(c_fc(x))) in one kernel, hidden on chip (lthm_mlp_fwd).
     x2d [M, D] bf16, w1_b [HID, D] bf16 (c_fc.weight), w2t_b [HID, D] bf16 (c_proj.weight^T)."""

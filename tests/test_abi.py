@@ -18,7 +18,8 @@ from recommendations_amd import _lib
 def test_every_header_symbol_is_exported():
     lib = _lib.load()
     protos = _lib.parse_header()
-    assert len(protos) >= 30 and {"lthm_kshift_fwd", "lthm_gemm", "lthm_gemm_plan", "lthm_mlp_plan"} <= set(protos)
+    assert len(protos) >= 30 and {"lthm_kshift_fwd", "lthm_gemm", "lthm_gemm_plan", "lthm_mlp_plan",
+                                 "lthm_product_tower_plan"} <= set(protos)
     missing = [n for n in protos if not hasattr(lib, n)]
     assert not missing, missing
 
@@ -40,7 +41,7 @@ def test_device_count_never_fails():
 def test_struct_layouts_match_c(tmp_path):
     structs = _lib.STRUCTS
     assert {"lthm_gemm_desc", "lthm_gemm_plan_out", "lthm_attn_desc", "lthm_ptower_desc", "lthm_tokens_desc",
-            "lthm_contrastive_desc"} <= set(structs)
+            "lthm_contrastive_desc", "lthm_mlp_plan_out", "lthm_ptower_plan_out"} <= set(structs)
     lines = ['#include "%s"' % _lib.HEADER, "#include <stdio.h>", "#include <stddef.h>", "int main(void) {"]
     for name, cls in structs.items():
         lines.append(f'  printf("{name} sizeof %zu\\n", sizeof({name}));')
