@@ -1503,6 +1503,55 @@ int64_t lthm_catalogue_update_ws_bytes(int64_t N, int64_t M, int64_t L);
 int lthm_catalogue_update(const lthm_catalogue_update_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* Ranking stage — the plumbing around the ranker's forward (csrc/rank.hip)  */
+/* ------------------------------------------------------------------------- */
+/* The longest candidate list of the two calls below: the k = 1,024 of the deep retrieval lists. */
+#define LTHM_RANK_MAX_LIST 1024
+/* lthm_rank_assemble: the ranker's input batch of Q users x M candidates each, in one pass.
+ *   out_dense[q M + m] = [ user_dense[q] | item_dense[rows[q, m]] ]   f32   [Q M, Du + Di]
+ *   out_cat  [q M + m] = [ user_cat[q]   | item_cat[rows[q, m]]   ]   int64 [Q M, Fu + Fi]
+ *   Q, M          users (>= 1) and candidates per user (1..LTHM_RANK_MAX_LIST); Q M <= 2^31 - 1
+ *   N             rows of the item matrices (0..2^31 - 1)
+ *   Du, Di, Fu, Fi  the widths, each >= 0; Du + Di and Fu + Fi at most 2^20.  A matrix of width 0 is
+ *                 not read and its pointer may be NULL
+ *   rows          int32 [Q, M]: a row of the item matrices; an index outside [0, N) is a pad: it is
+ *                 never followed, and its item columns are written as 0.0 and 0
+ * Every output element is written exactly once, by plain stores; the values are copies, bit for bit.
+ * Odd widths are not refused: a matrix moves in 16-byte units when both of its widths allow it (Du and
+ * Di multiples of 4; Fu and Fi multiples of 2) and its three pointers must then be 16-byte aligned;
+ * otherwise it moves element by element and the pointers need the element's alignment (4 / 8 bytes).
+ * NULL pointers, negative sizes, M outside its range and misaligned pointers are refused before any
+ * launch. */
+typedef struct lthm_rank_assemble_desc {
+  int64_t Q;
+  int64_t M;
+  int64_t N;
+  int64_t Du;
+  int64_t Di;
+  int64_t Fu;
+  int64_t Fi;
+  const float* user_dense;
+  const int64_t* user_cat;
+  const float* item_dense;
+  const int64_t* item_cat;
+  const int32_t* rows;
+  float* out_dense;
+  int64_t* out_cat;
+} lthm_rank_assemble_desc;
+int lthm_rank_assemble(const lthm_rank_assemble_desc* d, void* stream);
+/* lthm_rank_sort: every list of M (logit, row) entries in its total order, the first k of it.
+ *   logits f32 [Q, M], rows int32 [Q, M], 1 <= k <= M <= LTHM_RANK_MAX_LIST, 1 <= Q <= 2^31 - 1
+ *   out_scores f32 [Q, k], out_rows int32 [Q, k], out_src int32 [Q, k]: the logit as it came in, its
+ *   row, and the position m it had in the list
+ * An entry is a candidate when its row is >= 0 and its logit is not NaN; -inf and +inf are ordinary
+ * values and -0.0 orders as +0.0.  The candidates come in the order (logit descending, row ascending,
+ * position ascending), so a row that appears twice keeps both copies in input order; the slots behind
+ * the last candidate hold (-inf, -1, -1).  One block per list, the keys in LDS, no workspace and no
+ * atomics: the result is a pure function of the inputs. */
+int lthm_rank_sort(const float* logits, const int32_t* rows, int64_t Q, int32_t M, int32_t k, float* out_scores,
+                   int32_t* out_rows, int32_t* out_src, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Id ingest — commons/feature_utils.py (host CPU unless noted)              */
 /* ------------------------------------------------------------------------- */
 /* xxHash32 / xxHash64 of a byte string (python-xxhash intdigest()) */

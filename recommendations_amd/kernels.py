@@ -2852,3 +2852,84 @@ def catalogue_update(ids, emb, list_off, dead, delta_ids, delta_emb, delta_off, 
     row = RETRIEVE_WIDTH * 2 + 8 + 4 * sum(o is not None for o in outs)
     call("lthm_catalogue_update", ctypes.addressof(d), stream(), _key="cat_upd_merge_k", _bytes=2.0 * n_out * row)
     return out_ids, out_emb, out_off, outs[0], outs[1], outs[2]
+
+
+# ----------------------------------------------------------------- ranking stage (csrc/rank.hip)
+RANK_MAX_LIST = RETRIEVE_MAX_DEEP  # LTHM_RANK_MAX_LIST: the longest candidate list, a deep retrieval list
+
+
+def rank_assemble(user_dense, user_cat, item_dense, item_cat, rows):
+    """The ranker's input batch of Q users x M candidates each (lthm_rank_assemble, csrc/rank.hip).
+
+    user_dense f32 [Q, Du], user_cat int64 [Q, Fu], item_dense f32 [N, Di], item_cat int64 [N, Fi], rows
+    int32 [Q, M] with M in 1..RANK_MAX_LIST; any width may be 0.  Returns (dense f32 [Q M, Du + Di], cat
+    int64 [Q M, Fu + Fi]): row q M + m holds user q's columns, then the item columns of rows[q, m].  A row
+    index outside [0, N) is a pad: it is never followed and its item columns are 0.0 and 0.  Exact copies,
+    every element written once, no atomics; odd widths move element by element instead of in 16-byte
+    units."""
+    import ctypes
+    from ._lib import STRUCTS
+    who = "rank_assemble"
+    require_gpu(user_dense, user_cat, item_dense, item_cat, rows)
+    _check(rows.dtype == torch.int32 and rows.dim() == 2, f"{who} takes int32 [Q, M] rows (got {rows.dtype} {tuple(rows.shape)})")
+    Q, M = rows.shape
+    _check(Q >= 1 and 1 <= M <= RANK_MAX_LIST, f"{who} takes Q >= 1 lists of 1..{RANK_MAX_LIST} rows (got Q={Q}, M={M})")
+    _check(Q * M <= 2 ** 31 - 1, f"{who} takes Q M <= 2^31 - 1 rows (got {Q * M})")
+    _check(user_dense.dtype == torch.float32 and user_dense.dim() == 2 and user_dense.shape[0] == Q,
+           f"{who} takes f32 [Q, Du] user_dense (got {user_dense.dtype} {tuple(user_dense.shape)}, Q={Q})")
+    _check(user_cat.dtype == torch.int64 and user_cat.dim() == 2 and user_cat.shape[0] == Q,
+           f"{who} takes int64 [Q, Fu] user_cat (got {user_cat.dtype} {tuple(user_cat.shape)}, Q={Q})")
+    _check(item_dense.dtype == torch.float32 and item_dense.dim() == 2,
+           f"{who} takes f32 [N, Di] item_dense (got {item_dense.dtype} {tuple(item_dense.shape)})")
+    N = item_dense.shape[0]
+    _check(item_cat.dtype == torch.int64 and item_cat.dim() == 2 and item_cat.shape[0] == N,
+           f"{who} takes int64 [N, Fi] item_cat (got {item_cat.dtype} {tuple(item_cat.shape)}, N={N})")
+    _check(N <= 2 ** 31 - 1, f"{who} takes N <= 2^31 - 1 item rows (got {N})")
+    dev = rows.device
+    _check(all(t.device == dev for t in (user_dense, user_cat, item_dense, item_cat)), f"{who} takes tensors of one device")
+    Du, Di, Fu, Fi = user_dense.shape[1], item_dense.shape[1], user_cat.shape[1], item_cat.shape[1]
+    _check(Du + Di <= 2 ** 20 and Fu + Fi <= 2 ** 20, f"{who} takes rows of at most 2^20 columns")
+    # 16-byte units where both widths of a matrix allow them (a row slice of such a matrix stays aligned)
+    da = 16 if Du % 4 == 0 and Di % 4 == 0 else 4
+    ca = 16 if Fu % 2 == 0 and Fi % 2 == 0 else 8
+    _check(user_dense.data_ptr() % da == 0 and item_dense.data_ptr() % da == 0,
+           f"{who} takes {da}-byte aligned dense matrices of these widths")
+    _check(user_cat.data_ptr() % ca == 0 and item_cat.data_ptr() % ca == 0,
+           f"{who} takes {ca}-byte aligned categorical matrices of these widths")
+    dense = torch.empty((Q * M, Du + Di), dtype=torch.float32, device=dev)
+    cat = torch.empty((Q * M, Fu + Fi), dtype=torch.int64, device=dev)
+    d = STRUCTS["lthm_rank_assemble_desc"]()
+    d.Q, d.M, d.N, d.Du, d.Di, d.Fu, d.Fi = Q, M, N, Du, Di, Fu, Fi
+    d.user_dense, d.user_cat, d.item_dense, d.item_cat = ptr(user_dense), ptr(user_cat), ptr(item_dense), ptr(item_cat)
+    d.rows, d.out_dense, d.out_cat = ptr(rows), ptr(dense), ptr(cat)
+    row = 4 * (Du + Di) + 8 * (Fu + Fi)
+    call("lthm_rank_assemble", ctypes.addressof(d), stream(), _key="rank_assemble_k", _bytes=2.0 * Q * M * row + 4.0 * Q * M)
+    return dense, cat
+
+
+def rank_sort(logits, rows, k: int):
+    """Every list's first k entries in the order (logit descending, row ascending, position ascending)
+    (lthm_rank_sort, csrc/rank.hip).
+
+    logits f32 [Q, M], rows int32 [Q, M], 1 <= k <= M <= RANK_MAX_LIST.  An entry is a candidate when its
+    row is >= 0 and its logit is not NaN; +-inf are ordinary values and -0.0 orders as +0.0.  Returns
+    (scores f32 [Q, k], rows int32 [Q, k], src int32 [Q, k]), src the position the entry had in its list;
+    the slots behind the last candidate hold (-inf, -1, -1).  A pure function of the inputs: no atomics,
+    no workspace."""
+    who = "rank_sort"
+    require_gpu(logits, rows)
+    _check(logits.dtype == torch.float32 and logits.dim() == 2,
+           f"{who} takes f32 [Q, M] logits (got {logits.dtype} {tuple(logits.shape)})")
+    Q, M = logits.shape
+    _check(rows.dtype == torch.int32 and tuple(rows.shape) == (Q, M),
+           f"{who} takes int32 [Q, M] rows (got {rows.dtype} {tuple(rows.shape)}, Q={Q}, M={M})")
+    _check(Q >= 1 and 1 <= M <= RANK_MAX_LIST, f"{who} takes Q >= 1 lists of 1..{RANK_MAX_LIST} entries (got Q={Q}, M={M})")
+    _check(isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= M, f"{who} takes k in 1..M (got k={k!r}, M={M})")
+    _check(rows.device == logits.device, f"{who} takes tensors of one device")
+    dev = logits.device
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    out_rows = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    src = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    call("lthm_rank_sort", ptr(logits), ptr(rows), Q, M, k, ptr(scores), ptr(out_rows), ptr(src), stream(),
+         _key="rank_sort_k", _bytes=8.0 * Q * M + 12.0 * Q * k)
+    return scores, out_rows, src

@@ -15,9 +15,9 @@ the click label.
 from __future__ import annotations
 
 from statistics import NormalDist
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
-from pydantic import BaseModel, Field
+from pydantic import BaseModel, Field, model_validator
 
 
 def normal_quantiles(n: int = 20) -> List[float]:
@@ -49,6 +49,23 @@ class RankerModelConfig(BaseModel):
     weight_decay: float = 0.0
     betas: Tuple[float, float] = (0.9, 0.999)
     seed: int = 1234
+    # The serving split (models/ranker/serving.py, RankerModelWrapper.rank): the first n_user_dense dense
+    # columns and the first n_user_categorical categorical columns are the user's, the rest the item's.
+    # None: no split.  forward and training never read either field.
+    n_user_dense: Optional[int] = None
+    n_user_categorical: Optional[int] = None
+
+    @model_validator(mode="after")
+    def _check_split(self):
+        for name, n, of in (("n_user_dense", self.n_user_dense, self.n_dense),
+                            ("n_user_categorical", self.n_user_categorical, self.n_categorical)):
+            if n is not None and not 0 <= n <= of:
+                raise ValueError(f"{name} must lie in 0..{of}, the columns there are (got {n})")
+        return self
+
+    @property
+    def has_split(self) -> bool:
+        return self.n_user_dense is not None and self.n_user_categorical is not None
 
     @property
     def interaction_in(self) -> int:

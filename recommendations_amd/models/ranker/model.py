@@ -63,6 +63,23 @@ class RankerModelWrapper(BaseModelWrapper):
     def forward(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         return self._model(batch)
 
+    def rank(self, user_batch: Dict[str, torch.Tensor], item_ids: torch.Tensor, store, k: Optional[int] = None, *,
+             max_rows: int = 65536, probabilities: bool = False):
+        """Score and sort every query's candidate list (models/ranker/serving.py), under ``no_grad``.
+
+        ``user_batch`` = {"dense": f32 [Q, n_user_dense], "categorical": int64 [Q, n_user_categorical]}, the
+        user side of the config's split; ``item_ids`` int64 [Q, M], M <= 1024, what any catalogue's
+        ``topk`` / ``retrieve`` returns, pads as id 0 included; ``store`` an ``ItemFeatureStore`` with the
+        item side of the split.  Returns (item_ids int64 [Q, k], logits f32 [Q, k], src int32 [Q, k]),
+        best first, ``src`` the position the item had in its list; k defaults to M.  The order is (logit
+        descending, id ascending, position ascending).  Pads, ids the store does not hold and NaN logits
+        are no candidates; empty slots hold (0, -inf, -1).  With ``probabilities`` the second tensor is
+        sigmoid(logit), 0.0 in empty slots.  The logits are this model's ``forward`` on the assembled
+        batch, ``max(1, max_rows // M)`` queries at a time; nothing synchronises with the host, and the
+        ``training`` flag stays as it is."""
+        from .serving import rank
+        return rank(self, user_batch, item_ids, store, k, max_rows=max_rows, probabilities=probabilities)
+
     def _loss(self, batch, output):
         z = output["logits"].reshape(-1)
         y = batch["label"].reshape(-1).float().contiguous()
