@@ -57,9 +57,18 @@ and with the rows of an ``upsert`` catalogue replacing or joining the old ones, 
 its nearest centroid: per list one merge of two ascending id sequences (``K.catalogue_update``,
 csrc/catalogue_update.hip), bit for bit ``from_assignment`` of the rebuilt flat catalogue.  The quantised and
 the sharded catalogues refuse ``update`` and say what to do instead.
+
+Shared by the kinds, once each: the id lookup of the single-device catalogues (``_IdIndex``: ``rows_of``, ``holds``,
+``_ids_of``, ``filter_like`` where the kind scans tags; flat rows are in id order, clustered ones go through ``_ids`` / ``_order``), the
+argument checks every ``topk`` calls (``_check_exclude``, ``_check_tag_filter``, ``_check_bias_weight``,
+``_check_cursor``, ``_check_shortlist``, ``_check_probe_call``), ``_hit_fraction`` behind every ``recall``, ``_save`` /
+``_opened`` behind every ``save`` / ``load``, ``_sharded_target_score`` in both sharded scans, and what
+``LTHMModelWrapper.retrieve`` asks of a catalogue (``_Catalogue``: the keywords it takes, the sentence for the
+others, its checks ahead of the forward and the one ``topk`` call that answers with (item_ids, scores)).
 """
 from __future__ import annotations
 
+import contextlib
 import json
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -102,6 +111,232 @@ def make_tag_filter(n: int, tag_all: Union[int, torch.Tensor] = 0, tag_any: Unio
         raise ValueError("make_tag_filter takes n >= 1")
     cols = [_bits32(v, n, name, device) for v, name in ((tag_all, "tag_all"), (tag_any, "tag_any"), (tag_none, "tag_none"))]
     return torch.stack(cols, dim=1).to(torch.int32).contiguous()
+
+
+def _opt(t: Optional[torch.Tensor], f) -> Optional[torch.Tensor]:
+    """``f(t)``, or None for a column the catalogue does not carry."""
+    return None if t is None else f(t)
+
+
+def _filter_row(t: torch.Tensor, found: torch.Tensor, mask, device) -> torch.Tensor:
+    """``filter_like``'s int32 [Q, 3] rows (t & mask, 0, ~t & mask) from the targets' tag words ``t`` (int64 [Q],
+    the int32 values) and ``found`` (bool [Q]): (0, 0, 0) where no target was found."""
+    m = _bits32(mask, t.numel(), "mask", device)
+    m = torch.where(found, m, torch.zeros_like(m))
+    return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+
+
+# The argument checks of every ``topk`` / ``_scan``.  With ``Q`` they also check the shape against the queries;
+# without it they leave that to the kernel's wrapper (the flat scans, whose per-user arguments it knows).
+
+def _check_exclude(exclude_ids) -> None:
+    if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
+        raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+
+
+def _check_tag_filter(cat, tag_filter, Q: Optional[int] = None) -> None:
+    if tag_filter is None:
+        return
+    if not cat.has_tags:
+        raise ValueError("tag_filter given, but this catalogue carries no tags")
+    if Q is not None and (tag_filter.dtype != torch.int32 or tuple(tag_filter.shape) != (Q, 3)):
+        raise ValueError(f"tag_filter must be int32 [Q, 3] = (all, any, none) "
+                         f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, Q={Q})")
+
+
+def _check_bias_weight(cat, bias_weight, Q: Optional[int] = None) -> None:
+    if bias_weight is None:
+        return
+    if not cat.has_bias:
+        raise ValueError("bias_weight given, but this catalogue carries no bias")
+    if Q is None:
+        return
+    if isinstance(bias_weight, torch.Tensor):
+        if bias_weight.dtype != torch.float32 or tuple(bias_weight.shape) != (Q,):
+            raise ValueError(f"bias_weight must be None, a number or f32 [Q] "
+                             f"(got {bias_weight.dtype} {tuple(bias_weight.shape)}, Q={Q})")
+    elif isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float)):
+        raise ValueError(f"bias_weight must be None, a number or f32 [Q] (got {type(bias_weight).__name__})")
+
+
+def _check_cursor(after_scores, after_ids, Q: Optional[int] = None) -> None:
+    if (after_scores is None) != (after_ids is None):
+        raise ValueError("after_scores and after_ids are given together or neither")
+    if after_ids is None:
+        return
+    if after_ids.dtype != torch.int64 or (after_ids.dim() != 1 if Q is None else tuple(after_ids.shape) != (Q,)):
+        raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
+    if Q is not None and (after_scores.dtype != torch.float32 or tuple(after_scores.shape) != (Q,)):
+        raise ValueError(f"after_scores must be f32 [Q] (got {after_scores.dtype} {tuple(after_scores.shape)})")
+
+
+def _check_shortlist(k: int, shortlist, keyword: bool = False) -> int:
+    """The rows of the e4m3 scan's shortlist: ``shortlist``, or min(max(4 k, 128), 1024) for None; in k..1024.
+    ``keyword``: ``retrieve``'s argument, an int, refused in ``retrieve``'s words."""
+    if keyword and shortlist is not None and (isinstance(shortlist, bool) or not isinstance(shortlist, int)
+                                              or not int(k) <= shortlist <= K.RETRIEVE_Q8_MAX_POOL):
+        raise ValueError(f"shortlist takes k..{K.RETRIEVE_Q8_MAX_POOL} rows (got shortlist={shortlist!r}, k={k})")
+    M = QuantizedItemCatalogue.default_shortlist(k) if shortlist is None else int(shortlist)
+    if not keyword and not k <= M <= K.RETRIEVE_Q8_MAX_POOL:
+        raise ValueError(f"shortlist must lie in k..{K.RETRIEVE_Q8_MAX_POOL} (got shortlist={M}, k={k})")
+    return M
+
+
+def _check_probe_call(k: int, nprobe, max_k: int, nlist: Optional[int] = None) -> Tuple[int, int]:
+    """(k, nprobe) of a clustered scan: ``nprobe`` an int in 1..64 and, for one catalogue, at most its ``nlist``
+    (sharded: every shard probes min(nprobe, its nlist)); ``k`` in 1..``max_k``."""
+    if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
+        raise ValueError(f"a clustered catalogue takes nprobe, an int (got {nprobe!r})")
+    if nprobe > K.RETRIEVE_MAX_PROBE:
+        raise ValueError(f"nprobe takes at most {K.RETRIEVE_MAX_PROBE} lists per query (got {nprobe})")
+    if nlist is not None and nprobe > nlist:
+        raise ValueError(f"nprobe takes at most the {nlist} lists there are (got {nprobe})")
+    if nprobe < 1:
+        raise ValueError(f"nprobe takes at least one list (got {nprobe})")
+    k = int(k)
+    if not 1 <= k <= max_k:
+        raise ValueError(f"a clustered catalogue takes k in 1..{max_k} (got {k})")
+    return k, nprobe
+
+
+def _hit_fraction(want_ids: torch.Tensor, got_ids: torch.Tensor, k: int) -> float:
+    """Every ``recall``: the mean, over the queries whose reference list ``want_ids`` [Q, k] holds an id at all, of
+    the fraction of its ids (0 = an empty slot) that ``got_ids`` [Q, k] holds; 1.0 where no reference list does.
+    The comparison runs over at most 16 Mi (want, got) pairs at a time.
+
+    Two of the five callers (``QuantizedItemCatalogue``, ``ClusteredItemCatalogue``) used to write hits /
+    max(ids, 1) averaged over all queries, in one piece.  Their reference is the unfiltered flat list of a
+    catalogue that is never empty, so no list is empty: no query is left out, the hit and id counts are the
+    same integers, and the divisions and the mean are the same f64 operations on them.  The floats agree."""
+    real = want_ids != 0
+    rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison
+    hit = torch.cat([((want_ids[i:i + rows, :, None] == got_ids[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
+                     for i in range(0, want_ids.shape[0], rows)]).double()
+    n = real.sum(dim=1)
+    if not bool((n > 0).any()):
+        return 1.0
+    return float((hit[n > 0] / n[n > 0].double()).mean())
+
+
+def _save(path: str, tensors: dict, index: Optional[str] = None) -> None:
+    """The named tensors (None: a column not carried) as safetensors with the format tag and the kind's ``index`` tag."""
+    from safetensors.torch import save_file
+    meta = {"format": FORMAT} if index is None else {"format": FORMAT, "index": index}
+    save_file({n: t.detach().cpu().contiguous() for n, t in tensors.items() if t is not None}, path, metadata=meta)
+
+
+@contextlib.contextmanager
+def _opened(path: str, index: Optional[str], what: str):
+    """A catalogue file of the kind ``index`` (None: any item catalogue), checked: yields ``get(name)``, which reads
+    one tensor, and with ``optional=True`` gives None for one the file does not hold."""
+    from safetensors import safe_open
+    with safe_open(path, framework="pt") as f:
+        meta = f.metadata() or {}
+        if meta.get("format") != FORMAT or (index is not None and meta.get("index") != index):
+            raise ValueError(f"{path}: not {what} (metadata {json.dumps(meta)})")
+        names = set(f.keys())
+        yield lambda name, optional=False: f.get_tensor(name) if not optional or name in names else None
+
+
+# retrieve()'s optional keywords that a catalogue which does not take them refuses by name, in the message's order
+_NAMED = ("heads", "tag_all", "tag_any", "tag_none", "after", "bias_weight", "nprobe", "diversity", "pool", "group_cap")
+_TAGS = ("tag_all", "tag_any", "tag_none")
+
+
+def _refuse_named(cat, given: dict, order=_NAMED) -> None:
+    bad = [name for name in order if given[name] is not None and name not in cat.retrieve_takes]
+    if bad:
+        raise ValueError(cat._REFUSAL.format(", ".join(bad)))
+
+
+def _refuse_shortlist(given: dict) -> None:
+    if given["shortlist"] is not None:
+        raise ValueError("shortlist given, but this catalogue is not quantised (ItemCatalogue.quantize builds one)")
+
+
+def _need_nprobe(given: dict) -> None:
+    if given["nprobe"] is None:
+        raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
+
+
+class _Catalogue:
+    """What ``LTHMModelWrapper.retrieve`` and ``catalogue_metrics`` ask of every catalogue kind:
+
+    ``retrieve_takes``  the optional keywords of ``retrieve`` this catalogue takes (a property where views differ)
+    ``_REFUSAL``        the sentence for the others, with a slot for their names
+    ``_check_retrieve(k, given)``  refuses the keywords not taken and checks ``k`` / ``nprobe`` / ``shortlist``
+                        ahead of the forward, in this kind's order; ``given`` maps every keyword to its value
+    ``_retrieve(q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight)``
+                        the one ``topk`` call behind ``retrieve``: (item_ids, scores)
+    ``_NO_RANKS``       why ``catalogue_metrics`` does not take this kind (None: it does, by ``target_ranks``)
+    ``_RANKS_TAKE_NPROBE``  whether its ``target_ranks`` takes ``nprobe``"""
+    _NO_RANKS = None
+    _RANKS_TAKE_NPROBE = False
+    tags = bias = None
+
+    @property
+    def has_tags(self) -> bool:
+        return self.tags is not None
+
+    @property
+    def has_bias(self) -> bool:
+        return self.bias is not None
+
+
+class _IdIndex(_Catalogue):
+    """The id lookup of a single-device catalogue.  ``_ids`` are its ids ascending.  A flat catalogue's rows are in
+    that order: ``_order`` is None and row i holds ``_ids[i]``.  A clustered one's are list-major: ``_order[i]`` is
+    the row of ``_ids[i]`` and ``row_ids`` the id of every row."""
+    _order = None
+
+    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
+        """The catalogue row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
+        flat = ids.reshape(-1).to(self._ids.device)
+        at = torch.searchsorted(self._ids, flat).clamp_(max=len(self) - 1)
+        rows = torch.where(self._ids[at] == flat, at if self._order is None else self._order[at], torch.full_like(at, -1))
+        return rows.to(torch.int32).view(ids.shape)
+
+    def holds(self, ids: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of ``ids``: the catalogue holds this id."""
+        return self.rows_of(ids) >= 0
+
+    def _ids_of(self, rows: torch.Tensor) -> torch.Tensor:
+        """The id of every row (int64, same shape), 0 for a row < 0: ``rows_of``'s inverse."""
+        ids = self._ids if self._order is None else self.row_ids
+        return torch.where(rows >= 0, ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+
+    def _filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
+        """The filter "the same value as the target in the masked bit field": per target t the
+        row (tags[t] & mask, 0, ~tags[t] & mask) of an int32 [Q, 3] filter.  ``mask`` is a 32-bit
+        mask in 0..2^32-1.  A target the catalogue does not hold gets (0, 0, 0)."""
+        if self.tags is None:
+            raise ValueError("filter_like needs a catalogue with tags")
+        if target_ids.dim() != 1:
+            raise ValueError("filter_like takes target ids [Q]")
+        rows = self.rows_of(target_ids).long()
+        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
+        return _filter_row(t, rows >= 0, mask, self.tags.device)
+
+
+def _sharded_target_score(shards, q, target_ids, normalize_q: bool, bias_weight, use_bias: bool, reduce_max):
+    """The target's score over the shards of a catalogue, from the one shard that holds the target
+    (``K.retrieve_target_score`` per shard, NaN where it does not hold it, to -inf; the maximum over the shards and,
+    with ``reduce_max``, over the ranks: a real score is finite).  Returns (the score with NaN where no shard holds
+    the target, as ``target_scores`` of the scans; the same with -inf there, what one catalogue returns; the
+    target's row in every shard)."""
+    home = q.device
+    on = lambda t, dev: None if t is None else t.to(dev).contiguous()
+    parts, trows = [], []
+    for s in shards:
+        dev = s.emb.device
+        trows.append(s.rows_of(target_ids).contiguous())
+        with torch.cuda.device(dev):
+            parts.append(K.retrieve_target_score(on(q, dev), s.emb, trows[-1], normalize_q=normalize_q,
+                                                 bias=s.bias if use_bias else None,
+                                                 bias_weight=on(bias_weight, dev) if use_bias else None).to(home))
+    ts = torch.stack(parts)
+    ts = reduce_max(torch.where(torch.isnan(ts), torch.full_like(ts, float("-inf")), ts).amax(dim=0))
+    return torch.where(ts == float("-inf"), torch.full_like(ts, float("nan")), ts).contiguous(), ts, trows
 
 
 _UPDATE_COLUMNS = (("tags", torch.int32), ("bias", torch.float32), ("groups", torch.int32))
@@ -179,7 +414,7 @@ def _no_update(what: str, instead: str):
     raise ValueError(f"{what} has no update: {instead}")
 
 
-class ItemCatalogue:
+class ItemCatalogue(_IdIndex):
     """``ids`` int64 [N], strictly ascending (so unique) and without the pad id 0; ``emb`` bf16
     [N, 128], row i the normalised candidate vector of ``ids[i]``; ``tags`` int32 [N] or None,
     row i the 32 attribute bits of ``ids[i]``; ``bias`` f32 [N] or None, row i the score prior of
@@ -231,16 +466,11 @@ class ItemCatalogue:
         self.bias = bias
         self.groups = groups
 
+    _ids = property(lambda self: self.ids)
+    filter_like = _IdIndex._filter_like
+
     def __len__(self) -> int:
         return self.ids.shape[0]
-
-    @property
-    def has_tags(self) -> bool:
-        return self.tags is not None
-
-    @property
-    def has_bias(self) -> bool:
-        return self.bias is not None
 
     @property
     def has_groups(self) -> bool:
@@ -263,9 +493,8 @@ class ItemCatalogue:
                 raise ValueError("take: a row is named twice")
         if idx.numel() < 1:
             raise ValueError("take: no row remains, and a catalogue is never empty")
-        return ItemCatalogue(self.ids[idx], self.emb[idx], None if self.tags is None else self.tags[idx],
-                             None if self.bias is None else self.bias[idx],
-                             None if self.groups is None else self.groups[idx])
+        pick = lambda t: t[idx]
+        return ItemCatalogue(self.ids[idx], self.emb[idx], _opt(self.tags, pick), _opt(self.bias, pick), _opt(self.groups, pick))
 
     def split(self, n: int) -> List["ItemCatalogue"]:
         """n shards of contiguous id ranges: shard i holds rows [i N // n, (i + 1) N // n), so none
@@ -276,10 +505,6 @@ class ItemCatalogue:
         n = int(n)
         dev = self.ids.device
         return [self.take(torch.arange(i * N // n, (i + 1) * N // n, device=dev)) for i in range(n)]
-
-    def holds(self, ids: torch.Tensor) -> torch.Tensor:
-        """bool, the shape of ``ids``: the catalogue holds this id."""
-        return self.rows_of(ids) >= 0
 
     def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, exclude_ids: Optional[torch.Tensor] = None,
                      tag_filter: Optional[torch.Tensor] = None, bias_weight: Optional[float] = None) -> torch.Tensor:
@@ -307,36 +532,12 @@ class ItemCatalogue:
         if groups is not None and (groups.dim() != 1 or groups.shape[0] != ids.shape[0]):
             raise ValueError("from_embeddings takes groups [N], one key per id")
         order = torch.argsort(ids, stable=True)
-        return cls(ids[order], emb[order.to(emb.device)], None if tags is None else tags[order.to(tags.device)],
-                   None if bias is None else bias[order.to(bias.device)],
-                   None if groups is None else groups[order.to(groups.device)])
+        pick = lambda t: t[order.to(t.device)]
+        return cls(ids[order], pick(emb), _opt(tags, pick), _opt(bias, pick), _opt(groups, pick))
 
     def to(self, device) -> "ItemCatalogue":
-        return ItemCatalogue(self.ids.to(device), self.emb.to(device),
-                             None if self.tags is None else self.tags.to(device),
-                             None if self.bias is None else self.bias.to(device),
-                             None if self.groups is None else self.groups.to(device))
-
-    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
-        """The filter "the same value as the target in the masked bit field": per target t the
-        row (tags[t] & mask, 0, ~tags[t] & mask) of an int32 [Q, 3] filter.  ``mask`` is a 32-bit
-        mask in 0..2^32-1.  A target the catalogue does not hold gets (0, 0, 0)."""
-        if self.tags is None:
-            raise ValueError("filter_like needs a catalogue with tags")
-        if target_ids.dim() != 1:
-            raise ValueError("filter_like takes target ids [Q]")
-        rows = self.rows_of(target_ids).long()
-        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
-        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
-        m = torch.where(rows >= 0, m, torch.zeros_like(m))
-        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
-
-    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
-        """Catalogue row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
-        flat = ids.reshape(-1).to(self.ids.device)
-        at = torch.searchsorted(self.ids, flat).clamp_(max=len(self) - 1)
-        rows = torch.where(self.ids[at] == flat, at, torch.full_like(at, -1))
-        return rows.to(torch.int32).view(ids.shape)
+        on = lambda t: t.to(device)
+        return ItemCatalogue(on(self.ids), on(self.emb), _opt(self.tags, on), _opt(self.bias, on), _opt(self.groups, on))
 
     def cursor_rows(self, after_ids: torch.Tensor) -> torch.Tensor:
         """The row cursor of an id cursor (int32, same shape): (number of catalogue ids <=
@@ -374,32 +575,34 @@ class ItemCatalogue:
         the order, ``target_score``, ``rank`` and the cursors are those of the biased scores.
         ``bias_weight`` is w: None for 1, a number, or f32 [Q] ([U] with a 3-D ``q``), one weight
         per query.  A catalogue without a bias refuses a weight."""
-        if tag_filter is not None and self.tags is None:
-            raise ValueError("tag_filter given, but this catalogue carries no tags")
-        if bias_weight is not None and self.bias is None:
-            raise ValueError("bias_weight given, but this catalogue carries no bias")
-        if (after_scores is None) != (after_ids is None):
-            raise ValueError("after_scores and after_ids are given together or neither")
+        _check_tag_filter(self, tag_filter)
+        _check_bias_weight(self, bias_weight)
+        _check_cursor(after_scores, after_ids)
         ar = None
         if after_ids is not None:
-            if after_ids.dtype != torch.int64 or after_ids.dim() != 1:
-                raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
             ar = self.cursor_rows(after_ids).contiguous()
             after_scores = after_scores.contiguous()
         tr = self.rows_of(target_ids).contiguous() if target_ids is not None else None
-        xr = None
-        if exclude_ids is not None:
-            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
-                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-            xr = self.rows_of(exclude_ids).contiguous()  # -1 for unknown ids and for 0, which no catalogue holds
+        _check_exclude(exclude_ids)
+        xr = _opt(exclude_ids, lambda x: self.rows_of(x).contiguous())  # -1 for unknown ids and for 0, which no catalogue holds
         call = K.retrieve_topk_group if q.dim() == 3 else K.retrieve_topk
         scores, rows, rank, tscore = call(q, self.emb, k, normalize_q=normalize_q, target_rows=tr,
                                           slab_rows=slab_rows, exclude_rows=xr,
                                           tags=self.tags if tag_filter is not None else None, tag_filter=tag_filter,
                                           after_scores=after_scores, after_rows=ar, deep=int(k) > K.RETRIEVE_MAX_K,
                                           bias=self.bias, bias_weight=bias_weight)
-        item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
-        return item_ids, scores, rank, tscore
+        return self._ids_of(rows), scores, rank, tscore
+
+    retrieve_takes = frozenset(_NAMED) - {"nprobe"}
+
+    def _check_retrieve(self, k, given: dict) -> None:
+        _refuse_shortlist(given)
+        if given["nprobe"] is not None:
+            raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        return self.topk(q, k, normalize_q=True, exclude_ids=exclude_ids, tag_filter=tag_filter, after_scores=after_scores,
+                         after_ids=after_ids, bias_weight=bias_weight)[:2]
 
     def diversify(self, item_ids: torch.Tensor, scores: torch.Tensor, k: int, *,
                   lam: Union[float, torch.Tensor] = 1.0, group_cap: Optional[int] = None):
@@ -442,32 +645,15 @@ class ItemCatalogue:
         rows, sc, obj = K.retrieve_diversify(self.emb, self.rows_of(item_ids).contiguous(), scores.to(dev).contiguous(),
                                              int(k), lam=lam_t, groups=self.groups if group_cap is not None else None,
                                              cap=group_cap if group_cap is not None else 1)
-        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
-        return ids, sc, obj
+        return self._ids_of(rows), sc, obj
 
     def save(self, path: str) -> None:
-        from safetensors.torch import save_file
-        tensors = {"ids": self.ids.detach().cpu().contiguous(), "emb": self.emb.detach().cpu().contiguous()}
-        if self.tags is not None:
-            tensors["tags"] = self.tags.detach().cpu().contiguous()
-        if self.bias is not None:
-            tensors["bias"] = self.bias.detach().cpu().contiguous()
-        if self.groups is not None:
-            tensors["groups"] = self.groups.detach().cpu().contiguous()
-        save_file(tensors, path, metadata={"format": FORMAT})
+        _save(path, {"ids": self.ids, "emb": self.emb, "tags": self.tags, "bias": self.bias, "groups": self.groups})
 
     @classmethod
     def load(cls, path: str, *, device=None) -> "ItemCatalogue":
-        from safetensors import safe_open
-        with safe_open(path, framework="pt") as f:
-            meta = f.metadata() or {}
-            if meta.get("format") != FORMAT:
-                raise ValueError(f"{path}: not an item catalogue (metadata {json.dumps(meta)})")
-            ids, emb = f.get_tensor("ids"), f.get_tensor("emb")
-            tags = f.get_tensor("tags") if "tags" in f.keys() else None
-            bias = f.get_tensor("bias") if "bias" in f.keys() else None
-            groups = f.get_tensor("groups") if "groups" in f.keys() else None
-        cat = cls(ids, emb, tags, bias, groups)
+        with _opened(path, None, "an item catalogue") as get:
+            cat = cls(get("ids"), get("emb"), get("tags", True), get("bias", True), get("groups", True))
         return cat.to(device) if device is not None else cat
 
     def quantize(self, keep_exact: bool = True) -> "QuantizedItemCatalogue":
@@ -548,7 +734,7 @@ class ItemCatalogue:
 Q8_INDEX = "lthm-q8-v1"
 
 
-class QuantizedItemCatalogue:
+class QuantizedItemCatalogue(_IdIndex):
     """An ``ItemCatalogue`` stored as OCP e4m3fn codes: ``ids`` int64 [N] (strictly ascending, no 0),
     ``codes`` uint8 [N, 128] and ``scale`` f32 [N] as ``K.quantize_catalogue_q8`` writes them (row i
     stands for ``codes[i] * scale[i]``), and ``emb`` bf16 [N, 128] or None, the exact rows.  ``topk`` scans
@@ -578,6 +764,8 @@ class QuantizedItemCatalogue:
         self.scale = scale.contiguous()
         self.emb = None if emb is None else emb.contiguous()
 
+    _ids = property(lambda self: self.ids)
+
     def __len__(self) -> int:
         return self.ids.shape[0]
 
@@ -591,18 +779,7 @@ class QuantizedItemCatalogue:
 
     def to(self, device) -> "QuantizedItemCatalogue":
         return QuantizedItemCatalogue(self.ids.to(device), self.codes.to(device), self.scale.to(device),
-                                      None if self.emb is None else self.emb.to(device))
-
-    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
-        """Catalogue row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
-        flat = ids.reshape(-1).to(self.ids.device)
-        at = torch.searchsorted(self.ids, flat).clamp_(max=len(self) - 1)
-        rows = torch.where(self.ids[at] == flat, at, torch.full_like(at, -1))
-        return rows.to(torch.int32).view(ids.shape)
-
-    def holds(self, ids: torch.Tensor) -> torch.Tensor:
-        """bool, the shape of ``ids``: the catalogue holds this id."""
-        return self.rows_of(ids) >= 0
+                                      _opt(self.emb, lambda t: t.to(device)))
 
     def to_flat(self) -> ItemCatalogue:
         """The exact catalogue (without tags, bias or groups); needs ``keep_exact``."""
@@ -627,63 +804,55 @@ class QuantizedItemCatalogue:
         k = int(k)
         if not 1 <= k <= K.RETRIEVE_Q8_MAX_POOL:
             raise ValueError(f"a quantised catalogue takes k in 1..{K.RETRIEVE_Q8_MAX_POOL} (got {k})")
-        M = self.default_shortlist(k) if shortlist is None else int(shortlist)
-        if not k <= M <= K.RETRIEVE_Q8_MAX_POOL:
-            raise ValueError(f"shortlist must lie in k..{K.RETRIEVE_Q8_MAX_POOL} (got shortlist={M}, k={k})")
+        M = _check_shortlist(k, shortlist)
         if rescore and self.emb is None:
             raise ValueError("rescore=True needs the exact rows: this catalogue was built with keep_exact=False "
                              "(pass rescore=False)")
         if q.dim() != 2:
             raise ValueError(f"a quantised catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
-        xr = None
-        if exclude_ids is not None:
-            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
-                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-            xr = self.rows_of(exclude_ids).contiguous()
+        _check_exclude(exclude_ids)
+        xr = _opt(exclude_ids, lambda x: self.rows_of(x).contiguous())
         scores, rows = K.retrieve_q8_topk(q, self.codes, self.scale, M, normalize_q=normalize_q, exclude_rows=xr,
                                           slab_rows=slab_rows)
         if rescore:
             scores, rows = K.retrieve_rescore(q, self.emb, rows, k, normalize_q=normalize_q)
         else:
             scores, rows = scores[:, :k].contiguous(), rows[:, :k].contiguous()
-        item_ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
-        return item_ids, scores
+        return self._ids_of(rows), scores
+
+    retrieve_takes = frozenset()
+    _REFUSAL = "retrieve with a quantised catalogue does not take {}: use catalogue.to_flat() for it"
+
+    def _check_retrieve(self, k, given: dict) -> None:
+        _refuse_named(self, given)
+        _check_shortlist(k, given["shortlist"], keyword=True)
+        if not 1 <= int(k) <= K.RETRIEVE_Q8_MAX_POOL:
+            raise ValueError(f"a quantised catalogue takes k in 1..{K.RETRIEVE_Q8_MAX_POOL} (got {k})")
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        return self.topk(q, k, shortlist=shortlist, rescore=self.keep_exact, normalize_q=True, exclude_ids=exclude_ids)
 
     def recall(self, q: torch.Tensor, k: int, shortlist: Optional[int] = None) -> float:
         """The mean over the queries of the fraction of the flat scan's top-k ids that
         ``topk(q, k, shortlist=shortlist)`` returns; needs ``keep_exact``."""
-        want = self.to_flat().topk(q, k)[0]
-        got = self.topk(q, k, shortlist=shortlist)[0]
-        real = want != 0
-        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
-        return float((hit / real.sum(dim=1).clamp(min=1).double()).mean())
+        return _hit_fraction(self.to_flat().topk(q, k)[0], self.topk(q, k, shortlist=shortlist)[0], k)
 
     def save(self, path: str) -> None:
         """``ItemCatalogue.save``'s container with ``codes`` and ``scale`` beside ``ids`` (and ``emb``
         where the exact rows are kept: ``ItemCatalogue.load`` then reads the flat catalogue)."""
-        from safetensors.torch import save_file
-        tensors = {"ids": self.ids.detach().cpu().contiguous(), "codes": self.codes.detach().cpu().contiguous(),
-                   "scale": self.scale.detach().cpu().contiguous()}
-        if self.emb is not None:
-            tensors["emb"] = self.emb.detach().cpu().contiguous()
-        save_file(tensors, path, metadata={"format": FORMAT, "index": Q8_INDEX})
+        _save(path, {"ids": self.ids, "codes": self.codes, "scale": self.scale, "emb": self.emb}, Q8_INDEX)
 
     @classmethod
     def load(cls, path: str, *, device=None) -> "QuantizedItemCatalogue":
-        from safetensors import safe_open
-        with safe_open(path, framework="pt") as f:
-            meta = f.metadata() or {}
-            if meta.get("format") != FORMAT or meta.get("index") != Q8_INDEX:
-                raise ValueError(f"{path}: not a quantised item catalogue (metadata {json.dumps(meta)})")
-            cat = cls(f.get_tensor("ids"), f.get_tensor("codes"), f.get_tensor("scale"),
-                      f.get_tensor("emb") if "emb" in f.keys() else None)
+        with _opened(path, Q8_INDEX, "a quantised item catalogue") as get:
+            cat = cls(get("ids"), get("codes"), get("scale"), get("emb", True))
         return cat.to(device) if device is not None else cat
 
 
 IVF_INDEX = "lthm-ivf-v1"
 
 
-class ClusteredItemCatalogue:
+class ClusteredItemCatalogue(_IdIndex):
     """An ``ItemCatalogue`` whose rows are grouped into L lists around centroids (an inverted-file
     index), so that a query scans the ``nprobe`` lists nearest to it instead of every row
     (``K.retrieve_ivf_topk``, csrc/retrieve.hip ``retr_ivf_topk_k``).
@@ -768,9 +937,9 @@ class ClusteredItemCatalogue:
         order = torch.argsort(assign, stable=True)  # list-major, id-ascending inside a list
         counts = torch.bincount(assign, minlength=L)
         list_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)])
+        pick = lambda t: t[order]
         return cls(catalogue.ids[order], catalogue.emb[order], list_off, centroids.to(dev),
-                   None if catalogue.tags is None else catalogue.tags[order],
-                   None if catalogue.bias is None else catalogue.bias[order])
+                   _opt(catalogue.tags, pick), _opt(catalogue.bias, pick))
 
     @classmethod
     def _trusted(cls, row_ids, emb, list_off, centroids, tags, bias) -> "ClusteredItemCatalogue":
@@ -830,41 +999,22 @@ class ClusteredItemCatalogue:
     def nlist(self) -> int:
         return self.centroids.shape[0]
 
-    @property
-    def has_tags(self) -> bool:
-        return self.tags is not None
-
-    @property
-    def has_bias(self) -> bool:
-        return self.bias is not None
-
     def list_lengths(self) -> torch.Tensor:
         """int64 [L]: the rows of every list."""
         return self.list_off[1:] - self.list_off[:-1]
 
-    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
-        """The clustered row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
-        flat = ids.reshape(-1).to(self._ids.device)
-        at = torch.searchsorted(self._ids, flat).clamp_(max=len(self) - 1)
-        rows = torch.where(self._ids[at] == flat, self._order[at], torch.full_like(at, -1))
-        return rows.to(torch.int32).view(ids.shape)
-
-    def holds(self, ids: torch.Tensor) -> torch.Tensor:
-        return self.rows_of(ids) >= 0
-
     def to_flat(self) -> ItemCatalogue:
         """The id-sorted ``ItemCatalogue`` of the same items, bit for bit the one this was built from."""
-        o = self._order
-        return ItemCatalogue(self._ids, self.emb[o], None if self.tags is None else self.tags[o],
-                             None if self.bias is None else self.bias[o])
+        pick = lambda t: t[self._order]
+        return ItemCatalogue(self._ids, pick(self.emb), _opt(self.tags, pick), _opt(self.bias, pick))
 
     def to(self, device) -> "ClusteredItemCatalogue":
-        out = ClusteredItemCatalogue(self.row_ids.to(device), self.emb.to(device), self.list_off.to(device),
-                                     self.centroids.to(device), None if self.tags is None else self.tags.to(device),
-                                     None if self.bias is None else self.bias.to(device))
+        on = lambda t: t.to(device)
+        out = ClusteredItemCatalogue(on(self.row_ids), on(self.emb), on(self.list_off), on(self.centroids),
+                                     _opt(self.tags, on), _opt(self.bias, on))
         if self.scans_deep or self.scans_heads:
             view = out.with_deep() if self.scans_deep else out.with_heads()
-            view.groups = None if self.groups is None else self.groups.to(device)
+            view.groups = _opt(self.groups, on)
             return view
         return out.with_filters() if self.scans_filters else out
 
@@ -940,18 +1090,7 @@ class ClusteredItemCatalogue:
         return view
 
     def _check_call(self, k: int, nprobe) -> Tuple[int, int]:
-        if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
-            raise ValueError(f"a clustered catalogue takes nprobe, an int (got {nprobe!r})")
-        if nprobe > K.RETRIEVE_MAX_PROBE:
-            raise ValueError(f"nprobe takes at most {K.RETRIEVE_MAX_PROBE} lists per query (got {nprobe})")
-        if nprobe > self.nlist:
-            raise ValueError(f"nprobe takes at most the {self.nlist} lists there are (got {nprobe})")
-        if nprobe < 1:
-            raise ValueError(f"nprobe takes at least one list (got {nprobe})")
-        k = int(k)
-        if not 1 <= k <= self._MAX_K:
-            raise ValueError(f"a clustered catalogue takes k in 1..{self._MAX_K} (got {k})")
-        return k, nprobe
+        return _check_probe_call(k, nprobe, self._MAX_K, self.nlist)
 
     def probe(self, q: torch.Tensor, nprobe: int, *, normalize_q: bool = True) -> torch.Tensor:
         """int32 [Q, nprobe]: the lists of the nprobe best centroids per query, best first
@@ -971,25 +1110,44 @@ class ClusteredItemCatalogue:
         k, nprobe = self._check_call(k, nprobe)
         if q.dim() != 2:
             raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
-        xr = None
-        if exclude_ids is not None:
-            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
-                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-            xr = self.rows_of(exclude_ids).contiguous()
+        _check_exclude(exclude_ids)
+        xr = _opt(exclude_ids, lambda x: self.rows_of(x).contiguous())
         probes = self.probe(q, nprobe, normalize_q=normalize_q)
         return K.retrieve_ivf_topk(q, self.emb, self.row_ids, self.list_off, probes, k, normalize_q=normalize_q,
                                    exclude_rows=xr)
+
+    _REFUSAL = "retrieve with a clustered catalogue does not take {}: use catalogue.to_flat() for it"
+    _NO_RANKS = "catalogue_metrics counts exact ranks, which take the flat scan: pass catalogue.to_flat()"
+
+    @property
+    def retrieve_takes(self) -> frozenset:
+        """``nprobe``; a ``with_filters()`` view also the tags, the cursor and the weight it scans with, a
+        ``with_heads()`` view also ``heads``, a ``with_deep()`` view also what diversifies its own lists."""
+        takes = {"nprobe"}
+        if self.scans_filters:
+            takes |= {*_TAGS, "after", "bias_weight"}
+        if self.scans_heads:
+            takes |= {"heads"}
+        if self.scans_deep:
+            takes |= {"diversity", "pool", "group_cap"}
+        return frozenset(takes)
+
+    def _check_retrieve(self, k, given: dict) -> None:
+        _refuse_shortlist(given)
+        _refuse_named(self, given)
+        _need_nprobe(given)
+        self._check_call(k, given["nprobe"])
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        scores, item_ids = self.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=exclude_ids)
+        return item_ids, scores
 
     def recall(self, q: torch.Tensor, k: int, nprobe: int) -> float:
         """The mean over the queries of the fraction of the flat scan's top-k ids (plain dots, no
         filter) that ``topk(q, k, nprobe=nprobe)`` returns.  Never decreases in ``nprobe``; 1.0 at L."""
         if self._plain is None:
             self._plain = ItemCatalogue(self._ids, self.emb[self._order])
-        want = self._plain.topk(q, k)[0]
-        got = self.topk(q, k, nprobe=nprobe)[1]
-        real = want != 0
-        hit = ((want[:, :, None] == got[:, None, :]).any(dim=2) & real).sum(dim=1).double()
-        return float((hit / real.sum(dim=1).clamp(min=1).double()).mean())
+        return _hit_fraction(self._plain.topk(q, k)[0], self.topk(q, k, nprobe=nprobe)[1], k)
 
     def quantize(self, keep_exact: bool = True) -> "QuantizedClusteredItemCatalogue":
         """This catalogue as e4m3 codes with one power-of-two scale per row, in the same lists
@@ -1003,33 +1161,20 @@ class ClusteredItemCatalogue:
     def save(self, path: str) -> None:
         """The flat catalogue's file (``ItemCatalogue.load`` reads it as the id-sorted catalogue) with
         ``row_ids``, ``list_off`` and ``centroids`` beside its tensors."""
-        from safetensors.torch import save_file
         flat = self.to_flat()
-        tensors = {"ids": flat.ids.detach().cpu().contiguous(), "emb": flat.emb.detach().cpu().contiguous(),
-                   "row_ids": self.row_ids.detach().cpu().contiguous(), "list_off": self.list_off.detach().cpu().contiguous(),
-                   "centroids": self.centroids.detach().cpu().contiguous()}
-        if flat.tags is not None:
-            tensors["tags"] = flat.tags.detach().cpu().contiguous()
-        if flat.bias is not None:
-            tensors["bias"] = flat.bias.detach().cpu().contiguous()
-        save_file(tensors, path, metadata={"format": FORMAT, "index": IVF_INDEX})
+        _save(path, {"ids": flat.ids, "emb": flat.emb, "row_ids": self.row_ids, "list_off": self.list_off,
+                     "centroids": self.centroids, "tags": flat.tags, "bias": flat.bias}, IVF_INDEX)
 
     @classmethod
     def load(cls, path: str, *, device=None) -> "ClusteredItemCatalogue":
-        from safetensors import safe_open
-        with safe_open(path, framework="pt") as f:
-            meta = f.metadata() or {}
-            if meta.get("format") != FORMAT or meta.get("index") != IVF_INDEX:
-                raise ValueError(f"{path}: not a clustered item catalogue (metadata {json.dumps(meta)})")
-            flat = ItemCatalogue(f.get_tensor("ids"), f.get_tensor("emb"),
-                                 f.get_tensor("tags") if "tags" in f.keys() else None,
-                                 f.get_tensor("bias") if "bias" in f.keys() else None)
-            row_ids, list_off, centroids = f.get_tensor("row_ids"), f.get_tensor("list_off"), f.get_tensor("centroids")
+        with _opened(path, IVF_INDEX, "a clustered item catalogue") as get:
+            flat = ItemCatalogue(get("ids"), get("emb"), get("tags", True), get("bias", True))
+            row_ids, list_off, centroids = get("row_ids"), get("list_off"), get("centroids")
         rows = flat.rows_of(row_ids).long()
         if row_ids.shape != flat.ids.shape or bool((rows < 0).any()):
             raise ValueError(f"{path}: row_ids are not the catalogue's ids")
-        cat = cls(row_ids, flat.emb[rows], list_off, centroids, None if flat.tags is None else flat.tags[rows],
-                  None if flat.bias is None else flat.bias[rows])
+        pick = lambda t: t[rows]
+        cat = cls(row_ids, pick(flat.emb), list_off, centroids, _opt(flat.tags, pick), _opt(flat.bias, pick))
         return cat.to(device) if device is not None else cat
 
 
@@ -1047,45 +1192,22 @@ class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
     def with_filters(self) -> "FilteredClusteredItemCatalogue":
         return self
 
-    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
-        """``ItemCatalogue.filter_like``: per target t the row (tags[t] & mask, 0, ~tags[t] & mask) of an
-        int32 [Q, 3] filter, (0, 0, 0) for a target the catalogue does not hold."""
-        if self.tags is None:
-            raise ValueError("filter_like needs a catalogue with tags")
-        if target_ids.dim() != 1:
-            raise ValueError("filter_like takes target ids [Q]")
-        rows = self.rows_of(target_ids).long()
-        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
-        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
-        m = torch.where(rows >= 0, m, torch.zeros_like(m))
-        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+    filter_like = _IdIndex._filter_like
 
     def _check_filters(self, q, tag_filter, after_scores, after_ids, bias_weight) -> None:
         if q.dim() != 2:
             raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
-        Q = q.shape[0]
-        if tag_filter is not None:
-            if self.tags is None:
-                raise ValueError("tag_filter given, but this catalogue carries no tags")
-            if tag_filter.dtype != torch.int32 or tuple(tag_filter.shape) != (Q, 3):
-                raise ValueError(f"tag_filter must be int32 [Q, 3] = (all, any, none) "
-                                 f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, Q={Q})")
-        if bias_weight is not None:
-            if self.bias is None:
-                raise ValueError("bias_weight given, but this catalogue carries no bias")
-            if isinstance(bias_weight, torch.Tensor):
-                if bias_weight.dtype != torch.float32 or tuple(bias_weight.shape) != (Q,):
-                    raise ValueError(f"bias_weight must be None, a number or f32 [Q] "
-                                     f"(got {bias_weight.dtype} {tuple(bias_weight.shape)}, Q={Q})")
-            elif isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float)):
-                raise ValueError(f"bias_weight must be None, a number or f32 [Q] (got {type(bias_weight).__name__})")
-        if (after_scores is None) != (after_ids is None):
-            raise ValueError("after_scores and after_ids are given together or neither")
-        if after_ids is not None:
-            if after_ids.dtype != torch.int64 or tuple(after_ids.shape) != (Q,):
-                raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
-            if after_scores.dtype != torch.float32 or tuple(after_scores.shape) != (Q,):
-                raise ValueError(f"after_scores must be f32 [Q] (got {after_scores.dtype} {tuple(after_scores.shape)})")
+        _check_tag_filter(self, tag_filter, q.shape[0])
+        _check_bias_weight(self, bias_weight, q.shape[0])
+        _check_cursor(after_scores, after_ids, q.shape[0])
+
+    def _scan_args(self, exclude_ids, tag_filter, after_scores, after_ids, bias_weight) -> dict:
+        """The filter keywords of ``K.retrieve_ivf_topk`` / ``K.retrieve_ivf_topk_group`` for checked arguments."""
+        _check_exclude(exclude_ids)
+        tight = lambda t: t.contiguous()
+        return dict(exclude_rows=_opt(exclude_ids, lambda x: self.rows_of(x).contiguous()),
+                    tags=self.tags if tag_filter is not None else None, tag_filter=_opt(tag_filter, tight), bias=self.bias,
+                    bias_weight=bias_weight, after_scores=_opt(after_scores, tight), after_ids=_opt(after_ids, tight))
 
     def topk(self, q: torch.Tensor, k: int, *, nprobe: int, normalize_q: bool = True,
              exclude_ids: Optional[torch.Tensor] = None, tag_filter: Optional[torch.Tensor] = None,
@@ -1103,19 +1225,15 @@ class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
         page's cursor yields the following k items, and the (-inf, 0) of an exhausted page an empty one."""
         k, nprobe = self._check_call(k, nprobe)
         self._check_filters(q, tag_filter, after_scores, after_ids, bias_weight)
-        xr = None
-        if exclude_ids is not None:
-            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
-                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-            xr = self.rows_of(exclude_ids).contiguous()
+        kw = self._scan_args(exclude_ids, tag_filter, after_scores, after_ids, bias_weight)
         probes = self.probe(q, nprobe, normalize_q=normalize_q)
         return K.retrieve_ivf_topk(q, self.emb, self.row_ids, self.list_off, probes, k, normalize_q=normalize_q,
-                                   exclude_rows=xr, tags=self.tags if tag_filter is not None else None,
-                                   tag_filter=None if tag_filter is None else tag_filter.contiguous(),
-                                   bias=self.bias, bias_weight=bias_weight,
-                                   after_scores=None if after_scores is None else after_scores.contiguous(),
-                                   after_ids=None if after_ids is None else after_ids.contiguous(),
-                                   deep=self.scans_deep)
+                                   deep=self.scans_deep, **kw)
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        scores, item_ids = self.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=exclude_ids, tag_filter=tag_filter,
+                                     after_scores=after_scores, after_ids=after_ids, bias_weight=bias_weight)
+        return item_ids, scores
 
     def recall(self, q: torch.Tensor, k: int, nprobe: int, **filters) -> float:
         """The mean over the queries of the fraction of ``to_flat().topk(q, k, **filters)``'s ids that
@@ -1124,16 +1242,7 @@ class FilteredClusteredItemCatalogue(ClusteredItemCatalogue):
         empty (1.0 where every one is).  Never decreases in ``nprobe``; 1.0 at L."""
         if self._flat is None:
             self._flat = self.to_flat()
-        want = self._flat.topk(q, k, **filters)[0]
-        got = self.topk(q, k, nprobe=nprobe, **filters)[1]
-        real = want != 0
-        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
-        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
-                         for i in range(0, want.shape[0], rows)]).double()
-        n = real.sum(dim=1)
-        if not bool((n > 0).any()):
-            return 1.0
-        return float((hit[n > 0] / n[n > 0].double()).mean())
+        return _hit_fraction(self._flat.topk(q, k, **filters)[0], self.topk(q, k, nprobe=nprobe, **filters)[1], k)
 
 
 class DeepClusteredItemCatalogue(FilteredClusteredItemCatalogue):
@@ -1245,25 +1354,19 @@ class GroupedClusteredItemCatalogue(FilteredClusteredItemCatalogue):
         k, nprobe = self._check_call(k, nprobe)
         q = self._grouped(q)
         self._check_filters(q[:, 0], tag_filter, after_scores, after_ids, bias_weight)
-        xr = None
-        if exclude_ids is not None:
-            if exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2:
-                raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-            xr = self.rows_of(exclude_ids).contiguous()
+        kw = self._scan_args(exclude_ids, tag_filter, after_scores, after_ids, bias_weight)
         probes = self.probe(q, nprobe, normalize_q=normalize_q)
-        kw = dict(normalize_q=normalize_q, exclude_rows=xr, tags=self.tags if tag_filter is not None else None,
-                  tag_filter=None if tag_filter is None else tag_filter.contiguous(), bias=self.bias,
-                  bias_weight=bias_weight, after_scores=None if after_scores is None else after_scores.contiguous(),
-                  after_ids=None if after_ids is None else after_ids.contiguous())
         if q.shape[1] == 1:
-            return K.retrieve_ivf_topk(q[:, 0].contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
-        return K.retrieve_ivf_topk_group(q.contiguous(), self.emb, self.row_ids, self.list_off, probes, k, **kw)
+            return K.retrieve_ivf_topk(q[:, 0].contiguous(), self.emb, self.row_ids, self.list_off, probes, k,
+                                       normalize_q=normalize_q, **kw)
+        return K.retrieve_ivf_topk_group(q.contiguous(), self.emb, self.row_ids, self.list_off, probes, k,
+                                         normalize_q=normalize_q, **kw)
 
 
 IVF_Q8_INDEX = "lthm-ivf-q8-v1"
 
 
-class QuantizedClusteredItemCatalogue:
+class QuantizedClusteredItemCatalogue(_IdIndex):
     """``ClusteredItemCatalogue.quantize()``: the clustered catalogue stored as OCP e4m3fn codes, small and
     cheap to query at once, and still able to filter.
 
@@ -1338,41 +1441,20 @@ class QuantizedClusteredItemCatalogue:
         return self.centroids.shape[0]
 
     @property
-    def has_tags(self) -> bool:
-        return self.tags is not None
-
-    @property
-    def has_bias(self) -> bool:
-        return self.bias is not None
-
-    @property
     def keep_exact(self) -> bool:
         return self.emb is not None
 
-    def list_lengths(self) -> torch.Tensor:
-        """int64 [L]: the rows of every list."""
-        return self.list_off[1:] - self.list_off[:-1]
-
-    def rows_of(self, ids: torch.Tensor) -> torch.Tensor:
-        """The clustered row of every id (int32, same shape), -1 for ids the catalogue does not hold."""
-        flat = ids.reshape(-1).to(self._ids.device)
-        at = torch.searchsorted(self._ids, flat).clamp_(max=len(self) - 1)
-        rows = torch.where(self._ids[at] == flat, self._order[at], torch.full_like(at, -1))
-        return rows.to(torch.int32).view(ids.shape)
-
-    def holds(self, ids: torch.Tensor) -> torch.Tensor:
-        """bool, the shape of ``ids``: the catalogue holds this id."""
-        return self.rows_of(ids) >= 0
+    list_lengths = ClusteredItemCatalogue.list_lengths
+    filter_like = _IdIndex._filter_like
 
     def update(self, *args, **kwargs):
         """Refused: the codes and scales are made per catalogue by ``quantize()``."""
         _no_update("a QuantizedClusteredItemCatalogue", "update the bf16 ClusteredItemCatalogue and call quantize() again")
 
     def to(self, device) -> "QuantizedClusteredItemCatalogue":
-        on = lambda t: None if t is None else t.to(device)
-        return QuantizedClusteredItemCatalogue(self.row_ids.to(device), self.codes.to(device), self.scale.to(device),
-                                               self.list_off.to(device), self.centroids.to(device), on(self.tags),
-                                               on(self.bias), on(self.emb))
+        on = lambda t: _opt(t, lambda t: t.to(device))
+        return QuantizedClusteredItemCatalogue(on(self.row_ids), on(self.codes), on(self.scale), on(self.list_off),
+                                               on(self.centroids), on(self.tags), on(self.bias), on(self.emb))
 
     def to_clustered(self) -> ClusteredItemCatalogue:
         """The bf16 clustered catalogue over the same lists, tags and bias; needs ``keep_exact``."""
@@ -1384,19 +1466,6 @@ class QuantizedClusteredItemCatalogue:
         """The exact id-sorted ``ItemCatalogue`` of the same items, with tags and bias; needs ``keep_exact``."""
         return self.to_clustered().to_flat()
 
-    def filter_like(self, target_ids: torch.Tensor, mask: int) -> torch.Tensor:
-        """``ItemCatalogue.filter_like``: per target t the row (tags[t] & mask, 0, ~tags[t] & mask) of an
-        int32 [Q, 3] filter, (0, 0, 0) for a target the catalogue does not hold."""
-        if self.tags is None:
-            raise ValueError("filter_like needs a catalogue with tags")
-        if target_ids.dim() != 1:
-            raise ValueError("filter_like takes target ids [Q]")
-        rows = self.rows_of(target_ids).long()
-        m = _bits32(mask, rows.numel(), "mask", self.tags.device)
-        t = torch.where(rows >= 0, self.tags[rows.clamp(min=0)].long(), torch.zeros_like(rows))
-        m = torch.where(rows >= 0, m, torch.zeros_like(m))
-        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
-
     @staticmethod
     def default_shortlist(k: int) -> int:
         return QuantizedItemCatalogue.default_shortlist(k)
@@ -1405,25 +1474,23 @@ class QuantizedClusteredItemCatalogue:
     _check_call = ClusteredItemCatalogue._check_call
     probe = ClusteredItemCatalogue.probe
 
-    def _check_filters(self, q, exclude_ids, tag_filter, bias_weight) -> None:
-        if tag_filter is not None and self.tags is None:
-            raise ValueError("tag_filter given, but this catalogue carries no tags")
-        if bias_weight is not None and self.bias is None:
-            raise ValueError("bias_weight given, but this catalogue carries no bias")
-        if q.dim() != 2:
-            raise ValueError(f"a quantised catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
-        Q = q.shape[0]
-        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
-            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
-        if tag_filter is not None and (tag_filter.dtype != torch.int32 or tuple(tag_filter.shape) != (Q, 3)):
-            raise ValueError(f"tag_filter must be int32 [Q, 3] = (all, any, none) "
-                             f"(got {tag_filter.dtype} {tuple(tag_filter.shape)}, Q={Q})")
-        if isinstance(bias_weight, torch.Tensor):
-            if bias_weight.dtype != torch.float32 or tuple(bias_weight.shape) != (Q,):
-                raise ValueError(f"bias_weight must be None, a number or f32 [Q] "
-                                 f"(got {bias_weight.dtype} {tuple(bias_weight.shape)}, Q={Q})")
-        elif bias_weight is not None and (isinstance(bias_weight, bool) or not isinstance(bias_weight, (int, float))):
-            raise ValueError(f"bias_weight must be None, a number or f32 [Q] (got {type(bias_weight).__name__})")
+    retrieve_takes = frozenset({*_TAGS, "bias_weight", "nprobe", "shortlist"})
+    _REFUSAL = "retrieve with a quantised clustered catalogue does not take {}: use catalogue.to_clustered() for it"
+    _NO_RANKS = ("catalogue_metrics does not take a quantised clustered catalogue: it counts exact ranks, "
+                 "which take the flat scan (pass catalogue.to_flat())")
+
+    def _check_retrieve(self, k, given: dict) -> None:
+        _refuse_named(self, given)
+        _need_nprobe(given)
+        self._check_call(k, given["nprobe"])
+        _check_shortlist(k, given["shortlist"], keyword=True)
+        _check_bias_weight(self, given["bias_weight"])
+        if any(given[name] is not None for name in _TAGS) and not self.has_tags:
+            raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        return self.topk(q, k, nprobe=nprobe, shortlist=shortlist, rescore=self.keep_exact, normalize_q=True,
+                         exclude_ids=exclude_ids, tag_filter=tag_filter, bias_weight=bias_weight)
 
     def topk(self, q: torch.Tensor, k: int, *, nprobe: int, shortlist: Optional[int] = None, rescore: bool = True,
              normalize_q: bool = True, exclude_ids: Optional[torch.Tensor] = None,
@@ -1440,27 +1507,30 @@ class QuantizedClusteredItemCatalogue:
         descending, id ascending) are returned.  ``rescore=False`` returns the first k of the shortlist
         with the approximate scores.  ``k`` in 1..1024, ``q`` [Q, 128]."""
         k, nprobe = self._check_call(k, nprobe)
-        M = self.default_shortlist(k) if shortlist is None else int(shortlist)
-        if not k <= M <= K.RETRIEVE_Q8_MAX_POOL:
-            raise ValueError(f"shortlist must lie in k..{K.RETRIEVE_Q8_MAX_POOL} (got shortlist={M}, k={k})")
+        M = _check_shortlist(k, shortlist)
         if rescore and self.emb is None:
             raise ValueError("rescore=True needs the exact rows: this catalogue was built with keep_exact=False "
                              "(pass rescore=False)")
-        self._check_filters(q, exclude_ids, tag_filter, bias_weight)
-        xr = None if exclude_ids is None else self.rows_of(exclude_ids).contiguous()
+        _check_tag_filter(self, tag_filter)
+        _check_bias_weight(self, bias_weight)
+        if q.dim() != 2:
+            raise ValueError(f"a quantised catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
+        _check_exclude(exclude_ids)
+        _check_tag_filter(self, tag_filter, q.shape[0])
+        _check_bias_weight(self, bias_weight, q.shape[0])
+        xr = _opt(exclude_ids, lambda x: self.rows_of(x).contiguous())
         probes = self.probe(q, nprobe, normalize_q=normalize_q)
         scores, rows = K.retrieve_ivf_q8_topk(q, self.codes, self.scale, self.row_ids, self.list_off, probes, M,
                                               normalize_q=normalize_q, exclude_rows=xr,
                                               tags=self.tags if tag_filter is not None else None,
-                                              tag_filter=None if tag_filter is None else tag_filter.contiguous(),
+                                              tag_filter=_opt(tag_filter, lambda t: t.contiguous()),
                                               bias=self.bias, bias_weight=bias_weight)
         if rescore:
             scores, rows = K.retrieve_rescore_bias(q, self.emb, rows, k, normalize_q=normalize_q, bias=self.bias,
                                                    bias_weight=bias_weight, order_ids=self.row_ids)
         else:
             scores, rows = scores[:, :k].contiguous(), rows[:, :k].contiguous()
-        item_ids = torch.where(rows >= 0, self.row_ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
-        return item_ids, scores
+        return self._ids_of(rows), scores
 
     def recall(self, q: torch.Tensor, k: int, nprobe: int, shortlist: Optional[int] = None, **filters) -> float:
         """The mean over the queries of the fraction of the bf16 clustered list's ids (``with_deep()`` with
@@ -1469,43 +1539,24 @@ class QuantizedClusteredItemCatalogue:
         list is not empty (1.0 where every one is); needs ``keep_exact``."""
         if self._exact is None:
             self._exact = self.to_clustered().with_deep()
-        want = self._exact.topk(q, k, nprobe=nprobe, **filters)[1]
-        got = self.topk(q, k, nprobe=nprobe, shortlist=shortlist, **filters)[0]
-        real = want != 0
-        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
-        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
-                         for i in range(0, want.shape[0], rows)]).double()
-        n = real.sum(dim=1)
-        if not bool((n > 0).any()):
-            return 1.0
-        return float((hit[n > 0] / n[n > 0].double()).mean())
+        return _hit_fraction(self._exact.topk(q, k, nprobe=nprobe, **filters)[1],
+                             self.topk(q, k, nprobe=nprobe, shortlist=shortlist, **filters)[0], k)
 
     def save(self, path: str) -> None:
         """safetensors with the catalogue's tensors under their names (``emb`` where the exact rows are kept),
         all in the clustered order, and the format tag of this kind of catalogue."""
-        from safetensors.torch import save_file
-        tensors = {"row_ids": self.row_ids, "codes": self.codes, "scale": self.scale, "list_off": self.list_off,
-                   "centroids": self.centroids}
-        for name in ("tags", "bias", "emb"):
-            if getattr(self, name) is not None:
-                tensors[name] = getattr(self, name)
-        save_file({n: t.detach().cpu().contiguous() for n, t in tensors.items()}, path,
-                  metadata={"format": FORMAT, "index": IVF_Q8_INDEX})
+        _save(path, {"row_ids": self.row_ids, "codes": self.codes, "scale": self.scale, "list_off": self.list_off,
+                     "centroids": self.centroids, "tags": self.tags, "bias": self.bias, "emb": self.emb}, IVF_Q8_INDEX)
 
     @classmethod
     def load(cls, path: str, *, device=None) -> "QuantizedClusteredItemCatalogue":
-        from safetensors import safe_open
-        with safe_open(path, framework="pt") as f:
-            meta = f.metadata() or {}
-            if meta.get("format") != FORMAT or meta.get("index") != IVF_Q8_INDEX:
-                raise ValueError(f"{path}: not a quantised clustered item catalogue (metadata {json.dumps(meta)})")
-            opt = lambda n: f.get_tensor(n) if n in f.keys() else None
-            cat = cls(f.get_tensor("row_ids"), f.get_tensor("codes"), f.get_tensor("scale"), f.get_tensor("list_off"),
-                      f.get_tensor("centroids"), opt("tags"), opt("bias"), opt("emb"))
+        with _opened(path, IVF_Q8_INDEX, "a quantised clustered item catalogue") as get:
+            cat = cls(get("row_ids"), get("codes"), get("scale"), get("list_off"), get("centroids"), get("tags", True),
+                      get("bias", True), get("emb", True))
         return cat.to(device) if device is not None else cat
 
 
-class ShardedItemCatalogue:
+class ShardedItemCatalogue(_Catalogue):
     """One catalogue held as shards: ``local_shards`` are the ``ItemCatalogue``s of this process (on
     one device or on several; disjoint ids, checked here), and with ``group`` the catalogue also
     covers the shards of the group's other ranks.  All shards agree on carrying tags and on carrying
@@ -1603,24 +1654,15 @@ class ShardedItemCatalogue:
             word = s.tags[rows.clamp(min=0)].long() & 0xFFFFFFFF
             both = torch.maximum(both, torch.stack([(rows >= 0).long(), torch.where(rows >= 0, word, 0)]).to(dev))
         both = self._reduce_max(both)
-        found, t = both[0] > 0, both[1]
-        t = torch.where(t >= (1 << 31), t - (1 << 32), t)
-        m = _bits32(mask, t.numel(), "mask", dev)
-        m = torch.where(found, m, torch.zeros_like(m))
-        return torch.stack([t & m, torch.zeros_like(t), ~t & m], dim=1).to(torch.int32).contiguous()
+        t = both[1]
+        return _filter_row(torch.where(t >= (1 << 31), t - (1 << 32), t), both[0] > 0, mask, dev)
 
     def _scan(self, q, k, normalize_q, target_ids, slab_rows, exclude_ids, tag_filter, after_scores, after_ids,
               bias_weight, use_bias):
-        if tag_filter is not None and not self.has_tags:
-            raise ValueError("tag_filter given, but this catalogue carries no tags")
-        if bias_weight is not None and not self.has_bias:
-            raise ValueError("bias_weight given, but this catalogue carries no bias")
-        if (after_scores is None) != (after_ids is None):
-            raise ValueError("after_scores and after_ids are given together or neither")
-        if after_ids is not None and (after_ids.dtype != torch.int64 or after_ids.dim() != 1):
-            raise ValueError(f"after_ids must be int64 [Q] (got {after_ids.dtype} {tuple(after_ids.shape)})")
-        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
-            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+        _check_tag_filter(self, tag_filter)
+        _check_bias_weight(self, bias_weight)
+        _check_cursor(after_scores, after_ids)
+        _check_exclude(exclude_ids)
         k = int(k)
         if not 1 <= k <= K.RETRIEVE_MAX_DEEP:
             raise ValueError(f"topk takes k in 1..{K.RETRIEVE_MAX_DEEP} (got {k})")
@@ -1633,19 +1675,8 @@ class ShardedItemCatalogue:
         tscore = tscore_out = None
         trows = [None] * len(self.shards)
         if target_ids is not None:
-            parts = []
-            for i, s in enumerate(self.shards):
-                dev = s.ids.device
-                trows[i] = s.rows_of(target_ids).contiguous()
-                with torch.cuda.device(dev):
-                    parts.append(K.retrieve_target_score(on(q, dev), s.emb, trows[i], normalize_q=normalize_q,
-                                                         bias=s.bias if use_bias else None,
-                                                         bias_weight=on(bias_weight, dev) if use_bias else None).to(home))
-            ts = torch.stack(parts)
-            ts = torch.where(torch.isnan(ts), torch.full_like(ts, float("-inf")), ts).amax(dim=0)
-            ts = self._reduce_max(ts)  # a real score is finite; -inf: no shard holds the target
-            tscore = torch.where(ts == float("-inf"), torch.full_like(ts, float("nan")), ts).contiguous()
-            tscore_out = ts  # what one catalogue returns: -inf without a target
+            tscore, tscore_out, trows = _sharded_target_score(self.shards, q, target_ids, normalize_q, bias_weight, use_bias,
+                                                              self._reduce_max)
         # 3: every local shard's list, its rows as ids
         ls, li, lr = [], [], []
         for i, s in enumerate(self.shards):
@@ -1660,7 +1691,7 @@ class ShardedItemCatalogue:
                                          deep=k > K.RETRIEVE_MAX_K, bias=s.bias if use_bias else None,
                                          bias_weight=on(bias_weight, dev) if use_bias else None,
                                          target_scores=on(tscore, dev))
-                ids = torch.where(rows >= 0, s.ids[rows.clamp(min=0).long()], torch.zeros_like(rows, dtype=torch.int64))
+                ids = s._ids_of(rows)
             ls.append(sc.to(home))
             li.append(ids.to(home))
             if rank is not None:
@@ -1696,6 +1727,10 @@ class ShardedItemCatalogue:
         return self._scan(q, k, normalize_q, target_ids, slab_rows, exclude_ids, tag_filter, after_scores, after_ids,
                           bias_weight, True)
 
+    retrieve_takes = frozenset({"heads", *_TAGS, "after", "bias_weight"})
+    _check_retrieve = ItemCatalogue._check_retrieve
+    _retrieve = ItemCatalogue._retrieve
+
     def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, exclude_ids: Optional[torch.Tensor] = None,
                      tag_filter: Optional[torch.Tensor] = None, bias_weight: Optional[float] = None) -> torch.Tensor:
         """``ItemCatalogue.target_ranks`` over the union of the shards (int64)."""
@@ -1703,7 +1738,7 @@ class ShardedItemCatalogue:
                           bias_weight is not None)[2]
 
 
-class ShardedClusteredItemCatalogue:
+class ShardedClusteredItemCatalogue(_Catalogue):
     """One catalogue held as clustered shards: ``local_shards`` are ``ClusteredItemCatalogue``s of this
     process, all plain, all ``with_filters()`` views or all ``with_deep()`` views (on one device or on
     several; disjoint ids, checked here), and with ``group`` the catalogue also covers the shards of the
@@ -1824,16 +1859,7 @@ class ShardedClusteredItemCatalogue:
         return ItemCatalogue.from_embeddings(cat("ids"), cat("emb"), cat("tags"), cat("bias"))
 
     def _check_call(self, k: int, nprobe) -> Tuple[int, int]:
-        if nprobe is None or isinstance(nprobe, bool) or not isinstance(nprobe, int):
-            raise ValueError(f"a clustered catalogue takes nprobe, an int (got {nprobe!r})")
-        if nprobe > K.RETRIEVE_MAX_PROBE:
-            raise ValueError(f"nprobe takes at most {K.RETRIEVE_MAX_PROBE} lists per query (got {nprobe})")
-        if nprobe < 1:
-            raise ValueError(f"nprobe takes at least one list (got {nprobe})")
-        k = int(k)
-        if not 1 <= k <= self.max_k:
-            raise ValueError(f"a clustered catalogue takes k in 1..{self.max_k} (got {k})")
-        return k, nprobe
+        return _check_probe_call(k, nprobe, self.max_k)  # nprobe is per shard, which probes min(nprobe, its nlist)
 
     def _chunks(self, nprobe: int):
         """The local shards cut into the calls of ``K.retrieve_ivf_topk_shards``: consecutive shards of one
@@ -1863,8 +1889,7 @@ class ShardedClusteredItemCatalogue:
                 raise ValueError(f"a clustered catalogue takes [Q, {WIDTH}] queries, one per row (got {tuple(q.shape)})")
         else:
             self.shards[0]._check_filters(q, tag_filter, after_scores, after_ids, bias_weight)
-        if exclude_ids is not None and (exclude_ids.dtype != torch.int64 or exclude_ids.dim() != 2):
-            raise ValueError(f"exclude_ids must be int64 [Q, X] (got {exclude_ids.dtype} {tuple(exclude_ids.shape)})")
+        _check_exclude(exclude_ids)
         if target_ids is not None and (target_ids.dtype != torch.int64 or tuple(target_ids.shape) != (q.shape[0],)):
             raise ValueError(f"target_ids must be int64 [Q] (got {target_ids.dtype} {tuple(target_ids.shape)})")
         home = q.device
@@ -1872,20 +1897,10 @@ class ShardedClusteredItemCatalogue:
         if isinstance(bias_weight, (int, float)) and not isinstance(bias_weight, bool):
             bias_weight = torch.full((q.shape[0],), float(bias_weight), dtype=torch.float32, device=home)
         on = lambda t, dev: None if t is None else t.to(dev).contiguous()
-        # the target's score, from the one shard that holds the target (ShardedItemCatalogue._scan's steps 1, 2)
         tscore = tscore_out = None
         if target_ids is not None:
-            parts = []
-            for s in self.shards:
-                dev = s.emb.device
-                with torch.cuda.device(dev):
-                    parts.append(K.retrieve_target_score(on(q, dev), s.emb, s.rows_of(target_ids).contiguous(),
-                                                         normalize_q=normalize_q, bias=s.bias if use_bias else None,
-                                                         bias_weight=on(bias_weight, dev) if use_bias else None).to(home))
-            ts = torch.stack(parts)
-            ts = self._reduce_max(torch.where(torch.isnan(ts), torch.full_like(ts, float("-inf")), ts).amax(dim=0))
-            tscore = torch.where(ts == float("-inf"), torch.full_like(ts, float("nan")), ts).contiguous()
-            tscore_out = ts
+            tscore, tscore_out, _ = _sharded_target_score(self.shards, q, target_ids, normalize_q, bias_weight, use_bias,
+                                                          self._reduce_max)
         ls, li, lr = [], [], []
         for chunk in self._chunks(nprobe):
             dev = chunk[0].emb.device
@@ -1940,6 +1955,27 @@ class ShardedClusteredItemCatalogue:
         return self._scan(q, k, nprobe, normalize_q, target_ids, exclude_ids, tag_filter, after_scores, after_ids,
                           bias_weight, True)
 
+    _REFUSAL = ClusteredItemCatalogue._REFUSAL
+    _RANKS_TAKE_NPROBE = True
+
+    @property
+    def retrieve_takes(self) -> frozenset:
+        """What a clustered catalogue of the shards' kind takes, but ``heads`` and what diversifies a list."""
+        return self.shards[0].retrieve_takes - {"heads", "diversity", "pool", "group_cap"}
+
+    def _check_retrieve(self, k, given: dict) -> None:
+        if given["heads"] is not None:
+            raise ValueError("retrieve with a sharded clustered catalogue does not take heads: several queries "
+                             "per user over clustered shards are not supported (use catalogue.to_flat() for it)")
+        _refuse_named(self, given, ("diversity", "pool", "group_cap", *_TAGS, "after", "bias_weight"))
+        _need_nprobe(given)
+        self._check_call(k, given["nprobe"])
+        _refuse_shortlist(given)
+
+    def _retrieve(self, q, k, nprobe, shortlist, exclude_ids, tag_filter, after_scores, after_ids, bias_weight):
+        return self.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=exclude_ids, tag_filter=tag_filter,
+                         after_scores=after_scores, after_ids=after_ids, bias_weight=bias_weight)[:2]
+
     def target_ranks(self, q: torch.Tensor, target_ids: torch.Tensor, *, nprobe: int,
                      exclude_ids: Optional[torch.Tensor] = None, tag_filter: Optional[torch.Tensor] = None,
                      bias_weight: Optional[float] = None) -> torch.Tensor:
@@ -1956,16 +1992,7 @@ class ShardedClusteredItemCatalogue:
         if self._flat is None:
             flat = self.to_flat()
             self._flat = flat if self.scans_filters else ItemCatalogue(flat.ids, flat.emb, flat.tags)
-        want = self._flat.topk(q, k, **filters)[0]
-        got = self.topk(q, k, nprobe=nprobe, **filters)[0]
-        real = want != 0
-        rows = max(1, (1 << 24) // (int(k) * int(k)))  # queries per comparison: at most 16 Mi pairs at a time
-        hit = torch.cat([((want[i:i + rows, :, None] == got[i:i + rows, None, :]).any(dim=2) & real[i:i + rows]).sum(dim=1)
-                         for i in range(0, want.shape[0], rows)]).double()
-        n = real.sum(dim=1)
-        if not bool((n > 0).any()):
-            return 1.0
-        return float((hit[n > 0] / n[n > 0].double()).mean())
+        return _hit_fraction(self._flat.topk(q, k, **filters)[0], self.topk(q, k, nprobe=nprobe, **filters)[0], k)
 
 
 def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:

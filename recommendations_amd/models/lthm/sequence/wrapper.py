@@ -411,101 +411,15 @@ class LTHMModelWrapper(BaseModelWrapper):
         min(nprobe, nlist) nearest lists) and the arguments a clustered catalogue of its shards' kind takes,
         but ``heads`` and ``diversity`` / ``pool`` / ``group_cap``, which it refuses.  ``exclude_seen`` is ``catalogue_metrics``' name for
         ``exclude_history`` and means the same here, for every catalogue."""
-        from .retrieval import (ClusteredItemCatalogue, ItemCatalogue, QuantizedClusteredItemCatalogue,
-                                QuantizedItemCatalogue, ShardedClusteredItemCatalogue)
+        from .retrieval import make_tag_filter
         exclude_history = bool(exclude_history) or bool(exclude_seen)
-        sharded_ivf = isinstance(catalogue, ShardedClusteredItemCatalogue)
-        if sharded_ivf:
-            # the keyword checks of a clustered catalogue of the shards' kind; nprobe is per shard
-            if heads is not None:
-                raise ValueError("retrieve with a sharded clustered catalogue does not take heads: several queries "
-                                 "per user over clustered shards are not supported (use catalogue.to_flat() for it)")
-            given = {"diversity": diversity, "pool": pool, "group_cap": group_cap}
-            if not catalogue.scans_filters:
-                given.update({"tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
-                              "bias_weight": bias_weight})
-            bad = [name for name, v in given.items() if v is not None]
-            if bad:
-                raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
-                                 "use catalogue.to_flat() for it")
-            if nprobe is None:
-                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
-            catalogue._check_call(k, nprobe)
-        clustered = isinstance(catalogue, ClusteredItemCatalogue)
-        quantized = isinstance(catalogue, QuantizedItemCatalogue)
-        if isinstance(catalogue, QuantizedClusteredItemCatalogue):
-            given = {"heads": heads, "after": after, "diversity": diversity, "pool": pool, "group_cap": group_cap}
-            bad = [name for name, v in given.items() if v is not None]
-            if bad:
-                raise ValueError(f"retrieve with a quantised clustered catalogue does not take {', '.join(bad)}: "
-                                 "use catalogue.to_clustered() for it")
-            if nprobe is None:
-                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
-            catalogue._check_call(k, nprobe)
-            if shortlist is not None and (isinstance(shortlist, bool) or not isinstance(shortlist, int)
-                                          or not int(k) <= shortlist <= K.RETRIEVE_Q8_MAX_POOL):
-                raise ValueError(f"shortlist takes k..{K.RETRIEVE_Q8_MAX_POOL} rows (got shortlist={shortlist!r}, k={k})")
-            if bias_weight is not None and not catalogue.has_bias:
-                raise ValueError("bias_weight given, but this catalogue carries no bias")
-            filt = None
-            if tag_all is not None or tag_any is not None or tag_none is not None:
-                if not catalogue.has_tags:
-                    raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
-            out = self.forward(batch)
-            q = out["next_token_emb"][:, -1, head].contiguous()
-            if q.dtype not in (torch.float32, torch.bfloat16):
-                q = q.float()
-            seen = None
-            if exclude_history:
-                seen = out["current_token_ids"]
-                if seen.shape[1] > K.RETRIEVE_MAX_EXCLUDE:
-                    raise ValueError(f"exclude_history takes histories of at most {K.RETRIEVE_MAX_EXCLUDE} tokens "
-                                     f"(T = {seen.shape[1]})")
-            if tag_all is not None or tag_any is not None or tag_none is not None:
-                from .retrieval import make_tag_filter
-                filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
-                                       0 if tag_none is None else tag_none, device=q.device)
-            if isinstance(bias_weight, torch.Tensor):
-                bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
-            item_ids, scores = catalogue.topk(q, k, nprobe=nprobe, shortlist=shortlist, rescore=catalogue.keep_exact,
-                                              normalize_q=True, exclude_ids=seen, tag_filter=filt, bias_weight=bias_weight)
-            return {"item_ids": item_ids, "scores": scores}
-        if quantized:
-            given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
-                     "bias_weight": bias_weight, "nprobe": nprobe, "diversity": diversity, "pool": pool,
-                     "group_cap": group_cap}
-            bad = [name for name, v in given.items() if v is not None]
-            if bad:
-                raise ValueError(f"retrieve with a quantised catalogue does not take {', '.join(bad)}: "
-                                 "use catalogue.to_flat() for it")
-            if shortlist is not None and (isinstance(shortlist, bool) or not isinstance(shortlist, int)
-                                          or not int(k) <= shortlist <= K.RETRIEVE_Q8_MAX_POOL):
-                raise ValueError(f"shortlist takes k..{K.RETRIEVE_Q8_MAX_POOL} rows (got shortlist={shortlist!r}, k={k})")
-            if not 1 <= int(k) <= K.RETRIEVE_Q8_MAX_POOL:
-                raise ValueError(f"a quantised catalogue takes k in 1..{K.RETRIEVE_Q8_MAX_POOL} (got {k})")
-        elif shortlist is not None:
-            raise ValueError("shortlist given, but this catalogue is not quantised (ItemCatalogue.quantize builds one)")
-        if clustered:
-            given = {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none, "after": after,
-                     "bias_weight": bias_weight, "diversity": diversity, "pool": pool, "group_cap": group_cap}
-            if catalogue.scans_deep:  # a with_deep() view also diversifies its own lists
-                given = {"heads": heads}
-            elif catalogue.scans_heads:  # a with_heads() view is a with_filters() view that also takes heads
-                given = {name: given[name] for name in ("diversity", "pool", "group_cap")}
-            elif catalogue.scans_filters:  # a with_filters() view scans tags, prior and cursor itself
-                given = {name: given[name] for name in ("heads", "diversity", "pool", "group_cap")}
-            bad = [name for name, v in given.items() if v is not None]
-            if bad:
-                raise ValueError(f"retrieve with a clustered catalogue does not take {', '.join(bad)}: "
-                                 "use catalogue.to_flat() for it")
-            if nprobe is None:
-                raise ValueError("retrieve with a clustered catalogue takes nprobe, the lists each query scans")
-            catalogue._check_call(k, nprobe)
-        elif nprobe is not None and not sharded_ivf:
-            raise ValueError("nprobe given, but this catalogue is not clustered (ItemCatalogue.cluster builds one)")
+        # the catalogue refuses the keywords its kind does not take and checks k / nprobe / shortlist (retrieval.py)
+        catalogue._check_retrieve(k, {"heads": heads, "tag_all": tag_all, "tag_any": tag_any, "tag_none": tag_none,
+                                      "after": after, "bias_weight": bias_weight, "nprobe": nprobe, "diversity": diversity,
+                                      "pool": pool, "group_cap": group_cap, "shortlist": shortlist})
         diversify = diversity is not None or group_cap is not None
         if diversify:
-            if not isinstance(catalogue, ItemCatalogue) and not (clustered and catalogue.scans_deep):
+            if "diversity" not in catalogue.retrieve_takes:
                 raise ValueError("diversity / group_cap take a flat ItemCatalogue: a sharded or clustered list is "
                                  "diversified with ItemCatalogue.diversify on a flat catalogue over the same items")
             if after is not None:
@@ -555,7 +469,6 @@ class LTHMModelWrapper(BaseModelWrapper):
                                  f"(T = {seen.shape[1]})")
         filt = None
         if tag_all is not None or tag_any is not None or tag_none is not None:
-            from .retrieval import make_tag_filter
             if not catalogue.has_tags:
                 raise ValueError("tag_all / tag_any / tag_none given, but this catalogue carries no tags")
             filt = make_tag_filter(q.shape[0], 0 if tag_all is None else tag_all, 0 if tag_any is None else tag_any,
@@ -565,30 +478,8 @@ class LTHMModelWrapper(BaseModelWrapper):
             after_ids = after_ids.to(q.device).contiguous()
         if isinstance(bias_weight, torch.Tensor):
             bias_weight = bias_weight.to(device=q.device, dtype=torch.float32).contiguous()
-        if sharded_ivf:
-            item_ids, scores, _, _ = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen,
-                                                    tag_filter=filt, after_scores=after_scores, after_ids=after_ids,
-                                                    bias_weight=bias_weight)
-            return {"item_ids": item_ids, "scores": scores}
-        if clustered and catalogue.scans_filters:
-            scores, item_ids = catalogue.topk(q, pool if diversify else k, nprobe=nprobe, normalize_q=True,
-                                              exclude_ids=seen, tag_filter=filt, after_scores=after_scores,
-                                              after_ids=after_ids, bias_weight=bias_weight)
-            if diversify:  # a with_deep() view only: every other clustered catalogue has refused above
-                item_ids, scores, obj = catalogue.diversify(item_ids, scores, k, group_cap=group_cap,
-                                                            lam=1.0 if diversity is None else float(diversity))
-                return {"item_ids": item_ids, "scores": scores, "objective": obj}
-            return {"item_ids": item_ids, "scores": scores}
-        if clustered:
-            scores, item_ids = catalogue.topk(q, k, nprobe=nprobe, normalize_q=True, exclude_ids=seen)
-            return {"item_ids": item_ids, "scores": scores}
-        if quantized:
-            item_ids, scores = catalogue.topk(q, k, shortlist=shortlist, rescore=catalogue.keep_exact, normalize_q=True,
-                                              exclude_ids=seen)
-            return {"item_ids": item_ids, "scores": scores}
-        item_ids, scores, _, _ = catalogue.topk(q, pool if diversify else k, normalize_q=True, exclude_ids=seen,
-                                                tag_filter=filt, after_scores=after_scores, after_ids=after_ids,
-                                                bias_weight=bias_weight)
+        item_ids, scores = catalogue._retrieve(q, pool if diversify else k, nprobe, shortlist, seen, filt, after_scores,
+                                               after_ids, bias_weight)
         if diversify:
             item_ids, scores, obj = catalogue.diversify(item_ids, scores, k, lam=1.0 if diversity is None else float(diversity),
                                                         group_cap=group_cap)
@@ -623,9 +514,8 @@ class LTHMModelWrapper(BaseModelWrapper):
         A ``ShardedClusteredItemCatalogue`` takes ``nprobe`` (per shard): the hit position is then the
         number of items of the probed lists scoring strictly above the target, the flat catalogue's once
         every list is probed and a lower bound of it before (the target's own list need not be probed)."""
-        from .retrieval import ClusteredItemCatalogue, QuantizedClusteredItemCatalogue, ShardedClusteredItemCatalogue
-        sharded_ivf = isinstance(catalogue, ShardedClusteredItemCatalogue)
-        if sharded_ivf:
+        takes_nprobe = catalogue._RANKS_TAKE_NPROBE  # a sharded clustered catalogue: per shard
+        if takes_nprobe:
             if nprobe is None:
                 raise ValueError("catalogue_metrics with a sharded clustered catalogue takes nprobe, the lists each "
                                  "query scans in every shard")
@@ -634,11 +524,8 @@ class LTHMModelWrapper(BaseModelWrapper):
                 raise ValueError("same_tags_mask / bias_weight take with_filters() or with_deep() shards")
         elif nprobe is not None:
             raise ValueError("nprobe given, but this catalogue is not a sharded clustered one")
-        if isinstance(catalogue, ClusteredItemCatalogue):
-            raise ValueError("catalogue_metrics counts exact ranks, which take the flat scan: pass catalogue.to_flat()")
-        if isinstance(catalogue, QuantizedClusteredItemCatalogue):
-            raise ValueError("catalogue_metrics does not take a quantised clustered catalogue: it counts exact ranks, "
-                             "which take the flat scan (pass catalogue.to_flat())")
+        if catalogue._NO_RANKS is not None:  # a clustered catalogue on one device scans some lists only
+            raise ValueError(catalogue._NO_RANKS)
         ks = list(self._metrics_k_all if ks is None else ks)
         y, ids, mask = output["next_token_emb"], output["current_token_ids"], output["current_token_mask"]
         off = int(self._lookahead[head])
@@ -670,7 +557,7 @@ class LTHMModelWrapper(BaseModelWrapper):
             filt = catalogue.filter_like(tid, same_tags_mask)
         # the scans are the catalogue's (target_ranks): one K.retrieve_topk with k = 1 per call for an
         # ItemCatalogue, one per shard and a merge for a ShardedItemCatalogue
-        kw = {"nprobe": nprobe} if sharded_ivf else {}
+        kw = {"nprobe": nprobe} if takes_nprobe else {}
         if not exclude_seen:
             rank = catalogue.target_ranks(q, tid, tag_filter=filt, bias_weight=bias_weight, **kw)
         else:
